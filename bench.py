@@ -8,10 +8,15 @@ search channel 0, the reference's default 5 000 000 RANSAC iterations per search
 N > 1, one rank per GPU -- started by torch.distributed.run, or by this script itself: a parent
 that never touches the GPU spawns the N ranks (magnify_amd/launch.py) and relays rank 0's line.
   --scaling weak (default): every rank owns its own 64-timepoint block, runs the chain locally and
-      all-gathers the final marker table over RCCL; for N > 1 the line also carries a `strong` object,
-      measured right after the timed region.
+      all-gathers the final marker table over RCCL; with --full and N > 1 the line also carries a `strong`
+      object, measured right after the timed region.
   --scaling strong: north_star's C4 -- ONE 64-timepoint stack, contiguous shards of 64/N timepoints
       per rank (distributed.shard_range), same all-gather.
+A plain run sets up, warms up, times --steps steps and prints the headline (`value`, `ms_per_step`, marker
+counts); `--full` adds everything else measured after the timed region: the per-stage table and `roofline`,
+the streaming part, the isolated single-stream pass, the measured HBM copy ceiling, the CPU baseline and,
+for N > 1 with weak scaling, the `strong` object.  `--dump-outputs DIR` writes what the last timed step
+computed as .npy files (dump_outputs).
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -208,6 +213,54 @@ def hbm_copy_ceiling(dev, n_bytes=1 << 30, reps=10):
     return out
 
 
+DUMP_TABLE_BYTES = 32 << 20   # marker table (+ its row index) of --dump-outputs
+DUMP_SAMPLE_BYTES = 24 << 20  # ROI pixels + masks of the sampled markers (+ their index)
+DUMP_SAMPLE_MARKERS = 64
+
+
+def _sample(rng, n, k):
+    """k of range(n), drawn by ``rng`` and sorted; all of them when k >= n."""
+    import numpy as np
+
+    return np.arange(n) if k >= n else np.sort(rng.choice(n, size=k, replace=False))
+
+
+def dump_outputs(path, out, table, n_assays):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, as .npy files under ``path``
+    (under 64 MB in all; the same arguments give the same inputs, so two builds can be compared file by file):
+      marker_table.npy (K, 6 + 2C) float64 -- rows [assay, row, col, r, fg_count, bg_count, fg_sum[C], bg_sum[C]] of
+          the gathered marker table (exact integers): every row when they fit in DUMP_TABLE_BYTES, else a seeded
+          sample of rows, listed in marker_table_index.npy (K,) float64
+      markers_per_assay.npy (n_assays,) float64 -- from the whole table
+      roi_sample.npy (k, C, T, L, L), fg_sample.npy / bg_sample.npy (k, L, L) float32 -- ROI pixels and masks of a
+          seeded sample of at most DUMP_SAMPLE_MARKERS of this rank's markers (rank 0's markers are the first rows of
+          the table), listed in roi_sample_index.npy (k,) float64"""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(0)
+    tab = table.to(torch.float64).cpu().numpy()
+    m, width = tab.shape
+    rows = _sample(rng, m, DUMP_TABLE_BYTES // (8 * width + 8))
+    arrays = {"marker_table": tab[rows], "marker_table_index": rows.astype(np.float64),
+              "markers_per_assay": np.bincount(tab[:, 0].astype(np.int64), minlength=n_assays).astype(np.float64)}
+    roi, fg, bg = out["roi"], out["fg"], out["bg"]
+    m_local = int(roi.shape[0])
+    per_marker = 4 * (roi[0].numel() + fg[0].numel() + bg[0].numel()) + 8 if m_local else 1
+    idx = _sample(rng, m_local, min(DUMP_SAMPLE_MARKERS, DUMP_SAMPLE_BYTES // per_marker))
+    sel = torch.from_numpy(idx).to(roi.device)
+    for name, v in (("roi", roi), ("fg", fg), ("bg", bg)):
+        if v.dtype == torch.uint16:  # (torch has no uint16 gather on the device: the same bits as int16)
+            rows_np = v.view(torch.int16)[sel].cpu().numpy().view(np.uint16)
+        else:
+            rows_np = v[sel].cpu().numpy()
+        arrays[name + "_sample"] = rows_np.astype(np.float32)
+    arrays["roi_sample_index"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def per_assay_fg_sums(out, n_assays):
     """Sum of the foreground sums of every assay's markers (exact integers held in float64)."""
     import numpy as np
@@ -236,12 +289,17 @@ def main():
                     help="the stack starts every step in pinned HOST memory (PCIe-inclusive rate; not the headline)")
     ap.add_argument("--noiseless", action="store_true",
                     help="the reference tests' kind of image: zero background, beads of value 1000 (not the headline)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-isolated", action="store_true", help="skip the extra single-stream pass")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the per-stage table, roofline, streaming part, isolated pass, "
+                         "HBM copy ceiling, CPU baseline and (N > 1, weak scaling) the strong-scaling object")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-isolated", action="store_true", help="with --full: skip the extra single-stream pass")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak: --timepoints per GPU; strong: --timepoints in total, sharded over the GPUs")
     ap.add_argument("--no-strong-extra", action="store_true",
-                    help="weak scaling with N > 1: skip the extra strong-scaling measurement")
+                    help="with --full, weak scaling with N > 1: skip the extra strong-scaling measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, see dump_outputs)")
     args = ap.parse_args()
 
     from magnify_amd import launch
@@ -298,7 +356,7 @@ def main():
             dt = float(t.item())
         return dt
 
-    def run_steps(proc, src, first_assay, with_timer):
+    def run_steps(proc, src, first_assay, with_timer, dump_dir=None):
         """W untimed + K timed steps; a step = the chain on this rank's block + the marker-table all-gather.
         The detection RNG stream of an assay depends on its GLOBAL index only (seed + 1000003 * index)."""
         def step(seed):
@@ -319,6 +377,8 @@ def main():
         barrier()
         dt = time.perf_counter() - t0
         hp.set_timer(None)
+        if dump_dir is not None and rank == 0:  # before anything else reuses the pooled output buffers
+            dump_outputs(dump_dir, out, table, n_total)
         live = timer.summary() if with_timer else None
         stages = None
         if with_timer:
@@ -339,13 +399,13 @@ def main():
             out, table = step(args.warmup + args.steps - 1)  # (the results reported are those of the last timed step's seed)
         return out, table, max_over_ranks(dt), stages
 
+    n_total = args.timepoints if strong else world * args.timepoints  # timepoints all ranks processed per step
     proc = make_proc(T)
     src = stack.cpu().pin_memory() if args.from_host else stack
-    out, table, dt, stages = run_steps(proc, src, lo, True)
-    n_total = args.timepoints if strong else world * args.timepoints  # timepoints all ranks processed per step
+    out, table, dt, stages = run_steps(proc, src, lo, args.full, args.dump_outputs)
 
     strong_extra = None
-    if world > 1 and not strong and not args.no_strong_extra and args.timepoints >= world:
+    if args.full and world > 1 and not strong and not args.no_strong_extra and args.timepoints >= world:
         # the same ranks once more on north_star's C4 proper: ONE --timepoints stack, 1/N of it per rank
         # (the first timepoints of this rank's block stand in for its shard)
         slo, shi = mgd.shard_range(args.timepoints, rank, world)
@@ -385,30 +445,32 @@ def main():
              "edges": edges, "bitmap_words": f.bitmap_words, "unique": unique, "alive": alive, "scored": scored,
              "mean_perimeter": mean_perimeter, "ring_len": len(hp.nat.circle_points(proc.min_r, True)),
              "markers": markers_local, "mean_disk": 600, "L": proc.L}
-        # HBM bytes per step from the committed rocprofv3 PMC passes: only when they were taken on these sources
-        pmc, pmc_file = load_traffic((T, C, S, args.num_iter))
         n_all, n_s = T * C * S * S, search_planes * S * S
-        # SURVEY.md 8d's count minus the label map this build no longer writes (4 B/px of the searched
-        # planes) or reads (4 B per window pixel): masks come straight from the bead tables
-        # ... and minus the histogram pass's read of the blurred image (1 B/px) where the one-pass blur + histogram
-        # kernel ran (mg_to_uint8_blur_hist takes the magnitudes from registers): bytes saved are not bytes moved
-        one_pass_hist = "mg_to_uint8_blur_hist" in stages and "mg_scharr_hist" not in stages
-        stream_bytes = 6 * n_all + (7 if one_pass_hist else 8) * n_s + markers_local * proc.L**2 * (4 * C + 2)
-        breakdown, roofline, streaming, total_ms = stage_report(stages, args.steps, p, pmc, stream_bytes)
-        # the same stages against SURVEY 8d's own count, which includes the label map (4 B written per searched pixel,
-        # 4 B read per window pixel) that this build never materialises: bytes saved, not bytes moved
-        survey_stream = 6 * n_all + 12 * n_s + markers_local * proc.L**2 * (4 * C + 6)
-        if streaming.get("ms_per_step"):
-            streaming["survey_8d_bytes_incl_label_map"] = survey_stream
-            streaming["frac_of_peak_by_survey_bytes"] = survey_stream / (streaming["ms_per_step"] / 1e3) / 1e9 / HBM_PEAK_GBS
-        roofline["traffic_source"] = pmc_file  # None: no PMC pass on these exact sources under profiles/
+        breakdown = roofline = streaming = total_ms = None  # (--full)
+        if args.full:
+            # HBM bytes per step from the committed rocprofv3 PMC passes: only when they were taken on these sources
+            pmc, pmc_file = load_traffic((T, C, S, args.num_iter))
+            # SURVEY.md 8d's count minus the label map this build no longer writes (4 B/px of the searched
+            # planes) or reads (4 B per window pixel): masks come straight from the bead tables
+            # ... and minus the histogram pass's read of the blurred image (1 B/px) where the one-pass blur + histogram
+            # kernel ran (mg_to_uint8_blur_hist takes the magnitudes from registers): bytes saved are not bytes moved
+            one_pass_hist = "mg_to_uint8_blur_hist" in stages and "mg_scharr_hist" not in stages
+            stream_bytes = 6 * n_all + (7 if one_pass_hist else 8) * n_s + markers_local * proc.L**2 * (4 * C + 2)
+            breakdown, roofline, streaming, total_ms = stage_report(stages, args.steps, p, pmc, stream_bytes)
+            # the same stages against SURVEY 8d's own count, which includes the label map (4 B written per searched pixel,
+            # 4 B read per window pixel) that this build never materialises: bytes saved, not bytes moved
+            survey_stream = 6 * n_all + 12 * n_s + markers_local * proc.L**2 * (4 * C + 6)
+            if streaming.get("ms_per_step"):
+                streaming["survey_8d_bytes_incl_label_map"] = survey_stream
+                streaming["frac_of_peak_by_survey_bytes"] = survey_stream / (streaming["ms_per_step"] / 1e3) / 1e9 / HBM_PEAK_GBS
+            roofline["traffic_source"] = pmc_file  # None: no PMC pass on these exact sources under profiles/
         # SURVEY 8d's byte count of the whole step, B = 6 N_all + 12 N_s + K_u (12 + 5 P) + M L^2 (4 C + 6), with K_u
         # the circles that reach the exact sum; against the wall-clock step (kernels + host round trips)
         b8d = 6 * n_all + 12 * n_s + scored * (12 + 5 * mean_perimeter) + markers_local * proc.L**2 * (4 * C + 6)
         whole = {"algorithmic_bytes_survey_8d": b8d, "ms_per_step": ms_per_step,
                  "achieved_GBs": b8d / (ms_per_step / 1e3) / 1e9, "frac_of_peak": b8d / (ms_per_step / 1e3) / 1e9 / HBM_PEAK_GBS}
         isolated = None
-        if world == 1 and proc.n_streams > 1 and not args.no_isolated:
+        if args.full and world == 1 and proc.n_streams > 1 and not args.no_isolated:
             # the same step once more on ONE stream (untimed for `value`): kernel durations without the
             # overlap of the four detection streams, for the per-stage roofline table
             proc1 = StackProcessor(T, C, S, S, num_iter=args.num_iter, min_bead_diameter=10, max_bead_diameter=50,
@@ -464,16 +526,17 @@ def main():
                       # the processor's first call timed its passes into several image blocks / ROI output sets and
                       # kept the fastest (stack.StackProcessor placement trial; None: no trial)
                       "placement": getattr(proc, "placement", None),
-                      "stage_timing": "HIP events on the launch stream: live in the timed region for " + ", ".join(LIVE_STAGES)
-                                      + "; the stages inside the finder's chain from the same steps re-run eagerly right after it",
-                      "kernel_ms_per_step": total_ms / args.steps},
+                      "stage_timing": ("HIP events on the launch stream: live in the timed region for " + ", ".join(LIVE_STAGES)
+                                       + "; the stages inside the finder's chain from the same steps re-run eagerly right after it"
+                                       if args.full else None),
+                      "kernel_ms_per_step": total_ms / args.steps if args.full else None},
         }
-        result["hbm_copy_ceiling"] = hbm_copy_ceiling(dev)
+        result["hbm_copy_ceiling"] = hbm_copy_ceiling(dev) if args.full else None
         for part in (roofline, streaming, whole):
             if part and result["hbm_copy_ceiling"]:
                 gbs = part.get("achieved", part.get("achieved_GBs"))
                 part["frac_of_measured_copy"] = gbs / result["hbm_copy_ceiling"]["GBs"] if gbs else None
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             last = args.warmup + args.steps - 1  # seed of the step whose results are in `out`
             seeds = [(last + 1000003 * a) & 0xFFFFFFFFFFFFFFFF for a in range(T)]
             result["cpu_baseline"] = cpu_baseline(args, stack, flat_np, seeds, [len(b) for b in out["beads"]],

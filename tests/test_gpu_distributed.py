@@ -104,12 +104,12 @@ def test_rccl_collectives_on_one_rank():
     assert rec["mode_r_beads"] >= 5 and rec["mode_r_equal"]
 
 
-def _bench(*flags):
+def _bench(*flags, full=True):
     import json
     import subprocess
 
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--size", "512", "--num-iter", "40000",
-           "--no-cpu", *flags]
+           *(["--full", "--no-cpu"] if full else []), *flags]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     done = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert done.returncode == 0, done.stderr[-2000:]
@@ -136,6 +136,34 @@ def test_bench_starts_its_own_ranks():
     one = _bench("--gpus", "1", "--timepoints", "2")
     assert one["n_gpus"] == 1 and one["strong"] is None and one["ranks"]["world_size"] == 1
     assert one["roofline"]["frac"] is not None and "cpu_baseline" in one
+
+
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """`python bench.py` without --full: --steps timed steps and the headline, nothing measured after them;
+    --dump-outputs writes the last timed step's results as float32 / float64 .npy files, the same in two processes
+    (seeded inputs), and its marker table is the one the result line counts."""
+    recs = []
+    for name in ("a", "b"):
+        recs.append(_bench("--gpus", "1", "--timepoints", "2", "--steps", "3", "--dump-outputs", str(tmp_path / name),
+                           full=False))
+    rec = recs[0]
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["markers"] > 0
+    for k in ("roofline", "stages", "streaming_part", "isolated", "hbm_copy_ceiling", "cpu_baseline", "strong"):
+        assert rec[k] is None, k
+    assert abs(rec["value"] - 2 * 4 * 512 * 512 / 1e6 / (rec["ms_per_step"] / 1e3)) < 1e-6 * rec["value"]
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == sorted(n + ".npy" for n in ("marker_table", "marker_table_index", "markers_per_assay", "roi_sample",
+                                                "fg_sample", "bg_sample", "roi_sample_index"))
+    assert sum((tmp_path / "a" / n).stat().st_size for n in names) < 64 << 20
+    arrays = {n: np.load(tmp_path / "a" / n) for n in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    table = arrays["marker_table.npy"]
+    assert table.shape == (rec["markers"], 6 + 2 * 4)
+    assert arrays["markers_per_assay.npy"].tolist() == np.bincount(table[:, 0].astype(int), minlength=2).tolist()
+    k = min(64, rec["markers"])
+    assert arrays["roi_sample.npy"].shape == (k, 4, 1, 100, 100) and arrays["fg_sample.npy"].shape == (k, 100, 100)
+    for n in names:
+        assert np.array_equal(arrays[n], np.load(tmp_path / "b" / n)), n
 
 
 @pytest.mark.gpu

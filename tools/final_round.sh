@@ -7,12 +7,12 @@ set -e
 TAG=${1:-r4}
 OUT=gpurun_out
 # (the driver's command of rounds 1-3; `python bench.py` alone runs 10 steps after 6 warm-up calls)
-python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/${TAG}_final_bench.json 2> $OUT/${TAG}_final_bench.err || { tail -20 $OUT/${TAG}_final_bench.err; exit 1; }
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/${TAG}_final_bench.json 2> $OUT/${TAG}_final_bench.err || { tail -20 $OUT/${TAG}_final_bench.err; exit 1; }
 echo default done
-python bench.py --timepoints 8 --steps 40 --warmup 3 --no-cpu --no-isolated > $OUT/${TAG}_bench_8tp.json 2> $OUT/${TAG}_bench_8tp.err
-python bench.py --timepoints 1 --steps 40 --warmup 3 --no-cpu --no-isolated > $OUT/${TAG}_bench_1tp.json 2> $OUT/${TAG}_bench_1tp.err
-python bench.py --noiseless --steps 10 --warmup 2 --no-cpu --no-isolated > $OUT/${TAG}_noiseless_bench.json 2> $OUT/${TAG}_noiseless_bench.err
-python bench.py --steps 20 --warmup 3 --no-cpu --no-isolated > $OUT/${TAG}_bench_20steps.json 2> $OUT/${TAG}_bench_20steps.err
+python bench.py --timepoints 8 --steps 40 --warmup 3 --full --no-cpu --no-isolated > $OUT/${TAG}_bench_8tp.json 2> $OUT/${TAG}_bench_8tp.err
+python bench.py --timepoints 1 --steps 40 --warmup 3 --full --no-cpu --no-isolated > $OUT/${TAG}_bench_1tp.json 2> $OUT/${TAG}_bench_1tp.err
+python bench.py --noiseless --steps 10 --warmup 2 --full --no-cpu --no-isolated > $OUT/${TAG}_noiseless_bench.json 2> $OUT/${TAG}_noiseless_bench.err
+python bench.py --steps 20 --warmup 3 --full --no-cpu --no-isolated > $OUT/${TAG}_bench_20steps.json 2> $OUT/${TAG}_bench_20steps.err
 echo benches done
 timeout -k 10 600 python tests/config_table.py --out $OUT/${TAG}_configs.json > $OUT/${TAG}_configs.log 2>&1
 echo configs done

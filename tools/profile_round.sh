@@ -15,15 +15,15 @@ rm -rf $RAW; mkdir -p $RAW $OUT
 # the per-step division of the counters below would count them as steps' traffic
 export TMPDIR=/tmp MG_NO_GRAPH=1 MG_PLACEMENT_TRIES=0
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $RAW/stats -- python3 $ROOT/bench.py --steps 5 --warmup 2 --no-cpu > $OUT/${TAG}_stats_bench.json 2> $OUT/${TAG}_stats.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $RAW/stats -- python3 $ROOT/bench.py --steps 5 --warmup 2 --full --no-cpu > $OUT/${TAG}_stats_bench.json 2> $OUT/${TAG}_stats.log
 cp $(find $RAW/stats -name "*kernel_stats.csv" | head -1) $OUT/${TAG}_kernel_stats.csv
 echo stats done
 STEPS=3
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d $RAW/fetch -- python3 $ROOT/bench.py --steps $STEPS --warmup 1 --no-cpu > /dev/null 2> $OUT/${TAG}_pmc_fetch.log
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d $RAW/write -- python3 $ROOT/bench.py --steps $STEPS --warmup 1 --no-cpu > /dev/null 2> $OUT/${TAG}_pmc_write.log
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d $RAW/fetch -- python3 $ROOT/bench.py --steps $STEPS --warmup 1 --full --no-cpu > /dev/null 2> $OUT/${TAG}_pmc_fetch.log
+rocprofv3 --pmc WRITE_SIZE --output-format csv -d $RAW/write -- python3 $ROOT/bench.py --steps $STEPS --warmup 1 --full --no-cpu > /dev/null 2> $OUT/${TAG}_pmc_write.log
 echo pmc done
-rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES --kernel-trace --output-format csv -d $RAW/sq -- python3 $ROOT/bench.py --steps 2 --warmup 1 --no-cpu > /dev/null 2> $OUT/${TAG}_sq.log || \
-rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES --output-format csv -d $RAW/sq -- python3 $ROOT/bench.py --steps 2 --warmup 1 --no-cpu > /dev/null 2> $OUT/${TAG}_sq.log
+rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES --kernel-trace --output-format csv -d $RAW/sq -- python3 $ROOT/bench.py --steps 2 --warmup 1 --full --no-cpu > /dev/null 2> $OUT/${TAG}_sq.log || \
+rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES --output-format csv -d $RAW/sq -- python3 $ROOT/bench.py --steps 2 --warmup 1 --full --no-cpu > /dev/null 2> $OUT/${TAG}_sq.log
 echo sq done
 cd $ROOT
 # bench runs warmup + steps + the per-stage profile pass (min(steps, 5), at least 2) + 1 result step per process
