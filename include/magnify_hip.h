@@ -112,6 +112,47 @@ int mg_plane_minmax(const void* d_src, int dtype, int n_planes, int64_t plane_st
                     int64_t row_stride, double* d_minmax, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Shading model (BaSiC, Peng et al. 2017): fit of a flat- and a dark-field from training tiles and its apply fused
+ * with the stitch crop (DESIGN.md §4 "shading"; oracle tests/ref_shading.py).  The fit's state lives in one device
+ * workspace of mg_shading_workspace_bytes(n, w) bytes (n images, w x w working grid, 1 <= w <= 128), 256-byte aligned;
+ * mg_shading_offset(n, w, field) is the byte offset of region `field`:
+ *   0 D, 1 E, 2 Y, 3 weight (float32 n x w^2); 4 W_hat, 5 F_w, 6 A_off, 7 M (scratch; mean_n XA before
+ *   mg_shading_reweight), 8 T (scratch), 9 mean over images of D, 10 min over images of D (float64 w^2);
+ *   11 DCT-II table C[k][x], 12 its transpose (float64 w^2); 13 coeff (float64 n); 14-16 partial sums (internal);
+ *   17 Gram matrix D D^T (float64 n x n); 18 scalars (float64 x 32: 0 mu, 7 B1_offset); 19 flags (int32 x 8:
+ *   0 done, 1 ALM iterations of the pass).
+ * -1 / MG_EINVAL for a bad argument.
+ * ---------------------------------------------------------------------------------- */
+int64_t mg_shading_workspace_bytes(int n, int w);
+int64_t mg_shading_offset(int n, int w, int field);
+/* Area downsample of n (ty, tx) tiles of `dtype` (ty, tx >= w) to d_out[n][w][w] float32, float64 accumulation. */
+int mg_shading_downsample(const void* d_tiles, int dtype, int64_t n, int ty, int tx, int w, float* d_out, void* stream);
+/* From D in the workspace: DCT tables, per-pixel mean / min over images, Gram matrix, weight = 1. */
+int mg_shading_prepare(void* d_ws, int n, int w, void* stream);
+/* d_out = dct2(d_in) (inverse = 0) or idct2(d_in) (inverse = 1), orthonormal, float64 w x w; needs mg_shading_prepare. */
+int mg_shading_dct2(void* d_ws, int n, int w, const double* d_in, double* d_out, int inverse, void* stream);
+/* Fresh ALM state of one reweighting pass (mu_bar = 1e7 mu, rho = 1.5, ent1 = 1, ent2 = 10). */
+int mg_shading_alm_begin(void* d_ws, int n, int w, int get_darkfield, int max_iterations, double mu, double lam_f,
+                         double lam_d, double tol, double norm_f, double b_up, void* stream);
+/* Enqueue k ALM iterations; once the stop test holds or max_iterations is reached the `done` flag is set and the
+ * remaining iterations return at once.  No host synchronisation. */
+int mg_shading_alm_iterate(void* d_ws, int n, int w, int k, int get_darkfield, void* stream);
+/* weight = 1 / (|E / M| + epsilon), scaled to mean 1 (M: mean_n XA, written by the caller). */
+int mg_shading_reweight(void* d_ws, int n, int w, double epsilon, void* stream);
+/* Bilinear upsample (half-pixel centres, clamped) of the w x w float64 fields to ty x tx float32; the flat is divided
+ * by its float64 mean.  d_partial: 256 float64 of scratch. */
+int mg_shading_upsample(const double* d_flat_w, const double* d_dark_w, int w, int ty, int tx, double* d_partial,
+                        float* d_flat, float* d_dark, void* stream);
+/* out = (x - dark) / flat fused with the stitch crop / concat (as mg_flatfield_apply_stitch): tiles (n_fields *
+ * planes_per_field planes, n_tile_rows, n_tile_cols, ty, tx) of `dtype`; plane p uses field p / planes_per_field of
+ * d_flat / d_dark (float32, stride ty * tx).  u8 / u16 / f32 tiles in float32, f64 in float64; integer outputs
+ * clamped to [0, max] and truncated.  d_minmax (optional, double[planes][2] pre-set to {+inf, -inf}): per-plane
+ * min / max of the values written. */
+int mg_shading_apply_stitch(const void* d_tiles, int dtype, int n_fields, int64_t planes_per_field, int n_tile_rows,
+                            int n_tile_cols, int ty, int tx, int overlap, const float* d_flat, const float* d_dark,
+                            void* d_image, double* d_minmax, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * A3-A6 edge stage of find_circles (utils.py:20-27, 115-142)
  * ---------------------------------------------------------------------------------- */
 

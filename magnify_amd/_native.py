@@ -37,6 +37,16 @@ PROTOTYPES = {
     "mg_flatfield_bound": [_p, _i, _i, _i, _i, _p, _l, _p],
     "mg_flatfield_is_identity": [_i, _d, _p, _d, _p],
     "mg_flatfield_apply_stitch": [_p, _i, _l, _i, _i, _i, _i, _i, _i, _i, _d, _p, _i, _d, _p, _i, _p, _p, _p, _p],
+    "mg_shading_workspace_bytes": [_i, _i],
+    "mg_shading_offset": [_i, _i, _i],
+    "mg_shading_downsample": [_p, _i, _l, _i, _i, _i, _p, _p],
+    "mg_shading_prepare": [_p, _i, _i, _p],
+    "mg_shading_dct2": [_p, _i, _i, _p, _p, _i, _p],
+    "mg_shading_alm_begin": [_p, _i, _i, _i, _i, _d, _d, _d, _d, _d, _d, _p],
+    "mg_shading_alm_iterate": [_p, _i, _i, _i, _i, _p],
+    "mg_shading_reweight": [_p, _i, _i, _d, _p],
+    "mg_shading_upsample": [_p, _p, _i, _i, _i, _p, _p, _p, _p],
+    "mg_shading_apply_stitch": [_p, _i, _i, _l, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p],
     "mg_plane_minmax": [_p, _i, _i, _l, _i, _i, _l, _p, _p],
     "mg_to_uint8_blur": [_p, _i, _i, _l, _i, _i, _l, _p, _p, _p, _p],
     "mg_scharr_hist": [_p, _i, _i, _i, _i, _p, _p, _p, _l, _p],
@@ -85,7 +95,7 @@ PROTOTYPES = {
     "mg_host_write_runs": [_p, _p, _p, _p, _i, _i, _p],
 }
 
-RETURNS_INT64 = {"mg_scharr_hist_scratch_words", "mg_blur_hist_scratch_words", "mg_edge_grid_scan_words", "mg_flatfield_max_scratch_floats"}
+RETURNS_INT64 = {"mg_shading_workspace_bytes", "mg_shading_offset", "mg_scharr_hist_scratch_words", "mg_blur_hist_scratch_words", "mg_edge_grid_scan_words", "mg_flatfield_max_scratch_floats"}
 
 _lib = None
 

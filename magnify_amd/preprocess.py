@@ -193,5 +193,34 @@ def circle_mask(xp, center, diameter, mask_inner=False):
 @registry.component("basic_correct")
 def basic_correct(xp):
     """preprocess.py:91-115 fits a BaSiC illumination model with the third-party ``basicpy``; not part of
-    this build (use ``flatfield_correct`` with measured flat / dark images)."""
-    raise NotImplementedError("basic_correct needs the basicpy package; use flatfield_correct")
+    this build (use ``shading_correct``, this build's own BaSiC fit, or ``flatfield_correct`` with measured
+    flat / dark images)."""
+    raise NotImplementedError("basic_correct needs the basicpy package; use shading_correct or flatfield_correct")
+
+
+@registry.component("shading_correct")
+def shading_correct(xp, get_darkfield=True, smoothness_flatfield=1.0, smoothness_darkfield=1.0, timepoints=(0,),
+                    working_size=128):
+    """A BaSiC flat- / dark-field fit per channel on every tile of the listed timepoints (time 0 by default, as the
+    reference's basic_correct, preprocess.py:91-115), applied lazily to every timepoint: ``stitch`` fuses the apply
+    with its crop/concat.  Adds no dataset variables."""
+    from . import shading
+
+    v = xp.data_vars["tile"].transpose(*DESIRED_ORDER)
+    raw = v.raw
+    tiles = raw.materialize() if hasattr(raw, "materialize") else to_device(raw)
+    tiles = tiles.contiguous()
+    c, t, nr, nc, ty, tx = tiles.shape
+    times = [int(i) for i in np.atleast_1d(np.asarray(timepoints))]
+    if not times or any(i < -t or i >= t for i in times):
+        raise ValueError(f"timepoints {list(times)} outside the {t} timepoints of the tiles")
+    flats, darks = [], []
+    for ch in range(c):
+        train = torch.stack([tiles[ch, i] for i in times])  # (slices: index kernels lack uint16)
+        model = shading.fit(train, get_darkfield=get_darkfield, smoothness_flatfield=smoothness_flatfield,
+                            smoothness_darkfield=smoothness_darkfield, working_size=working_size)
+        flats.append(model.flatfield)
+        darks.append(model.darkfield)
+    xp.data_vars["tile"] = DataArray(shading.LazyShading(tiles, torch.stack(flats), torch.stack(darks)),
+                                     DESIRED_ORDER, name="tile")
+    return xp

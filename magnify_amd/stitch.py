@@ -4,7 +4,7 @@ the crop/concat, fused with a pending flat-field correction and with the per-pla
 ``to_uint8`` needs later."""
 from __future__ import annotations
 
-from . import hotpath, preprocess, registry
+from . import hotpath, preprocess, registry, shading
 from .xr_lite import DataArray
 
 
@@ -23,6 +23,13 @@ class Stitcher:
                              f"({sizes['tile_y']}x{sizes['tile_x']}).")
         tile = assay.data_vars["tile"].transpose("channel", "time", "tile_row", "tile_col", "tile_y", "tile_x")
         raw = tile.raw
+        if isinstance(raw, shading.LazyShading):
+            # a fitted shading model: its apply fused with the crop/concat, one launch for all channels (also for one
+            # tile without overlap -- the shortcut below would skip the correction)
+            image, minmax = shading.apply_stitch(raw.tiles, self.overlap, raw.flatfield, raw.darkfield)
+            assay["image"] = DataArray(image, ("channel", "time", "im_y", "im_x"))
+            assay._cache["image_minmax"] = (image.data_ptr(), minmax)
+            return assay
         lazy = isinstance(raw, preprocess.LazyFlatfield)
         if self.overlap == 0 and sizes["tile_row"] == 1 and sizes["tile_col"] == 1 and (not lazy or raw.max2 is None):
             # One tile, nothing to crop and (integer pixels, flat 1, dark 0: LazyFlatfield.max2 is None) nothing to
