@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import math
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -325,6 +326,17 @@ class CircleFinder:
     # a caller whose launch sequences never repeat pays at most ~0.15 ms a call for trying; one whose hints drift over a
     # long run keeps getting graphs)
     MAX_CAPTURES = 12
+    # The status block: every per-plane counter the host ever looks at is a row of it -- one fill clears it, one copy fetches
+    # it.  Eight counters (ROW_UNRESOLVED: "thresholds still need a window pass" in the low byte, the window passes the plane
+    # needed above it), then `changed` per hysteresis sweep and `undecided` per suppression round of a group of launches.
+    (ROW_EDGES, ROW_EDGE_TOTALS, ROW_UNRESOLVED, ROW_ALIVE, ROW_OUT, ROW_SCORED, ROW_SURV, ROW_CIRCLES) = range(8)
+    ROW_CHANGED, ROW_UNDECIDED, STATUS_ROWS = 8, 8 + MAX_GROUP, 8 + 2 * MAX_GROUP
+    # what an optimistic call launches without looking (_plan): window passes, hysteresis sweeps, suppression rounds
+    Plan = namedtuple("Plan", "win sweeps rounds")
+    # the arguments of one `find` call that the chain needs
+    Request = namedtuple("Request", "planes minmax low_q high_q min_roundness min_dist seeds keep_raw keep_u8 passthrough_u8")
+    # host-side state that the eager launches of a chain leave behind and a graph replay restores (_capture_chain)
+    REPLAY_STATE = ("_last_layer", "coord_cap", "u8", "raw", "_tie_keys", "_quantiles", "_gammas")
 
     def __init__(self, n_planes, h, w, min_radius, max_radius, num_iter, device="cuda", grid_length=GRID_LENGTH):
         require_gpu()
@@ -347,39 +359,45 @@ class CircleFinder:
         self.hist_scratch = torch.empty((int(nat.lib().mg_blur_hist_scratch_words(P, h, w)),), dtype=i32, device=dev)
         self.thresh = torch.zeros((P, 2), dtype=i32, device=dev)
         self.quant_d = torch.zeros((P, 2), dtype=torch.float32, device=dev)  # np.quantile's two values per plane
-        # Every per-plane counter the host ever looks at lives in ONE block: one fill clears it, one copy fetches it
-        # (rows: the eight counters, then `changed` per hysteresis sweep, then `undecided` per suppression round).
         G = self.MAX_GROUP
-        self.status = torch.zeros((8 + 2 * G, P), dtype=i32, device=dev)
-        (self.num_edges, self.edge_totals, self.unresolved, self.num_alive, self.num_out, self.num_scored,
-         self.num_surv, self.num_circles) = (self.status[k] for k in range(8))
-        self.changed, self.undecided = self.status[8: 8 + G], self.status[8 + G: 8 + 2 * G]
-        self.status_host = torch.zeros((8 + 2 * G, P), dtype=i32).pin_memory()
-        self._quantiles = None
+        self.status = torch.zeros((self.STATUS_ROWS, P), dtype=i32, device=dev)  # rows: ROW_* above
+        st = self.status
+        self.num_edges, self.edge_totals, self.unresolved = st[self.ROW_EDGES], st[self.ROW_EDGE_TOTALS], st[self.ROW_UNRESOLVED]
+        self.num_alive, self.num_out, self.num_scored = st[self.ROW_ALIVE], st[self.ROW_OUT], st[self.ROW_SCORED]
+        self.num_surv, self.num_circles = st[self.ROW_SURV], st[self.ROW_CIRCLES]
+        self.scoring_counters = st[self.ROW_ALIVE: self.ROW_SURV + 1]  # num_alive, num_out, num_scored, num_surv
+        self.changed, self.undecided = st[self.ROW_CHANGED: self.ROW_CHANGED + G], st[self.ROW_UNDECIDED: self.ROW_UNDECIDED + G]
+        self.status_host = torch.zeros((self.STATUS_ROWS, P), dtype=i32).pin_memory()
+        self._side = self._cap_stream = None  # streams, made on first use: of copies beside the caller's work, of captures
+        # of the last call: host copy of quant_d (made on demand), np.quantile's two weights, the uint8 planes (keep_u8)
+        self._quantiles = self._gammas = self.u8 = None
         # window passes of the threshold search (ranks inside coarse histogram bins), all on the device: per-plane state
         # block, the base of the next pass, the window histogram (allocated when a shape first needs a pass)
         self.win_state = torch.zeros((P, 16), dtype=i32, device=dev)
         self.hist_win = None
-        self._recent_win = []
+        self._recent_win = []  # window passes the last calls needed (as _recent_sweeps below)
         tx, ty = nat.C.c_int(0), nat.C.c_int(0)
         nat.check(nat.lib().mg_hysteresis_tiles(h, w, nat.C.byref(tx), nat.C.byref(ty)), "mg_hysteresis_tiles")
         # active-tile flags of the hysteresis sweeps, one layer per sweep of a group (+ the last layer of the group before)
         self.tile_flags = torch.zeros((G + 1, P, ty.value, tx.value), dtype=u8, device=dev)
+        self._last_layer = None  # the layer the last group of sweeps left its flags in = sweeps of that group (_sweeps)
         self.scan_state = torch.zeros((max(1, int(nat.lib().mg_edge_grid_scan_words(P, h, w, self.grid))),),
                                       dtype=torch.int64, device=dev)
         # Optimistic chain (see find): sweeps / rounds / capacities taken from the calls before, everything checked
         # at the one host round trip at the end.  MG_CHECKED_CHAIN=1 keeps the three-round-trip chain.
         self.optimistic = not os.environ.get("MG_CHECKED_CHAIN")
-        self._recent_sweeps, self._recent_rounds = [], []
+        self._recent_sweeps, self._recent_rounds = [], []  # what the last four calls needed (_note): the hints
         # how the calls of this finder went (find); followed_again: optimistic calls whose follow-up pass ran twice
         self.calls = {"optimistic": 0, "repaired": 0, "checked": 0, "followed_again": 0}
         self._out_sets, self._out_turn, self._out_cap = [None, None], 0, 0
         self._n_collects, self.follow_result = 0, None
+        # of the last call: circles per plane on the host (_nms_finish), event "the ordered tables are written" (_collect)
+        self._out_counts = self._results_ready = None
         # hipGraphs of the optimistic chain (_optimistic_chain), by launch-sequence key
         self._graphs = None if os.environ.get("MG_NO_GRAPH") else {}
         self.graph_replays, self.graph_captures = 0, 0
         self._graph_seen, self._in_stage, self._retired_graphs = set(), None, []
-        self._round_spare = 0
+        self._round_spare = 0  # spare suppression rounds of this call's plan (find)
         self._mm = torch.empty((P, 2), dtype=torch.float64, device=dev)
         self.words = 2 * ((h * w + 63) // 64) + 2  # bitmap words per plane (even, one spare)
         self.edge_bits = torch.zeros((P, self.words), dtype=i32, device=dev)  # strong bits = edges
@@ -389,7 +407,8 @@ class CircleFinder:
         self.keep_debug_maps = False  # True: also produce the {0,1} byte map and the angle map (tests)
         self.cell_counts = torch.zeros((P, self.n_cells), dtype=i32, device=dev)
         self.cell_starts = torch.zeros((P, self.n_cells), dtype=i32, device=dev)
-        self.coords = None
+        # edge coordinate lists (P, coord_cap, 2), sized by the checked chain; edges per plane of the last call on the host
+        self.coords = self.coord_cap = self.n_edges_host = None
         ntr, ntc, self.n_layers, self.bitmap_words = nat.dedup_layout(h, w, self.min_r, self.max_r)
         self.n_tiles = ntr * ntc
         self.bitmap = self.layer_offsets = None  # only the atomicOr path needs them (allocated on first use)
@@ -422,7 +441,9 @@ class CircleFinder:
             self.pair_table = torch.from_numpy(nat.score_pair_table().view(np.int64)).to(dev)
             self.layer_starts = torch.zeros((P, self.n_tiles, self.max_r - self.min_r + 2), dtype=i32, device=dev)
             self.surv_list = torch.empty((P, self.cap, 2), dtype=i32, device=dev)  # (list index, key) per survivor
-        self.nms_grid = None
+        self.nms_grid = None  # claim grid of the suppression rounds, sized for a min_dist (_nms_prepare)
+        # ring of _nms_dist, its difference bitmap (mg_nms_sparse) and the planes that kernel decided, made with the grid
+        self._nms_dist = self._nms_ring = self._nms_dbits = self.nms_done = None
         self.seeds = torch.zeros((P,), dtype=torch.int64, device=dev)
         self.seeds_host = torch.zeros((P,), dtype=torch.int64).pin_memory()
         self.raw = None
@@ -430,20 +451,41 @@ class CircleFinder:
 
     # -- host <-> device bookkeeping ---------------------------------------------------------------
     def _fetch_status(self, after=None):
-        """The status block on the host (one pinned copy + a stream sync): rows as laid out in __init__.
+        """The status block on the host (one pinned copy + a stream sync): rows ROW_*.
         ``after`` (an event): the copy runs on a side stream that only waits for that event -- not for what the caller
         has queued behind it (the ROI pass of `follow`)."""
         if after is None:
             self.status_host.copy_(self.status, non_blocking=True)
             torch.cuda.current_stream().synchronize()
             return self.status_host.numpy()
-        if getattr(self, "_side", None) is None:
+        side = self._side_stream(after)
+        with torch.cuda.stream(side):
+            self.status_host.copy_(self.status, non_blocking=True)
+        side.synchronize()
+        return self.status_host.numpy()
+
+    def _side_stream(self, after):
+        """The finder's side stream, made to wait for the event ``after`` and for nothing else the caller has queued."""
+        if self._side is None:
             self._side = torch.cuda.Stream(device=self.dev)
         self._side.wait_event(after)
-        with torch.cuda.stream(self._side):
-            self.status_host.copy_(self.status, non_blocking=True)
-        self._side.synchronize()
-        return self.status_host.numpy()
+        return self._side
+
+    # what a fetched status block ``st`` says
+    @classmethod
+    def _any_unresolved(cls, st):  # some plane's thresholds still need a window pass
+        return bool((st[cls.ROW_UNRESOLVED] & 0xFF).any())
+
+    @classmethod
+    def _win_needed(cls, st):  # window passes the planes needed
+        return int(st[cls.ROW_UNRESOLVED].max()) >> 8
+
+    @staticmethod
+    def _launches_needed(st, first_row, group):
+        """Of ``group`` launches that counted in the rows from ``first_row`` (sweeps: what changed; rounds: what stayed
+        undecided): up to and including the first one that left nothing; None if the last one left something."""
+        per_launch = st[first_row: first_row + group].sum(axis=1)
+        return int(np.argmax(per_launch == 0)) + 1 if per_launch[group - 1] == 0 else None
 
     @staticmethod
     def _hint(recent, floor, spare=1):
@@ -456,12 +498,26 @@ class CircleFinder:
         recent.append(int(needed))
         del recent[:-4]
 
+    def _plan(self, min_dist=0):
+        """The launch counts of a call from the hints: the one place that computes them.  The rounds get _round_spare
+        on top (a missing round is cheap to add -- unless a follow-up pass has been queued on the tables: find)."""
+        rounds = min(self._hint(self._recent_rounds, 2, spare=self._round_spare), self.MAX_GROUP) if min_dist > 0 else 0
+        return self.Plan(max(self._recent_win) if self._recent_win else 0,
+                         min(self._hint(self._recent_sweeps, 2), self.MAX_GROUP), rounds)
+
+    def _stage_seeds(self, seeds):
+        """The seeds of this call into the pinned block that the (eager or captured) upload reads."""
+        self.seeds_host.numpy()[:] = np.asarray(seeds, dtype=np.uint64).reshape(self.P).view(np.int64)
+
     # -- stage 1: to_uint8 + blur + Scharr/quantiles + Canny + hysteresis + edge grid --------
     def edge_stage(self, planes: torch.Tensor, minmax, low_q: float, high_q: float, keep_u8=False,
-                   passthrough_u8=False, optimistic=False):
+                   passthrough_u8=False, optimistic=False, *, plan=None):
         """``optimistic``: nothing comes back to the host -- the sweeps and the coordinate capacity are those of the
-        calls before and the caller (find) checks convergence / overflow when it fetches the status block."""
-        L, P, h, w, s = nat.lib(), self.P, self.h, self.w, _stream()
+        calls before and the caller (find) checks convergence / overflow when it fetches the status block.
+        ``plan``: the launch counts (none: made here from the hints)."""
+        P, h, w, s = self.P, self.h, self.w, _stream()
+        if plan is None:
+            plan = self._plan()
         assert tuple(planes.shape) == (P, h, w)
         if planes.stride(2) != 1:
             planes = planes.contiguous()
@@ -491,25 +547,25 @@ class CircleFinder:
               self.thresh.data_ptr(), self.quant_d.data_ptr(), self.unresolved.data_ptr(), self.win_state.data_ptr(),
               self.hist_base.data_ptr(), s)
         self._quantiles = None
-        n_win = max(self._recent_win) if self._recent_win else 0
+        n_win = plan.win
         for k in range(n_win):
             self._window_pass(k)
         self.stats["hist_passes"] = 1 + n_win
         if optimistic:
             self._canny()
-            self._sweeps(0, min(self._hint(self._recent_sweeps, 2), self.MAX_GROUP))
+            self._sweeps(0, plan.sweeps)
             self._edge_grid(3)
             n_edges = None
         else:
-            n_edges, sweeps, needed, unresolved = self._edges_from_thresholds()
+            n_edges, sweeps, needed, unresolved = self._edges_from_thresholds(plan.sweeps)
             if unresolved:  # more window passes than launched: one at a time until every plane is resolved, then again
                 while unresolved:
                     self._window_pass(n_win)
                     n_win += 1
-                    unresolved = bool((self._fetch_status()[2] & 0xFF).any())
+                    unresolved = self._any_unresolved(self._fetch_status())
                 self.stats["hist_passes"] = 1 + n_win
-                n_edges, sweeps, needed, _ = self._edges_from_thresholds()
-            self._note(self._recent_win, int(self.status_host.numpy()[2].max()) >> 8)  # what the planes needed
+                n_edges, sweeps, needed, _ = self._edges_from_thresholds(plan.sweeps)
+            self._note(self._recent_win, self._win_needed(self.status_host.numpy()))
             self.stats["hysteresis_sweeps"] = sweeps
             self._note(self._recent_sweeps, needed)
             need_cap = max(1, int(n_edges.max()))
@@ -571,14 +627,13 @@ class CircleFinder:
               self.win_state.data_ptr(), self.hist_base.data_ptr(), self.thresh.data_ptr(), self.quant_d.data_ptr(),
               self.unresolved.data_ptr(), _stream(), stage="mg_edge_thresholds")
 
-    def _edges_from_thresholds(self):
+    def _edges_from_thresholds(self, group):
         """Canny NMS + hysteresis to convergence + the cell counts of the edge grid, from self.thresh.
         Returns (n_edges per plane, sweeps run, sweeps needed, any plane whose thresholds still need window passes)."""
         self._canny()
-        sweeps, unresolved, needed = 0, False, 0
-        # sweeps per host check: first as many as the calls before needed (a sweep after convergence only
+        sweeps = 0
+        # sweeps per host check: first ``group``, as many as the calls before needed (a sweep after convergence only
         # runs the tile-flag test), then two at a time -- one host round trip in the steady state
-        group = min(self._hint(self._recent_sweeps, 2), self.MAX_GROUP)
         while True:
             self.changed[:group].zero_()
             self._sweeps(sweeps, group)
@@ -587,17 +642,12 @@ class CircleFinder:
             # (they are recomputed in the rare case that more sweeps are needed)
             self._edge_grid(1)
             st = self._fetch_status()
-            per_sweep, n_edges = st[8: 8 + group].sum(axis=1), st[0].copy()
-            unresolved = bool((st[2] & 0xFF).any())
-            if unresolved:  # these edges come from invalid thresholds: the caller redoes them
-                needed = sweeps
-                break
-            if per_sweep[group - 1] == 0:
-                # sweeps this image needed = up to and including the first one that changed nothing
-                needed = sweeps - group + int(np.argmax(per_sweep == 0)) + 1
-                break
+            n_edges, of_group = st[self.ROW_EDGES].copy(), self._launches_needed(st, self.ROW_CHANGED, group)
+            if self._any_unresolved(st):  # these edges come from invalid thresholds: the caller redoes them
+                return n_edges, sweeps, sweeps, True
+            if of_group is not None:
+                return n_edges, sweeps, sweeps - group + of_group, False
             group = 2
-        return n_edges, sweeps, needed, unresolved
 
     @property
     def quantiles(self):
@@ -614,8 +664,8 @@ class CircleFinder:
     # -- stage 2: candidates -> unique integer circles -> scores ------------------------------
     def circle_stage(self, seeds, min_roundness: float, keep_raw=False, dedup_centres=False, counters_clear=False):
         """``counters_clear``: the caller has just cleared the whole status block (find's optimistic chain)."""
-        L, P, h, w, s = nat.lib(), self.P, self.h, self.w, _stream()
-        self.seeds_host.numpy()[:] = np.asarray(seeds, dtype=np.uint64).reshape(P).view(np.int64)
+        P, h, w, s = self.P, self.h, self.w, _stream()
+        self._stage_seeds(seeds)
         self.seeds.copy_(self.seeds_host, non_blocking=True)  # pinned: queued on the stream, the host does not wait
         self.raw = torch.empty((P, self.num_iter, 3), dtype=torch.float32, device=self.dev) if keep_raw else None
         if self.keyed:
@@ -641,7 +691,7 @@ class CircleFinder:
                   self.layer_offsets.data_ptr(), self.circles.data_ptr(), self.cap,
                   self.num_circles.data_ptr(), s)
         if not counters_clear:
-            self.status[3:7].zero_()  # num_alive, num_out, num_scored, num_surv
+            self.scoring_counters.zero_()
         self.max_rc.fill_(-(2**31))
         if self.keyed_score and self._tie_keys is not None:
             _call("mg_score_circles_keyed", self.blur.data_ptr(), 0, self.edge_bits.data_ptr(), self.class_bits.data_ptr(),
@@ -683,14 +733,12 @@ class CircleFinder:
     def _drop_graphs(self):
         """Forget every captured chain: a buffer its launches have baked in was made anew."""
         if self._graphs:
-            if os.environ.get("MG_GRAPH_DESTROY"):
-                self._graphs.clear()
-            else:
+            if not os.environ.get("MG_GRAPH_DESTROY"):
                 # the forgotten graphs are kept alive until the finder goes (a handful over a finder's life: buffers
                 # regrow rarely): destroying a hipGraphExec between a replay and the next capture aborted the process
                 # on ROCm 7.2
                 self._retired_graphs.extend(self._graphs.values())
-                self._graphs.clear()
+            self._graphs.clear()
         self._graph_seen.clear()
 
     def _collect(self, bufs, min_dist, cleared=False):
@@ -714,11 +762,11 @@ class CircleFinder:
             self.nms_grid.fill_(-1)  # once: every call restores the cells it touched (mg_nms_cleanup)
             self.state.zero_()
             self._drop_graphs()
-        if getattr(self, "_nms_dist", None) != min_dist:
+        if self._nms_dist != min_dist:
             ring = nat.circle_points(min_dist, True)
             self._nms_ring = torch.from_numpy(ring).to(self.dev)
             self._nms_dbits = torch.from_numpy(_ring_difference_bits(ring, min_dist)).to(self.dev)
-            if getattr(self, "nms_done", None) is None:
+            if self.nms_done is None:
                 self.nms_done = torch.zeros((self.P,), dtype=torch.int32, device=self.dev)
             self._nms_dist = min_dist
             self._drop_graphs()
@@ -757,22 +805,22 @@ class CircleFinder:
               self._nms_ring.shape[0], self.nms_grid.data_ptr(), self.nms_grid.shape[1], self.state.data_ptr(),
               out_cap, self.nms_done.data_ptr() if self._sparse_nms() else 0, _stream())
 
-    def nms_stage(self, min_dist: int, optimistic=False, bufs=None, cleared=False):
+    def nms_stage(self, min_dist: int, optimistic=False, bufs=None, cleared=False, *, plan=None):
         """Checked chain: the alive counts come to the host first (they size the output), the rounds are checked for
-        convergence afterwards.  ``optimistic``: output capacity and rounds from the calls before; the caller's (find's)
-        single status fetch follows -- returns (buffers, rounds launched) and leaves the checks to ``_nms_finish``."""
+        convergence afterwards.  ``optimistic``: output capacity and rounds (``plan``; none: made here from the hints)
+        from the calls before; the caller's (find's) single status fetch follows -- returns (buffers, rounds launched)
+        and leaves the checks to ``_nms_finish``."""
         if optimistic:
             if bufs is None:
                 bufs = self._out_buffers(self._out_cap)
-            rounds = 0
+            if plan is None:
+                plan = self._plan(min_dist)
             if min_dist > 0:
                 self._nms_prepare(min_dist)
-                # (a missing round is cheap to add -- unless a follow-up pass has been queued on the tables: _round_spare)
-                rounds = min(self._hint(self._recent_rounds, 2, spare=self._round_spare), self.MAX_GROUP)
-                self._nms_rounds(min_dist, True, rounds, bufs[0].shape[1], cleared=cleared)
+                self._nms_rounds(min_dist, True, plan.rounds, bufs[0].shape[1], cleared=cleared)
             self._collect(bufs, min_dist, cleared=cleared)
-            return bufs, rounds
-        n_alive = self._fetch_status()[3]
+            return bufs, plan.rounds
+        n_alive = self._fetch_status()[self.ROW_ALIVE]
         bufs = self._out_buffers(max(1, int(n_alive.max())))
         return self._nms_finish(min_dist, bufs, 0, int(n_alive.max()), None)
 
@@ -786,9 +834,9 @@ class CircleFinder:
             group = rounds
             while True:
                 if st is not None:
-                    per_round = st[8 + self.MAX_GROUP: 8 + self.MAX_GROUP + group].sum(axis=1)
-                    if per_round[group - 1] == 0:
-                        self._note(self._recent_rounds, rounds - group + int(np.argmax(per_round == 0)) + 1)
+                    of_group = self._launches_needed(st, self.ROW_UNDECIDED, group)
+                    if of_group is not None:
+                        self._note(self._recent_rounds, rounds - group + of_group)
                         break
                     if rounds > 10000:
                         raise RuntimeError("greedy suppression did not converge")
@@ -802,7 +850,7 @@ class CircleFinder:
         elif st is None:
             self._collect(bufs, min_dist)
             st = self._fetch_status()
-        counts = st[4].copy()
+        counts = st[self.ROW_OUT].copy()
         self.stats["nms_rounds"] = rounds
         if rounds or launched:
             self._nms_cleanup(min_dist, out_cap)
@@ -810,40 +858,55 @@ class CircleFinder:
         return bufs[0], bufs[1], self.num_out
 
     # -- the optimistic chain, eager or as a hipGraph -----------------------------------------------------------
-    def _launch_chain(self, planes, minmax, low_q, high_q, min_roundness, min_dist, seeds, keep_raw, keep_u8, passthrough_u8,
-                      bufs=None):
-        """Everything between the inputs and the status fetch, launched without looking: returns (output buffers,
-        suppression rounds launched).  ``bufs``: the ordered output goes there instead of into the next public set."""
+    def _launch_chain(self, req, plan, bufs=None):
+        """Everything between the inputs and the status fetch, launched without looking, as ``plan`` says: returns the
+        output buffers.  ``bufs``: the ordered output goes there instead of into the next public set."""
         self.status.zero_()
-        self.edge_stage(planes, minmax, low_q, high_q, keep_u8=keep_u8, passthrough_u8=passthrough_u8, optimistic=True)
-        self.circle_stage(seeds, min_roundness, keep_raw=keep_raw, dedup_centres=min_dist > 0, counters_clear=True)
-        return self.nms_stage(min_dist, optimistic=True, bufs=bufs, cleared=True)  # (status.zero_() above)
+        self.edge_stage(req.planes, req.minmax, req.low_q, req.high_q, keep_u8=req.keep_u8,
+                        passthrough_u8=req.passthrough_u8, optimistic=True, plan=plan)
+        self.circle_stage(req.seeds, req.min_roundness, keep_raw=req.keep_raw, dedup_centres=req.min_dist > 0,
+                          counters_clear=True)
+        return self.nms_stage(req.min_dist, optimistic=True, bufs=bufs, cleared=True, plan=plan)[0]  # (status.zero_() above)
 
-    def _optimistic_chain(self, planes, minmax, low_q, high_q, min_roundness, min_dist, seeds, keep_raw, keep_u8,
-                          passthrough_u8, stable_input=False):
-        """The chain as ONE hipGraph launch: the ~40 kernel launches / clears of a call are a fixed sequence as long as
-        the inputs sit at the same addresses and the hints (window passes, sweeps, rounds, list and output capacities)
-        have not moved, for each of the two output sets used in turn -- all of that is the graph's key (up to 16 graphs are
-        kept).  What changes from call to call
-        travels through fixed buffers: the per-plane min / max (copied into the finder's own block before the launch),
-        the seeds (the pinned block the captured upload reads) and, for small inputs (<= 32 MB: the chip's 784 chamber windows, gathered afresh every call), the
-        planes themselves (copied into the finder's own input block).  A sequence is captured the first time it shows
-        when the input is the finder's block or the caller vouches for its buffer (``stable_input``), else the second
-        time (a capture costs ~9 ms: not to be spent on addresses that never come back).  A single plane from a caller
-        that does not vouch for its buffer is launched eagerly (measured through mg.beads: C2 1.06 ms eager, 1.07 replayed,
-        C3 3.83 / 3.90;
-        a one-timepoint StackProcessor shard, which does: 1.31 eager, 1.17 replayed).  Per-stage timing (a
-        StageTimer without allow_graphs), debug maps and the raw / uint8 side outputs need the eager launches.
-        MG_NO_GRAPH=1 turns the graphs off."""
-        usable = (self._graphs is not None and (self.P >= 2 or stable_input) and (TIMER is _NO_TIMER or getattr(TIMER, "allow_graphs", False))
-                  and not (keep_raw or keep_u8 or self.keep_debug_maps)
+    def _graph_key(self, req, plan, bufs):
+        """EVERY buffer whose address or size is baked into the captured kernel arguments and that may be made anew
+        between two calls belongs to the key (the caching allocator can hand a regrown output set the
+        address of a dropped one -- a graph captured for the old capacity would then gather with the old stride):
+        the three tensors of the output set and its capacity, the coordinate list, the claim grid and ring, the
+        window histogram; and the switches that select other kernels."""
+        planes, grid = req.planes, self.nms_grid
+        return (planes.data_ptr(), planes.stride(0), planes.stride(1), planes.dtype, req.passthrough_u8, float(req.low_q),
+                float(req.high_q), float(req.min_roundness), int(req.min_dist), plan.win, plan.sweeps, plan.rounds,
+                self.coords.data_ptr(), self.coords.shape[1],
+                bufs[0].data_ptr(), bufs[0].shape[1], bufs[1].data_ptr(), bufs[2].data_ptr(),
+                grid.data_ptr() if grid is not None else 0, grid.shape[1] if grid is not None else 0,
+                self._nms_ring.data_ptr() if req.min_dist > 0 and self._nms_ring is not None else 0,
+                self.hist_win.data_ptr() if self.hist_win is not None else 0, bool(self.keyed), bool(self.keyed_score))
+
+    def _optimistic_chain(self, req, plan, stable_input=False):
+        """The chain as ONE hipGraph launch where it can be: the ~40 kernel launches / clears of a call are a fixed sequence.
+        Key (_graph_key): where and how the inputs lie, the parameters, the plan, every buffer the launches bake in -- among
+        them the output set: two are used in turn, so a graph per set -- and the kernel switches; up to 16 graphs are kept.
+        Through fixed buffers travels what changes from call to call: the per-plane min / max (copied into the finder's own
+        block before the launch), the seeds (the pinned block the captured upload reads) and, for small inputs (<= 32 MB: the
+        chip's 784 chamber windows, gathered afresh every call), the planes themselves (copied into the finder's own input
+        block).  Captured is a sequence the first time it shows when the input is the finder's block or the caller vouches
+        for its buffer (``stable_input``), else the second time (a capture costs ~9 ms: not to be spent on addresses that
+        never come back) -- once nothing is left to allocate or upload, and within MAX_CAPTURES.  Eager launches: with
+        MG_NO_GRAPH=1; for per-stage timing (a StageTimer without allow_graphs), debug maps, the angle map and the raw /
+        uint8 side outputs; for rows that are not contiguous; for a single plane from a caller that does not vouch for its
+        buffer (measured through mg.beads: C2 1.06 ms eager, 1.07 replayed, C3 3.83 / 3.90; a one-timepoint StackProcessor
+        shard, which does: 1.31 eager, 1.17 replayed).  Returns the output buffers; ``plan.rounds`` rounds were launched."""
+        planes, minmax, min_dist = req.planes, req.minmax, req.min_dist
+        usable = (self._graphs is not None and (self.P >= 2 or stable_input)
+                  and (TIMER is _NO_TIMER or getattr(TIMER, "allow_graphs", False))
+                  and not (req.keep_raw or req.keep_u8 or self.keep_debug_maps)
                   and not self.need_angle_map() and planes.stride(2) == 1)
         if not usable:
             if minmax is not None:
-                minmax = minmax.contiguous()
-            return self._launch_chain(planes, minmax, low_q, high_q, min_roundness, min_dist, seeds, keep_raw, keep_u8,
-                                      passthrough_u8)
-        if minmax is None and not passthrough_u8:
+                req = req._replace(minmax=minmax.contiguous())
+            return self._launch_chain(req, plan)
+        if minmax is None and not req.passthrough_u8:
             minmax = plane_minmax(planes)
         if minmax is not None:
             # (stream-ordered: the values are read by the launch behind it; a strided view -- one channel's rows of a
@@ -855,26 +918,13 @@ class CircleFinder:
                 self._in_stage = torch.empty((self.P, self.h, self.w), dtype=planes.dtype, device=self.dev)
             self._in_stage.copy_(planes)
             planes, stable_input = self._in_stage, True
-        win = max(self._recent_win) if self._recent_win else 0
-        sweeps = min(self._hint(self._recent_sweeps, 2), self.MAX_GROUP)
-        rounds = min(self._hint(self._recent_rounds, 2, spare=self._round_spare), self.MAX_GROUP) if min_dist > 0 else 0
+        req = req._replace(planes=planes, minmax=minmax)
         # the ordered output goes straight into the public set whose turn it is (two sets used in turn: a graph per
         # set -- twice the captures, once; a set of the graph's own cost two copies per call)
         bufs = self._out_buffers(self._out_cap)
-        ready = ((self.nms_grid is not None or min_dist <= 0) and (self.hist_win is not None or win == 0)
-                 and (min_dist <= 0 or getattr(self, "_nms_dist", None) == min_dist))  # nothing left to allocate / upload
-        # EVERY buffer whose address or size is baked into the captured kernel arguments and that may be made anew
-        # between two calls belongs to the key (the caching allocator can hand a regrown output set the
-        # address of a dropped one -- a graph captured for the old capacity would then gather with the old stride):
-        # the three tensors of the output set and its capacity, the coordinate list, the claim grid and ring, the
-        # window histogram; and the switches that select other kernels.
-        key = (planes.data_ptr(), planes.stride(0), planes.stride(1), planes.dtype, passthrough_u8, float(low_q), float(high_q),
-               float(min_roundness), int(min_dist), win, sweeps, rounds, self.coords.data_ptr(), self.coords.shape[1],
-               bufs[0].data_ptr(), bufs[0].shape[1], bufs[1].data_ptr(), bufs[2].data_ptr(),
-               self.nms_grid.data_ptr() if self.nms_grid is not None else 0,
-               self.nms_grid.shape[1] if self.nms_grid is not None else 0,
-               self._nms_ring.data_ptr() if min_dist > 0 and getattr(self, "_nms_ring", None) is not None else 0,
-               self.hist_win.data_ptr() if self.hist_win is not None else 0, bool(self.keyed), bool(self.keyed_score))
+        ready = ((self.nms_grid is not None or min_dist <= 0) and (self.hist_win is not None or plan.win == 0)
+                 and (min_dist <= 0 or self._nms_dist == min_dist))  # nothing left to allocate / upload
+        key = self._graph_key(req, plan, bufs)
         entry = self._graphs.get(key)
         if entry is None and ready and self.graph_captures < self.MAX_CAPTURES + self.calls["optimistic"] // 64:
             # (hints that drift -- one sweep more or less -- add a few graphs; a caller whose sequences never repeat stops
@@ -884,26 +934,23 @@ class CircleFinder:
                 self._graph_seen.clear()
             self._graph_seen.add(key)
             if seen:
-                entry = self._capture_chain(key, planes, minmax, low_q, high_q, min_roundness, min_dist, seeds, passthrough_u8,
-                                            bufs)
+                entry = self._capture_chain(key, req, plan, bufs)
                 if self._graphs is None:
                     entry = None
         if entry is None:
-            return self._launch_chain(planes, minmax, low_q, high_q, min_roundness, min_dist, seeds, keep_raw, keep_u8,
-                                      passthrough_u8, bufs=bufs)
-        self.seeds_host.numpy()[:] = np.asarray(seeds, dtype=np.uint64).reshape(self.P).view(np.int64)
+            return self._launch_chain(req, plan, bufs=bufs)
+        self._stage_seeds(req.seeds)
         entry["graph"].replay()
         # the host-side state the eager launches would have left behind
-        for name, value in entry["state"].items():
-            setattr(self, name, value)
+        vars(self).update(entry["state"])
         self.stats.update(entry["stats"])
         self._n_collects += 1
         self._results_ready = torch.cuda.Event()
         self._results_ready.record()
         self.graph_replays += 1
-        return bufs, entry["rounds"]
+        return bufs
 
-    def _capture_chain(self, key, planes, minmax, low_q, high_q, min_roundness, min_dist, seeds, passthrough_u8, bufs):
+    def _capture_chain(self, key, req, plan, bufs):
         """Stream capture of _launch_chain (on a side stream; nothing runs); None if the capture fails -- the graphs
         of this finder are then off for good and the caller launches eagerly."""
         global _CAPTURING
@@ -912,7 +959,7 @@ class CircleFinder:
                 del self._graphs[old_key]
         self.graph_captures += 1
         main = torch.cuda.current_stream()
-        if getattr(self, "_cap_stream", None) is None:
+        if self._cap_stream is None:
             self._cap_stream = torch.cuda.Stream(device=self.dev)
         try:
             graph = torch.cuda.CUDAGraph()
@@ -925,8 +972,8 @@ class CircleFinder:
             with torch.cuda.stream(self._cap_stream):
                 graph.capture_begin(capture_error_mode="thread_local")
                 try:
-                    _, rounds = self._launch_chain(planes, minmax, low_q, high_q, min_roundness, min_dist, seeds, False,
-                                                   False, passthrough_u8, bufs=bufs)
+                    # (a request with side outputs never gets here: _optimistic_chain launches it eagerly)
+                    self._launch_chain(req, plan, bufs=bufs)
                 finally:
                     graph.capture_end()
             main.wait_stream(self._cap_stream)
@@ -940,9 +987,7 @@ class CircleFinder:
             return None
         finally:
             _CAPTURING = False
-        entry = {"graph": graph, "rounds": rounds,
-                 "state": {k: getattr(self, k) for k in ("_last_layer", "coord_cap", "u8", "raw", "_tie_keys", "_quantiles",
-                                                          "_gammas")},
+        entry = {"graph": graph, "state": {k: vars(self)[k] for k in self.REPLAY_STATE},
                  "stats": {k: self.stats[k] for k in ("hist_passes",) if k in self.stats}}
         self._graphs[key] = entry
         return entry
@@ -980,8 +1025,10 @@ class CircleFinder:
         # 20 steps) -- one spare round (~10 us when nothing is undecided) is launched instead
         self._round_spare = 1 if follow is not None else 0
         if opt:
-            bufs, rounds = self._optimistic_chain(planes, minmax, low_q, high_q, min_roundness, min_dist, seeds, keep_raw,
-                                                  keep_u8, passthrough_u8, stable_input)
+            req = self.Request(planes, minmax, low_q, high_q, min_roundness, min_dist, seeds, keep_raw, keep_u8,
+                               passthrough_u8)
+            plan = self._plan(min_dist)
+            bufs, rounds = self._optimistic_chain(req, plan, stable_input), plan.rounds
             followed = None
             if follow is not None:
                 chain_done = torch.cuda.Event()
@@ -992,16 +1039,15 @@ class CircleFinder:
             else:
                 st = self._fetch_status()
             sweeps = self._last_layer
-            per_sweep = st[8: 8 + sweeps].sum(axis=1)
-            edges_ok = (not (st[2] & 0xFF).any() and per_sweep[sweeps - 1] == 0
-                        and int(st[1].max()) <= self.coords.shape[1])
-            if edges_ok:
-                n_edges = st[0].copy()
+            sweeps_needed = self._launches_needed(st, self.ROW_CHANGED, sweeps)
+            list_fits = int(st[self.ROW_EDGE_TOTALS].max()) <= self.coords.shape[1]
+            if not self._any_unresolved(st) and sweeps_needed is not None and list_fits:
+                n_edges = st[self.ROW_EDGES].copy()
                 self.n_edges_host = n_edges
                 self.stats.update(hysteresis_sweeps=sweeps, optimistic=True)
-                self._note(self._recent_sweeps, int(np.argmax(per_sweep == 0)) + 1)
-                self._note(self._recent_win, int(st[2].max()) >> 8)
-                max_alive = int(st[3].max())
+                self._note(self._recent_sweeps, sweeps_needed)
+                self._note(self._recent_win, self._win_needed(st))
+                max_alive = int(st[self.ROW_ALIVE].max())
                 if max_alive > bufs[0].shape[1]:  # the ordered output did not fit: gather it again (the rounds hold)
                     bufs = self._out_buffers(max_alive)
                     self._collect(bufs, min_dist)
@@ -1012,7 +1058,7 @@ class CircleFinder:
                 self.calls["repaired"] += 1
                 if rounds:
                     self._nms_cleanup(min_dist, bufs[0].shape[1])
-                if int(st[1].max()) > self.coords.shape[1]:
+                if not list_fits:
                     self.coords = None  # sized again from the counts
                 opt = False
         self.calls["optimistic" if opt else "checked"] += 1
@@ -1038,12 +1084,10 @@ class CircleFinder:
         # only the filled prefix comes back (the full-capacity copies left the GPU idle for ~0.5 ms)
         mx = max(int(counts.max()) if self.P else 0, 1)
         if overlap:
-            if getattr(self, "_side", None) is None:
-                self._side = torch.cuda.Stream(device=self.dev)
-            self._side.wait_event(self._results_ready)
-            with torch.cuda.stream(self._side):
-                out.record_stream(self._side)
-                out_scores.record_stream(self._side)
+            side = self._side_stream(self._results_ready)
+            with torch.cuda.stream(side):
+                out.record_stream(side)
+                out_scores.record_stream(side)
                 out_h, sc_h = out[:, :mx].contiguous().cpu().numpy(), out_scores[:, :mx].contiguous().cpu().numpy()
         else:
             out_h, sc_h = out[:, :mx].contiguous().cpu().numpy(), out_scores[:, :mx].contiguous().cpu().numpy()
