@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
 import numpy as np
 
@@ -18,90 +19,45 @@ MG_U8, MG_U16, MG_F32, MG_F64 = 0, 1, 2, 3
 MG_NO_EDGE = 100.0
 MG_SCORE_SKIPPED = -2.0
 
-_p = C.c_void_p
-_i = C.c_int
-_l = C.c_int64
-_d = C.c_double
-_f = C.c_float
-
-# name -> argtypes, exactly the prototypes of include/magnify_hip.h
-PROTOTYPES = {
-    "mg_version": [],
-    "mg_circle_points": [_i, _i, _p, _i],
-    "mg_disk_halfwidths": [_i, _p],
-    "mg_cv_disk_halfwidths": [_i, _p],
-    "mg_perimeter_table": [_i, _i, _p, _p, _p, _i],
-    "mg_flatfield_max": [_p, _i, _l, _i, _i, _i, _d, _p, _i, _d, _p, _i, _p, _p, _l, _p],
-    "mg_flatfield_max_scratch_floats": [_i, _i, _i],
-    "mg_marker_table": [_p, _l, _p, _i, _i, _i, _p, _p, _i, _i, _i, _p, _p],
-    "mg_flatfield_bound": [_p, _i, _i, _i, _i, _p, _l, _p],
-    "mg_flatfield_is_identity": [_i, _d, _p, _d, _p],
-    "mg_flatfield_apply_stitch": [_p, _i, _l, _i, _i, _i, _i, _i, _i, _i, _d, _p, _i, _d, _p, _i, _p, _p, _p, _p],
-    "mg_shading_workspace_bytes": [_i, _i],
-    "mg_shading_offset": [_i, _i, _i],
-    "mg_shading_downsample": [_p, _i, _l, _i, _i, _i, _p, _p],
-    "mg_shading_prepare": [_p, _i, _i, _p],
-    "mg_shading_dct2": [_p, _i, _i, _p, _p, _i, _p],
-    "mg_shading_alm_begin": [_p, _i, _i, _i, _i, _d, _d, _d, _d, _d, _d, _p],
-    "mg_shading_alm_iterate": [_p, _i, _i, _i, _i, _p],
-    "mg_shading_reweight": [_p, _i, _i, _d, _p],
-    "mg_shading_upsample": [_p, _p, _i, _i, _i, _p, _p, _p, _p],
-    "mg_shading_apply_stitch": [_p, _i, _i, _l, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p],
-    "mg_plane_minmax": [_p, _i, _i, _l, _i, _i, _l, _p, _p],
-    "mg_to_uint8_blur": [_p, _i, _i, _l, _i, _i, _l, _p, _p, _p, _p],
-    "mg_scharr_hist": [_p, _i, _i, _i, _i, _p, _p, _p, _l, _p],
-    "mg_scharr_hist_scratch_words": [_i, _i, _i, _i],
-    "mg_to_uint8_blur_hist": [_p, _i, _i, _l, _i, _i, _l, _p, _p, _p, _p, _p, _l, _p],
-    "mg_blur_hist_scratch_words": [_i, _i, _i],
-    "mg_edge_thresholds": [_p, _i, _p, _f, _f, _p, _p, _p, _p, _p, _p],
-    "mg_edge_thresholds_window": [_p, _i, _i, _f, _f, _p, _p, _p, _p, _p, _p],
-    "mg_canny_nms": [_p, _i, _i, _i, _p, _p, _p, _p, _l, _p],
-    "mg_canny_hysteresis": [_p, _p, _l, _i, _i, _i, _p, _p, _p, _p],
-    "mg_unpack_bits": [_p, _l, _i, _l, _p, _p],
-    "mg_hysteresis_tiles": [_i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int)],
-    "mg_edge_grid_scan_words": [_i, _i, _i, _i],
-    "mg_edge_grid": [_p, _l, _i, _i, _i, _i, _p, _p, _p, _p, _l, _p, _p, _i, _p],
-    "mg_candidate_circles": [_p, _l, _p, _p, _p, _i, _i, _i, _i, _p, _l, _i, _i, _p, _l, _p, _p],
-    "mg_candidate_keys": [_p, _l, _p, _p, _p, _i, _i, _i, _i, _p, _l, _i, _i, _p, _p, _p],
-    "mg_keys_to_circles": [_p, _l, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _l, _p, _p, _p, _i, _p],
-    "mg_bitmap_to_circles": [_p, _l, _i, _i, _i, _i, _i, _p, _p, _l, _p, _p],
-    "mg_edge_angles": [_p, _i, _i, _i, _p, _l, _p, _p, _p],
-    "mg_dedup_layout": [_i, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
-    "mg_score_circles": [_p, _p, _p, _l, _i, _i, _i, _p, _l, _p, _p, _p, _i, _i, _p, _p, _p, _i, _f, _i, _i, _p, _p, _p, _p, _p, _p],
-    "mg_score_keyed_supported": [_i, _i],
-    "mg_score_pair_table": [_p, _i],
-    "mg_score_pairs": [_i, _p, _i],
-    "mg_score_circles_keyed": [_p, _p, _p, _p, _l, _i, _i, _i, _p, _l, _p, _p, _i, _i, _p, _p, _p, _i, _p, _f, _i,
-                               _p, _p, _p, _p, _p, _p, _l, _p, _i, _p],
-    "mg_nms_rounds": [_p, _l, _p, _p, _p, _p, _i, _i, _p, _i, _p, _l, _p, _p, _l, _i, _i, _p, _l, _p, _p],
-    "mg_nms_same_centre": [_p, _l, _p, _p, _p, _p, _i, _i, _p, _l, _p, _p, _l, _p, _p],
-    "mg_nms_sparse": [_p, _l, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p],
-    "mg_nms_sparse_max_dist": [],
-    "mg_collect_circles": [_p, _l, _p, _p, _p, _p, _i, _i, _p, _p, _l, _p, _p, _p, _i, _p],
-    "mg_circle_labels": [_p, _l, _p, _i, _i, _i, _p, _i, _p, _i, _p],
-    "mg_nms_cleanup": [_p, _l, _p, _p, _p, _p, _i, _i, _p, _i, _p, _l, _p, _l, _p, _p],
-    "mg_roi_gather_reduce": [_p, _i, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p],
-    "mg_roi_gather_reduce_batched": [_p, _i, _l, _i, _i, _i, _i, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p],
-    "mg_counts_to_offsets": [_p, _i, _i, _p, _p],
-    "mg_roi_segment_reduce": [_p, _i, _l, _i, _i, _i, _i, _i, _p, _l, _p, _i, _i, _p, _i, _p, _i, _p, _p, _p, _p, _p, _p],
-    "mg_roi_window_order": [_p, _l, _p, _i, _i, _p, _p],
-    "mg_roi_masked_median": [_p, _i, _p, _l, _l, _i, _i, _i, _i, _p, _p],
-    "mg_roi_masked_median_u16": [_p, _p, _i, _i, _i, _i, _p, _p],
-    "mg_cluster1d_costs": [_p, _i, _i, _i, _d, _p, _d, _p, _p],
-    "mg_button_masks": [_p, _p, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p],
-    "mg_stream_probe": [_p, _p, _l, _i, _p, _i, _p],
-    "mg_masked_sums": [_p, _i, _p, _p, _i, _i, _i, _p, _p, _p],
-    "mg_host_read_runs": [_p, _p, _p, _p, _i, _i, _p],
-    "mg_host_write_runs": [_p, _p, _p, _p, _i, _i, _p],
-}
-
-RETURNS_INT64 = {"mg_shading_workspace_bytes", "mg_shading_offset", "mg_scharr_hist_scratch_words", "mg_blur_hist_scratch_words", "mg_edge_grid_scan_words", "mg_flatfield_max_scratch_floats"}
-
-_lib = None
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "magnify_hip.h")
 
 
 class NativeLibraryMissing(RuntimeError):
     pass
+
+
+_CTYPES = {"int": C.c_int, "int64_t": C.c_int64, "double": C.c_double, "float": C.c_float}
+
+
+def _ctype(decl: str, what: str):
+    """ctypes type of one declared parameter or return type; every pointer is passed as an address."""
+    if "*" in decl:
+        return C.c_void_p
+    words = [w for w in decl.split() if w != "const"]
+    if not words or words[0] not in _CTYPES or len(words) > 2:
+        raise TypeError(f"{HEADER_PATH}: no ctypes mapping for `{decl.strip()}` in {what}")
+    return _CTYPES[words[0]]
+
+
+def _parse_header():
+    """(name -> argtypes, name -> restype) of every `int|int64_t mg_*(...);` declared in the header."""
+    if not os.path.exists(HEADER_PATH):
+        raise NativeLibraryMissing(f"{HEADER_PATH} not found: the ctypes binding is read from it.  "
+                                   "magnify_amd has no fallback table.")
+    with open(HEADER_PATH) as f:
+        text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", f.read(), flags=re.S)
+    argtypes, restypes = {}, {}
+    for ret, name, args in re.findall(r"\b(\w+)\s+(mg_\w+)\s*\(([^)]*)\)\s*;", text):
+        args = [] if args.strip() in ("", "void") else args.split(",")
+        argtypes[name] = [_ctype(a, name) for a in args]
+        restypes[name] = _ctype(ret, name)
+    return argtypes, restypes
+
+
+# name -> argtypes / restype: the prototypes of include/magnify_hip.h, read from it
+PROTOTYPES, RESTYPES = _parse_header()
+
+_lib = None
 
 
 def lib():
@@ -117,7 +73,7 @@ def lib():
         for name, argtypes in PROTOTYPES.items():
             fn = getattr(handle, name)
             fn.argtypes = argtypes
-            fn.restype = C.c_int64 if name in RETURNS_INT64 else C.c_int
+            fn.restype = RESTYPES[name]
         _lib = handle
     return _lib
 

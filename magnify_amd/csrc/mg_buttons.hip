@@ -157,22 +157,11 @@ extern "C" int mg_masked_sums(const void* d_roi, int dtype, const uint8_t* d_fg,
   const dim3 g(m, n_ct);
   hipStream_t s = mg_stream(stream);
   const int n = roi_len * roi_len;
-  switch (dtype) {
-    case MG_U8:
-      hipLaunchKernelGGL((k_masked_sums<uint8_t, long long>), g, dim3(NT), 0, s, (const uint8_t*)d_roi, d_fg, d_bg, n_ct, n, d_sums, d_counts);
-      break;
-    case MG_U16:
-      hipLaunchKernelGGL((k_masked_sums<uint16_t, long long>), g, dim3(NT), 0, s, (const uint16_t*)d_roi, d_fg, d_bg, n_ct, n, d_sums, d_counts);
-      break;
-    case MG_F32:
-      hipLaunchKernelGGL((k_masked_sums<float, double>), g, dim3(NT), 0, s, (const float*)d_roi, d_fg, d_bg, n_ct, n, d_sums, d_counts);
-      break;
-    case MG_F64:
-      hipLaunchKernelGGL((k_masked_sums<double, double>), g, dim3(NT), 0, s, (const double*)d_roi, d_fg, d_bg, n_ct, n, d_sums, d_counts);
-      break;
-    default:
-      return MG_EINVAL;
-  }
-  MG_CHECK_LAUNCH();
-  return MG_OK;
+  return mg_dispatch_pixel(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((k_masked_sums<T, mg_acc_t<T>>), g, dim3(NT), 0, s, (const T*)d_roi, d_fg, d_bg, n_ct, n, d_sums,
+                       d_counts);
+    MG_CHECK_LAUNCH();
+    return MG_OK;
+  });
 }

@@ -5,6 +5,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/magnify_hip.h"
 
 #define MG_WAVE 64
@@ -44,6 +46,32 @@ static inline hipError_t mg_zero_async(void* p, size_t bytes, hipStream_t s) {  
 
 __host__ __device__ static inline int mg_elem_size(int dtype) {
   return dtype == MG_U8 ? 1 : dtype == MG_U16 ? 2 : dtype == MG_F32 ? 4 : 8;
+}
+
+// The pixel-type switch of the C ABI, once: f(T{}) with T the element type of `dtype`; MG_EINVAL for any other code.
+template <class F>
+static inline int mg_dispatch_pixel(int dtype, F&& f) {
+  switch (dtype) {
+    case MG_U8: return f(uint8_t{});
+    case MG_U16: return f(uint16_t{});
+    case MG_F32: return f(float{});
+    case MG_F64: return f(double{});
+  }
+  return MG_EINVAL;
+}
+// Accumulator of masked sums: exact for integer pixels (below 2^53 in the float64 result), float64 otherwise.
+template <class T>
+using mg_acc_t = std::conditional_t<std::is_integral<T>::value, long long, double>;
+
+// Stitch crop (stitch.py:22-39): every tile keeps rows / columns [clip, clip + hy / hx) -- half the overlap goes on
+// each side, the odd pixel on the far one -- and the n_tr x n_tc kept parts are laid side by side.
+struct MgStitchGeom {
+  int clip, hy, hx, h_out, w_out;
+};
+static inline MgStitchGeom mg_stitch_geom(int ty, int tx, int overlap, int n_tr, int n_tc) {
+  const int clip = overlap / 2, rem = overlap % 2;
+  const int hy = ty - 2 * clip - rem, hx = tx - 2 * clip - rem;
+  return {clip, hy, hx, n_tr * hy, n_tc * hx};
 }
 
 // cv::borderInterpolate(p, n, BORDER_REFLECT_101)
@@ -102,6 +130,73 @@ __device__ __forceinline__ void mg_atomic_nanmin(double* addr, double v) {
     unsigned long long seen = atomicCAS(a, old, (unsigned long long)__double_as_longlong(v));
     if (seen == old) return;
     old = seen;
+  }
+}
+
+// The per-plane min/max tail of the kernels that feed to_uint8 (utils.py:24-26).  Contract: d_minmax is
+// double[n_planes][2], pre-initialised by the caller to {+inf, -inf}; every workgroup folds what its threads saw of PB
+// consecutive planes from plane0 on (np <= PB of them in use) and publishes it with mg_atomic_nanmin / _nanmax, one
+// thread per plane.  A workgroup that saw nothing of a plane -- its running values are still the identity
+// (+inf, -inf), or (0xFFFFFFFF, 0) in the integer form -- leaves the plane's slot alone; NaN propagates as in np.min /
+// np.max (mg_nanmin / mg_nanmax; once a slot is NaN it stays NaN).  Workgroups of MG_MINMAX_WAVES * 64 = 256 threads:
+// every caller is a __launch_bounds__(256) kernel launched with dim3(256).  Called by all threads (it synchronises).
+// A thread's running values of a plane are the float64 pair, or, where the kernel kept integer pixels in uint32
+// registers and saw one, the integer pair (a kernel instance uses one of the two; the other stays at its identity).
+constexpr int MG_MINMAX_WAVES = 4;
+template <int PB, class I>
+__device__ __forceinline__ void mg_block_minmax(double* vmin, double* vmax, const uint32_t* imin, const uint32_t* imax,
+                                                int np, double* d_minmax, I plane0) {
+  __shared__ double s_min[PB][MG_MINMAX_WAVES], s_max[PB][MG_MINMAX_WAVES];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int b = 0; b < PB; ++b) {
+    if (imin[b] <= imax[b]) vmin[b] = (double)imin[b], vmax[b] = (double)imax[b];
+    const double a = mg_wave_nanmin(vmin[b]), c = mg_wave_nanmax(vmax[b]);
+    if (lane == 0) {
+      s_min[b][wave] = a;
+      s_max[b][wave] = c;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < np) {
+    const int b = threadIdx.x;
+    double a = s_min[b][0], c = s_max[b][0];
+    for (int i = 1; i < MG_MINMAX_WAVES; ++i) {
+      a = mg_nanmin(a, s_min[b][i]);
+      c = mg_nanmax(c, s_max[b][i]);
+    }
+    if (!(a == INFINITY && c == -INFINITY)) {
+      mg_atomic_nanmin(d_minmax + 2 * (plane0 + b), a);
+      mg_atomic_nanmax(d_minmax + 2 * (plane0 + b) + 1, c);
+    }
+  }
+}
+// The same for integer pixels kept as uint32 (no NaN; the identity is min > max).
+template <int PB, class I>
+__device__ __forceinline__ void mg_block_minmax_u32(const uint32_t* imin, const uint32_t* imax, int np, double* d_minmax,
+                                                    I plane0) {
+  static_assert(MG_MINMAX_WAVES == 4, "the fold below is written out for four waves");
+  __shared__ uint32_t s_min[PB][MG_MINMAX_WAVES], s_max[PB][MG_MINMAX_WAVES];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int b = 0; b < PB; ++b) {
+    uint32_t a = imin[b], c = imax[b];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      a = min(a, (uint32_t)__shfl_xor((int)a, off));
+      c = max(c, (uint32_t)__shfl_xor((int)c, off));
+    }
+    if (lane == 0) s_min[b][wave] = a, s_max[b][wave] = c;
+  }
+  __syncthreads();
+  if (threadIdx.x < np) {
+    const int b = threadIdx.x;
+    const uint32_t a = min(min(s_min[b][0], s_min[b][1]), min(s_min[b][2], s_min[b][3]));
+    const uint32_t c = max(max(s_max[b][0], s_max[b][1]), max(s_max[b][2], s_max[b][3]));
+    if (a <= c) {
+      mg_atomic_nanmin(d_minmax + 2 * (plane0 + b), (double)a);
+      mg_atomic_nanmax(d_minmax + 2 * (plane0 + b) + 1, (double)c);
+    }
   }
 }
 

@@ -1416,28 +1416,13 @@ extern "C" int mg_to_uint8_blur(const void* d_src, int dtype, int n_planes, int6
   const dim3 g = tile_grid(h, w, n_planes);
   if (g.y > 65535 || g.z > 65535) return MG_EINVAL;
   hipStream_t s = mg_stream(stream);
-  switch (dtype) {
-    case MG_U8:
-      hipLaunchKernelGGL((k_u8_blur<uint8_t>), g, dim3(NT), 0, s, (const uint8_t*)d_src, plane_stride, h, w,
-                         row_stride, d_minmax, d_blur, d_u8);
-      break;
-    case MG_U16:
-      hipLaunchKernelGGL((k_u8_blur<uint16_t>), g, dim3(NT), 0, s, (const uint16_t*)d_src, plane_stride, h, w,
-                         row_stride, d_minmax, d_blur, d_u8);
-      break;
-    case MG_F32:
-      hipLaunchKernelGGL((k_u8_blur<float>), g, dim3(NT), 0, s, (const float*)d_src, plane_stride, h, w, row_stride,
-                         d_minmax, d_blur, d_u8);
-      break;
-    case MG_F64:
-      hipLaunchKernelGGL((k_u8_blur<double>), g, dim3(NT), 0, s, (const double*)d_src, plane_stride, h, w, row_stride,
-                         d_minmax, d_blur, d_u8);
-      break;
-    default:
-      return MG_EINVAL;
-  }
-  MG_CHECK_LAUNCH();
-  return MG_OK;
+  return mg_dispatch_pixel(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((k_u8_blur<T>), g, dim3(NT), 0, s, (const T*)d_src, plane_stride, h, w, row_stride, d_minmax,
+                       d_blur, d_u8);
+    MG_CHECK_LAUNCH();
+    return MG_OK;
+  });
 }
 
 extern "C" int64_t mg_scharr_hist_scratch_words(int n_planes, int h, int w, int mode) {

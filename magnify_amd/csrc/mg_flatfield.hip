@@ -626,32 +626,7 @@ __global__ __launch_bounds__(256) void k_apply_stitch(const T* __restrict__ tile
       }
     }
   }
-  if (d_minmax) {
-    __shared__ double smin[PB][4], smax[PB][4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int b = 0; b < PB; ++b) {
-      if (IsIntegral<T>::value && imin[b] <= imax[b]) vmin[b] = (double)imin[b], vmax[b] = (double)imax[b];
-      const double a = mg_wave_nanmin(vmin[b]), c = mg_wave_nanmax(vmax[b]);
-      if (lane == 0) {
-        smin[b][wave] = a;
-        smax[b][wave] = c;
-      }
-    }
-    __syncthreads();
-    if (threadIdx.x < np) {
-      const int b = threadIdx.x;
-      double a = smin[b][0], c = smax[b][0];
-      for (int i = 1; i < 4; ++i) {
-        a = mg_nanmin(a, smin[b][i]);
-        c = mg_nanmax(c, smax[b][i]);
-      }
-      if (!(a == INFINITY && c == -INFINITY)) {
-        mg_atomic_nanmin(d_minmax + 2 * (plane0 + b), a);
-        mg_atomic_nanmax(d_minmax + 2 * (plane0 + b) + 1, c);
-      }
-    }
-  }
+  if (d_minmax) mg_block_minmax<PB>(vmin, vmax, imin, imax, np, d_minmax, plane0);
 }
 
 // A value that is the same in every lane, held in scalar registers (the compiler keeps uniform float64 values in
@@ -859,30 +834,7 @@ __global__ __launch_bounds__(256) void k_apply_stitch_aligned(const T* __restric
       }
     }
   }
-  if (d_minmax) {
-    __shared__ uint32_t smin[PB][4], smax[PB][4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int b = 0; b < PB; ++b) {
-      uint32_t a = imin[b], c = imax[b];
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {
-        a = min(a, (uint32_t)__shfl_xor((int)a, off));
-        c = max(c, (uint32_t)__shfl_xor((int)c, off));
-      }
-      if (lane == 0) smin[b][wave] = a, smax[b][wave] = c;
-    }
-    __syncthreads();
-    if (threadIdx.x < np) {
-      const int b = threadIdx.x;
-      const uint32_t a = min(min(smin[b][0], smin[b][1]), min(smin[b][2], smin[b][3]));
-      const uint32_t c = max(max(smax[b][0], smax[b][1]), max(smax[b][2], smax[b][3]));
-      if (a <= c) {
-        mg_atomic_nanmin(d_minmax + 2 * (plane0 + b), (double)a);
-        mg_atomic_nanmax(d_minmax + 2 * (plane0 + b) + 1, (double)c);
-      }
-    }
-  }
+  if (d_minmax) mg_block_minmax_u32<PB>(imin, imax, np, d_minmax, plane0);
 }
 
 // ---- per-plane min/max of strided planes ------------------------------------------------
@@ -893,6 +845,7 @@ __global__ __launch_bounds__(256) void k_plane_minmax(const T* __restrict__ src,
   const int plane = blockIdx.y;
   const T* base = src + (int64_t)plane * plane_stride;
   double vmin = INFINITY, vmax = -INFINITY;
+  uint32_t imin = 0xFFFFFFFFu, imax = 0u;
   const int vec_per_row = (w + N - 1) / N;
   const int64_t total = (int64_t)h * vec_per_row;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -900,7 +853,6 @@ __global__ __launch_bounds__(256) void k_plane_minmax(const T* __restrict__ src,
   if (IsIntegral<T>::value && w % N == 0 && (reinterpret_cast<uintptr_t>(base) & 15) == 0 && (row_stride * (int64_t)sizeof(T)) % 16 == 0) {
     // integer pixels, rows of whole 16-byte vectors: integer min / max, four loads in flight per lane (one 4096^2
     // uint16 plane: 28 -> ~10 us; the float64 compares of the general loop kept the lanes busy, one load at a time)
-    uint32_t imin = 0xFFFFFFFFu, imax = 0u;
     for (; i < total; i += 4 * stride) {
       T x[4][N];
 #pragma unroll
@@ -918,7 +870,6 @@ __global__ __launch_bounds__(256) void k_plane_minmax(const T* __restrict__ src,
           imax = max(imax, (uint32_t)x[q][j]);
         }
     }
-    if (imin <= imax) vmin = (double)imin, vmax = (double)imax;
     i = total;
   }
   for (; i < total; i += stride) {
@@ -940,25 +891,7 @@ __global__ __launch_bounds__(256) void k_plane_minmax(const T* __restrict__ src,
       }
     }
   }
-  __shared__ double smin[4], smax[4];
-  vmin = mg_wave_nanmin(vmin);
-  vmax = mg_wave_nanmax(vmax);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-    smin[wave] = vmin;
-    smax[wave] = vmax;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int i = 1; i < 4; ++i) {
-      vmin = mg_nanmin(vmin, smin[i]);
-      vmax = mg_nanmax(vmax, smax[i]);
-    }
-    if (!(vmin == INFINITY && vmax == -INFINITY)) {
-      mg_atomic_nanmin(d_minmax + 2 * plane, vmin);
-      mg_atomic_nanmax(d_minmax + 2 * plane + 1, vmax);
-    }
-  }
+  mg_block_minmax<1>(&vmin, &vmax, &imin, &imax, 1, d_minmax, plane);
 }
 
 template <typename T>
@@ -1014,9 +947,7 @@ template <typename T>
 int launch_apply(const void* d_tiles, int64_t n_planes, int n_tr, int n_tc, int ty, int tx, int overlap, int apply,
                  int planes_per_group, double dark, const void* d_dark, int dark_dt, double flat, const void* d_flat, int flat_dt,
                  const double* d_max2, void* d_image, double* d_minmax, hipStream_t s) {
-  const int clip = overlap / 2, rem = overlap % 2;
-  const int hy = ty - 2 * clip - rem, hx = tx - 2 * clip - rem;
-  const int h_out = n_tr * hy, w_out = n_tc * hx;
+  const auto [clip, hy, hx, h_out, w_out] = mg_stitch_geom(ty, tx, overlap, n_tr, n_tc);
   if (n_planes == 0 || h_out == 0 || w_out == 0) return MG_OK;
   constexpr int N = VecOf<T>::N;
   if (n_planes > 0x7FFFFFF0) return MG_EINVAL;
@@ -1116,17 +1047,10 @@ extern "C" int mg_flatfield_max(const void* d_tiles, int dtype, int64_t n_tiles,
   if (!df_dtype_ok(d_dark, dark_dtype) || !df_dtype_ok(d_flat, flat_dtype)) return MG_EINVAL;
   const int64_t tile_elems = (int64_t)ty * tx, tpg = n_tiles / n_groups;
   hipStream_t s = mg_stream(stream);
-#define MG_MAX(T) \
-  return launch_max<T>(d_tiles, tpg, n_groups, tile_elems, dark, d_dark, dark_dtype, flat, d_flat, flat_dtype, d_max2, \
-                       d_scratch, scratch_floats, s)
-  switch (dtype) {
-    case MG_U8: MG_MAX(uint8_t);
-    case MG_U16: MG_MAX(uint16_t);
-    case MG_F32: MG_MAX(float);
-    case MG_F64: MG_MAX(double);
-  }
-#undef MG_MAX
-  return MG_EINVAL;
+  return mg_dispatch_pixel(dtype, [&](auto t) {
+    return launch_max<decltype(t)>(d_tiles, tpg, n_groups, tile_elems, dark, d_dark, dark_dtype, flat, d_flat, flat_dtype,
+                                   d_max2, d_scratch, scratch_floats, s);
+  });
 }
 
 extern "C" int mg_flatfield_is_identity(int dtype, double dark, const void* d_dark, double flat, const void* d_flat) {
@@ -1149,18 +1073,11 @@ extern "C" int mg_flatfield_apply_stitch(const void* d_tiles, int dtype, int64_t
   if (apply_flatfield && (!d_max2 || planes_per_group <= 0)) return MG_EINVAL;
   if (!df_dtype_ok(d_dark, dark_dtype) || !df_dtype_ok(d_flat, flat_dtype)) return MG_EINVAL;
   hipStream_t s = mg_stream(stream);
-#define MG_APPLY(T) \
-  return launch_apply<T>(d_tiles, n_planes, n_tile_rows, n_tile_cols, ty, tx, overlap, apply_flatfield, \
-                         planes_per_group > 0 ? planes_per_group : 1, dark, d_dark, dark_dtype, flat, d_flat, \
-                         flat_dtype, d_max2, d_image, d_minmax, s)
-  switch (dtype) {
-    case MG_U8: MG_APPLY(uint8_t);
-    case MG_U16: MG_APPLY(uint16_t);
-    case MG_F32: MG_APPLY(float);
-    case MG_F64: MG_APPLY(double);
-  }
-#undef MG_APPLY
-  return MG_EINVAL;
+  return mg_dispatch_pixel(dtype, [&](auto t) {
+    return launch_apply<decltype(t)>(d_tiles, n_planes, n_tile_rows, n_tile_cols, ty, tx, overlap, apply_flatfield,
+                                     planes_per_group > 0 ? planes_per_group : 1, dark, d_dark, dark_dtype, flat, d_flat,
+                                     flat_dtype, d_max2, d_image, d_minmax, s);
+  });
 }
 
 extern "C" int mg_plane_minmax(const void* d_src, int dtype, int n_planes, int64_t plane_stride, int h, int w,
@@ -1168,11 +1085,7 @@ extern "C" int mg_plane_minmax(const void* d_src, int dtype, int n_planes, int64
   if (!d_src || !d_minmax || n_planes < 0 || h < 0 || w < 0) return MG_EINVAL;
   if (n_planes > 65535) return MG_EINVAL;
   hipStream_t s = mg_stream(stream);
-  switch (dtype) {
-    case MG_U8: return launch_minmax<uint8_t>(d_src, n_planes, plane_stride, h, w, row_stride, d_minmax, s);
-    case MG_U16: return launch_minmax<uint16_t>(d_src, n_planes, plane_stride, h, w, row_stride, d_minmax, s);
-    case MG_F32: return launch_minmax<float>(d_src, n_planes, plane_stride, h, w, row_stride, d_minmax, s);
-    case MG_F64: return launch_minmax<double>(d_src, n_planes, plane_stride, h, w, row_stride, d_minmax, s);
-  }
-  return MG_EINVAL;
+  return mg_dispatch_pixel(dtype, [&](auto t) {
+    return launch_minmax<decltype(t)>(d_src, n_planes, plane_stride, h, w, row_stride, d_minmax, s);
+  });
 }

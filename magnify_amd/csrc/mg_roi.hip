@@ -996,25 +996,12 @@ int roi_dispatch(const void* d_image, int dtype, int64_t assay_stride, int n_c, 
     MG_CHECK_LAUNCH();
     return MG_OK;
   }
-  switch (dtype) {
-    case MG_U8:
-      return launch_roi<uint8_t, long long>(d_image, assay_stride, n_c, n_t, h, w, d_beads, d_marker_assay,
-                                            d_marker_local, grid, roi_len, d_labels, d_assay_offsets, n_assays, bead_stride, time_major, d_order, d_halfwidths, max_r,
-                                            d_roi, d_fg, d_bg, d_sums, d_counts, s);
-    case MG_U16:
-      return launch_roi<uint16_t, long long>(d_image, assay_stride, n_c, n_t, h, w, d_beads, d_marker_assay,
-                                             d_marker_local, grid, roi_len, d_labels, d_assay_offsets, n_assays, bead_stride, time_major, d_order, d_halfwidths, max_r,
-                                             d_roi, d_fg, d_bg, d_sums, d_counts, s);
-    case MG_F32:
-      return launch_roi<float, double>(d_image, assay_stride, n_c, n_t, h, w, d_beads, d_marker_assay, d_marker_local,
-                                       grid, roi_len, d_labels, d_assay_offsets, n_assays, bead_stride, time_major, d_order, d_halfwidths, max_r, d_roi, d_fg, d_bg,
-                                       d_sums, d_counts, s);
-    case MG_F64:
-      return launch_roi<double, double>(d_image, assay_stride, n_c, n_t, h, w, d_beads, d_marker_assay, d_marker_local,
-                                        grid, roi_len, d_labels, d_assay_offsets, n_assays, bead_stride, time_major, d_order, d_halfwidths, max_r, d_roi, d_fg, d_bg,
-                                        d_sums, d_counts, s);
-  }
-  return MG_EINVAL;
+  return mg_dispatch_pixel(dtype, [&](auto t) {
+    using T = decltype(t);
+    return launch_roi<T, mg_acc_t<T>>(d_image, assay_stride, n_c, n_t, h, w, d_beads, d_marker_assay, d_marker_local, grid,
+                                      roi_len, d_labels, d_assay_offsets, n_assays, bead_stride, time_major, d_order,
+                                      d_halfwidths, max_r, d_roi, d_fg, d_bg, d_sums, d_counts, s);
+  });
 }
 }  // namespace
 
@@ -1202,13 +1189,9 @@ extern "C" int mg_roi_masked_median(const void* d_roi, int dtype, const uint8_t*
   if (mask_stride_m < 0 || mask_stride_t < 0 || (int64_t)n_c * n_t > 65535) return MG_EINVAL;
   if (m == 0) return MG_OK;
   hipStream_t s = mg_stream(stream);
-  switch (dtype) {
-    case MG_U8: return launch_median<uint8_t>(d_roi, d_mask, mask_stride_m, mask_stride_t, m, n_c, n_t, roi_len, d_median, s);
-    case MG_U16: return launch_median<uint16_t>(d_roi, d_mask, mask_stride_m, mask_stride_t, m, n_c, n_t, roi_len, d_median, s);
-    case MG_F32: return launch_median<float>(d_roi, d_mask, mask_stride_m, mask_stride_t, m, n_c, n_t, roi_len, d_median, s);
-    case MG_F64: return launch_median<double>(d_roi, d_mask, mask_stride_m, mask_stride_t, m, n_c, n_t, roi_len, d_median, s);
-  }
-  return MG_EINVAL;
+  return mg_dispatch_pixel(dtype, [&](auto t) {
+    return launch_median<decltype(t)>(d_roi, d_mask, mask_stride_m, mask_stride_t, m, n_c, n_t, roi_len, d_median, s);
+  });
 }
 
 extern "C" int mg_roi_masked_median_u16(const uint16_t* d_roi, const uint8_t* d_mask, int m, int n_c, int n_t,

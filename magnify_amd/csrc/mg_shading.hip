@@ -533,29 +533,14 @@ __global__ __launch_bounds__(256) void k_shading_apply(const T* __restrict__ til
       }
     }
   if (!d_minmax) return;
-  if (ShadeOp<T>::kInt && imin <= imax) vmin = (double)imin, vmax = (double)imax;
-  __shared__ double smin[4], smax[4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const double a = mg_wave_nanmin(vmin), c = mg_wave_nanmax(vmax);
-  if (lane == 0) smin[wave] = a, smax[wave] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double lo = smin[0], hi = smax[0];
-    for (int i = 1; i < 4; ++i) lo = mg_nanmin(lo, smin[i]), hi = mg_nanmax(hi, smax[i]);
-    if (!(lo == INFINITY && hi == -INFINITY)) {
-      mg_atomic_nanmin(d_minmax + 2 * plane, lo);
-      mg_atomic_nanmax(d_minmax + 2 * plane + 1, hi);
-    }
-  }
+  mg_block_minmax<1>(&vmin, &vmax, &imin, &imax, 1, d_minmax, plane);
 }
 
 template <typename T>
 int launch_shading_apply(const void* d_tiles, int64_t n_planes, int64_t ppf, int n_tr, int n_tc, int ty, int tx,
                          int overlap, const float* d_flat, const float* d_dark, void* d_image, double* d_minmax,
                          hipStream_t s) {
-  const int clip = overlap / 2, rem = overlap % 2;
-  const int hy = ty - 2 * clip - rem, hx = tx - 2 * clip - rem;
-  const int h_out = n_tr * hy, w_out = n_tc * hx;
+  const auto [clip, hy, hx, h_out, w_out] = mg_stitch_geom(ty, tx, overlap, n_tr, n_tc);
   if (n_planes == 0) return MG_OK;
   const int gx = (w_out + 256 * SH_APPLY_VEC - 1) / (256 * SH_APPLY_VEC);
   const int rows = 8;
@@ -590,15 +575,12 @@ extern "C" int mg_shading_downsample(const void* d_tiles, int dtype, int64_t n, 
   if (!d_tiles || !d_out || n < 1 || n > 65535 || w < 1 || w > 128 || ty < w || tx < w) return MG_EINVAL;
   hipStream_t s = mg_stream(stream);
   const dim3 grid((unsigned)((w * w + 255) / 256), (unsigned)n);
-  switch (dtype) {
-    case MG_U8: hipLaunchKernelGGL((k_downsample<uint8_t>), grid, dim3(256), 0, s, (const uint8_t*)d_tiles, ty, tx, w, d_out); break;
-    case MG_U16: hipLaunchKernelGGL((k_downsample<uint16_t>), grid, dim3(256), 0, s, (const uint16_t*)d_tiles, ty, tx, w, d_out); break;
-    case MG_F32: hipLaunchKernelGGL((k_downsample<float>), grid, dim3(256), 0, s, (const float*)d_tiles, ty, tx, w, d_out); break;
-    case MG_F64: hipLaunchKernelGGL((k_downsample<double>), grid, dim3(256), 0, s, (const double*)d_tiles, ty, tx, w, d_out); break;
-    default: return MG_EINVAL;
-  }
-  MG_CHECK_LAUNCH();
-  return MG_OK;
+  return mg_dispatch_pixel(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((k_downsample<T>), grid, dim3(256), 0, s, (const T*)d_tiles, ty, tx, w, d_out);
+    MG_CHECK_LAUNCH();
+    return MG_OK;
+  });
 }
 
 extern "C" int mg_shading_prepare(void* d_ws, int n, int w, void* stream) {
@@ -696,15 +678,8 @@ extern "C" int mg_shading_apply_stitch(const void* d_tiles, int dtype, int n_fie
   const int64_t n_planes = (int64_t)n_fields * planes_per_field;
   if (n_planes > 65535) return MG_EINVAL;
   hipStream_t s = mg_stream(stream);
-#define MG_SH(T) \
-  return launch_shading_apply<T>(d_tiles, n_planes, planes_per_field, n_tile_rows, n_tile_cols, ty, tx, overlap, \
-                                 d_flat, d_dark, d_image, d_minmax, s)
-  switch (dtype) {
-    case MG_U8: MG_SH(uint8_t);
-    case MG_U16: MG_SH(uint16_t);
-    case MG_F32: MG_SH(float);
-    case MG_F64: MG_SH(double);
-  }
-#undef MG_SH
-  return MG_EINVAL;
+  return mg_dispatch_pixel(dtype, [&](auto t) {
+    return launch_shading_apply<decltype(t)>(d_tiles, n_planes, planes_per_field, n_tile_rows, n_tile_cols, ty, tx,
+                                             overlap, d_flat, d_dark, d_image, d_minmax, s);
+  });
 }

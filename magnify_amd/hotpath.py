@@ -182,6 +182,13 @@ def flatfield_max(tiles: torch.Tensor, flatfield=1.0, darkfield=0.0, n_groups=1)
 _BOUND_OF = {}  # scratch block -> (key of the flat image it bounds, the image)
 
 
+def stitch_geometry(ty: int, tx: int, overlap: int):
+    """(clip, hy, hx) of the stitch crop (stitch.py:22-39): a (ty, tx) tile keeps rows [clip, clip + hy) and columns
+    [clip, clip + hx) -- half the overlap goes on each side, the odd pixel on the far one (mg_stitch_geom in C++)."""
+    clip, rem = overlap // 2, overlap % 2
+    return clip, ty - 2 * clip - rem, tx - 2 * clip - rem
+
+
 def flatfield_stitch(tiles: torch.Tensor, overlap: int, flatfield=1.0, darkfield=0.0, apply_flatfield=True,
                      max2: torch.Tensor | None = None, want_minmax=True, out: torch.Tensor | None = None,
                      minmax_out: torch.Tensor | None = None, n_groups=1):
@@ -195,8 +202,7 @@ def flatfield_stitch(tiles: torch.Tensor, overlap: int, flatfield=1.0, darkfield
     if overlap >= ty or overlap >= tx:
         raise ValueError(f"Overlap ({overlap}) must be smaller than tile size ({ty}x{tx}).")
     tiles = tiles.contiguous()
-    clip, rem = overlap // 2, overlap % 2
-    hy, hx = ty - 2 * clip - rem, tx - 2 * clip - rem
+    _, hy, hx = stitch_geometry(ty, tx, overlap)
     dk, dkt, dkc = _df_operand(darkfield, ty, tx, tiles.device)
     fl, flt, flc = _df_operand(flatfield, ty, tx, tiles.device)
     if (c * t) % n_groups:

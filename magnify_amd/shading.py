@@ -67,8 +67,7 @@ def apply_stitch(tiles: torch.Tensor, overlap: int, flats: torch.Tensor, darks: 
     tiles = tiles.contiguous()
     flats = flats.to(tiles.device, torch.float32).contiguous()
     darks = darks.to(tiles.device, torch.float32).contiguous()
-    clip, rem = overlap // 2, overlap % 2
-    hy, hx = ty - 2 * clip - rem, tx - 2 * clip - rem
+    _, hy, hx = hotpath.stitch_geometry(ty, tx, overlap)
     image = out if out is not None else torch.empty((c, t, nr * hy, nc * hx), dtype=tiles.dtype, device=tiles.device)
     minmax = None
     if want_minmax:

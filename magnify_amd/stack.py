@@ -350,8 +350,8 @@ class StackProcessor:
 
 def stitched_shape(rows, cols, tile_y, tile_x, overlap):
     """Size of the image Stitcher makes of a (rows, cols) grid of (tile_y, tile_x) tiles (stitch.py:22-39)."""
-    clip, rem = overlap // 2, overlap % 2
-    return rows * (tile_y - 2 * clip - rem), cols * (tile_x - 2 * clip - rem)
+    _, hy, hx = hp.stitch_geometry(tile_y, tile_x, overlap)
+    return rows * hy, cols * hx
 
 
 def process_stream(chunks, flatfield=1.0, darkfield=0.0, seed=0, want_roi=False, prefetch=2, overlap=0, sink=None,

@@ -32,6 +32,30 @@ def test_library_exports_every_declared_symbol():
         name, args = m.group(1), m.group(2).strip()
         n = 0 if args in ("", "void") else len(args.split(","))
         assert len(nat.PROTOTYPES[name]) == n, (name, n, len(nat.PROTOTYPES[name]))
+        # 64-bit strides, counts and sizes are bound 64 bits wide, as parameters and as return values
+        fn = getattr(nat.lib(), name)
+        ret64 = m.group(0).split()[0] == "int64_t"
+        assert (fn.restype is ctypes.c_int64) == ret64 and fn.restype in (ctypes.c_int, ctypes.c_int64), name
+        for k, arg in enumerate(args.split(",") if n else []):
+            if re.match(r"\s*int64_t\s+\w+\s*$", arg):
+                assert fn.argtypes[k] is ctypes.c_int64, (name, k, arg)
+            else:
+                assert fn.argtypes[k] is not ctypes.c_int64, (name, k, arg)
+    # a few signatures written out: the binding as the loaded functions carry it
+    p, i, l, d = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_double
+    literal = {
+        "mg_plane_minmax": ([p, i, i, l, i, i, l, p, p], i),
+        "mg_flatfield_max": ([p, i, l, i, i, i, d, p, i, d, p, i, p, p, l, p], i),
+        "mg_shading_offset": ([i, i, i], l),
+        "mg_dedup_layout": ([i, i, i, i, p, p, p, p], i),
+        "mg_edge_thresholds_window": ([p, i, i, ctypes.c_float, ctypes.c_float, p, p, p, p, p, p], i),
+        "mg_version": ([], i),
+    }
+    for name, (argtypes, restype) in literal.items():
+        fn = getattr(nat.lib(), name)
+        assert list(fn.argtypes) == argtypes and nat.PROTOTYPES[name] == argtypes, name
+        assert fn.restype is restype, name
+    assert nat.dedup_layout(300, 200, 5, 13) == (6, 4, 6 * 4 * 9, 128 * 6 * 4 * 9)  # out-parameters through byref
 
 
 def test_product_fails_loudly_without_gpu():

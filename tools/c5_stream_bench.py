@@ -57,13 +57,13 @@ def main():
     import torch
 
     from magnify_amd import distributed as mgd
+    from magnify_amd.hotpath import stitch_geometry
     from magnify_amd.stack import process_stream, stitched_shape, synthetic_stack
 
     rank, world, _ = mgd.init_from_env()
     T, C, R, ty, ov = args.timepoints, args.channels, args.grid, args.tile, args.overlap
     h, w = stitched_shape(R, R, ty, ty, ov)
-    clip, rem = ov // 2, ov % 2
-    step = ty - 2 * clip - rem
+    _, step, _ = stitch_geometry(ty, ty, ov)
     side = (R - 1) * step + ty  # a canvas large enough to cut overlapping tiles from: tile (r, c) starts at (r step, c step)
     lo, hi = mgd.shard_range(T, rank, world)
     if world > 1 and (lo % args.chunk or (hi - lo) % args.chunk):
