@@ -106,6 +106,17 @@ int mg_flatfield_apply_stitch(const void* d_tiles, int dtype, int64_t n_planes, 
                               double flat, const void* d_flat, int flat_dtype,
                               const double* d_max2, void* d_image, double* d_minmax, void* stream);
 
+/* Pass 2 for a selection of planes: as mg_flatfield_apply_stitch with apply_flatfield = 1, but only the planes c of
+ * every group of planes_per_group (<= 31) planes whose bit c is set in plane_mask are corrected -- written to their
+ * usual place in d_image, their rows of d_minmax updated; the other planes and rows are left untouched.  n_planes (all
+ * planes, a multiple of planes_per_group) and the layouts are those of the full pass; a later call with the
+ * complementary mask completes the image block to what the full pass writes. */
+int mg_flatfield_apply_stitch_planes(const void* d_tiles, int dtype, int64_t n_planes, int n_tile_rows, int n_tile_cols,
+                                     int ty, int tx, int overlap, int planes_per_group, int plane_mask,
+                                     double dark, const void* d_dark, int dark_dtype,
+                                     double flat, const void* d_flat, int flat_dtype,
+                                     const double* d_max2, void* d_image, double* d_minmax, void* stream);
+
 /* Per-plane min/max (utils.py:24-25) of strided planes.  d_minmax double[n_planes][2],
  * pre-initialised to {+inf, -inf}.  Strides are in elements. */
 int mg_plane_minmax(const void* d_src, int dtype, int n_planes, int64_t plane_stride, int h, int w,
@@ -513,6 +524,23 @@ int mg_roi_segment_reduce(const void* d_image, int dtype, int64_t assay_stride, 
                           int time_major, const int32_t* d_beads, int64_t bead_stride, const int32_t* d_assay_offsets,
                           int n_assays, int m, const int32_t* d_order, int roi_len, const int32_t* d_halfwidths, int max_r,
                           void* d_roi, uint8_t* d_fg, uint8_t* d_bg, double* d_sums, int32_t* d_counts, void* stream);
+
+/* mg_roi_segment_reduce for an image block in which only some channels have been corrected
+ * (mg_flatfield_apply_stitch_planes): the channels c with bit c set in raw_channel_mask are gathered from the RAW
+ * stack d_raw -- same layout and assay stride as d_image, un-tiled -- and flat-field corrected on the way, pixel for
+ * pixel what the correction pass writes (one definition of the arithmetic, csrc/mg_flatcorr.h): scalar dark, flat
+ * scalar (d_flat NULL) or a float32 (h, w) image, d_max2 / planes_per_group as for mg_flatfield_apply_stitch with
+ * planes_per_group a multiple of n_c * n_t.  The other channels are read from d_image as they are.
+ * Only the fast window kernel has this form: uint16 pixels, even roi_len <= 126, even w, 16-byte aligned d_image /
+ * d_raw / d_flat, time_major == 0 (a time-major block is refused).  MG_EINVAL otherwise: the caller then corrects the
+ * channels with the correction pass and calls mg_roi_segment_reduce. */
+int mg_roi_segment_reduce_raw(const void* d_image, const void* d_raw, int dtype, int64_t assay_stride, int n_c, int n_t,
+                              int h, int w, int time_major, int raw_channel_mask, double dark, double flat,
+                              const float* d_flat, const double* d_max2, int planes_per_group,
+                              const int32_t* d_beads, int64_t bead_stride, const int32_t* d_assay_offsets,
+                              int n_assays, int m, const int32_t* d_order, int roi_len, const int32_t* d_halfwidths,
+                              int max_r, void* d_roi, uint8_t* d_fg, uint8_t* d_bg, double* d_sums, int32_t* d_counts,
+                              void* stream);
 
 /* d_order[0 .. m) for mg_roi_segment_reduce (NULL there: markers are visited as listed): the markers of every assay
  * band by band (64 rows) and left to right inside a band, so that windows which share image lines are gathered at

@@ -6,6 +6,7 @@
 #include <math.h>
 
 #include "mg_common.h"
+#include "mg_flatcorr.h"
 
 namespace {
 
@@ -69,26 +70,6 @@ __device__ __forceinline__ void store_vec16(T* p, const T (&v)[N], bool nt) {
 }
 
 template <typename T>
-__device__ __forceinline__ T cast_trunc(double v);
-// NumPy's astype from float64 truncates toward zero.
-template <>
-__device__ __forceinline__ uint8_t cast_trunc<uint8_t>(double v) {
-  return (uint8_t)(unsigned int)v;
-}
-template <>
-__device__ __forceinline__ uint16_t cast_trunc<uint16_t>(double v) {
-  return (uint16_t)(unsigned int)v;
-}
-template <>
-__device__ __forceinline__ float cast_trunc<float>(double v) {
-  return (float)v;
-}
-template <>
-__device__ __forceinline__ double cast_trunc<double>(double v) {
-  return v;
-}
-
-template <typename T>
 struct IsIntegral {
   static constexpr bool value = false;
 };
@@ -126,8 +107,6 @@ __device__ __forceinline__ void block_atomic_max2(double m1, double m2, double* 
 // Division-free filter for M2 = max(t / flat): the float32 reciprocal gives the quotient to
 // ~2e-7; only pixels whose approximate quotient is within 1e-6 of the running maximum pay for
 // the exact float64 division, so the result is the exact maximum of the exact quotients.
-__device__ __forceinline__ bool flat_in_range(double fl) { return fl > 1e-30 && fl < 1e30; }
-
 __device__ __forceinline__ void max_step(double t, double fl, bool fast_m2, double& m1, double& m2) {
   m1 = mg_nanmax(m1, t);
   if (fast_m2) return;
@@ -449,20 +428,6 @@ __global__ __launch_bounds__(256) void k_flatfield_max_lean(const T* __restrict_
 // ---- pass 2: apply + stitch (+ output min/max) ----------------------------------------
 constexpr int ROWS_PER_BLOCK = 32;  // rows of a workgroup at large batches; fewer when the grid would not fill the chip
 
-// out = trunc(((t / fl) * m1) / m2) for an integer output type without the two float64 divisions:
-// v = t * rcp(fl) * (m1 / m2) with a Newton-refined reciprocal agrees with the reference's three
-// roundings to ~1e-15 relative, so the truncation is the same unless v lies within 1e-6 of an
-// integer -- those (rare) pixels take the exact path.
-// Newton-refined reciprocal of a flat-field value (float32 seed, two steps in float64: ~1e-16).
-// Returns 0 when the value is outside the range in which the fast path is valid.
-__device__ __forceinline__ double refined_rcp(double fl) {
-  if (!flat_in_range(fl)) return 0.0;
-  double r = (double)__builtin_amdgcn_rcpf((float)fl);
-  r = r * (2.0 - fl * r);
-  r = r * (2.0 - fl * r);
-  return r;
-}
-
 // out = trunc(((t / fl) * m1) / m2) for an integer output type.  With r = refined_rcp(fl) != 0 and
 // k = m1 / m2, v = t * r * k agrees with the reference's three roundings to ~1e-15 relative, so the
 // truncation is the same unless v lies within 1e-6 of an integer -- those (rare) pixels, and every
@@ -476,72 +441,62 @@ __device__ __forceinline__ T correct_pixel(double t, double fl, double r, double
     const double fr = v - fv;
     if (fr > 1e-6 && fr < 1.0 - 1e-6 && v < 4.0e9) return (T)(unsigned int)fv;
   }
-  double e = t / fl;
-  e = e * m1;
-  e = e / m2;
-  return cast_trunc<T>(e);
-}
-
-// N pixels at once for an integer output type: the fast products of all N first (straight-line code), ONE test whether
-// any of them sits too close to an integer (or the operands are out of the fast path's range), and only then -- a few
-// chunks in a million -- the exact two-division path for the chunk.  (A branch per pixel made the pass VALU / branch
-// bound: ~25 vector and ~6 scalar instructions per pixel; the data path itself is a dozen.)
-template <typename T, int N>
-__device__ __forceinline__ void correct_chunk(const T (&x)[N], const double (&dk)[N], const double (&fl)[N],
-                                              const double (&r)[N], double m1, double m2, double k, bool fast_ok, T (&o)[N]) {
-  double t[N];
-  bool unsure = !fast_ok || !IsIntegral<T>::value;  // (other output types: always the reference's own operations)
-#pragma unroll
-  for (int j = 0; j < N; ++j) {
-    t[j] = (double)x[j] - dk[j];
-    t[j] = t[j] < 0.0 ? 0.0 : t[j];
-    if (!IsIntegral<T>::value) continue;
-    const double v = t[j] * r[j] * k;
-    const double fv = floor(v);
-    const double fr = v - fv;
-    o[j] = (T)(unsigned int)fv;
-    // t == 0 gives exactly 0 (m1, m2 finite and positive under fast_ok); r == 0 marks a flat value outside the range
-    unsure |= !((fr > 1e-6 && fr < 1.0 - 1e-6 && v < 4.0e9) || t[j] == 0.0) || r[j] == 0.0;
-  }
-  if (unsure) {
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-      double e = t[j] / fl[j];
-      e = e * m1;
-      e = e / m2;
-      o[j] = cast_trunc<T>(e);
-    }
-  }
+  return cast_trunc<T>(exact_quotient(t, fl, m1, m2));
 }
 
 constexpr int PLANES_PER_BLOCK = 8;
 
+// Selected planes of every group (mg_flatfield_apply_stitch_planes): bit c of `mask` selects plane c of each group of
+// planes_per_group planes; the s-th selected plane of the stack is plane (s / n_sel) * planes_per_group + the
+// (s % n_sel)-th set bit.  A workgroup takes PLANES_PER_BLOCK consecutive SELECTED planes; without a selection
+// (SUBSET false) plane s is plane s.
+struct PlaneSel {
+  uint32_t mask;
+  int n_sel;
+};
+template <bool SUBSET>
+__device__ __forceinline__ int sel_plane(int s, int planes_per_group, PlaneSel sel) {
+  if (!SUBSET) return s;
+  const int g = s / sel.n_sel;
+  uint32_t m = sel.mask;
+  for (int k = s - g * sel.n_sel; k > 0; --k) m &= m - 1u;  // without its k lowest set bits
+  return g * planes_per_group + __builtin_ctz(m);
+}
+// plane0 of mg_block_minmax for a selection: `base + b` is the plane the workgroup's b-th running pair belongs to
+struct SelBase {
+  int s0, planes_per_group;
+  PlaneSel sel;
+  __device__ __forceinline__ int operator+(int b) const { return sel_plane<true>(s0 + b, planes_per_group, sel); }
+};
+
 // Block = 256 lanes x N pixels of ROWS_PER_BLOCK output rows, for PLANES_PER_BLOCK consecutive
 // planes: the dark/flat operands of a pixel chunk are loaded once and reused across those planes.
-template <typename T, bool APPLY>
+template <typename T, bool APPLY, bool SUBSET = false>
 __global__ __launch_bounds__(256) void k_apply_stitch(const T* __restrict__ tiles, int n_planes, int n_tr, int n_tc,
                                                        int ty, int tx, int clip, int hy, int hx, int planes_per_group,
                                                        double dark, const void* __restrict__ d_dark, int dark_dt,
                                                        double flat, const void* __restrict__ d_flat, int flat_dt,
                                                        const double* __restrict__ d_max2, T* __restrict__ image,
-                                                       double* __restrict__ d_minmax, int rows_per_block) {
+                                                       double* __restrict__ d_minmax, int rows_per_block, PlaneSel sel) {
   constexpr int N = VecOf<T>::N;
   constexpr int PB = PLANES_PER_BLOCK;
-  const int plane0 = blockIdx.z * PB;
+  const int plane0 = blockIdx.z * PB;  // (SUBSET: n_planes, plane0 count SELECTED planes; pl[b] is the plane itself)
   const int np = min(PB, n_planes - plane0);
   const int h_out = n_tr * hy, w_out = n_tc * hx;
   const int ox0 = (blockIdx.x * blockDim.x + threadIdx.x) * N;
+  int pl[PB];
+#pragma unroll
+  for (int b = 0; b < PB; ++b) pl[b] = (!SUBSET || b < np) ? sel_plane<SUBSET>(plane0 + b, planes_per_group, sel) : 0;
   double m1[PB], m2[PB], kk[PB];
   bool fast_ok[PB];
 #pragma unroll
   for (int b = 0; b < PB; ++b) {
     m1[b] = 0.0, m2[b] = 1.0, kk[b] = 1.0, fast_ok[b] = false;
     if (APPLY && b < np) {
-      const int group = (plane0 + b) / planes_per_group;
+      const int group = pl[b] / planes_per_group;
       m1[b] = d_max2[2 * group];
       m2[b] = d_max2[2 * group + 1];
-      kk[b] = m1[b] / m2[b];
-      fast_ok[b] = kk[b] > 0.0 && kk[b] < 1e30 && m1[b] > 0.0 && m1[b] < 1e300 && m2[b] > 0.0 && m2[b] < 1e300;
+      fast_ok[b] = group_quotient(m1[b], m2[b], kk[b]);
     }
   }
   double vmin[PB], vmax[PB];
@@ -589,7 +544,7 @@ __global__ __launch_bounds__(256) void k_apply_stitch(const T* __restrict__ tile
 #pragma unroll
       for (int b = 0; b < PB; ++b) {
         if (b >= np) break;
-        const int64_t plane_base = (int64_t)(plane0 + b) * n_tr * n_tc * tile_elems;
+        const int64_t plane_base = (int64_t)pl[b] * n_tr * n_tc * tile_elems;
         T x[N], o[N];
         if (one_tile) {
           load_vec<T, N>(tiles + plane_base + toff[0] + pix[0], x);
@@ -617,7 +572,7 @@ __global__ __launch_bounds__(256) void k_apply_stitch(const T* __restrict__ tile
             }
           }
         }
-        T* dst = image + ((int64_t)(plane0 + b) * h_out + oy) * w_out + ox0;
+        T* dst = image + ((int64_t)pl[b] * h_out + oy) * w_out + ox0;
         if (cnt == N) {
           store_vec<T, N>(dst, o);
         } else {
@@ -626,68 +581,10 @@ __global__ __launch_bounds__(256) void k_apply_stitch(const T* __restrict__ tile
       }
     }
   }
-  if (d_minmax) mg_block_minmax<PB>(vmin, vmax, imin, imax, np, d_minmax, plane0);
-}
-
-// A value that is the same in every lane, held in scalar registers (the compiler keeps uniform float64 values in
-// vector registers otherwise: 2 per value and lane).
-__device__ __forceinline__ double uniform_f64(double v) {
-  const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u), hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
-  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-
-// max(x - d, 0) of N integer pixels in the integer domain (d: an integer-valued scalar dark in [0, 65535]); uint16
-// pixels two at a time (v_pk_sub_u16 with clamp).
-typedef unsigned short mg_u16x2 __attribute__((ext_vector_type(2)));
-template <typename T, int N>
-__device__ __forceinline__ void sub_dark_int(const T (&x)[N], uint32_t d, uint32_t (&ti)[N]) {
-#pragma unroll
-  for (int j = 0; j < N; ++j) {
-    const uint32_t xi = (uint32_t)x[j];
-    ti[j] = xi > d ? xi - d : 0u;
+  if (d_minmax) {
+    if (SUBSET) mg_block_minmax<PB>(vmin, vmax, imin, imax, np, d_minmax, SelBase{plane0, planes_per_group, sel});
+    else mg_block_minmax<PB>(vmin, vmax, imin, imax, np, d_minmax, plane0);
   }
-}
-template <>
-__device__ __forceinline__ void sub_dark_int<uint16_t, 8>(const uint16_t (&x)[8], uint32_t d, uint32_t (&ti)[8]) {
-  uint32_t w[4];
-  __builtin_memcpy(w, x, 16);
-  const mg_u16x2 dd = {(unsigned short)d, (unsigned short)d};
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const mg_u16x2 r = __builtin_elementwise_sub_sat(__builtin_bit_cast(mg_u16x2, w[q]), dd);
-    ti[2 * q] = r.x;
-    ti[2 * q + 1] = r.y;
-  }
-}
-
-// The fast products of a chunk against per-position factors rk = rcp(flat) * (M1 / M2) (made once per position and
-// group, not per pixel): v = t * rk agrees with the reference's three roundings to ~1e-15 relative; the integer part
-// is the conversion's own truncation (v >= 0), the distance to the next integer comes from v_fract_f64.  Returns
-// whether any pixel sits within 1e-6 of an integer (t == 0 gives exactly 0 either way and does not count).
-template <typename T, int N>
-__device__ __forceinline__ bool fast_chunk_int(const uint32_t (&ti)[N], const double (&rk)[N], T (&o)[N]) {
-  bool unsure = false;
-#pragma unroll
-  for (int j = 0; j < N; ++j) {
-    const double v = (double)ti[j] * rk[j];
-    const double fr = __builtin_amdgcn_fract(v);
-    o[j] = (T)(unsigned int)v;
-    unsure |= !(fr > 1e-6 && fr < 1.0 - 1e-6) && ti[j] != 0u;
-  }
-  return unsure;
-}
-template <typename T, int N>
-__device__ __forceinline__ bool fast_chunk_f64(const double (&t)[N], const double (&rk)[N], T (&o)[N]) {
-  bool unsure = false;
-#pragma unroll
-  for (int j = 0; j < N; ++j) {
-    const double v = t[j] * rk[j];
-    const double fr = __builtin_amdgcn_fract(v);
-    o[j] = (T)(unsigned int)v;
-    unsure |= !(fr > 1e-6 && fr < 1.0 - 1e-6) && t[j] != 0.0;
-  }
-  return unsure;
 }
 
 // Lean variant for the aligned case (hx % N == 0 and aligned bases: every N-pixel chunk lies
@@ -698,7 +595,7 @@ __device__ __forceinline__ bool fast_chunk_f64(const double (&t)[N], const doubl
 // 24: 2.55 -> 1.65 ms of vector issue at 64 assays; what it bought is at small batches, 0.55 -> 0.50 ms at 8 assays --
 // at 64 the pass waits for memory, see the workgroup order below).  INT_DARK: an integer-valued scalar dark,
 // subtracted in the integer domain (two uint16 pixels per instruction).
-template <typename T, bool APPLY, bool INT_DARK>
+template <typename T, bool APPLY, bool INT_DARK, bool SUBSET = false>
 __global__ __launch_bounds__(256) void k_apply_stitch_aligned(const T* __restrict__ tiles, int n_planes, int n_tr,
                                                                int n_tc, int ty, int tx, int clip, int hy, int hx,
                                                                int planes_per_group, double dark,
@@ -706,7 +603,7 @@ __global__ __launch_bounds__(256) void k_apply_stitch_aligned(const T* __restric
                                                                double flat, const void* __restrict__ d_flat,
                                                                int flat_dt, const double* __restrict__ d_max2,
                                                                T* __restrict__ image, double* __restrict__ d_minmax,
-                                                               int rows_per_block) {
+                                                               int rows_per_block, PlaneSel sel) {
   constexpr int N = VecOf<T>::N;
   constexpr int PB = PLANES_PER_BLOCK;
   // Which part of the grid this workgroup is: the plane groups (z) of one (x, y) part read the same rows of the flat /
@@ -723,10 +620,13 @@ __global__ __launch_bounds__(256) void k_apply_stitch_aligned(const T* __restric
     bx = xy % gridDim.x;
     by = xy / gridDim.x;
   }
-  const int plane0 = bz * PB;
+  const int plane0 = bz * PB;  // (SUBSET: n_planes, plane0 count SELECTED planes; pl[b] is the plane itself)
   const int np = min(PB, n_planes - plane0);
   const int h_out = n_tr * hy, w_out = n_tc * hx;
   const int ox0 = (bx * blockDim.x + threadIdx.x) * N;
+  int pl[PB];
+#pragma unroll
+  for (int b = 0; b < PB; ++b) pl[b] = (!SUBSET || b < np) ? sel_plane<SUBSET>(plane0 + b, planes_per_group, sel) : 0;
   uint32_t imin[PB], imax[PB];
 #pragma unroll
   for (int b = 0; b < PB; ++b) imin[b] = 0xFFFFFFFFu, imax[b] = 0u;
@@ -739,11 +639,11 @@ __global__ __launch_bounds__(256) void k_apply_stitch_aligned(const T* __restric
   for (int b = 0; b < PB; ++b) {
     kka[b] = 1.0;
     if (APPLY && b < np) {
-      const int group = (plane0 + b) / planes_per_group;
+      const int group = pl[b] / planes_per_group;
       const double m1 = d_max2[2 * group], m2 = d_max2[2 * group + 1];
-      const double kk = m1 / m2;
+      double kk;
+      const bool ok = group_quotient(m1, m2, kk);
       kka[b] = uniform_f64(kk);
-      const bool ok = kk > 0.0 && kk < 1e30 && m1 > 0.0 && m1 < 1e300 && m2 > 0.0 && m2 < 1e300;
       ok_mask |= ok ? (1u << b) : 0u;
     }
   }
@@ -773,7 +673,7 @@ __global__ __launch_bounds__(256) void k_apply_stitch_aligned(const T* __restric
       T xin[PB][N];
 #pragma unroll
       for (int b = 0; b < PB; ++b)
-        if (b < np) load_vec16<T, N>(tiles + (int64_t)(plane0 + b) * plane_elems + src0, xin[b], false);
+        if (b < np) load_vec16<T, N>(tiles + (int64_t)pl[b] * plane_elems + src0, xin[b], false);
       double rk[N];
       double kk_of_rk = -1.0;  // the quotient rk was made with (planes of one group follow each other)
       bool rk_large = true;
@@ -785,40 +685,10 @@ __global__ __launch_bounds__(256) void k_apply_stitch_aligned(const T* __restric
         if (APPLY) {
           if (kka[b] != kk_of_rk) {  // (uniform: a new group)
             kk_of_rk = kka[b];
-            rk_large = false;
-#pragma unroll
-            for (int j = 0; j < N; ++j) {
-              rk[j] = rr[j] * kk_of_rk;
-              rk_large |= !(rk[j] < 61035.0);  // t <= 65535: v = t rk stays below 4e9 (the unsigned conversion)
-            }
+            rk_large = chunk_factors<N>(rr, kk_of_rk, rk);
           }
           const bool rk_bad = rk_large || flat_bad || !((ok_mask >> b) & 1u);
-          bool unsure;
-          uint32_t ti[N];
-          double t[N];
-          if (INT_DARK) {
-            sub_dark_int<T, N>(x, dark_i, ti);
-            unsure = fast_chunk_int<T, N>(ti, rk, o);
-          } else {
-#pragma unroll
-            for (int j = 0; j < N; ++j) {
-              t[j] = (double)x[j] - dk[j];
-              t[j] = t[j] < 0.0 ? 0.0 : t[j];
-            }
-            unsure = fast_chunk_f64<T, N>(t, rk, o);
-          }
-          if (unsure || rk_bad) {  // a few chunks in a million: the reference's own operations
-            const int group = (plane0 + b) / planes_per_group;
-            const double m1 = d_max2[2 * group], m2 = d_max2[2 * group + 1];
-#pragma unroll
-            for (int j = 0; j < N; ++j) {
-              const double tj = INT_DARK ? (double)ti[j] : t[j];
-              double e = tj / fl[j];
-              e = e * m1;
-              e = e / m2;
-              o[j] = cast_trunc<T>(e);
-            }
-          }
+          correct_chunk_rk<T, N, INT_DARK>(x, dark_i, dk, fl, rk, rk_bad, d_max2, pl[b], planes_per_group, o);
         } else {
 #pragma unroll
           for (int j = 0; j < N; ++j) o[j] = x[j];
@@ -830,11 +700,14 @@ __global__ __launch_bounds__(256) void k_apply_stitch_aligned(const T* __restric
             imax[b] = max(imax[b], (uint32_t)o[j]);
           }
         }
-        store_vec16<T, N>(image + ((int64_t)(plane0 + b) * h_out + oy) * w_out + ox0, o, false);
+        store_vec16<T, N>(image + ((int64_t)pl[b] * h_out + oy) * w_out + ox0, o, false);
       }
     }
   }
-  if (d_minmax) mg_block_minmax_u32<PB>(imin, imax, np, d_minmax, plane0);
+  if (d_minmax) {
+    if (SUBSET) mg_block_minmax_u32<PB>(imin, imax, np, d_minmax, SelBase{plane0, planes_per_group, sel});
+    else mg_block_minmax_u32<PB>(imin, imax, np, d_minmax, plane0);
+  }
 }
 
 // ---- per-plane min/max of strided planes ------------------------------------------------
@@ -946,11 +819,14 @@ int launch_max(const void* d_tiles, int64_t tiles_per_group, int n_groups, int64
 template <typename T>
 int launch_apply(const void* d_tiles, int64_t n_planes, int n_tr, int n_tc, int ty, int tx, int overlap, int apply,
                  int planes_per_group, double dark, const void* d_dark, int dark_dt, double flat, const void* d_flat, int flat_dt,
-                 const double* d_max2, void* d_image, double* d_minmax, hipStream_t s) {
+                 const double* d_max2, void* d_image, double* d_minmax, hipStream_t s, uint32_t plane_mask = 0) {
   const auto [clip, hy, hx, h_out, w_out] = mg_stitch_geom(ty, tx, overlap, n_tr, n_tc);
   if (n_planes == 0 || h_out == 0 || w_out == 0) return MG_OK;
   constexpr int N = VecOf<T>::N;
   if (n_planes > 0x7FFFFFF0) return MG_EINVAL;
+  // a selection (plane_mask != 0, apply only): from here on n_planes counts the selected planes, the kernels map them
+  const PlaneSel sel{plane_mask, __builtin_popcount(plane_mask)};
+  if (plane_mask) n_planes = n_planes / planes_per_group * sel.n_sel;
   // rows per workgroup: 32 when that still gives ~8 workgroups per CU, down to 2 for a single assay
   int rows = ROWS_PER_BLOCK;
   const int64_t cols_planes = (int64_t)((w_out + 256 * N - 1) / (256 * N)) * ((n_planes + PLANES_PER_BLOCK - 1) / PLANES_PER_BLOCK);
@@ -968,29 +844,37 @@ int launch_apply(const void* d_tiles, int64_t n_planes, int n_tr, int n_tc, int 
                        (!d_dark || (reinterpret_cast<uintptr_t>(d_dark) & 15) == 0);
   if (aligned) {
     // an integer-valued scalar dark inside the pixel range: subtracted in the integer domain
-    const bool int_dark = apply && !d_dark && dark >= 0.0 && dark <= 65535.0 && dark == (double)(uint32_t)dark;
-#define MG_ALIGNED(AP, ID) \
-    hipLaunchKernelGGL((k_apply_stitch_aligned<T, AP, ID>), grid, dim3(256), 0, s, (const T*)d_tiles, (int)n_planes, n_tr, \
+    const bool int_dark = apply && dark_is_int(d_dark, dark);
+#define MG_ALIGNED(AP, ID, SUB) \
+    hipLaunchKernelGGL((k_apply_stitch_aligned<T, AP, ID, SUB>), grid, dim3(256), 0, s, (const T*)d_tiles, (int)n_planes, n_tr, \
                        n_tc, ty, tx, clip, hy, hx, planes_per_group, dark, d_dark, dark_dt, flat, d_flat, flat_dt, \
-                       d_max2, (T*)d_image, d_minmax, rows)
-    if (!apply)
-      MG_ALIGNED(false, false);
+                       d_max2, (T*)d_image, d_minmax, rows, sel)
+    if (plane_mask && int_dark)
+      MG_ALIGNED(true, true, true);
+    else if (plane_mask)
+      MG_ALIGNED(true, false, true);
+    else if (!apply)
+      MG_ALIGNED(false, false, false);
     else if (int_dark)
-      MG_ALIGNED(true, true);
+      MG_ALIGNED(true, true, false);
     else
-      MG_ALIGNED(true, false);
+      MG_ALIGNED(true, false, false);
 #undef MG_ALIGNED
     MG_CHECK_LAUNCH();
     return MG_OK;
   }
-  if (apply)
+  if (plane_mask)
+    hipLaunchKernelGGL((k_apply_stitch<T, true, true>), grid, dim3(256), 0, s, (const T*)d_tiles, (int)n_planes, n_tr, n_tc,
+                       ty, tx, clip, hy, hx, planes_per_group, dark, d_dark, dark_dt, flat, d_flat, flat_dt, d_max2,
+                       (T*)d_image, d_minmax, rows, sel);
+  else if (apply)
     hipLaunchKernelGGL((k_apply_stitch<T, true>), grid, dim3(256), 0, s, (const T*)d_tiles, (int)n_planes, n_tr, n_tc,
                        ty, tx, clip, hy, hx, planes_per_group, dark, d_dark, dark_dt, flat, d_flat, flat_dt, d_max2,
-                       (T*)d_image, d_minmax, rows);
+                       (T*)d_image, d_minmax, rows, sel);
   else
     hipLaunchKernelGGL((k_apply_stitch<T, false>), grid, dim3(256), 0, s, (const T*)d_tiles, (int)n_planes, n_tr, n_tc,
                        ty, tx, clip, hy, hx, planes_per_group, dark, d_dark, dark_dt, flat, d_flat, flat_dt, d_max2,
-                       (T*)d_image, d_minmax, rows);
+                       (T*)d_image, d_minmax, rows, sel);
   MG_CHECK_LAUNCH();
   return MG_OK;
 }
@@ -1077,6 +961,29 @@ extern "C" int mg_flatfield_apply_stitch(const void* d_tiles, int dtype, int64_t
     return launch_apply<decltype(t)>(d_tiles, n_planes, n_tile_rows, n_tile_cols, ty, tx, overlap, apply_flatfield,
                                      planes_per_group > 0 ? planes_per_group : 1, dark, d_dark, dark_dtype, flat, d_flat,
                                      flat_dtype, d_max2, d_image, d_minmax, s);
+  });
+}
+
+extern "C" int mg_flatfield_apply_stitch_planes(const void* d_tiles, int dtype, int64_t n_planes, int n_tile_rows,
+                                                int n_tile_cols, int ty, int tx, int overlap, int planes_per_group,
+                                                int plane_mask, double dark, const void* d_dark, int dark_dtype,
+                                                double flat, const void* d_flat, int flat_dtype, const double* d_max2,
+                                                void* d_image, double* d_minmax, void* stream) {
+  if (!d_tiles || !d_image || !d_max2 || n_planes < 0 || n_tile_rows <= 0 || n_tile_cols <= 0 || ty <= 0 || tx <= 0)
+    return MG_EINVAL;
+  if (overlap < 0 || overlap >= ty || overlap >= tx) return MG_EINVAL;
+  if (planes_per_group <= 0 || planes_per_group > 31 || n_planes % planes_per_group || plane_mask < 0 ||
+      (plane_mask >> planes_per_group))
+    return MG_EINVAL;
+  if (!df_dtype_ok(d_dark, dark_dtype) || !df_dtype_ok(d_flat, flat_dtype)) return MG_EINVAL;
+  if (plane_mask == 0) return MG_OK;  // nothing selected
+  hipStream_t s = mg_stream(stream);
+  // (no identity shortcut: the selected planes always go through the correction's arithmetic, whose result for the
+  // identity operands is the pixel itself)
+  return mg_dispatch_pixel(dtype, [&](auto t) {
+    return launch_apply<decltype(t)>(d_tiles, n_planes, n_tile_rows, n_tile_cols, ty, tx, overlap, 1, planes_per_group,
+                                     dark, d_dark, dark_dtype, flat, d_flat, flat_dtype, d_max2, d_image, d_minmax, s,
+                                     (uint32_t)plane_mask);
   });
 }
 

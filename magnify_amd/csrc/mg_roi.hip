@@ -8,6 +8,7 @@
 #include <stdlib.h>
 
 #include "mg_common.h"
+#include "mg_flatcorr.h"
 
 namespace {
 
@@ -297,8 +298,39 @@ __device__ __forceinline__ uint32_t roi_dot2(uint32_t v, uint32_t m, uint32_t ac
 // bits 0, 1 of b -> the 0/1 halves of a packed pair
 __device__ __forceinline__ uint32_t roi_pair(uint32_t b) { return (b & 1u) | ((b & 2u) << 15); }
 
-template <int U, int CTB, bool PIPE>
-__global__ __launch_bounds__(NT) void k_roi_u16_even(const uint16_t* __restrict__ d_image, int64_t assay_stride,
+// FUSE (mg_roi_segment_reduce_raw): the channels of `rw.chan_mask` have no corrected copy in the image block -- their
+// dwords come from the raw stack at the same coordinates and are flat-field corrected here, with the functions the
+// correction pass itself uses (mg_flatcorr.h), before they are shifted, stored and summed; the other channels are read
+// from the image block as they are.  The flat pair of a lane's dword is loaded once per window row (beside the pixel
+// loads, so it rides in the same software pipeline) and its factors rk = rcp(flat) * (M1 / M2) are made once per row
+// for all raw channels: the planes of an assay share one group of maxima.  FUSE 1: an integer-valued scalar dark
+// (subtracted in the integer domain, two pixels per instruction), 2: any scalar dark.
+struct RoiRaw {
+  const uint16_t* raw;   // the uncorrected stack, laid out as the image block (same assay stride)
+  const float* flat;     // float32 flat image (h, w), or nullptr: the scalar flat_s
+  const double* max2;    // double[groups][2], the maxima of the correction's pass 1
+  double flat_s, dark;
+  int planes_per_group;  // a multiple of n_c * n_t: the planes of an assay share one group
+  uint32_t chan_mask;    // bit c: channel c is gathered from the raw stack
+};
+
+// the two pixels of a dword through the correction
+template <bool INT_DARK>
+__device__ __forceinline__ uint32_t roi_correct_dword(uint32_t d, uint32_t dark_i, double dark, const double (&fl)[2],
+                                                      const double (&rk)[2], bool rk_bad,
+                                                      const double* __restrict__ d_max2, int group) {
+  const uint16_t x[2] = {(uint16_t)(d & 0xFFFFu), (uint16_t)(d >> 16)};
+  const double dk[2] = {dark, dark};
+  uint16_t o[2];
+  correct_chunk_rk<uint16_t, 2, INT_DARK>(x, dark_i, dk, fl, rk, rk_bad, d_max2, group, 1, o);
+  return (uint32_t)o[0] | ((uint32_t)o[1] << 16);
+}
+
+// Registers: 62 VGPRs / 8 waves per SIMD without FUSE; the float64 correction brings the fused variants to 97 (4 waves)
+// when the compiler is left alone, 89 without scratch when asked for 5 -- asked for 6 it spills 11 registers.  The
+// hint leaves the plain variant's code as it was.
+template <int U, int CTB, bool PIPE, int FUSE = 0>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(5, 8))) void k_roi_u16_even(const uint16_t* __restrict__ d_image, int64_t assay_stride,
                                                      int n_c, int n_t, int h, int w,
                                                      const int32_t* __restrict__ d_beads,
                                                      const int32_t* __restrict__ d_marker_assay,
@@ -309,7 +341,7 @@ __global__ __launch_bounds__(NT) void k_roi_u16_even(const uint16_t* __restrict_
                                                      const int32_t* __restrict__ d_halfwidths, int max_r,
                                                      uint16_t* __restrict__ d_roi, uint8_t* __restrict__ d_fg,
                                                      uint8_t* __restrict__ d_bg, double* __restrict__ d_sums,
-                                                     int32_t* __restrict__ d_counts) {
+                                                     int32_t* __restrict__ d_counts, RoiRaw rw) {
   extern __shared__ __attribute__((aligned(4))) uint8_t smem[];  // three bit-row arrays of len x wpr words
   constexpr int WV = NT / 64;
   __shared__ uint32_t s_red[2][CTB][WV];
@@ -411,14 +443,27 @@ __global__ __launch_bounds__(NT) void k_roi_u16_even(const uint16_t* __restrict_
   const uint32_t shift = odd ? 16u : 0u;
   const uint32_t lidx = (uint32_t)min(lane, half - 1 + odd);  // idle lanes repeat the last dword: no branch around a load
   const int64_t plane_elems = (int64_t)h * w;
+  // FUSE: the assay's group of maxima, its quotient and whether the fast path holds for it (uniform, once)
+  const int group = FUSE ? (int)(((int64_t)assay * nct) / rw.planes_per_group) : 0;
+  double kk = 1.0;
+  bool group_ok = false;
+  if (FUSE) {
+    group_ok = group_quotient(rw.max2[2 * group], rw.max2[2 * group + 1], kk);
+    kk = uniform_f64(kk);
+  }
+  const uint32_t dark_i = FUSE == 1 ? (uint32_t)rw.dark : 0u;
+  const uint16_t* rawimg = FUSE ? rw.raw + (int64_t)assay * assay_stride : nullptr;
   for (int ct0 = 0; ct0 < nct; ct0 += CTB) {
     // outputs are (channel, time)-ordered; the image block may be stored time-major (t, c, h, w)
     const uint32_t* plane[CTB];
     uint32_t* out[CTB];
+    uint32_t raw_c = 0u;  // FUSE: which of this trip's planes are raw (the launcher refuses time_major)
 #pragma unroll
     for (int c = 0; c < CTB; ++c) {
       const int ct = min(ct0 + c, nct - 1);
-      plane[c] = reinterpret_cast<const uint32_t*>(img + (int64_t)(time_major ? (ct % n_t) * n_c + ct / n_t : ct) * plane_elems);
+      const bool is_raw = FUSE && ((rw.chan_mask >> (ct / n_t)) & 1u);
+      raw_c |= is_raw ? (1u << c) : 0u;
+      plane[c] = reinterpret_cast<const uint32_t*>((is_raw ? rawimg : img) + (int64_t)(time_major ? (ct % n_t) * n_c + ct / n_t : ct) * plane_elems);
       out[c] = d_roi ? reinterpret_cast<uint32_t*>(d_roi + ((int64_t)g * nct + ct) * n) : nullptr;
     }
     uint32_t sf[CTB], sb[CTB];
@@ -427,20 +472,23 @@ __global__ __launch_bounds__(NT) void k_roi_u16_even(const uint16_t* __restrict_
     // U rows x CTB planes per trip and wave, software-pipelined: the loads of the NEXT trip are issued before this
     // trip's dwords are shifted, stored and summed (the gather is latency-bound otherwise: a wave would sit out a
     // full load round trip, and the write acknowledgements of its stores, between two batches of requests)
-    auto load_rows = [&](int r0, uint32_t (&dd)[U][CTB]) {
+    // (FUSE: ff = the flat values of the dword's two pixels -- the pair before the funnel shift, 8-byte aligned)
+    auto load_rows = [&](int r0, uint32_t (&dd)[U][CTB], float2 (&ff)[U]) {
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int ry = min(r0 + u * WV, len - 1);
         const uint32_t di = (uint32_t)(((top + ry) * w + left - odd) >> 1) + lidx;  // dword index in the plane (h w < 2^31)
 #pragma unroll
         for (int c = 0; c < CTB; ++c) dd[u][c] = plane[c][di];
+        if (FUSE && rw.flat) ff[u] = reinterpret_cast<const float2*>(rw.flat)[di];
       }
     };
     uint32_t dd[U][CTB], dn[U][CTB];
-    load_rows(wave, dd);
+    float2 ff[U], fn[U];
+    load_rows(wave, dd, ff);
     for (int r0 = wave; r0 < len; r0 += WV * U) {
       if (PIPE) {
-        load_rows(r0 + WV * U, dn);  // (rows beyond the window repeat its last row: no branch)
+        load_rows(r0 + WV * U, dn, fn);  // (rows beyond the window repeat its last row: no branch)
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -448,10 +496,21 @@ __global__ __launch_bounds__(NT) void k_roi_u16_even(const uint16_t* __restrict_
         if (ry >= len) break;  // wave-uniform
         const uint32_t mf = roi_pair((fgw[ry * wpr + mword] >> msh) & 3u), mb = roi_pair((bgw[ry * wpr + mword] >> msh) & 3u);
         const uint32_t oi = (uint32_t)(ry * half + lane);
+        double fl[2], rk[2];
+        bool rk_bad = false;
+        if (FUSE && raw_c) {  // the row's factors, shared by its raw planes
+          fl[0] = rw.flat ? (double)ff[u].x : rw.flat_s;
+          fl[1] = rw.flat ? (double)ff[u].y : rw.flat_s;
+          const double rr[2] = {refined_rcp(fl[0]), refined_rcp(fl[1])};
+          const bool rk_large = chunk_factors<2>(rr, kk, rk);
+          rk_bad = rk_large || rr[0] == 0.0 || rr[1] == 0.0 || !group_ok;
+        }
 #pragma unroll
         for (int c = 0; c < CTB; ++c) {
           if (ct0 + c >= nct) break;  // uniform
-          const uint32_t d = dd[u][c];
+          uint32_t d = dd[u][c];
+          if (FUSE && ((raw_c >> c) & 1u))  // (uniform; every lane, idle ones too: the shift below reads lane + 1)
+            d = roi_correct_dword<FUSE == 1>(d, dark_i, rw.dark, fl, rk, rk_bad, rw.max2, group);
           const uint32_t nx = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)d, 0x130, 0xF, 0xF, false);  // lane + 1
           const uint32_t v = __builtin_amdgcn_alignbit(nx, d, shift);
           if (act) {
@@ -466,8 +525,12 @@ __global__ __launch_bounds__(NT) void k_roi_u16_even(const uint16_t* __restrict_
         for (int u = 0; u < U; ++u)
 #pragma unroll
           for (int c = 0; c < CTB; ++c) dd[u][c] = dn[u][c];
+        if (FUSE) {
+#pragma unroll
+          for (int u = 0; u < U; ++u) ff[u] = fn[u];
+        }
       } else if (r0 + WV * U < len) {
-        load_rows(r0 + WV * U, dd);
+        load_rows(r0 + WV * U, dd, ff);
       }
     }
     if (d_sums) {
@@ -950,12 +1013,34 @@ int roi_dispatch(const void* d_image, int dtype, int64_t assay_stride, int n_c, 
                  const int32_t* d_beads, const int32_t* d_marker_assay, const int32_t* d_marker_local, int m, int roi_len,
                  const int32_t* d_labels, const int32_t* d_assay_offsets, int64_t bead_stride, int time_major, int n_assays,
                  const int32_t* d_order, const int32_t* d_halfwidths, int max_r, void* d_roi, uint8_t* d_fg, uint8_t* d_bg,
-                 double* d_sums, int32_t* d_counts, void* stream) {
+                 double* d_sums, int32_t* d_counts, void* stream, const RoiRaw* fuse = nullptr) {
   if (!d_image || !d_beads || m < 0 || roi_len <= 0 || n_c <= 0 || n_t <= 0) return MG_EINVAL;
   if (roi_len > h || roi_len > w || roi_lds_bytes(roi_len, d_halfwidths != nullptr) > 60000) return MG_EINVAL;
   if (m == 0) return MG_OK;
   hipStream_t s = mg_stream(stream);
   const dim3 grid(m);
+  if (fuse) {
+    // the fast window kernel's own conditions, 16-byte aligned bases, one geometry for the raw stack and the image
+    // block; anything else is refused (the caller corrects the channels with the correction pass and gathers as usual)
+    const auto al = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; };
+    if (dtype != MG_U16 || (roi_len & 1) || roi_len > 126 || (w & 1) || (assay_stride & 7) || (int64_t)h * w >= (1LL << 31) ||
+        time_major || !fuse->raw || !fuse->max2 || n_c > 31 || (fuse->chan_mask >> n_c) || fuse->planes_per_group <= 0 ||
+        fuse->planes_per_group % (n_c * n_t) || !al(d_image, 16) || !al(fuse->raw, 16) || !al(fuse->flat, 16) ||
+        !al(fuse->max2, 8) || (d_roi && !al(d_roi, 4)) || (d_fg && !al(d_fg, 2)) || (d_bg && !al(d_bg, 2)))
+      return MG_EINVAL;
+#define MG_ROI_FUSED(F) \
+    hipLaunchKernelGGL((k_roi_u16_even<2, 4, true, F>), grid, dim3(NT), (size_t)mask_words(roi_len) * 4, s, \
+                       (const uint16_t*)d_image, assay_stride, n_c, n_t, h, w, d_beads, d_marker_assay, d_marker_local, \
+                       roi_len, d_labels, d_assay_offsets, n_assays, bead_stride, time_major, d_order, d_halfwidths, max_r, \
+                       (uint16_t*)d_roi, d_fg, d_bg, d_sums, d_counts, *fuse)
+    if (dark_is_int(nullptr, fuse->dark))
+      MG_ROI_FUSED(1);
+    else
+      MG_ROI_FUSED(2);
+#undef MG_ROI_FUSED
+    MG_CHECK_LAUNCH();
+    return MG_OK;
+  }
   // MG_ROI_TILES=1 (looked at on every call: the tests switch it): the image-centric pass of round 4 -- masks from the
   // bead tables of whole assays, uint16, 16-byte aligned rows.  Measured at C4 (profiles/r4_roi_tiles.txt): 21.9 GB of
   // HBM traffic instead of 28.2 (fetches 15.7 -> 8.5 GB: every line once), but 7.05 ms against 4.37 -- 16 waves per CU
@@ -992,7 +1077,7 @@ int roi_dispatch(const void* d_image, int dtype, int64_t assay_stride, int n_c, 
     hipLaunchKernelGGL((k_roi_u16_even<2, 4, true>), grid, dim3(NT), (size_t)mask_words(roi_len) * 4, s,
                        (const uint16_t*)d_image, assay_stride, n_c, n_t, h, w, d_beads, d_marker_assay, d_marker_local,
                        roi_len, d_labels, d_assay_offsets, n_assays, bead_stride, time_major, d_order, d_halfwidths, max_r, (uint16_t*)d_roi, d_fg, d_bg,
-                       d_sums, d_counts);
+                       d_sums, d_counts, RoiRaw{});
     MG_CHECK_LAUNCH();
     return MG_OK;
   }
@@ -1173,6 +1258,22 @@ extern "C" int mg_roi_segment_reduce(const void* d_image, int dtype, int64_t ass
   return roi_dispatch(d_image, dtype, assay_stride, n_c, n_t, h, w, d_beads, nullptr, nullptr, m, roi_len, nullptr,
                       d_assay_offsets, bead_stride, time_major, n_assays, d_order, d_halfwidths, max_r, d_roi, d_fg, d_bg,
                       d_sums, d_counts, stream);
+}
+
+extern "C" int mg_roi_segment_reduce_raw(const void* d_image, const void* d_raw, int dtype, int64_t assay_stride, int n_c,
+                                         int n_t, int h, int w, int time_major, int raw_channel_mask, double dark,
+                                         double flat, const float* d_flat, const double* d_max2, int planes_per_group,
+                                         const int32_t* d_beads, int64_t bead_stride, const int32_t* d_assay_offsets,
+                                         int n_assays, int m, const int32_t* d_order, int roi_len,
+                                         const int32_t* d_halfwidths, int max_r, void* d_roi, uint8_t* d_fg, uint8_t* d_bg,
+                                         double* d_sums, int32_t* d_counts, void* stream) {
+  if (!d_assay_offsets || !d_halfwidths || n_assays <= 0 || n_assays > 65535 || max_r < 0 || bead_stride < 0 ||
+      raw_channel_mask < 0)
+    return MG_EINVAL;
+  const RoiRaw rw{(const uint16_t*)d_raw, d_flat, d_max2, flat, dark, planes_per_group, (uint32_t)raw_channel_mask};
+  return roi_dispatch(d_image, dtype, assay_stride, n_c, n_t, h, w, d_beads, nullptr, nullptr, m, roi_len, nullptr,
+                      d_assay_offsets, bead_stride, time_major, n_assays, d_order, d_halfwidths, max_r, d_roi, d_fg, d_bg,
+                      d_sums, d_counts, stream, &rw);
 }
 
 extern "C" int mg_roi_gather_reduce(const void* d_image, int dtype, int n_c, int n_t, int h, int w,

@@ -231,6 +231,41 @@ def flatfield_stitch(tiles: torch.Tensor, overlap: int, flatfield=1.0, darkfield
     return image, minmax
 
 
+def flatfield_apply_planes(tiles: torch.Tensor, overlap: int, flatfield, darkfield, max2: torch.Tensor, plane_mask: int,
+                           planes_per_group: int, out: torch.Tensor, minmax_out: torch.Tensor, init_minmax=True):
+    """Pass 2 of ``flatfield_stitch`` for the planes c of every group of ``planes_per_group`` planes with bit c set in
+    ``plane_mask`` (mg_flatfield_apply_stitch_planes): they are written to their place in ``out`` and their rows of
+    ``minmax_out``; everything else in both is left as it is.  ``init_minmax``: all rows start from (+inf, -inf) --
+    the first selection of a stack; a later call with the complementary mask (``init_minmax=False``) completes ``out``
+    and ``minmax_out`` to what the full pass writes.  Timed as the full pass's stage."""
+    require_gpu()
+    c, t, nr, nc, ty, tx = tiles.shape
+    assert tiles.is_contiguous() and out.is_contiguous() and out.dtype == tiles.dtype
+    assert minmax_out.is_contiguous() and minmax_out.numel() == c * t * 2 and minmax_out.dtype == torch.float64
+    assert (c * t) % planes_per_group == 0 and max2.numel() == 2 * (c * t) // planes_per_group
+    dk, dkt, dkc = _df_operand(darkfield, ty, tx, tiles.device)
+    fl, flt, flc = _df_operand(flatfield, ty, tx, tiles.device)
+    if init_minmax:
+        minmax_out.view(-1, 2).copy_(_minmax_init(c * t, tiles.device))
+    _call("mg_flatfield_apply_stitch_planes", tiles.data_ptr(), nat.dtype_code(tiles.dtype), c * t, nr, nc, ty, tx, overlap,
+          int(planes_per_group), int(plane_mask), dk, _ptr(dkt), dkc, fl, _ptr(flt), flc, max2.data_ptr(), out.data_ptr(),
+          minmax_out.data_ptr(), _stream(), stage="mg_flatfield_apply_stitch")
+    return out, minmax_out
+
+
+RawChannels = namedtuple("RawChannels", "stack mask flatfield darkfield max2 planes_per_group complete")
+RawChannels.__doc__ = """What ``roi_gather_reduce(raw=...)`` needs to gather channels that have no corrected copy in the
+image block: the raw ``stack`` (laid out as the image block), the bit ``mask`` of those channels, the correction's
+operands (scalar dark; flat scalar or a float32 device image), the maxima ``max2`` of pass 1 with their
+``planes_per_group``, and ``complete()``: corrects those channels into the image block with the correction pass -- the
+way out when the fused kernel refuses the call (MG_EINVAL)."""
+
+
+def fused_roi_enabled() -> bool:
+    """MG_FUSED_ROI=0 (looked at on every call) keeps the non-searched channels in the full correction pass."""
+    return os.environ.get("MG_FUSED_ROI", "1") != "0"
+
+
 _MINMAX_INIT = {}
 
 
@@ -1240,7 +1275,7 @@ def _window_order(d_beads, bead_stride, d_off, n_assays, m, pool_tag, planes=1):
 
 def roi_gather_reduce(images: torch.Tensor, centers_per_assay, roi_len: int, labels: torch.Tensor | None,
                       want_roi=True, want_masks=True, want_sums=True, reuse_buffers=False, disks=False,
-                      device_tables=None, time_major=False, device_counts=None, pool_tag=""):
+                      device_tables=None, time_major=False, device_counts=None, pool_tag="", raw=None):
     """images (A, C, T, h, w) -- or, with ``time_major`` (and ``disks``), (A, T, C, h, w): the outputs
     are (channel, time)-ordered either way; centers_per_assay: list of (M_a, >=2) int arrays [row, col, ...].
 
@@ -1260,7 +1295,11 @@ def roi_gather_reduce(images: torch.Tensor, centers_per_assay, roi_len: int, lab
     Returns dict: roi (M, C, T, L, L), fg/bg (M, L, L) uint8, sums (M, C, T, 2) float64
     [fg sum, bg sum], counts (M, 2) int32, offsets (A+1,) numpy.  ``reuse_buffers`` returns views of
     pooled buffers that the next call overwrites (steady-state streaming use); ``pool_tag`` names a separate set of them
-    (a streaming caller alternates two: the host copy of one chunk's outputs runs beside the next chunk's pass)."""
+    (a streaming caller alternates two: the host copy of one chunk's outputs runs beside the next chunk's pass).
+
+    ``raw`` (a ``RawChannels``, with ``disks``): the channels of ``raw.mask`` are not valid in ``images`` -- they are
+    gathered from the raw stack and corrected by the ROI kernel itself (mg_roi_segment_reduce_raw); if that kernel
+    refuses the call, ``raw.complete()`` corrects them into ``images`` first and the pass runs as without ``raw``."""
     require_gpu()
     if time_major:
         if not disks:
@@ -1302,9 +1341,7 @@ def roi_gather_reduce(images: torch.Tensor, centers_per_assay, roi_len: int, lab
         # where the markers' rows and offsets are on the device (marker_table reads them there)
         res["device_tables"] = (d_tab, int(d_tab.shape[1]), d_off)
         d_order = _window_order(d_tab, d_tab.shape[1], d_off, a, m, pool_tag if reuse_buffers else None, c * t)
-        _call("mg_roi_segment_reduce", images.data_ptr(), nat.dtype_code(images.dtype), c * t * h * w, c, t, h, w,
-              int(time_major), d_tab.data_ptr(), d_tab.shape[1], d_off.data_ptr(), a, m, _ptr(d_order), L, tab.data_ptr(), max_r,
-              _ptr(res["roi"]), _ptr(res["fg"]), _ptr(res["bg"]), _ptr(res["sums"]), _ptr(res["counts"]), _stream())
+        _segment_reduce(images, raw, c, t, h, w, time_major, d_tab, d_tab.shape[1], d_off, a, m, d_order, L, tab, max_r, res)
         return res
     beads = np.zeros((m, 3), dtype=np.int32)
     assay = np.zeros(m, dtype=np.int32)
@@ -1322,10 +1359,10 @@ def roi_gather_reduce(images: torch.Tensor, centers_per_assay, roi_len: int, lab
         tab = _halfwidth_table(max_r, dev)
         d_off = torch.from_numpy(offsets.astype(np.int32)).to(dev)
         d_order = _window_order(d_beads, 0, d_off, a, m, pool_tag if reuse_buffers else None, c * t)
-        _call("mg_roi_segment_reduce", images.data_ptr(), nat.dtype_code(images.dtype), c * t * h * w, c, t, h, w,
-              int(time_major), d_beads.data_ptr(), 0, d_off.data_ptr(), a, m, _ptr(d_order), L, tab.data_ptr(), max_r,
-              _ptr(res["roi"]), _ptr(res["fg"]), _ptr(res["bg"]), _ptr(res["sums"]), _ptr(res["counts"]), _stream())
+        _segment_reduce(images, raw, c, t, h, w, time_major, d_beads, 0, d_off, a, m, d_order, L, tab, max_r, res)
         return res
+    if raw is not None:
+        raise ValueError("raw channels need the bead-table masks (disks=True)")
     d_assay = torch.from_numpy(assay).to(dev)
     d_local = torch.from_numpy(local).to(dev)
     _call("mg_roi_gather_reduce_batched", 
@@ -1333,6 +1370,30 @@ def roi_gather_reduce(images: torch.Tensor, centers_per_assay, roi_len: int, lab
         d_assay.data_ptr(), d_local.data_ptr(), m, L, _ptr(labels), _ptr(res["roi"]), _ptr(res["fg"]),
         _ptr(res["bg"]), _ptr(res["sums"]), _ptr(res["counts"]), _stream())
     return res
+
+
+def _segment_reduce(images, raw, c, t, h, w, time_major, d_beads, bead_stride, d_off, a, m, d_order, L, tab, max_r, res):
+    """The launch of mg_roi_segment_reduce, or of its form that corrects the raw channels itself."""
+    tail = (d_beads.data_ptr(), int(bead_stride), d_off.data_ptr(), a, m, _ptr(d_order), L, tab.data_ptr(), max_r,
+            _ptr(res["roi"]), _ptr(res["fg"]), _ptr(res["bg"]), _ptr(res["sums"]), _ptr(res["counts"]), _stream())
+    code = nat.dtype_code(images.dtype)
+    if raw is not None and raw.mask:
+        assert raw.stack.is_contiguous() and raw.stack.numel() == images.numel() and raw.stack.dtype == images.dtype
+        assert raw.max2.numel() * raw.planes_per_group == 2 * a * c * t
+        fl, flt, _ = _df_operand(raw.flatfield, h, w, images.device)
+        assert flt is None or flt.dtype == torch.float32
+        args = (images.data_ptr(), raw.stack.data_ptr(), code, c * t * h * w, c, t, h, w, int(time_major), int(raw.mask),
+                float(raw.darkfield), fl, _ptr(flt), raw.max2.data_ptr(), int(raw.planes_per_group)) + tail
+        if TIMER is _NO_TIMER or _CAPTURING:
+            rc = nat.lib().mg_roi_segment_reduce_raw(*args)
+        else:
+            with TIMER.stage("mg_roi_segment_reduce"):
+                rc = nat.lib().mg_roi_segment_reduce_raw(*args)
+        if rc != -1:  # (MG_EINVAL: not a case the fused kernel takes)
+            nat.check(rc, "mg_roi_segment_reduce_raw")
+            return
+        raw.complete()
+    _call("mg_roi_segment_reduce", images.data_ptr(), code, c * t * h * w, c, t, h, w, int(time_major), *tail)
 
 
 def finish_roi(res, counts):

@@ -80,19 +80,96 @@ class StackProcessor:
         else:
             self.batch = min(self.n_assays, plane_batch or self.n_assays)
             self.finder = hp.CircleFinder(self.batch, h, w, self.min_r, self.max_r, num_iter, device=device)
-        self.image = torch.empty((n_t, n_c, h, w), dtype=dtype, device=self.dev)
-        self.minmax = torch.empty((n_t, n_c, 2), dtype=torch.float64, device=self.dev)
+        self._image = torch.empty((n_t, n_c, h, w), dtype=dtype, device=self.dev)
+        self._minmax = torch.empty((n_t, n_c, 2), dtype=torch.float64, device=self.dev)
+        self._raw = None        # hp.RawChannels of the last call when it left channels to the ROI pass, else None
+        self._deferred = False  # those channels are still missing from the image block / minmax
+
+    # ---- the corrected stack ----------------------------------------------------------------------------------------
+    # A call on a device-resident, un-tiled uint16 stack (single stream, mode P) corrects only the SEARCHED channels as
+    # full frames: detection is their only full-frame consumer.  The other channels are read by the ROI pass alone,
+    # which gathers their windows from the raw stack and corrects those pixels itself (mg_roi_segment_reduce_raw; one
+    # definition of the arithmetic, csrc/mg_flatcorr.h) -- three quarters of the correction pass's traffic at four
+    # channels are not moved at all.  ``image`` / ``minmax`` stay what they were for a reader: the first access after
+    # such a call runs the correction pass for the channels left out (same raw stack, same maxima, the same kernel).
+    # For this the processor holds a reference to the caller's stack (and flat-field image) until the next call; a
+    # caller that overwrites the stack in place before reading ``image`` gets the correction of the new content.
+    # MG_FUSED_ROI=0 keeps every channel in the correction pass.
+    @property
+    def image(self):
+        """The corrected stack (T, C, H, W), complete (see above: completed on first access where a call deferred it)."""
+        self._complete()
+        return self._image
+
+    @image.setter
+    def image(self, block):
+        self._image = block
+
+    @property
+    def minmax(self):
+        """Per-plane (min, max) of ``image`` (T, C, 2), complete."""
+        self._complete()
+        return self._minmax
+
+    @minmax.setter
+    def minmax(self, block):
+        self._minmax = block
+
+    def _complete(self):
+        if not self._deferred:
+            return
+        self._deferred = False
+        r = self._raw
+        hp.flatfield_apply_planes(r.stack.view(self.T * self.C, 1, *self.tile_grid), 0, r.flatfield, r.darkfield, r.max2,
+                                  r.mask, self.C, out=self._image, minmax_out=self._minmax, init_minmax=False)
+
+    def _fused_flat(self, stack, flatfield, darkfield):
+        """The flat operand as the fused path takes it (scalar or a float32 device image) when this call can leave the
+        non-searched channels to the ROI pass, else None: the conditions of mg_roi_segment_reduce_raw."""
+        T, C, h, w = self.T, self.C, self.h, self.w
+        scalar = lambda v: np.isscalar(v) or (isinstance(v, np.ndarray) and v.ndim == 0)  # noqa: E731
+        deferred = [c for c in range(C) if c not in self.search_channels]
+        if (not hp.fused_roi_enabled() or self.mode != "P" or self.n_streams > 1 or not deferred or C > 31
+                or not all(0 <= c < C for c in self.search_channels)
+                or not (isinstance(stack, torch.Tensor) and stack.is_cuda and stack.dtype == torch.uint16
+                        and self._image.dtype == torch.uint16 and stack.is_contiguous() and tuple(stack.shape) == (T, C, h, w))
+                or self.tile_grid != (1, 1, h, w) or self.overlap or self.L % 2 or self.L > 126 or self.L > min(h, w) or w % 2
+                or not scalar(darkfield) or stack.data_ptr() % 16 or self._image.data_ptr() % 16):
+            return None
+        if scalar(flatfield):
+            return None if hp.flatfield_is_identity(stack.dtype, flatfield, darkfield) else float(flatfield)
+        if isinstance(flatfield, np.ndarray) and flatfield.dtype == np.float32 and flatfield.shape == (h, w):
+            flatfield = torch.from_numpy(np.ascontiguousarray(flatfield)).to(self.dev)
+        if (isinstance(flatfield, torch.Tensor) and flatfield.dtype == torch.float32 and flatfield.device == stack.device
+                and tuple(flatfield.shape) == (h, w) and flatfield.is_contiguous() and flatfield.data_ptr() % 16 == 0):
+            return flatfield
+        return None
+
+    def _correct(self, stack, flatfield, darkfield, fused_flat=None):
+        """The correction pass of a call: every channel (``flatfield``), or -- ``fused_flat`` from _fused_flat -- the
+        searched channels only; the ROI passes of the call then get ``self._raw``."""
+        if fused_flat is None:
+            return self.flatfield(stack, flatfield, darkfield)
+        T, C = self.T, self.C
+        tiles = stack.view(T * C, 1, *self.tile_grid)
+        searched = sum(1 << c for c in set(self.search_channels))
+        max2 = hp.flatfield_max(tiles, fused_flat, darkfield, n_groups=T)
+        hp.flatfield_apply_planes(tiles, 0, fused_flat, darkfield, max2, searched, C, out=self._image, minmax_out=self._minmax)
+        self._raw = hp.RawChannels(stack, ((1 << C) - 1) & ~searched, fused_flat, float(darkfield), max2, C, self._complete)
+        self._deferred = True
+        return self._image
 
     def flatfield(self, stack: torch.Tensor, flatfield=1.0, darkfield=0.0, max2=None):
-        """stack (T, C, H, W) -- or (T, C, rows, cols, tile_y, tile_x) with a tile grid -- -> self.image
-        (T, C, H, W), self.minmax (T, C, 2)."""
+        """stack (T, C, H, W) -- or (T, C, rows, cols, tile_y, tile_x) with a tile grid -- -> self._image
+        (T, C, H, W), self._minmax (T, C, 2)."""
         T, C = self.T, self.C
+        self._raw, self._deferred = None, False
         tiles = stack.view(T * C, 1, *self.tile_grid)
         # mode P: every time slice is its own assay -> its own pair of maxima (n_groups = T);
         # mode R: single assay, the maxima span the whole stack (preprocess.py:84,86)
-        hp.flatfield_stitch(tiles, self.overlap, flatfield, darkfield, out=self.image, minmax_out=self.minmax, max2=max2,
+        hp.flatfield_stitch(tiles, self.overlap, flatfield, darkfield, out=self._image, minmax_out=self._minmax, max2=max2,
                             n_groups=T if self.mode == "P" else 1)
-        return self.image
+        return self._image
 
     def detect(self, seed=0):
         """Bead tables per assay: list of (M_a, 3) int32 [row, col, r] (find.py:475-501)."""
@@ -108,8 +185,8 @@ class StackProcessor:
                 # instead of being ragged; already finished assays are skipped on output)
                 lo = min(done, len(assays) - self.batch)
                 ids = assays[lo : lo + self.batch]
-                planes = self.image[lo : lo + self.batch, ch]  # strided view, no copy
-                mm = self.minmax[lo : lo + self.batch, ch].contiguous()
+                planes = self._image[lo : lo + self.batch, ch]  # strided view, no copy
+                mm = self._minmax[lo : lo + self.batch, ch].contiguous()
                 seeds = [(seed + 1000003 * a + 7919 * k) & 0xFFFFFFFFFFFFFFFF for a in ids]
                 res, _ = self.finder.find(planes, mm, self.low_q, self.high_q, self.min_roundness, self.min_r, seeds,
                                           stable_input=True)  # (a view of this processor's own image block)
@@ -148,11 +225,11 @@ class StackProcessor:
                         if host:
                             self.stage.view(stack.shape)[lo:hi].copy_(stack[lo:hi], non_blocking=True)
                         if tiles is not None:
-                            hp.flatfield_stitch(tiles[lo * C : hi * C], self.overlap, flatfield, darkfield, out=self.image[lo:hi],
-                                                minmax_out=self.minmax[lo:hi], n_groups=hi - lo)
+                            hp.flatfield_stitch(tiles[lo * C : hi * C], self.overlap, flatfield, darkfield, out=self._image[lo:hi],
+                                                minmax_out=self._minmax[lo:hi], n_groups=hi - lo)
                         for j, ch in enumerate(self.search_channels):
-                            planes = self.image[lo:hi, ch]
-                            mm = self.minmax[lo:hi, ch].contiguous()
+                            planes = self._image[lo:hi, ch]
+                            mm = self._minmax[lo:hi, ch].contiguous()
                             seeds = [(seed + 1000003 * a + 7919 * j) & 0xFFFFFFFFFFFFFFFF for a in range(lo, hi)]
                             res, _ = self.finders[k].find(planes, mm, self.low_q, self.high_q, self.min_roundness,
                                                           self.min_r, seeds)
@@ -177,28 +254,30 @@ class StackProcessor:
     def segment_reduce(self, beads, want_roi=True, image=None, pool_tag=None):
         """fg/bg masks, ROI gather and masked sums for every marker (find.py:561-602)."""
         T, C, h, w = self.T, self.C, self.h, self.w
-        image = self.image if image is None else image
+        image = self._image if image is None else image
         tag = self.pool_tag if pool_tag is None else pool_tag
         # masks straight from the bead tables (mg_roi_segment_reduce): no label map is written or read
         if self.mode == "P":
             return hp.roi_gather_reduce(image.view(T, C, 1, h, w), beads, self.L, None, want_roi=want_roi,
-                                        reuse_buffers=True, disks=True, pool_tag=tag)
+                                        reuse_buffers=True, disks=True, pool_tag=tag, raw=self._raw)
         # mode R: one assay whose image block is stored (T, C, h, w); gathered in place (time_major)
         return hp.roi_gather_reduce(image.view(1, T, C, h, w), beads, self.L, None, want_roi=want_roi,
                                     reuse_buffers=True, disks=True, time_major=True, pool_tag=tag)
 
     def __call__(self, stack, flatfield=1.0, darkfield=0.0, seed=0, want_roi=True):
         if self.n_streams > 1 and self.mode == "P":
+            self._raw, self._deferred = None, False
             beads = [np.empty((0, 3), dtype=np.int32) for _ in range(self.n_assays)]
             beads = self._detect_streams(seed, beads, stack, flatfield, darkfield)  # flat-field per sub-batch
         else:
+            fused_flat = self._fused_flat(stack, flatfield, darkfield)  # (a host-resident stack keeps the full pass)
             if not stack.is_cuda:
                 stack = stack.to(self.dev, non_blocking=True)
             tries = self._placement_tries()
             if tries:
-                self._trial_image_blocks(stack, flatfield, darkfield, tries[0])
+                self._trial_image_blocks(stack, flatfield, darkfield, tries[0], fused_flat)
             else:
-                self.flatfield(stack, flatfield, darkfield)
+                self._correct(stack, flatfield, darkfield, fused_flat)
             if self.mode == "P" and len(self.search_channels) == 1 and self.batch >= self.n_assays:
                 out = self._detect_reduce_on_device(seed, want_roi)
                 return self._trial_roi_sets(out, want_roi, tries[1]) if tries else out
@@ -228,7 +307,7 @@ class StackProcessor:
             n_img, n_set = (int(v) for v in os.environ.get("MG_PLACEMENT_TRIES", "6,3").split(","))
         except ValueError:
             return None
-        block = self.image.numel() * self.image.element_size()
+        block = self._image.numel() * self._image.element_size()
         if (n_img < 2 and n_set < 2) or self.pool_tag or self.n_streams > 1 or block < (1 << 31):
             return None  # (small stacks are bound by latencies; the streaming path alternates two sets of its own)
         free, _ = torch.cuda.mem_get_info(self.dev)
@@ -250,19 +329,20 @@ class StackProcessor:
             best = min(best, a.elapsed_time(b))
         return best
 
-    def _trial_image_blocks(self, stack, flatfield, darkfield, tries):
+    def _trial_image_blocks(self, stack, flatfield, darkfield, tries, fused_flat=None):
         """The flat-field passes timed into ``tries`` image blocks.  All of them are kept until the ROI pass has been
-        tried from them too (_trial_roi_sets; each holds the corrected stack); the fastest is self.image meanwhile."""
+        tried from them too (_trial_roi_sets; each holds the corrected stack -- its searched channels where the call
+        leaves the others to the ROI pass); the fastest is self._image meanwhile."""
         blocks, times = [], []
         for k in range(tries):
             if k:
                 try:
-                    self.image = torch.empty_like(self.image)
+                    self._image = torch.empty_like(self._image)
                 except torch.OutOfMemoryError:  # (less free memory than the estimate said: as many blocks as there are)
                     break
-            blocks.append(self.image)
-            times.append(self._timed(lambda: self.flatfield(stack, flatfield, darkfield)))
-        self.image = blocks[int(np.argmin(times))]
+            blocks.append(self._image)
+            times.append(self._timed(lambda: self._correct(stack, flatfield, darkfield, fused_flat)))
+        self._image = blocks[int(np.argmin(times))]
         self._trial_blocks = blocks
         self.placement.update(flatfield_ms=[round(t, 3) for t in times])
 
@@ -279,7 +359,7 @@ class StackProcessor:
         counts = [len(b) for b in out["beads"]]
         res = self._trial_pairs(lambda img, tag: hp.roi_gather_reduce(
             img.view(T, C, 1, h, w), None, self.L, None, want_roi=want_roi, reuse_buffers=True, disks=True,
-            device_tables=(tabs[0], counts, self.max_r), pool_tag=tag), tries, markers=int(sum(counts)))
+            device_tables=(tabs[0], counts, self.max_r), pool_tag=tag, raw=self._raw), tries, markers=int(sum(counts)))
         res["beads"] = out["beads"]
         return res
 
@@ -308,19 +388,19 @@ class StackProcessor:
                 roi_ms = None
         if roi_ms is None:
             hp.drop_pool_tags(tags)
-            self.image = blocks[int(np.argmin(flat_ms))]
+            self._image = blocks[int(np.argmin(flat_ms))]
             del blocks
             torch.cuda.empty_cache()
             self.placement.update(image_block=int(np.argmin(flat_ms)), roi_ms=None, roi_set=None)
-            return run(self.image, self.pool_tag)
+            return run(self._image, self.pool_tag)
         total = np.asarray(roi_ms) + np.asarray(flat_ms)[:, None]
         bi, bj = (int(v) for v in np.unravel_index(int(np.argmin(total)), total.shape))
         hp.drop_pool_tags([t for k, t in enumerate(tags) if k != bj])
-        self.image, self.pool_tag = blocks[bi], tags[bj]
+        self._image, self.pool_tag = blocks[bi], tags[bj]
         del blocks
         torch.cuda.empty_cache()  # the blocks not kept go back to the driver NOW (~0.4 s for 50 GB), not at the next graph capture
         self.placement.update(roi_ms=[[round(t, 3) for t in row] for row in roi_ms], image_block=bi, roi_set=bj)
-        return run(self.image, self.pool_tag)
+        return run(self._image, self.pool_tag)
 
     def _detect_reduce_on_device(self, seed, want_roi):
         """One search channel, the whole stack in one batch: there is no cross-channel de-duplication
@@ -331,16 +411,17 @@ class StackProcessor:
         seeds = [(seed + 1000003 * a) & 0xFFFFFFFFFFFFFFFF for a in range(self.n_assays)]
         # the ROI pass is queued behind the suppression before the host has seen the bead counts (find's `follow`)
         roi_pass = lambda d_out, d_num, cap: hp.roi_gather_reduce(  # noqa: E731
-            self.image.view(T, C, 1, h, w), None, self.L, None, want_roi=want_roi, reuse_buffers=True, disks=True,
-            device_tables=(d_out, None, self.max_r), device_counts=(d_num, cap, self._roi_bound), pool_tag=self.pool_tag)
-        counts, (d_beads, d_scores, _) = self.finder.find(self.image[:, ch], self.minmax[:, ch], self.low_q,
+            self._image.view(T, C, 1, h, w), None, self.L, None, want_roi=want_roi, reuse_buffers=True, disks=True,
+            device_tables=(d_out, None, self.max_r), device_counts=(d_num, cap, self._roi_bound), pool_tag=self.pool_tag,
+            raw=self._raw)
+        counts, (d_beads, d_scores, _) = self.finder.find(self._image[:, ch], self._minmax[:, ch], self.low_q,
                                                            self.high_q, self.min_roundness, self.min_r, seeds,
                                                            host_results=False, follow=roi_pass, stable_input=True)
         out = hp.finish_roi(self.finder.follow_result, counts)
         if out is None:  # more markers than the pass was launched for: once more, with the counts
-            out = hp.roi_gather_reduce(self.image.view(T, C, 1, h, w), None, self.L, None, want_roi=want_roi,
+            out = hp.roi_gather_reduce(self._image.view(T, C, 1, h, w), None, self.L, None, want_roi=want_roi,
                                        reuse_buffers=True, disks=True, device_tables=(d_beads, counts, self.max_r),
-                                       pool_tag=self.pool_tag)
+                                       pool_tag=self.pool_tag, raw=self._raw)
         # the next call's launch bound: 10 % above this call's markers (its workgroups beyond the real count only cost
         # their start; the per-plane capacity x planes would be ~30 % above)
         self._roi_bound = int(1.1 * int(np.sum(counts))) + 16 * self.n_assays
