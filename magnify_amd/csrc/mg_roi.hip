@@ -164,6 +164,68 @@ inline size_t roi_lds_bytes(int len, bool disks) {
   return fl + (disks ? (size_t)3 * len * ((len + 31) >> 5) * 4 : 0);
 }
 
+// The assay of marker g in the assays' concatenated tables = the last one that starts at or before it (empty assays
+// have empty ranges).
+__device__ __forceinline__ int roi_assay_of(const int32_t* __restrict__ d_assay_offsets, int n_assays, int g) {
+  int lo = 0, hi = n_assays;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (d_assay_offsets[mid] <= g) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// The marker a workgroup of the window kernels takes: of a flat list with per-marker assay / local index (label mode),
+// or of the assays' concatenated bead tables (disk mode).
+struct RoiMarker {
+  int g, assay, first, local;  // marker (row of the outputs), its assay, the assay's first marker, index in the assay
+  int64_t bead0, gb;           // the assay's first bead / this marker's bead in d_beads
+};
+// false: nothing to do for this workgroup
+__device__ __forceinline__ bool roi_marker(const int32_t* __restrict__ d_assay_offsets, int n_assays, int64_t bead_stride,
+                                           const int32_t* __restrict__ d_order,
+                                           const int32_t* __restrict__ d_marker_assay,
+                                           const int32_t* __restrict__ d_marker_local, RoiMarker& mk) {
+  int g = blockIdx.x;
+  mk.first = 0;
+  mk.bead0 = 0;
+  mk.gb = g;
+  if (d_assay_offsets) {
+    // flat grid over the markers of all assays (the launch may be sized by an upper bound: the rest leaves at once)
+    if (g >= d_assay_offsets[n_assays]) return false;
+    if (d_order) g = d_order[g];  // the order the windows are visited in (mg_roi_window_order); outputs stay in place
+    mk.assay = roi_assay_of(d_assay_offsets, n_assays, g);
+    mk.first = d_assay_offsets[mk.assay];
+    mk.local = g - mk.first;
+    // bead table: compact (markers and beads share the index) or one padded row per assay
+    mk.bead0 = bead_stride ? (int64_t)mk.assay * bead_stride : mk.first;
+    mk.gb = mk.bead0 + mk.local;
+  } else {
+    mk.assay = d_marker_assay ? d_marker_assay[g] : 0;
+    mk.local = d_marker_local ? d_marker_local[g] : g;
+  }
+  mk.g = g;
+  return true;
+}
+
+// The window's fg / bg pixel counts: per-thread counts -> d_counts[g] (a workgroup of four waves).  Ends behind a
+// barrier: what the workgroup wrote to LDS before the call is complete, too.
+__device__ __forceinline__ void roi_store_counts(int cf, int cb, int (&s_cnt)[2][NT / 64], int g,
+                                                 int32_t* __restrict__ d_counts) {
+  cf = mg_wave_sum_i32(cf);
+  cb = mg_wave_sum_i32(cb);
+  if ((threadIdx.x & 63) == 0) {
+    s_cnt[0][threadIdx.x >> 6] = cf;
+    s_cnt[1][threadIdx.x >> 6] = cb;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && d_counts) {
+    d_counts[2 * (int64_t)g] = s_cnt[0][0] + s_cnt[0][1] + s_cnt[0][2] + s_cnt[0][3];
+    d_counts[2 * (int64_t)g + 1] = s_cnt[1][0] + s_cnt[1][1] + s_cnt[1][2] + s_cnt[1][3];
+  }
+}
+
 template <typename T, typename ACC>
 __global__ __launch_bounds__(NT) void k_roi(const T* __restrict__ d_image, int64_t assay_stride, int n_c, int n_t, int h,
                                             int w, const int32_t* __restrict__ d_beads,
@@ -178,31 +240,10 @@ __global__ __launch_bounds__(NT) void k_roi(const T* __restrict__ d_image, int64
   extern __shared__ __attribute__((aligned(4))) uint8_t flags[];
   __shared__ ACC s_red[2][NT / 64];
   __shared__ int s_cnt[2][NT / 64];
-  // one block per marker: of a flat list with per-marker assay / local index (label mode), or of the assays'
-  // concatenated bead tables (disk mode)
-  int g = blockIdx.x, assay, first = 0, local;
-  int64_t bead0 = 0, gb = g;  // the assay's first bead / this marker's bead in d_beads
-  if (d_assay_offsets) {
-    // flat grid over the markers of all assays (the launch may be sized by an upper bound: the rest leaves at once);
-    // the marker's assay = the last one that starts at or before it
-    if (g >= d_assay_offsets[n_assays]) return;
-    if (d_order) g = d_order[g];  // the order the windows are visited in (mg_roi_window_order); outputs stay in place
-    int lo = 0, hi = n_assays;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (d_assay_offsets[mid] <= g) lo = mid;
-      else hi = mid;
-    }
-    assay = lo;
-    first = d_assay_offsets[assay];
-    local = g - first;
-    // bead table: compact (markers and beads share the index) or one padded row per assay
-    bead0 = bead_stride ? (int64_t)assay * bead_stride : first;
-    gb = bead0 + local;
-  } else {
-    assay = d_marker_assay ? d_marker_assay[g] : 0;
-    local = d_marker_local ? d_marker_local[g] : g;
-  }
+  RoiMarker mk;  // one block per marker
+  if (!roi_marker(d_assay_offsets, n_assays, bead_stride, d_order, d_marker_assay, d_marker_local, mk)) return;
+  const int g = mk.g, assay = mk.assay, first = mk.first, local = mk.local;
+  const int64_t bead0 = mk.bead0, gb = mk.gb;
   const int cy = d_beads[3 * gb], cx = d_beads[3 * gb + 1];
   int top, left;
   window(cy, len, h, top);
@@ -235,17 +276,7 @@ __global__ __launch_bounds__(NT) void k_roi(const T* __restrict__ d_image, int64
     cf += f;
     cb += b;
   }
-  cf = mg_wave_sum_i32(cf);
-  cb = mg_wave_sum_i32(cb);
-  if (lane == 0) {
-    s_cnt[0][wave] = cf;
-    s_cnt[1][wave] = cb;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0 && d_counts) {
-    d_counts[2 * (int64_t)g] = s_cnt[0][0] + s_cnt[0][1] + s_cnt[0][2] + s_cnt[0][3];
-    d_counts[2 * (int64_t)g + 1] = s_cnt[1][0] + s_cnt[1][1] + s_cnt[1][2] + s_cnt[1][3];
-  }
+  roi_store_counts(cf, cb, s_cnt, g, d_counts);
   // gather every (channel, time) window (find.py:589-602) and reduce under the masks
   const T* img = d_image + (int64_t)assay * assay_stride;
   for (int ct = 0; ct < n_c * n_t; ++ct) {
@@ -346,31 +377,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(5, 8))) void
   constexpr int WV = NT / 64;
   __shared__ uint32_t s_red[2][CTB][WV];
   __shared__ int s_cnt[2][WV];
-  // one block per marker: of a flat list with per-marker assay / local index (label mode), or of the assays'
-  // concatenated bead tables (disk mode)
-  int g = blockIdx.x, assay, first = 0, local;
-  int64_t bead0 = 0, gb = g;  // the assay's first bead / this marker's bead in d_beads
-  if (d_assay_offsets) {
-    // flat grid over the markers of all assays (the launch may be sized by an upper bound: the rest leaves at once);
-    // the marker's assay = the last one that starts at or before it
-    if (g >= d_assay_offsets[n_assays]) return;
-    if (d_order) g = d_order[g];  // the order the windows are visited in (mg_roi_window_order); outputs stay in place
-    int lo = 0, hi = n_assays;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (d_assay_offsets[mid] <= g) lo = mid;
-      else hi = mid;
-    }
-    assay = lo;
-    first = d_assay_offsets[assay];
-    local = g - first;
-    // bead table: compact (markers and beads share the index) or one padded row per assay
-    bead0 = bead_stride ? (int64_t)assay * bead_stride : first;
-    gb = bead0 + local;
-  } else {
-    assay = d_marker_assay ? d_marker_assay[g] : 0;
-    local = d_marker_local ? d_marker_local[g] : g;
-  }
+  RoiMarker mk;  // one block per marker
+  if (!roi_marker(d_assay_offsets, n_assays, bead_stride, d_order, d_marker_assay, d_marker_local, mk)) return;
+  const int g = mk.g, assay = mk.assay, first = mk.first, local = mk.local;
+  const int64_t bead0 = mk.bead0, gb = mk.gb;
   int top, left;
   window(d_beads[3 * gb], len, h, top);
   window(d_beads[3 * gb + 1], len, w, left);
@@ -414,17 +424,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(5, 8))) void
       }
     }
   }
-  cf = mg_wave_sum_i32(cf);
-  cb = mg_wave_sum_i32(cb);
-  if (lane == 0) {
-    s_cnt[0][wave] = cf;
-    s_cnt[1][wave] = cb;
-  }
-  __syncthreads();  // bit rows complete, counts in place
-  if (threadIdx.x == 0 && d_counts) {
-    d_counts[2 * (int64_t)g] = s_cnt[0][0] + s_cnt[0][1] + s_cnt[0][2] + s_cnt[0][3];
-    d_counts[2 * (int64_t)g + 1] = s_cnt[1][0] + s_cnt[1][1] + s_cnt[1][2] + s_cnt[1][3];
-  }
+  roi_store_counts(cf, cb, s_cnt, g, d_counts);  // (its barrier completes the bit rows)
   const int mword = x >> 5, msh = x & 31;  // this lane's two bits inside a bit row
   if (d_fg || d_bg) {
     for (int ry = wave; ry < len; ry += WV) {
@@ -980,17 +980,111 @@ int launch_median(const void* d_roi, const uint8_t* d_mask, int64_t sm, int64_t 
   return MG_OK;
 }
 
-template <typename T, typename ACC>
-int launch_roi(const void* d_image, int64_t assay_stride, int n_c, int n_t, int h, int w, const int32_t* d_beads,
-               const int32_t* d_marker_assay, const int32_t* d_marker_local, dim3 grid, int len,
-               const int32_t* d_labels, const int32_t* d_assay_offsets, int n_assays, int64_t bead_stride, int time_major,
-               const int32_t* d_order, const int32_t* d_halfwidths,
-               int max_r, void* d_roi, uint8_t* d_fg, uint8_t* d_bg, double* d_sums, int32_t* d_counts, hipStream_t s) {
-  hipLaunchKernelGGL((k_roi<T, ACC>), grid, dim3(NT), roi_lds_bytes(len, d_halfwidths != nullptr), s,
-                     (const T*)d_image, assay_stride, n_c, n_t, h, w, d_beads, d_marker_assay, d_marker_local, len,
-                     d_labels, d_assay_offsets, n_assays, bead_stride, time_major, d_order, d_halfwidths, max_r, (T*)d_roi, d_fg, d_bg, d_sums, d_counts);
+// ---- host side of the ROI pass ---------------------------------------------------------------------------------------
+// What one call of the pass is given: the entry points fill it, roi_dispatch chooses the kernel.
+struct RoiCall {
+  const void* d_image;
+  int dtype;
+  int64_t assay_stride;
+  int n_c, n_t, h, w;
+  const int32_t* d_beads;
+  int64_t bead_stride;
+  const int32_t *d_marker_assay, *d_marker_local;  // label mode: per-marker assay / index in the assay
+  int m, len;
+  const int32_t* d_labels;
+  const int32_t* d_assay_offsets;  // disk mode: where every assay's markers start
+  int n_assays, time_major;
+  const int32_t *d_order, *d_halfwidths;
+  int max_r;
+  void* d_roi;
+  uint8_t *d_fg, *d_bg;
+  double* d_sums;
+  int32_t* d_counts;
+  hipStream_t stream;
+};
+
+// The window kernels' parameter list (k_roi<T, ACC> and k_roi_u16_even<...> share it; `raw` = the RoiRaw of the
+// latter), one workgroup per marker.
+template <typename T, typename K, typename... Raw>
+int roi_launch(K kernel, size_t lds, const RoiCall& c, Raw... raw) {
+  hipLaunchKernelGGL(kernel, dim3(c.m), dim3(NT), lds, c.stream, (const T*)c.d_image, c.assay_stride, c.n_c, c.n_t, c.h,
+                     c.w, c.d_beads, c.d_marker_assay, c.d_marker_local, c.len, c.d_labels, c.d_assay_offsets, c.n_assays,
+                     c.bead_stride, c.time_major, c.d_order, c.d_halfwidths, c.max_r, (T*)c.d_roi, c.d_fg, c.d_bg, c.d_sums,
+                     c.d_counts, raw...);
   MG_CHECK_LAUNCH();
   return MG_OK;
+}
+
+inline bool aligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
+
+// Can the uint16 even-window kernels take this call?  A lane works on dwords: uint16, an even window of at most 126
+// (a row's dwords fit one wave), dword indices below 2^31, dword stores to d_roi and 2-byte stores to the masks.  What
+// differs between the branches:
+//   fast   (k_roi_u16_even)        image_align 4,  w_div 2, stride_div 2: every plane and row starts on a dword
+//   fused  (k_roi_u16_even, FUSE)  image_align 16, w_div 2, stride_div 8: every assay starts on 16 bytes, in the image
+//                                  block and in the raw stack alike (its other bases: roi_dispatch)
+//   tiles  (k_roi_tiles_u16)       image_align 16, w_div 8, stride_div 8: tile rows are fetched in 16-byte pieces
+bool roi_u16_even_ok(const RoiCall& c, int image_align, int w_div, int stride_div) {
+  return c.dtype == MG_U16 && (c.len & 1) == 0 && c.len <= 126 && (c.w & (w_div - 1)) == 0 &&
+         (c.assay_stride & (stride_div - 1)) == 0 && (int64_t)c.h * c.w < (1LL << 31) && aligned(c.d_image, image_align) &&
+         aligned(c.d_roi, 4) && aligned(c.d_fg, 2) && aligned(c.d_bg, 2);
+}
+
+// MG_ROI_TILES=1 (looked at on every call: the tests switch it): the image-centric pass of round 4 -- masks from the
+// bead tables of whole assays, uint16, 16-byte aligned rows.  Measured at C4 (profiles/r4_roi_tiles.txt): 21.9 GB of
+// HBM traffic instead of 28.2 (fetches 15.7 -> 8.5 GB: every line once), but 7.05 ms against 4.37 -- 16 waves per CU
+// behind 68 KB of LDS and ten barriers per tile leave its latencies in the open.  Not the default.
+constexpr int RT_HW_MAX = 27 * 53 * 4 + 8192;  // bytes of the half-width table the tile kernel may be given in LDS
+bool roi_tiles_wanted(const RoiCall& c) {
+  const char* env = getenv("MG_ROI_TILES");
+  return env && env[0] == '1' && roi_u16_even_ok(c, 16, 8, 8) && c.d_halfwidths && c.d_assay_offsets && !c.d_labels &&
+         c.n_assays > 0 && c.n_assays <= 65535 && (c.bead_stride ? c.bead_stride : (int64_t)c.m) <= 65535 &&
+         c.max_r >= 2 && (c.max_r + 1) * (2 * c.max_r + 1) * 4 <= RT_HW_MAX;
+}
+int roi_launch_tiles(const RoiCall& c) {
+  const int nct = c.n_c * c.n_t;
+  if (c.d_sums && mg_zero_async(c.d_sums, (size_t)c.m * nct * 2 * sizeof(double), c.stream) != hipSuccess) return MG_ELAUNCH;
+  if (c.d_counts && mg_zero_async(c.d_counts, (size_t)c.m * 2 * sizeof(int32_t), c.stream) != hipSuccess) return MG_ELAUNCH;
+  static bool attr_set = false;
+  if (!attr_set) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_roi_tiles_u16), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)RT_LDS + RT_HW_MAX) != hipSuccess)
+      return MG_ELAUNCH;
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(k_roi_tiles_u16, dim3((c.w + RT_W - 1) / RT_W, (c.h + RT_H - 1) / RT_H, c.n_assays), dim3(RTN),
+                     RT_LDS + (size_t)(c.max_r + 1) * (2 * c.max_r + 1) * 4, c.stream, (const uint16_t*)c.d_image,
+                     c.assay_stride, c.n_c, c.n_t, c.h, c.w, c.d_beads, c.bead_stride, c.d_assay_offsets, c.time_major, c.len,
+                     c.d_halfwidths, c.max_r, (uint16_t*)c.d_roi, c.d_fg, c.d_bg, c.d_sums, c.d_counts);
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}
+
+// Argument checks, then the first branch that takes the call: fused (`fuse` given: it or a refusal), tiles, fast, generic.
+int roi_dispatch(const RoiCall& c, const RoiRaw* fuse = nullptr) {
+  if (!c.d_image || !c.d_beads || c.m < 0 || c.len <= 0 || c.n_c <= 0 || c.n_t <= 0) return MG_EINVAL;
+  // (the LDS bound is the generic kernel's; windows beyond it are refused whichever kernel would run)
+  if (c.len > c.h || c.len > c.w || roi_lds_bytes(c.len, c.d_halfwidths != nullptr) > 60000) return MG_EINVAL;
+  if (c.m == 0) return MG_OK;
+  const size_t bit_rows = (size_t)mask_words(c.len) * 4;  // LDS of k_roi_u16_even
+  if (fuse) {
+    // one geometry for the raw stack and the image block; anything the kernel does not take is refused (the caller
+    // corrects the channels with the correction pass and gathers as usual)
+    if (!roi_u16_even_ok(c, 16, 2, 8) || c.time_major || !fuse->raw || !fuse->max2 || c.n_c > 31 ||
+        (fuse->chan_mask >> c.n_c) || fuse->planes_per_group <= 0 || fuse->planes_per_group % (c.n_c * c.n_t) ||
+        !aligned(fuse->raw, 16) || !aligned(fuse->flat, 16) || !aligned(fuse->max2, 8))
+      return MG_EINVAL;
+    if (dark_is_int(nullptr, fuse->dark)) return roi_launch<uint16_t>(k_roi_u16_even<2, 4, true, 1>, bit_rows, c, *fuse);
+    return roi_launch<uint16_t>(k_roi_u16_even<2, 4, true, 2>, bit_rows, c, *fuse);
+  }
+  if (roi_tiles_wanted(c)) return roi_launch_tiles(c);
+  // 2 rows x 4 planes per trip, next trip's loads in flight while this one is worked on (measured at 16 x 4 x 4096^2:
+  // 1.14 ms; without the pipelining 1.22, one row per trip 1.22, 4 rows x 2 planes 1.20, 4 x 4 unpipelined 1.24)
+  if (roi_u16_even_ok(c, 4, 2, 2)) return roi_launch<uint16_t>(k_roi_u16_even<2, 4, true>, bit_rows, c, RoiRaw{});
+  return mg_dispatch_pixel(c.dtype, [&](auto t) {
+    using T = decltype(t);
+    return roi_launch<T>(k_roi<T, mg_acc_t<T>>, roi_lds_bytes(c.len, c.d_halfwidths != nullptr), c);
+  });
 }
 
 }  // namespace
@@ -1007,88 +1101,6 @@ extern "C" int mg_circle_labels(const int32_t* d_beads, int64_t bead_cap, const 
   MG_CHECK_LAUNCH();
   return MG_OK;
 }
-
-namespace {
-int roi_dispatch(const void* d_image, int dtype, int64_t assay_stride, int n_c, int n_t, int h, int w,
-                 const int32_t* d_beads, const int32_t* d_marker_assay, const int32_t* d_marker_local, int m, int roi_len,
-                 const int32_t* d_labels, const int32_t* d_assay_offsets, int64_t bead_stride, int time_major, int n_assays,
-                 const int32_t* d_order, const int32_t* d_halfwidths, int max_r, void* d_roi, uint8_t* d_fg, uint8_t* d_bg,
-                 double* d_sums, int32_t* d_counts, void* stream, const RoiRaw* fuse = nullptr) {
-  if (!d_image || !d_beads || m < 0 || roi_len <= 0 || n_c <= 0 || n_t <= 0) return MG_EINVAL;
-  if (roi_len > h || roi_len > w || roi_lds_bytes(roi_len, d_halfwidths != nullptr) > 60000) return MG_EINVAL;
-  if (m == 0) return MG_OK;
-  hipStream_t s = mg_stream(stream);
-  const dim3 grid(m);
-  if (fuse) {
-    // the fast window kernel's own conditions, 16-byte aligned bases, one geometry for the raw stack and the image
-    // block; anything else is refused (the caller corrects the channels with the correction pass and gathers as usual)
-    const auto al = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; };
-    if (dtype != MG_U16 || (roi_len & 1) || roi_len > 126 || (w & 1) || (assay_stride & 7) || (int64_t)h * w >= (1LL << 31) ||
-        time_major || !fuse->raw || !fuse->max2 || n_c > 31 || (fuse->chan_mask >> n_c) || fuse->planes_per_group <= 0 ||
-        fuse->planes_per_group % (n_c * n_t) || !al(d_image, 16) || !al(fuse->raw, 16) || !al(fuse->flat, 16) ||
-        !al(fuse->max2, 8) || (d_roi && !al(d_roi, 4)) || (d_fg && !al(d_fg, 2)) || (d_bg && !al(d_bg, 2)))
-      return MG_EINVAL;
-#define MG_ROI_FUSED(F) \
-    hipLaunchKernelGGL((k_roi_u16_even<2, 4, true, F>), grid, dim3(NT), (size_t)mask_words(roi_len) * 4, s, \
-                       (const uint16_t*)d_image, assay_stride, n_c, n_t, h, w, d_beads, d_marker_assay, d_marker_local, \
-                       roi_len, d_labels, d_assay_offsets, n_assays, bead_stride, time_major, d_order, d_halfwidths, max_r, \
-                       (uint16_t*)d_roi, d_fg, d_bg, d_sums, d_counts, *fuse)
-    if (dark_is_int(nullptr, fuse->dark))
-      MG_ROI_FUSED(1);
-    else
-      MG_ROI_FUSED(2);
-#undef MG_ROI_FUSED
-    MG_CHECK_LAUNCH();
-    return MG_OK;
-  }
-  // MG_ROI_TILES=1 (looked at on every call: the tests switch it): the image-centric pass of round 4 -- masks from the
-  // bead tables of whole assays, uint16, 16-byte aligned rows.  Measured at C4 (profiles/r4_roi_tiles.txt): 21.9 GB of
-  // HBM traffic instead of 28.2 (fetches 15.7 -> 8.5 GB: every line once), but 7.05 ms against 4.37 -- 16 waves per CU
-  // behind 68 KB of LDS and ten barriers per tile leave its latencies in the open.  Not the default.
-  const char* tiles_env = getenv("MG_ROI_TILES");
-  const bool tiles = tiles_env && tiles_env[0] == '1';
-  if (tiles && dtype == MG_U16 && d_halfwidths && d_assay_offsets && !d_labels && (roi_len & 1) == 0 && roi_len <= 126 &&
-      (w & 7) == 0 && (assay_stride & 7) == 0 && (int64_t)h * w < (1LL << 31) && n_assays > 0 && n_assays <= 65535 &&
-      (bead_stride ? bead_stride : (int64_t)m) <= 65535 && max_r >= 2 && (max_r + 1) * (2 * max_r + 1) * 4 <= 27 * 53 * 4 + 8192 &&
-      (reinterpret_cast<uintptr_t>(d_image) & 15) == 0 && (!d_roi || (reinterpret_cast<uintptr_t>(d_roi) & 3) == 0) &&
-      (!d_fg || (reinterpret_cast<uintptr_t>(d_fg) & 1) == 0) && (!d_bg || (reinterpret_cast<uintptr_t>(d_bg) & 1) == 0)) {
-    const int nct = n_c * n_t;
-    if (d_sums && mg_zero_async(d_sums, (size_t)m * nct * 2 * sizeof(double), s) != hipSuccess) return MG_ELAUNCH;
-    if (d_counts && mg_zero_async(d_counts, (size_t)m * 2 * sizeof(int32_t), s) != hipSuccess) return MG_ELAUNCH;
-    static bool attr_set = false;
-    if (!attr_set) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_roi_tiles_u16), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)RT_LDS + 27 * 53 * 4 + 8192) != hipSuccess)
-        return MG_ELAUNCH;
-      attr_set = true;
-    }
-    hipLaunchKernelGGL(k_roi_tiles_u16, dim3((w + RT_W - 1) / RT_W, (h + RT_H - 1) / RT_H, n_assays), dim3(RTN), RT_LDS + (size_t)(max_r + 1) * (2 * max_r + 1) * 4, s,
-                       (const uint16_t*)d_image, assay_stride, n_c, n_t, h, w, d_beads, bead_stride, d_assay_offsets,
-                       time_major, roi_len, d_halfwidths, max_r, (uint16_t*)d_roi, d_fg, d_bg, d_sums, d_counts);
-    MG_CHECK_LAUNCH();
-    return MG_OK;
-  }
-  if (dtype == MG_U16 && (roi_len & 1) == 0 && roi_len <= 126 && (w & 1) == 0 && (assay_stride & 1) == 0 &&
-      (int64_t)h * w < (1LL << 31) &&
-      (reinterpret_cast<uintptr_t>(d_image) & 3) == 0 && (!d_roi || (reinterpret_cast<uintptr_t>(d_roi) & 3) == 0) &&
-      (!d_fg || (reinterpret_cast<uintptr_t>(d_fg) & 1) == 0) && (!d_bg || (reinterpret_cast<uintptr_t>(d_bg) & 1) == 0)) {
-    // 2 rows x 4 planes per trip, next trip's loads in flight while this one is worked on (measured at 16 x 4 x 4096^2:
-    // 1.14 ms; without the pipelining 1.22, one row per trip 1.22, 4 rows x 2 planes 1.20, 4 x 4 unpipelined 1.24)
-    hipLaunchKernelGGL((k_roi_u16_even<2, 4, true>), grid, dim3(NT), (size_t)mask_words(roi_len) * 4, s,
-                       (const uint16_t*)d_image, assay_stride, n_c, n_t, h, w, d_beads, d_marker_assay, d_marker_local,
-                       roi_len, d_labels, d_assay_offsets, n_assays, bead_stride, time_major, d_order, d_halfwidths, max_r, (uint16_t*)d_roi, d_fg, d_bg,
-                       d_sums, d_counts, RoiRaw{});
-    MG_CHECK_LAUNCH();
-    return MG_OK;
-  }
-  return mg_dispatch_pixel(dtype, [&](auto t) {
-    using T = decltype(t);
-    return launch_roi<T, mg_acc_t<T>>(d_image, assay_stride, n_c, n_t, h, w, d_beads, d_marker_assay, d_marker_local, grid,
-                                      roi_len, d_labels, d_assay_offsets, n_assays, bead_stride, time_major, d_order,
-                                      d_halfwidths, max_r, d_roi, d_fg, d_bg, d_sums, d_counts, s);
-  });
-}
-}  // namespace
 
 namespace {
 // d_offsets[0 .. n] = exclusive prefix of min(d_counts[i], cap): where every assay's markers start in the compact
@@ -1127,12 +1139,7 @@ __global__ __launch_bounds__(256) void k_marker_table(const int32_t* __restrict_
   const int total = d_assay_offsets[n_assays];
   const int width = 6 + 2 * n_c;
   for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < total; g += gridDim.x * blockDim.x) {
-    int lo = 0, hi = n_assays;  // the assay whose offset range holds g (empty assays have empty ranges)
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (d_assay_offsets[mid] <= g) lo = mid;
-      else hi = mid;
-    }
+    const int lo = roi_assay_of(d_assay_offsets, n_assays, g);
     const int local = g - d_assay_offsets[lo];
     const int32_t* b = bead_stride > 0 ? d_beads + ((int64_t)lo * bead_stride + local) * 3 : d_beads + (int64_t)g * 3;
     double* row = d_table + (int64_t)g * width;
@@ -1168,8 +1175,12 @@ extern "C" int mg_roi_gather_reduce_batched(const void* d_image, int dtype, int6
                                             const int32_t* d_marker_local, int m, int roi_len,
                                             const int32_t* d_labels, void* d_roi, uint8_t* d_fg, uint8_t* d_bg,
                                             double* d_sums, int32_t* d_counts, void* stream) {
-  return roi_dispatch(d_image, dtype, assay_stride, n_c, n_t, h, w, d_beads, d_marker_assay, d_marker_local, m, roi_len,
-                      d_labels, nullptr, 0, 0, 0, nullptr, nullptr, 0, d_roi, d_fg, d_bg, d_sums, d_counts, stream);
+  // label mode: no assay offsets, window order or half-width table
+  return roi_dispatch(RoiCall{.d_image = d_image, .dtype = dtype, .assay_stride = assay_stride, .n_c = n_c, .n_t = n_t,
+                              .h = h, .w = w, .d_beads = d_beads, .d_marker_assay = d_marker_assay,
+                              .d_marker_local = d_marker_local, .m = m, .len = roi_len, .d_labels = d_labels, .d_roi = d_roi,
+                              .d_fg = d_fg, .d_bg = d_bg, .d_sums = d_sums, .d_counts = d_counts,
+                              .stream = mg_stream(stream)});
 }
 
 namespace {
@@ -1255,9 +1266,12 @@ extern "C" int mg_roi_segment_reduce(const void* d_image, int dtype, int64_t ass
                                      uint8_t* d_bg, double* d_sums, int32_t* d_counts, void* stream) {
   if (!d_assay_offsets || !d_halfwidths || n_assays <= 0 || n_assays > 65535 || max_r < 0 || bead_stride < 0)
     return MG_EINVAL;
-  return roi_dispatch(d_image, dtype, assay_stride, n_c, n_t, h, w, d_beads, nullptr, nullptr, m, roi_len, nullptr,
-                      d_assay_offsets, bead_stride, time_major, n_assays, d_order, d_halfwidths, max_r, d_roi, d_fg, d_bg,
-                      d_sums, d_counts, stream);
+  return roi_dispatch(RoiCall{.d_image = d_image, .dtype = dtype, .assay_stride = assay_stride, .n_c = n_c, .n_t = n_t,
+                              .h = h, .w = w, .d_beads = d_beads, .bead_stride = bead_stride, .m = m, .len = roi_len,
+                              .d_assay_offsets = d_assay_offsets, .n_assays = n_assays, .time_major = time_major,
+                              .d_order = d_order, .d_halfwidths = d_halfwidths, .max_r = max_r, .d_roi = d_roi,
+                              .d_fg = d_fg, .d_bg = d_bg, .d_sums = d_sums, .d_counts = d_counts,
+                              .stream = mg_stream(stream)});
 }
 
 extern "C" int mg_roi_segment_reduce_raw(const void* d_image, const void* d_raw, int dtype, int64_t assay_stride, int n_c,
@@ -1271,9 +1285,13 @@ extern "C" int mg_roi_segment_reduce_raw(const void* d_image, const void* d_raw,
       raw_channel_mask < 0)
     return MG_EINVAL;
   const RoiRaw rw{(const uint16_t*)d_raw, d_flat, d_max2, flat, dark, planes_per_group, (uint32_t)raw_channel_mask};
-  return roi_dispatch(d_image, dtype, assay_stride, n_c, n_t, h, w, d_beads, nullptr, nullptr, m, roi_len, nullptr,
-                      d_assay_offsets, bead_stride, time_major, n_assays, d_order, d_halfwidths, max_r, d_roi, d_fg, d_bg,
-                      d_sums, d_counts, stream, &rw);
+  return roi_dispatch(RoiCall{.d_image = d_image, .dtype = dtype, .assay_stride = assay_stride, .n_c = n_c, .n_t = n_t,
+                              .h = h, .w = w, .d_beads = d_beads, .bead_stride = bead_stride, .m = m, .len = roi_len,
+                              .d_assay_offsets = d_assay_offsets, .n_assays = n_assays, .time_major = time_major,
+                              .d_order = d_order, .d_halfwidths = d_halfwidths, .max_r = max_r, .d_roi = d_roi,
+                              .d_fg = d_fg, .d_bg = d_bg, .d_sums = d_sums, .d_counts = d_counts,
+                              .stream = mg_stream(stream)},
+                      &rw);
 }
 
 extern "C" int mg_roi_gather_reduce(const void* d_image, int dtype, int n_c, int n_t, int h, int w,

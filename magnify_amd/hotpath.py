@@ -95,20 +95,24 @@ _SYNC_EVERY_CALL = bool(os.environ.get("MG_SYNC_CALLS"))
 _CAPTURING = False  # inside a stream capture (CircleFinder._capture_chain): no timing events
 
 
-def _call(name, *args, stage=None):
-    """One C-ABI call: timed (if a StageTimer is installed) and status-checked."""
+def _call(name, *args, stage=None, accept=()):
+    """One C-ABI call: timed (if a StageTimer is installed) and status-checked.  Returns the status: 0, or one of
+    ``accept`` (statuses that are an answer of this entry, not an error)."""
     if TIMER is _NO_TIMER or _CAPTURING:
         rc = getattr(nat.lib(), name)(*args)
-        if rc:
+        if rc and rc not in accept:
             nat.check(rc, name)
         if _SYNC_EVERY_CALL and not _CAPTURING:  # MG_SYNC_CALLS=1: a kernel that faults is named by the call it came from
             import sys
 
             print(f"[mg] {name}", file=sys.stderr, flush=True)
             torch.cuda.synchronize()
-        return
+        return rc
     with TIMER.stage(stage or name):
-        nat.check(getattr(nat.lib(), name)(*args), name)
+        rc = getattr(nat.lib(), name)(*args)
+        if rc not in accept:
+            nat.check(rc, name)
+    return rc
 
 
 def require_gpu():
@@ -1329,37 +1333,36 @@ def roi_gather_reduce(images: torch.Tensor, centers_per_assay, roi_len: int, lab
     if m == 0:
         return res
     if device_tables is not None:
-        d_tab, _, max_r = device_tables
-        assert disks and d_tab.dtype == torch.int32 and d_tab.is_contiguous() and d_tab.shape[0] == a
-        max_r = max(int(max_r), 2)
-        tab = _halfwidth_table(max_r, dev)
+        d_beads, _, max_r = device_tables
+        assert disks and d_beads.dtype == torch.int32 and d_beads.is_contiguous() and d_beads.shape[0] == a
+        bead_stride = int(d_beads.shape[1])  # one padded row per assay
         if device_counts is not None:
             d_off = pooled("roi_offsets" + pool_tag, a + 1, (), torch.int32, dev)
-            _call("mg_counts_to_offsets", d_counts.data_ptr(), a, min(int(cap), d_tab.shape[1]), d_off.data_ptr(), _stream())
+            _call("mg_counts_to_offsets", d_counts.data_ptr(), a, min(int(cap), bead_stride), d_off.data_ptr(), _stream())
         else:
             d_off = _upload_i32(offsets, dev)
         # where the markers' rows and offsets are on the device (marker_table reads them there)
-        res["device_tables"] = (d_tab, int(d_tab.shape[1]), d_off)
-        d_order = _window_order(d_tab, d_tab.shape[1], d_off, a, m, pool_tag if reuse_buffers else None, c * t)
-        _segment_reduce(images, raw, c, t, h, w, time_major, d_tab, d_tab.shape[1], d_off, a, m, d_order, L, tab, max_r, res)
-        return res
-    beads = np.zeros((m, 3), dtype=np.int32)
-    assay = np.zeros(m, dtype=np.int32)
-    local = np.zeros(m, dtype=np.int32)
-    for k, b in enumerate(centers_per_assay):
-        b = np.asarray(b)
-        lo, hi = offsets[k], offsets[k + 1]
-        if hi > lo:
-            beads[lo:hi, : 3 if disks else 2] = b[:, : 3 if disks else 2]
-            assay[lo:hi] = k
-            local[lo:hi] = np.arange(hi - lo)
-    d_beads = torch.from_numpy(beads).to(dev)
+        res["device_tables"] = (d_beads, bead_stride, d_off)
+    else:
+        beads = np.zeros((m, 3), dtype=np.int32)
+        assay = np.zeros(m, dtype=np.int32)
+        local = np.zeros(m, dtype=np.int32)
+        for k, b in enumerate(centers_per_assay):
+            b = np.asarray(b)
+            lo, hi = offsets[k], offsets[k + 1]
+            if hi > lo:
+                beads[lo:hi, : 3 if disks else 2] = b[:, : 3 if disks else 2]
+                assay[lo:hi] = k
+                local[lo:hi] = np.arange(hi - lo)
+        d_beads, bead_stride = torch.from_numpy(beads).to(dev), 0  # compact: markers and beads share the index
+        if disks:
+            max_r = int(beads[:, 2].max())
+            d_off = torch.from_numpy(offsets.astype(np.int32)).to(dev)
     if disks:
-        max_r = max(int(beads[:, 2].max()), 2)
+        max_r = max(int(max_r), 2)
         tab = _halfwidth_table(max_r, dev)
-        d_off = torch.from_numpy(offsets.astype(np.int32)).to(dev)
-        d_order = _window_order(d_beads, 0, d_off, a, m, pool_tag if reuse_buffers else None, c * t)
-        _segment_reduce(images, raw, c, t, h, w, time_major, d_beads, 0, d_off, a, m, d_order, L, tab, max_r, res)
+        d_order = _window_order(d_beads, bead_stride, d_off, a, m, pool_tag if reuse_buffers else None, c * t)
+        _segment_reduce(images, raw, time_major, _BeadTable(d_beads, bead_stride, d_off, a, m, d_order, tab, max_r), L, res)
         return res
     if raw is not None:
         raise ValueError("raw channels need the bead-table masks (disks=True)")
@@ -1372,25 +1375,32 @@ def roi_gather_reduce(images: torch.Tensor, centers_per_assay, roi_len: int, lab
     return res
 
 
-def _segment_reduce(images, raw, c, t, h, w, time_major, d_beads, bead_stride, d_off, a, m, d_order, L, tab, max_r, res):
+# The bead tables of a disk-mode pass on the device: rows [row, col, r] of ``a`` assays (``bead_stride`` rows per assay,
+# or 0: compact, assay after assay), the markers' offsets per assay, the launch's marker count (or bound), the order
+# the windows are visited in (or None) and the disks' half-width table up to ``max_r``.
+_BeadTable = namedtuple("_BeadTable", "d_beads bead_stride d_off a m d_order halfwidths max_r")
+
+
+def _segment_reduce(images, raw, time_major, table, L, res):
     """The launch of mg_roi_segment_reduce, or of its form that corrects the raw channels itself."""
-    tail = (d_beads.data_ptr(), int(bead_stride), d_off.data_ptr(), a, m, _ptr(d_order), L, tab.data_ptr(), max_r,
-            _ptr(res["roi"]), _ptr(res["fg"]), _ptr(res["bg"]), _ptr(res["sums"]), _ptr(res["counts"]), _stream())
+    if time_major:
+        _, t, c, h, w = images.shape
+    else:
+        _, c, t, h, w = images.shape
+    tail = (table.d_beads.data_ptr(), int(table.bead_stride), table.d_off.data_ptr(), table.a, table.m, _ptr(table.d_order),
+            L, table.halfwidths.data_ptr(), table.max_r, _ptr(res["roi"]), _ptr(res["fg"]), _ptr(res["bg"]),
+            _ptr(res["sums"]), _ptr(res["counts"]), _stream())
     code = nat.dtype_code(images.dtype)
     if raw is not None and raw.mask:
         assert raw.stack.is_contiguous() and raw.stack.numel() == images.numel() and raw.stack.dtype == images.dtype
-        assert raw.max2.numel() * raw.planes_per_group == 2 * a * c * t
+        assert raw.max2.numel() * raw.planes_per_group == 2 * table.a * c * t
         fl, flt, _ = _df_operand(raw.flatfield, h, w, images.device)
         assert flt is None or flt.dtype == torch.float32
-        args = (images.data_ptr(), raw.stack.data_ptr(), code, c * t * h * w, c, t, h, w, int(time_major), int(raw.mask),
-                float(raw.darkfield), fl, _ptr(flt), raw.max2.data_ptr(), int(raw.planes_per_group)) + tail
-        if TIMER is _NO_TIMER or _CAPTURING:
-            rc = nat.lib().mg_roi_segment_reduce_raw(*args)
-        else:
-            with TIMER.stage("mg_roi_segment_reduce"):
-                rc = nat.lib().mg_roi_segment_reduce_raw(*args)
-        if rc != -1:  # (MG_EINVAL: not a case the fused kernel takes)
-            nat.check(rc, "mg_roi_segment_reduce_raw")
+        # -1 (MG_EINVAL) from this entry: not a case the fused kernel takes
+        rc = _call("mg_roi_segment_reduce_raw", images.data_ptr(), raw.stack.data_ptr(), code, c * t * h * w, c, t, h, w,
+                   int(time_major), int(raw.mask), float(raw.darkfield), fl, _ptr(flt), raw.max2.data_ptr(),
+                   int(raw.planes_per_group), *tail, stage="mg_roi_segment_reduce", accept=(-1,))
+        if rc != -1:
             return
         raw.complete()
     _call("mg_roi_segment_reduce", images.data_ptr(), code, c * t * h * w, c, t, h, w, int(time_major), *tail)

@@ -21,6 +21,11 @@ import torch
 from . import hotpath as hp
 
 
+def _seed(seed, assay, k=0):
+    """The detection seed of an assay (its index in the stack) for the k-th search channel."""
+    return (seed + 1000003 * assay + 7919 * k) & 0xFFFFFFFFFFFFFFFF
+
+
 class StackProcessor:
     """Reusable workspaces for stacks of a fixed shape (T, C, H, W)."""
 
@@ -187,7 +192,7 @@ class StackProcessor:
                 ids = assays[lo : lo + self.batch]
                 planes = self._image[lo : lo + self.batch, ch]  # strided view, no copy
                 mm = self._minmax[lo : lo + self.batch, ch].contiguous()
-                seeds = [(seed + 1000003 * a + 7919 * k) & 0xFFFFFFFFFFFFFFFF for a in ids]
+                seeds = [_seed(seed, a, k) for a in ids]
                 res, _ = self.finder.find(planes, mm, self.low_q, self.high_q, self.min_roundness, self.min_r, seeds,
                                           stable_input=True)  # (a view of this processor's own image block)
                 for j, a in enumerate(ids):
@@ -230,7 +235,7 @@ class StackProcessor:
                         for j, ch in enumerate(self.search_channels):
                             planes = self._image[lo:hi, ch]
                             mm = self._minmax[lo:hi, ch].contiguous()
-                            seeds = [(seed + 1000003 * a + 7919 * j) & 0xFFFFFFFFFFFFFFFF for a in range(lo, hi)]
+                            seeds = [_seed(seed, a, j) for a in range(lo, hi)]
                             res, _ = self.finders[k].find(planes, mm, self.low_q, self.high_q, self.min_roundness,
                                                           self.min_r, seeds)
                             for i, a in enumerate(range(lo, hi)):
@@ -251,18 +256,23 @@ class StackProcessor:
             raise errors[0]
         return beads
 
-    def segment_reduce(self, beads, want_roi=True, image=None, pool_tag=None):
-        """fg/bg masks, ROI gather and masked sums for every marker (find.py:561-602)."""
+    def _roi_pass(self, want_roi, *, image=None, tag=None, beads=None, tables=None, counts=None):
+        """The ROI pass of this processor from ``image`` (default: its own block) into the pooled output set ``tag``
+        (default: its own), masks straight from the bead tables (mg_roi_segment_reduce: no label map is written or
+        read): host lists ``beads``, or ``tables`` / ``counts`` = roi_gather_reduce's device_tables / device_counts."""
         T, C, h, w = self.T, self.C, self.h, self.w
         image = self._image if image is None else image
-        tag = self.pool_tag if pool_tag is None else pool_tag
-        # masks straight from the bead tables (mg_roi_segment_reduce): no label map is written or read
-        if self.mode == "P":
-            return hp.roi_gather_reduce(image.view(T, C, 1, h, w), beads, self.L, None, want_roi=want_roi,
-                                        reuse_buffers=True, disks=True, pool_tag=tag, raw=self._raw)
-        # mode R: one assay whose image block is stored (T, C, h, w); gathered in place (time_major)
-        return hp.roi_gather_reduce(image.view(1, T, C, h, w), beads, self.L, None, want_roi=want_roi,
-                                    reuse_buffers=True, disks=True, time_major=True, pool_tag=tag)
+        if self.mode == "P":  # every timepoint an assay; channels left to the pass come from the raw stack
+            view, time_major, raw = image.view(T, C, 1, h, w), False, self._raw
+        else:  # mode R: one assay whose image block is stored (T, C, h, w); gathered in place
+            view, time_major, raw = image.view(1, T, C, h, w), True, None
+        return hp.roi_gather_reduce(view, beads, self.L, None, want_roi=want_roi, reuse_buffers=True, disks=True,
+                                    device_tables=tables, time_major=time_major, device_counts=counts,
+                                    pool_tag=self.pool_tag if tag is None else tag, raw=raw)
+
+    def segment_reduce(self, beads, want_roi=True, image=None, pool_tag=None):
+        """fg/bg masks, ROI gather and masked sums for every marker (find.py:561-602)."""
+        return self._roi_pass(want_roi, image=image, tag=pool_tag, beads=beads)
 
     def __call__(self, stack, flatfield=1.0, darkfield=0.0, seed=0, want_roi=True):
         if self.n_streams > 1 and self.mode == "P":
@@ -355,11 +365,10 @@ class StackProcessor:
             torch.cuda.empty_cache()
             self.placement.update(image_block=int(np.argmin(self.placement["flatfield_ms"])))
             return out
-        T, C, h, w = self.T, self.C, self.h, self.w
         counts = [len(b) for b in out["beads"]]
-        res = self._trial_pairs(lambda img, tag: hp.roi_gather_reduce(
-            img.view(T, C, 1, h, w), None, self.L, None, want_roi=want_roi, reuse_buffers=True, disks=True,
-            device_tables=(tabs[0], counts, self.max_r), pool_tag=tag, raw=self._raw), tries, markers=int(sum(counts)))
+        res = self._trial_pairs(lambda img, tag: self._roi_pass(want_roi, image=img, tag=tag,
+                                                                tables=(tabs[0], counts, self.max_r)),
+                                tries, markers=int(sum(counts)))
         res["beads"] = out["beads"]
         return res
 
@@ -406,22 +415,17 @@ class StackProcessor:
         """One search channel, the whole stack in one batch: there is no cross-channel de-duplication
         (find.py:490-500) to do on the host, so the ROI pass reads the suppression's bead tables where
         they are -- on the device -- and the host fetches its copy of them while that pass runs."""
-        T, C, h, w = self.T, self.C, self.h, self.w
         ch = self.search_channels[0]
-        seeds = [(seed + 1000003 * a) & 0xFFFFFFFFFFFFFFFF for a in range(self.n_assays)]
+        seeds = [_seed(seed, a) for a in range(self.n_assays)]
         # the ROI pass is queued behind the suppression before the host has seen the bead counts (find's `follow`)
-        roi_pass = lambda d_out, d_num, cap: hp.roi_gather_reduce(  # noqa: E731
-            self._image.view(T, C, 1, h, w), None, self.L, None, want_roi=want_roi, reuse_buffers=True, disks=True,
-            device_tables=(d_out, None, self.max_r), device_counts=(d_num, cap, self._roi_bound), pool_tag=self.pool_tag,
-            raw=self._raw)
+        roi_pass = lambda d_out, d_num, cap: self._roi_pass(  # noqa: E731
+            want_roi, tables=(d_out, None, self.max_r), counts=(d_num, cap, self._roi_bound))
         counts, (d_beads, d_scores, _) = self.finder.find(self._image[:, ch], self._minmax[:, ch], self.low_q,
                                                            self.high_q, self.min_roundness, self.min_r, seeds,
                                                            host_results=False, follow=roi_pass, stable_input=True)
         out = hp.finish_roi(self.finder.follow_result, counts)
         if out is None:  # more markers than the pass was launched for: once more, with the counts
-            out = hp.roi_gather_reduce(self._image.view(T, C, 1, h, w), None, self.L, None, want_roi=want_roi,
-                                       reuse_buffers=True, disks=True, device_tables=(d_beads, counts, self.max_r),
-                                       pool_tag=self.pool_tag, raw=self._raw)
+            out = self._roi_pass(want_roi, tables=(d_beads, counts, self.max_r))
         # the next call's launch bound: 10 % above this call's markers (its workgroups beyond the real count only cost
         # their start; the per-plane capacity x planes would be ~30 % above)
         self._roi_bound = int(1.1 * int(np.sum(counts))) + 16 * self.n_assays
