@@ -66,24 +66,28 @@ __device__ __forceinline__ uint8_t to_u8<double>(double x, const U8Scale& s) {
   return (uint8_t)(int)(255.0 * a / s.top);
 }
 
-// 16 consecutive elements of a row starting at column gx0 (may be outside the image: reflect-101).
+// Element i of a row-major array of `per_row` columns -> (row, column).
+struct RowCol {
+  int r, c;
+};
+__device__ __forceinline__ RowCol row_col(int i, int per_row) { return RowCol{i / per_row, i - (i / per_row) * per_row}; }
+
+// 16 elements, as the 16-byte loads that fetched them -> to_u8 -> the 16 bytes of one tile chunk.
 template <typename T>
-__device__ __forceinline__ void fetch16(const T* __restrict__ rowp, int gx0, int w, const U8Scale& sc, uint8_t (&v)[16]) {
-  const T* p = rowp + gx0;
-  if (gx0 >= 0 && gx0 + 16 <= w && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
-    constexpr int PER = 16 / sizeof(T);  // elements per 16-byte load
+__device__ __forceinline__ void decode_chunk(const uint4 (&raw)[sizeof(T)], const U8Scale& sc, uint8_t (&v)[16]) {
+  constexpr int PER = 16 / sizeof(T);  // elements per 16-byte load
 #pragma unroll
-    for (int q = 0; q < 16 / PER; ++q) {
-      T e[PER];
-      const uint4 raw = reinterpret_cast<const uint4*>(p)[q];
-      __builtin_memcpy(e, &raw, 16);
+  for (int q = 0; q < (int)sizeof(T); ++q) {
+    T e[PER];
+    __builtin_memcpy(e, &raw[q], 16);
 #pragma unroll
-      for (int j = 0; j < PER; ++j) v[q * PER + j] = to_u8<T>(e[j], sc);
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < 16; ++j) v[j] = to_u8<T>(rowp[mg_reflect101(gx0 + j, w)], sc);
+    for (int m = 0; m < PER; ++m) v[q * PER + m] = to_u8<T>(e[m], sc);
   }
+}
+__device__ __forceinline__ void store_chunk(uint8_t (*tile)[LS], int j, int k, const uint8_t (&v)[16]) {
+  uint4 out;
+  __builtin_memcpy(&out, v, 16);
+  *reinterpret_cast<uint4*>(&tile[j][16 * k]) = out;
 }
 
 // Stage tile rows [ty0 - HALO, ty0 + TH + HALO) x cols [tx0 - 16, tx0 + TW + 16) into LDS.
@@ -94,8 +98,7 @@ __device__ __forceinline__ void load_tile(const T* __restrict__ base, int64_t ro
                                           const U8Scale& sc, uint8_t (*tile)[LS]) {
   constexpr int TOTAL = (TH + 2 * HALO) * CHUNKS;
   constexpr int ITER = (TOTAL + NT - 1) / NT;
-  constexpr int PER = 16 / sizeof(T);   // elements per 16-byte load
-  constexpr int NLD = 16 / PER;         // 16-byte loads per 16-element chunk
+  constexpr int NLD = sizeof(T);  // 16-byte loads per 16-element chunk
   const bool interior = tx0 >= LPAD && tx0 + TW + LPAD <= w && ty0 >= HALO && ty0 + TH + HALO <= h &&
                         ((row_stride * sizeof(T)) & 15) == 0 &&
                         (reinterpret_cast<uintptr_t>(base + (int64_t)(ty0 - HALO) * row_stride + tx0 - LPAD) & 15) == 0;
@@ -105,7 +108,7 @@ __device__ __forceinline__ void load_tile(const T* __restrict__ base, int64_t ro
     for (int it = 0; it < ITER; ++it) {
       const int i = threadIdx.x + it * NT;
       if (i < TOTAL) {
-        const int j = i / CHUNKS, k = i - j * CHUNKS;
+        const auto [j, k] = row_col(i, CHUNKS);  // LDS row, chunk of that row
         const uint4* p = reinterpret_cast<const uint4*>(base + (int64_t)(ty0 - HALO + j) * row_stride + tx0 - LPAD + 16 * k);
 #pragma unroll
         for (int q = 0; q < NLD; ++q) raw[it][q] = p[q];
@@ -115,18 +118,10 @@ __device__ __forceinline__ void load_tile(const T* __restrict__ base, int64_t ro
     for (int it = 0; it < ITER; ++it) {
       const int i = threadIdx.x + it * NT;
       if (i < TOTAL) {
-        const int j = i / CHUNKS, k = i - j * CHUNKS;
+        const auto [j, k] = row_col(i, CHUNKS);  // LDS row, chunk of that row
         uint8_t v[16];
-#pragma unroll
-        for (int q = 0; q < NLD; ++q) {
-          T e[PER];
-          __builtin_memcpy(e, &raw[it][q], 16);
-#pragma unroll
-          for (int m = 0; m < PER; ++m) v[q * PER + m] = to_u8<T>(e[m], sc);
-        }
-        uint4 out;
-        __builtin_memcpy(&out, v, 16);
-        *reinterpret_cast<uint4*>(&tile[j][16 * k]) = out;
+        decode_chunk<T>(raw[it], sc, v);
+        store_chunk(tile, j, k, v);
       }
     }
     return;
@@ -144,7 +139,7 @@ __device__ __forceinline__ void load_tile(const T* __restrict__ base, int64_t ro
     const int i = threadIdx.x + it * NT;
     fast[it] = false;
     if (i < TOTAL) {
-      const int j = i / CHUNKS, k = i - j * CHUNKS;
+      const auto [j, k] = row_col(i, CHUNKS);
       const int gy = mg_reflect101(ty0 - HALO + j, h), gx0 = tx0 - LPAD + 16 * k;
       const T* p = base + (int64_t)gy * row_stride + gx0;
       fast[it] = rows_ok && gx0 >= 0 && gx0 + 16 <= w && (reinterpret_cast<uintptr_t>(p) & 15) == 0;
@@ -158,16 +153,10 @@ __device__ __forceinline__ void load_tile(const T* __restrict__ base, int64_t ro
   for (int it = 0; it < ITER; ++it) {
     const int i = threadIdx.x + it * NT;
     if (i < TOTAL) {
-      const int j = i / CHUNKS, k = i - j * CHUNKS;
+      const auto [j, k] = row_col(i, CHUNKS);
       uint8_t v[16];
       if (fast[it]) {
-#pragma unroll
-        for (int q = 0; q < NLD; ++q) {
-          T e[PER];
-          __builtin_memcpy(e, &raw[it][q], 16);
-#pragma unroll
-          for (int m = 0; m < PER; ++m) v[q * PER + m] = to_u8<T>(e[m], sc);
-        }
+        decode_chunk<T>(raw[it], sc, v);
       } else {
         const int gy = mg_reflect101(ty0 - HALO + j, h), gx0 = tx0 - LPAD + 16 * k;
         const T* rowp = base + (int64_t)gy * row_stride;
@@ -178,9 +167,7 @@ __device__ __forceinline__ void load_tile(const T* __restrict__ base, int64_t ro
           v[m] = needed ? to_u8<T>(rowp[mg_reflect101(gx0 + m, w)], sc) : (uint8_t)0;
         }
       }
-      uint4 out;
-      __builtin_memcpy(&out, v, 16);
-      *reinterpret_cast<uint4*>(&tile[j][16 * k]) = out;
+      store_chunk(tile, j, k, v);
     }
   }
 }
@@ -197,6 +184,72 @@ struct Row12 {
 __device__ __forceinline__ Row12 read_row(const uint8_t (*tile)[LS], int r, int c0) {
   const uint32_t* p = reinterpret_cast<const uint32_t*>(&tile[r][LPAD + c0 - 4]);
   return Row12{p[0], p[1], p[2]};
+}
+
+// ---- packed 16-bit arithmetic: two pixels per register, two per instruction -------------------
+typedef short s2 __attribute__((ext_vector_type(2)));
+typedef unsigned short u2 __attribute__((ext_vector_type(2)));
+
+// Pixel pairs out of packed bytes (one v_perm_b32 each; byte 0 of a word is its leftmost pixel).
+// Bytes 0, 1 of d.
+__device__ __forceinline__ u2 pair_01(uint32_t d) { return __builtin_bit_cast(u2, __builtin_amdgcn_perm(0u, d, 0x0C010C00u)); }
+// Bytes 1, 2 of d.
+__device__ __forceinline__ u2 pair_12(uint32_t d) { return __builtin_bit_cast(u2, __builtin_amdgcn_perm(0u, d, 0x0C020C01u)); }
+// Bytes 2, 3 of d.
+__device__ __forceinline__ u2 pair_23(uint32_t d) { return __builtin_bit_cast(u2, __builtin_amdgcn_perm(0u, d, 0x0C030C02u)); }
+// Byte 3 of lo with byte 0 of hi: the pair that straddles two adjacent words.
+__device__ __forceinline__ u2 pair_across(uint32_t lo, uint32_t hi) {
+  return __builtin_bit_cast(u2, __builtin_amdgcn_perm(hi, lo, 0x0C040C03u));
+}
+// The low bytes of the pairs p01, p23 (values < 256) as four packed bytes.
+__device__ __forceinline__ uint32_t pack_bytes(uint32_t p01, uint32_t p23) { return __builtin_amdgcn_perm(p23, p01, 0x06040200u); }
+// (x.lo | y.lo << 16) and (x.hi | y.hi << 16): two pairs transposed.
+__device__ __forceinline__ uint32_t zip_lo(s2 x, s2 y) {
+  return __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, y), __builtin_bit_cast(uint32_t, x), 0x05040100u);
+}
+__device__ __forceinline__ uint32_t zip_hi(s2 x, s2 y) {
+  return __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, y), __builtin_bit_cast(uint32_t, x), 0x07060302u);
+}
+
+// v of lane - 1 / lane + 1 by a whole-wave DPP shift (wave_shr:1 / wave_shl:1; no LDS permute).  The lane without
+// such a neighbour -- lane 0 from the left, lane 63 from the right -- gets 0: k_scharr_hist<true> fills in the image
+// edge or the next tile's word there, blur_hist_strip never uses what those two lanes compute from it (not owners).
+__device__ __forceinline__ uint32_t wave_from_left(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xF, 0xF, false);
+}
+__device__ __forceinline__ uint32_t wave_from_right(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x130, 0xF, 0xF, false);
+}
+
+// Scharr gradients of 2 (NP - 1) adjacent pixels from three rows a, b, c given as NP pixel PAIRS, the first pair
+// starting one pixel left of the first result: xy[i] = (dx | dy << 16) of pixel i + 1 of the 2 NP.  Via the separable
+// parts S = 3 (a + c) + 10 b <= 4080 (vertical smooth) and D = c - a (vertical difference), both exact in 16 bits:
+//   dx[x] = S[x+1] - S[x-1],  dy[x] = 3 (D[x-1] + D[x+1]) + 10 D[x].
+// Result pair jp = pixels (2 jp + 1, 2 jp + 2): their left and right neighbours are exactly the pairs jp and jp + 1,
+// their own D the word that straddles the two (alignbit).  The quantile histogram and the NMS magnitudes must agree
+// to the bit: both come from here.
+template <int NP>
+__device__ __forceinline__ void scharr_pairs(const u2 (&a)[NP], const u2 (&b)[NP], const u2 (&c)[NP],
+                                             uint32_t (&xy)[2 * (NP - 1)]) {
+  s2 S[NP], D[NP];
+#pragma unroll
+  for (int k = 0; k < NP; ++k) {
+    S[k] = __builtin_bit_cast(s2, (u2)((a[k] + c[k]) * (unsigned short)3 + b[k] * (unsigned short)10));
+    D[k] = __builtin_bit_cast(s2, c[k]) - __builtin_bit_cast(s2, a[k]);
+  }
+#pragma unroll
+  for (int jp = 0; jp < NP - 1; ++jp) {
+    const s2 dxp = S[jp + 1] - S[jp];
+    const s2 mid = __builtin_bit_cast(s2, __builtin_amdgcn_alignbit(__builtin_bit_cast(uint32_t, D[jp + 1]),
+                                                                     __builtin_bit_cast(uint32_t, D[jp]), 16));
+    const s2 dyp = (D[jp] + D[jp + 1]) * (short)3 + mid * (short)10;
+    xy[2 * jp] = zip_lo(dxp, dyp);
+    xy[2 * jp + 1] = zip_hi(dxp, dyp);
+  }
+}
+// |gradient|^2 = dx^2 + dy^2 of one (dx | dy << 16): one dot2.
+__device__ __forceinline__ int grad_sq(uint32_t xy) {
+  return __builtin_amdgcn_sdot2(__builtin_bit_cast(s2, xy), __builtin_bit_cast(s2, xy), 0, false);
 }
 
 // ---- K1: to_uint8 + 5x5 Gaussian ([1 4 6 4 1] x [1 4 6 4 1], (sum + 128) >> 8) ----------
@@ -251,25 +304,6 @@ __global__ __launch_bounds__(NT) void k_u8_blur(const T* __restrict__ src, int64
   }
 }
 
-// Scharr of N adjacent pixels starting at pixel c0 + FIRST from three rows, via the separable
-// parts S = 3a + 10b + 3c (vertical smooth) and D = c - a (vertical difference):
-//   dx[q] = S[q+1] - S[q-1],  dy[q] = 3 (D[q-1] + D[q+1]) + 10 D[q].
-template <int FIRST, int N>
-__device__ __forceinline__ void scharr_n(const Row12& a, const Row12& b, const Row12& c, int (&dx)[N], int (&dy)[N]) {
-  int S[N + 2], D[N + 2];
-#pragma unroll
-  for (int j = 0; j < N + 2; ++j) {
-    const int o = FIRST - 1 + j;
-    S[j] = 3 * (a.at(o) + c.at(o)) + 10 * b.at(o);
-    D[j] = c.at(o) - a.at(o);
-  }
-#pragma unroll
-  for (int q = 0; q < N; ++q) {
-    dx[q] = S[q + 2] - S[q];
-    dy[q] = 3 * (D[q] + D[q + 2]) + 10 * D[q + 1];
-  }
-}
-
 // ---- K2: histogram of m = dx^2 + dy^2 ------------------------------------------------------
 // mode 0 (combined): bins [0, 8192) hold m exactly, bins 8192 + (m >> 13) hold the rest coarsely;
 // mode 1 (window):   bin m - base for m in [base, base + 8192).
@@ -289,36 +323,16 @@ constexpr uint32_t MG_HIST_SKIP = 0xFFFFFFFFu;  // mode 1: d_base[plane] of a pl
 // through the LDS-staged path (reflect-101) in a second launch.
 constexpr int HIST_TILES = 3;
 
-typedef short hs2 __attribute__((ext_vector_type(2)));
-typedef unsigned short hu2 __attribute__((ext_vector_type(2)));
-
 // The four pixels c0 .. c0+3 of the centre row pb2, from three rows given as pixel PAIRS (c0-1, c0), (c0+1, c0+2),
-// (c0+3, c0+4): packed 16-bit arithmetic, two pixels per instruction; |gradient|^2 by one dot2 per pixel (see
-// k_canny_nms).
-__device__ __forceinline__ void hist_add4_pairs(const hu2 (&pa)[3], const hu2 (&pb2)[3], const hu2 (&pc)[3], int gx, int w,
+// (c0+3, c0+4).
+__device__ __forceinline__ void hist_add4_pairs(const u2 (&pa)[3], const u2 (&pb2)[3], const u2 (&pc)[3], int gx, int w,
                                                 int mode, uint32_t base, int n_bins, uint32_t* hist, uint32_t& zeros) {
-  typedef hs2 s2;
-  typedef hu2 u2;
-  s2 S[3], D[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    S[k] = __builtin_bit_cast(s2, (u2)((pa[k] + pc[k]) * (unsigned short)3 + pb2[k] * (unsigned short)10));
-    D[k] = __builtin_bit_cast(s2, pc[k]) - __builtin_bit_cast(s2, pa[k]);
-  }
   uint32_t xy[4];  // (dx | dy << 16) of pixels c0 .. c0+3
-#pragma unroll
-  for (int jp = 0; jp < 2; ++jp) {
-    const s2 dxp = S[jp + 1] - S[jp];
-    const s2 mid = __builtin_bit_cast(s2, __builtin_amdgcn_alignbit(__builtin_bit_cast(uint32_t, D[jp + 1]),
-                                                                     __builtin_bit_cast(uint32_t, D[jp]), 16));
-    const s2 dyp = (D[jp] + D[jp + 1]) * (short)3 + mid * (short)10;
-    xy[2 * jp] = __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, dyp), __builtin_bit_cast(uint32_t, dxp), 0x05040100u);
-    xy[2 * jp + 1] = __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, dyp), __builtin_bit_cast(uint32_t, dxp), 0x07060302u);
-  }
+  scharr_pairs(pa, pb2, pc, xy);
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     if (gx + q >= w) continue;
-    const uint32_t m = (uint32_t)__builtin_amdgcn_sdot2(__builtin_bit_cast(s2, xy[q]), __builtin_bit_cast(s2, xy[q]), 0, false);
+    const uint32_t m = (uint32_t)grad_sq(xy[q]);
     if (mode == 0) {
       if (m == 0) ++zeros;
       else {
@@ -337,17 +351,30 @@ __device__ __forceinline__ void hist_add4_pairs(const hu2 (&pa)[3], const hu2 (&
 
 __device__ __forceinline__ void hist_add4(const Row12& ra, const Row12& rb, const Row12& rc, int gx, int w, int mode,
                                           uint32_t base, int n_bins, uint32_t* hist, uint32_t& zeros) {
-  typedef hu2 u2;
   u2 pa[3], pb2[3], pc[3];
-#define MG_UNPACK3(r, o)                                                                    \
-  o[0] = __builtin_bit_cast(u2, __builtin_amdgcn_perm(r.d1, r.d0, 0x0C040C03u)); /* c0-1, c0 */ \
-  o[1] = __builtin_bit_cast(u2, __builtin_amdgcn_perm(0u, r.d1, 0x0C020C01u));   /* c0+1, c0+2 */ \
-  o[2] = __builtin_bit_cast(u2, __builtin_amdgcn_perm(r.d2, r.d1, 0x0C040C03u)); /* c0+3, c0+4 */
-  MG_UNPACK3(ra, pa)
-  MG_UNPACK3(rb, pb2)
-  MG_UNPACK3(rc, pc)
-#undef MG_UNPACK3
+  auto unpack = [](const Row12& r, u2 (&o)[3]) {
+    o[0] = pair_across(r.d0, r.d1);  // c0-1, c0
+    o[1] = pair_12(r.d1);            // c0+1, c0+2
+    o[2] = pair_across(r.d1, r.d2);  // c0+3, c0+4
+  };
+  unpack(ra, pa);
+  unpack(rb, pb2);
+  unpack(rc, pc);
   hist_add4_pairs(pa, pb2, pc, gx, w, mode, base, n_bins, hist, zeros);
+}
+
+// The workgroup's slot of d_partial: n_bins / 2 packed words, slots in the order (plane = blockIdx.z, y, x) of the grid.
+__device__ __forceinline__ uint32_t* hist_slot(uint32_t* __restrict__ d_partial, int n_bins) {
+  return d_partial + ((int64_t)blockIdx.z * gridDim.y * gridDim.x + (int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (n_bins / 2);
+}
+// Hand the workgroup's LDS histogram over to its slot.  Bin 0 was counted in registers: its wave sums join the packed
+// counters first (a workgroup's pixels, <= 63 488, fit 16 bits; one atomic per wave on the plane's one global counter
+// serialised ~1400 deep).
+__device__ __forceinline__ void hist_hand_over(uint32_t* hist, uint32_t zeros, uint32_t* __restrict__ slot, int n_bins) {
+  zeros = (uint32_t)mg_wave_sum_i32((int)zeros);
+  if ((threadIdx.x & 63) == 0 && zeros) atomicAdd(&hist[0], zeros);
+  __syncthreads();
+  for (int i = threadIdx.x; i < n_bins / 2; i += NT) slot[i] = hist[i];
 }
 
 __device__ __forceinline__ bool hist_group_interior(const uint8_t* pb, int h, int w, int tx0, int gy) {
@@ -371,9 +398,7 @@ __global__ __launch_bounds__(NT) void k_scharr_hist(const uint8_t* __restrict__ 
   const uint8_t* pb = d_blur + (int64_t)plane * h * w;
   // DIRECT: grid.y counts tile groups; staged: grid.y counts tiles (one tile per workgroup)
   const bool interior = hist_group_interior(pb, h, w, tx0, DIRECT ? blockIdx.y : blockIdx.y / HIST_TILES);
-  uint32_t* slot = (DIRECT && d_partial) ? d_partial + ((int64_t)plane * gridDim.y * gridDim.x +
-                                                        (int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (n_bins / 2)
-                                         : nullptr;
+  uint32_t* slot = (DIRECT && d_partial) ? hist_slot(d_partial, n_bins) : nullptr;
   const uint32_t base = (mode == 1 && d_base) ? d_base[plane] : 0u;
   if (mode == 1 && base == MG_HIST_SKIP) return;  // this plane needs no window pass (k_hist_reduce skips it too)
   if (DIRECT && !interior) {  // the staged launch handles this group (and adds straight into d_hist)
@@ -406,9 +431,7 @@ __global__ __launch_bounds__(NT) void k_scharr_hist(const uint8_t* __restrict__ 
       Row12 ra, rb;
 #pragma unroll
       for (int j = 0; j < RPW + 2; ++j) {
-        // neighbours' words by whole-wave DPP shifts (wave_shr:1 / wave_shl:1), not LDS permutes
-        uint32_t d0 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mid[j], 0x138, 0xF, 0xF, false);
-        uint32_t d2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mid[j], 0x130, 0xF, 0xF, false);
+        uint32_t d0 = wave_from_left(mid[j]), d2 = wave_from_right(mid[j]);  // the neighbours' words
         // pixel -1 of the image is pixel 1, pixel w is pixel w - 2 (only those two bytes are ever read)
         if (lane == 0) d0 = at_left ? (mid[j] & 0x0000FF00u) << 16 : edge[j];
         if (lane == 63) d2 = at_right ? (mid[j] >> 16) & 0xFFu : edge[j];
@@ -419,10 +442,8 @@ __global__ __launch_bounds__(NT) void k_scharr_hist(const uint8_t* __restrict__ 
       }
     }
   } else {
-    U8Scale sc;
-    sc.passthrough = 1;
     const int ty0 = blockIdx.y * TH;
-    load_tile<uint8_t, 1>(pb, w, h, w, tx0, ty0, sc, tile);
+    load_tile<uint8_t, 1>(pb, w, h, w, tx0, ty0, make_scale(nullptr, 0), tile);
     __syncthreads();  // tile staged, histogram zeroed
     Row12 ra = read_row(tile, wave * RPW, c0), rb = read_row(tile, wave * RPW + 1, c0);
 #pragma unroll 4
@@ -434,19 +455,15 @@ __global__ __launch_bounds__(NT) void k_scharr_hist(const uint8_t* __restrict__ 
       rb = rc;
     }
   }
-  zeros = (uint32_t)mg_wave_sum_i32((int)zeros);
-  uint32_t* out = d_hist + (int64_t)plane * n_bins;
-  // bin 0: counted in registers.  With a slot it joins the workgroup's packed counters (<= 3 x 16384 pixels fit 16
-  // bits; one atomic per wave on the plane's one global counter serialised ~1400 deep), else global memory.
-  if (lane == 0 && zeros) {
-    if (slot) atomicAdd(&hist[0], zeros);
-    else atomicAdd(&out[0], zeros);
-  }
-  __syncthreads();
   if (slot) {
-    for (int i = threadIdx.x; i < n_bins / 2; i += NT) slot[i] = hist[i];
+    hist_hand_over(hist, zeros, slot, n_bins);
     return;
   }
+  // no scratch: bin 0 and every non-empty bin by global atomics
+  zeros = (uint32_t)mg_wave_sum_i32((int)zeros);
+  uint32_t* out = d_hist + (int64_t)plane * n_bins;
+  if (lane == 0 && zeros) atomicAdd(&out[0], zeros);
+  __syncthreads();
   for (int i = threadIdx.x; i < n_bins / 2; i += NT) {
     const uint32_t v = hist[i];
     if (v & 0xFFFFu) atomicAdd(&out[2 * i], v & 0xFFFFu);
@@ -483,7 +500,6 @@ template <typename T, bool VEC>
 __device__ __forceinline__ void blur_hist_strip(const T* __restrict__ pin, int64_t row_stride, int h, int w, int y0, int cx,
                                                 bool owner, const U8Scale& sc, uint8_t* __restrict__ pout, uint32_t* hist,
                                                 uint32_t& zeros) {
-  typedef hu2 u2;
   constexpr int n_bins = FINE + COARSE;
   const int y_end = min(y0 + FR, h);
   uint32_t col[4];
@@ -527,16 +543,10 @@ __device__ __forceinline__ void blur_hist_strip(const T* __restrict__ pin, int64
         // correction, seven single-rate instructions per pixel, ran 2 % slower)
         const uint32_t d1 = (uint32_t)to_u8<T>(cur[b].v[0], sc) | ((uint32_t)to_u8<T>(cur[b].v[1], sc) << 8) |
                             ((uint32_t)to_u8<T>(cur[b].v[2], sc) << 16) | ((uint32_t)to_u8<T>(cur[b].v[3], sc) << 24);
-        const uint32_t d0 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)d1, 0x138, 0xF, 0xF, false);  // lane - 1
-        const uint32_t d2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)d1, 0x130, 0xF, 0xF, false);  // lane + 1
+        const uint32_t d0 = wave_from_left(d1), d2 = wave_from_right(d1);
         // pixel pairs at even and odd offsets: (-2, -1) (0, 1) (2, 3) (4, 5) and (-1, 0) (1, 2) (3, 4)
-        const u2 em = __builtin_bit_cast(u2, __builtin_amdgcn_perm(0u, d0, 0x0C030C02u));
-        const u2 e0 = __builtin_bit_cast(u2, __builtin_amdgcn_perm(0u, d1, 0x0C010C00u));
-        const u2 e2 = __builtin_bit_cast(u2, __builtin_amdgcn_perm(0u, d1, 0x0C030C02u));
-        const u2 e4 = __builtin_bit_cast(u2, __builtin_amdgcn_perm(0u, d2, 0x0C010C00u));
-        const u2 om = __builtin_bit_cast(u2, __builtin_amdgcn_perm(d1, d0, 0x0C040C03u));
-        const u2 o1 = __builtin_bit_cast(u2, __builtin_amdgcn_perm(0u, d1, 0x0C020C01u));
-        const u2 o3 = __builtin_bit_cast(u2, __builtin_amdgcn_perm(d2, d1, 0x0C040C03u));
+        const u2 em = pair_23(d0), e0 = pair_01(d1), e2 = pair_23(d1), e4 = pair_01(d2);
+        const u2 om = pair_across(d0, d1), o1 = pair_12(d1), o3 = pair_across(d1, d2);
 #pragma unroll
         for (int k = 0; k < 4; ++k) H[k][0] = H[k + 1][0], H[k][1] = H[k + 1][1];
         H[4][0] = (em + e2) + (om + o1) * (unsigned short)4 + e0 * (unsigned short)6;
@@ -550,10 +560,9 @@ __device__ __forceinline__ void blur_hist_strip(const T* __restrict__ pin, int64
                   (unsigned short)128) >> (unsigned short)8;
         const uint32_t b01 = __builtin_bit_cast(uint32_t, B[0]), b23 = __builtin_bit_cast(uint32_t, B[1]);
         if (br >= y0 && br < y_end && owner)
-          *reinterpret_cast<uint32_t*>(pout + (int64_t)br * w + cx) = __builtin_amdgcn_perm(b23, b01, 0x06040200u);
+          *reinterpret_cast<uint32_t*>(pout + (int64_t)br * w + cx) = pack_bytes(b01, b23);
         // pairs at odd offsets of the blurred row: (-1, 0) with the left lane's (2, 3), (3, 4) with the right lane's (0, 1)
-        const uint32_t l23 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)b23, 0x138, 0xF, 0xF, false);
-        const uint32_t r01 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)b01, 0x130, 0xF, 0xF, false);
+        const uint32_t l23 = wave_from_left(b23), r01 = wave_from_right(b01);
 #pragma unroll
         for (int k = 0; k < 3; ++k) P[0][k] = P[1][k], P[1][k] = P[2][k];
         P[2][0] = __builtin_bit_cast(u2, __builtin_amdgcn_alignbit(b01, l23, 16));
@@ -591,11 +600,7 @@ __global__ __launch_bounds__(NT) void k_blur_hist(const T* __restrict__ src, int
     if (tx0 >= 4 && tx0 + FW + 4 <= w) blur_hist_strip<T, true>(pin, row_stride, h, w, y0, cx, owner, sc, pout, hist, zeros);
     else blur_hist_strip<T, false>(pin, row_stride, h, w, y0, cx, owner, sc, pout, hist, zeros);
   }
-  zeros = (uint32_t)mg_wave_sum_i32((int)zeros);
-  if (lane == 0 && zeros) atomicAdd(&hist[0], zeros);  // (bin 0 shares the packed counters: <= 63 488 in all)
-  __syncthreads();
-  uint32_t* slot = d_partial + ((int64_t)plane * gridDim.y * gridDim.x + (int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (n_bins / 2);
-  for (int i = threadIdx.x; i < n_bins / 2; i += NT) slot[i] = hist[i];
+  hist_hand_over(hist, zeros, hist_slot(d_partial, n_bins), n_bins);
 }
 
 // d_hist[plane][bin] += sum over the plane's workgroup slots (packed 16-bit pairs).  The slots are split over
@@ -799,12 +804,23 @@ __global__ __launch_bounds__(NT) void k_window_resolve(const uint32_t* __restric
 }
 
 // ---- bit helpers on the linear (y * w + x) bitmaps --------------------------------------------
+// n (1..32) consecutive bits starting at linear bit index bit0, in two forms:
+//   bits_at     reads the second word only when the group reaches into it.  For row_word (hysteresis, w % 32 != 0)
+//               and k_cell_fill, whose loads are behind data-dependent branches anyway.
+//   bits_at_nb  reads it always (the bitmaps carry a spare word): no branch.  For k_cell_count and k_cell_fill_rows,
+//               whose loads are meant to be in flight together -- a load behind a lane-level branch ends with a wait.
 __device__ __forceinline__ uint32_t bits_at(const uint32_t* __restrict__ bits, int64_t bit0, int n) {
-  // n (1..32) consecutive bits starting at linear bit index bit0
   const int64_t wi = bit0 >> 5;
   const int sh = (int)(bit0 & 31);
   uint64_t two = bits[wi];
   if (sh + n > 32) two |= (uint64_t)bits[wi + 1] << 32;
+  const uint32_t v = (uint32_t)(two >> sh);
+  return n >= 32 ? v : (v & ((1u << n) - 1u));
+}
+__device__ __forceinline__ uint32_t bits_at_nb(const uint32_t* __restrict__ bits, int64_t bit0, int n) {
+  const int64_t wi = bit0 >> 5;
+  const int sh = (int)(bit0 & 31);
+  const uint64_t two = (uint64_t)bits[wi] | ((uint64_t)bits[wi + 1] << 32);
   const uint32_t v = (uint32_t)(two >> sh);
   return n >= 32 ? v : (v & ((1u << n) - 1u));
 }
@@ -849,9 +865,7 @@ __global__ __launch_bounds__(NT) void k_canny_nms(const uint8_t* __restrict__ d_
   __shared__ __attribute__((aligned(16))) uint8_t tile[TH + 4][LS];
   const int plane = blockIdx.z;
   const int tx0 = blockIdx.x * TW, ty0 = blockIdx.y * TH;
-  U8Scale sc;
-  sc.passthrough = 1;
-  load_tile<uint8_t, 2>(d_blur + (int64_t)plane * h * w, w, h, w, tx0, ty0, sc, tile);
+  load_tile<uint8_t, 2>(d_blur + (int64_t)plane * h * w, w, h, w, tx0, ty0, make_scale(nullptr, 0), tile);
   __syncthreads();
   const int low = d_thresh[2 * plane], high = d_thresh[2 * plane + 1];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -867,20 +881,16 @@ __global__ __launch_bounds__(NT) void k_canny_nms(const uint8_t* __restrict__ d_
   uint32_t* cls2 = d_class ? d_class + (3 * plane + 2) * words_per_plane : nullptr;
   constexpr int TG22 = 13573;
   const uint32_t in_row = gx + 4 <= w ? 0xFu : ((1u << max(w - gx, 0)) - 1u);  // the lane's pixels left of the row end
-  // Packed 16-bit arithmetic, two pixels per instruction: a row is held as four registers of pixel pairs
-  // (columns c0-2 .. c0+5); the Scharr sums S = 3 (above + below) + 10 centre <= 4080 and differences fit 16 bits;
-  // |gradient|^2 = dot2((dx, dy), (dx, dy)) in one instruction per pixel.
-  typedef short s2 __attribute__((ext_vector_type(2)));
-  typedef unsigned short u2 __attribute__((ext_vector_type(2)));
+  // A row is held as four registers of pixel pairs (columns c0-2 .. c0+5), see scharr_pairs.
   struct Pairs4 {
     u2 p[4];
   };
   auto unpack = [](const Row12& r) {
     Pairs4 o;
-    o.p[0] = __builtin_bit_cast(u2, __builtin_amdgcn_perm(0u, r.d0, 0x0C030C02u));  // pixels c0-2, c0-1
-    o.p[1] = __builtin_bit_cast(u2, __builtin_amdgcn_perm(0u, r.d1, 0x0C010C00u));  // c0, c0+1
-    o.p[2] = __builtin_bit_cast(u2, __builtin_amdgcn_perm(0u, r.d1, 0x0C030C02u));  // c0+2, c0+3
-    o.p[3] = __builtin_bit_cast(u2, __builtin_amdgcn_perm(0u, r.d2, 0x0C010C00u));  // c0+4, c0+5
+    o.p[0] = pair_23(r.d0);  // pixels c0-2, c0-1
+    o.p[1] = pair_01(r.d1);  // c0, c0+1
+    o.p[2] = pair_23(r.d1);  // c0+2, c0+3
+    o.p[3] = pair_01(r.d2);  // c0+4, c0+5
     return o;
   };
   // mag rows: 6 magnitudes (cols c0-1 .. c0+4) of image rows y-1, y, y+1; zero outside the image
@@ -897,28 +907,13 @@ __global__ __launch_bounds__(NT) void k_canny_nms(const uint8_t* __restrict__ d_
 #pragma unroll
     for (int q = 0; q < 4; ++q) cxy[0][q] = cxy[1][q];
     {
-      s2 S[4], D[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        S[k] = __builtin_bit_cast(s2, (u2)((ua.p[k] + uc.p[k]) * (unsigned short)3 + ub.p[k] * (unsigned short)10));
-        D[k] = __builtin_bit_cast(s2, uc.p[k]) - __builtin_bit_cast(s2, ua.p[k]);
-      }
       uint32_t xy[6];  // columns c0-1 .. c0+4
-#pragma unroll
-      for (int jp = 0; jp < 3; ++jp) {
-        // pair jp = columns (c0-1+2jp, c0+2jp): dx[x] = S[x+1] - S[x-1], dy[x] = 3 (D[x-1] + D[x+1]) + 10 D[x]
-        const s2 dxp = S[jp + 1] - S[jp];
-        const s2 mid = __builtin_bit_cast(s2, __builtin_amdgcn_alignbit(__builtin_bit_cast(uint32_t, D[jp + 1]),
-                                                                         __builtin_bit_cast(uint32_t, D[jp]), 16));
-        const s2 dyp = (D[jp] + D[jp + 1]) * (short)3 + mid * (short)10;
-        xy[2 * jp] = __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, dyp), __builtin_bit_cast(uint32_t, dxp), 0x05040100u);
-        xy[2 * jp + 1] = __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, dyp), __builtin_bit_cast(uint32_t, dxp), 0x07060302u);
-      }
+      scharr_pairs(ua.p, ub.p, uc.p, xy);
       const bool row_in = ym >= 0 && ym < h;
 #pragma unroll
       for (int k = 0; k < 6; ++k) {
         const int x = gx + k - 1;
-        const int m = __builtin_amdgcn_sdot2(__builtin_bit_cast(s2, xy[k]), __builtin_bit_cast(s2, xy[k]), 0, false);
+        const int m = grad_sq(xy[k]);
         mg[2][k] = (row_in && x >= 0 && x < w) ? m : 0;
         if (k >= 1 && k <= 4) cxy[1][k - 1] = xy[k];
       }
@@ -1011,8 +1006,21 @@ constexpr int HTH = 256;     // tile rows: taller than the stencil tiles -- grow
 // can move it again.  (Until round 3 a tile was active whenever it or any of its 8 neighbours had changed, which in the
 // sweeps after the first is nearly every tile: they cost 0.2 ms each at 64 planes where a few per cent of the tiles
 // had anything to do.)  A request made from a stale view (the pixel was promoted meanwhile) costs one re-check.
+// The LDS maps hold (HTH + 2) x (HW + 2) words: the tile and a halo of one row / one word (32 pixels) around it.
+__device__ __forceinline__ bool hyst_interior(int r, int k) { return r >= 1 && r <= HTH && k >= 1 && k <= HW; }
 __device__ __forceinline__ uint32_t lds_interior(const uint32_t (*a)[HW + 2], int r, int k) {
-  return (r >= 1 && r <= HTH && k >= 1 && k <= HW) ? a[r][k] : 0u;
+  return hyst_interior(r, k) ? a[r][k] : 0u;
+}
+// Bits of word (r, k) that are 8-neighbours of (or are) a set bit of the map that at(r, k) reads word by word.
+template <typename At>
+__device__ __forceinline__ uint32_t dilate3x3(At at, int r, int k) {
+  uint32_t dil = 0;
+#pragma unroll
+  for (int dr = -1; dr <= 1; ++dr) {
+    const uint32_t c = at(r + dr, k), l = at(r + dr, k - 1), rt = at(r + dr, k + 1);
+    dil |= c | (c << 1) | (c >> 1) | (l >> 31) | (rt << 31);
+  }
+  return dil;
 }
 
 __global__ __launch_bounds__(NT) void k_hysteresis(const uint32_t* __restrict__ d_weak, uint32_t* __restrict__ d_strong,
@@ -1039,7 +1047,7 @@ __global__ __launch_bounds__(NT) void k_hysteresis(const uint32_t* __restrict__ 
 #pragma unroll
     for (int it = 0; it < ITER; ++it) {
       const int i = min((int)threadIdx.x + it * NT, TOTAL - 1);
-      const int r = i / (HW + 2), kk = i - r * (HW + 2);
+      const auto [r, kk] = row_col(i, HW + 2);
       const int y = ty0 - 1 + r, x = tx0 - 32 + 32 * kk;
       const bool in = y >= 0 && y < h && x >= 0 && x < w;
       const int64_t wi = in ? ((int64_t)y * w + x) >> 5 : 0;
@@ -1051,20 +1059,20 @@ __global__ __launch_bounds__(NT) void k_hysteresis(const uint32_t* __restrict__ 
     for (int it = 0; it < ITER; ++it) {
       const int i = threadIdx.x + it * NT;
       if (i < TOTAL) {
-        const int r = i / (HW + 2), kk = i - r * (HW + 2);
+        const auto [r, kk] = row_col(i, HW + 2);
         st[r][kk] = sv[it];
         wk[r][kk] = wv[it];
-        if (r >= 1 && r <= HTH && kk >= 1 && kk <= HW) pending |= (wv[it] & ~sv[it]) != 0;
+        if (hyst_interior(r, kk)) pending |= (wv[it] & ~sv[it]) != 0;
       }
     }
   } else {
     for (int i = threadIdx.x; i < (HTH + 2) * (HW + 2); i += NT) {
-      const int r = i / (HW + 2), kk = i - r * (HW + 2);
+      const auto [r, kk] = row_col(i, HW + 2);
       const uint32_t sv = row_word(strong, h, w, ty0 - 1 + r, tx0 - 32 + 32 * kk);
       const uint32_t wv = row_word(weak, h, w, ty0 - 1 + r, tx0 - 32 + 32 * kk);
       st[r][kk] = sv;
       wk[r][kk] = wv;
-      if (r >= 1 && r <= HTH && kk >= 1 && kk <= HW) pending |= (wv & ~sv) != 0;
+      if (hyst_interior(r, kk)) pending |= (wv & ~sv) != 0;
     }
   }
   if (threadIdx.x == 0) s_mark = 0u;
@@ -1088,13 +1096,7 @@ __global__ __launch_bounds__(NT) void k_hysteresis(const uint32_t* __restrict__ 
       uint32_t cur = st[r][k];
       uint32_t cand = wk[r][k] & ~cur;
       if (!cand) continue;
-      uint32_t dil = 0;
-#pragma unroll
-      for (int dr = -1; dr <= 1; ++dr) {
-        const uint32_t c = st[r + dr][k], l = st[r + dr][k - 1], rt = st[r + dr][k + 1];
-        dil |= c | (c << 1) | (c >> 1) | (l >> 31) | (rt << 31);
-      }
-      uint32_t nw = cand & dil;
+      uint32_t nw = cand & dilate3x3([&](int rr, int kk) { return st[rr][kk]; }, r, k);
       if (!nw) continue;
       cur |= nw;
       cand &= ~nw;
@@ -1124,13 +1126,7 @@ __global__ __launch_bounds__(NT) void k_hysteresis(const uint32_t* __restrict__ 
     else r = i - 2 * (HW + 2) - HTH + 1, kk = HW + 1;
     const uint32_t cand = wk[r][kk] & ~st[r][kk];
     if (!cand) continue;
-    uint32_t dil = 0;
-#pragma unroll
-    for (int dr = -1; dr <= 1; ++dr) {
-      const uint32_t c = lds_interior(wk, r + dr, kk), l = lds_interior(wk, r + dr, kk - 1), rt = lds_interior(wk, r + dr, kk + 1);
-      dil |= c | (c << 1) | (c >> 1) | (l >> 31) | (rt << 31);
-    }
-    if (cand & dil) {
+    if (cand & dilate3x3([&](int rr, int k2) { return lds_interior(wk, rr, k2); }, r, kk)) {
       const int dy = r == 0 ? -1 : (r == HTH + 1 ? 1 : 0), dx = kk == 0 ? -1 : (kk == HW + 1 ? 1 : 0);
       atomicOr(&s_mark, 1u << ((dy + 1) * 3 + dx + 1));
     }
@@ -1161,17 +1157,17 @@ __global__ __launch_bounds__(NT) void k_unpack_bits(const uint32_t* __restrict__
     d_out[plane * npix + i] = (bits[i >> 5] >> (i & 31)) & 1u;
 }
 
-// bits_at without its branch around the second word (the bitmaps carry a spare word): a load behind a lane-level branch
-// ends with a wait, and the loads of a wave's groups are meant to be in flight together
-__device__ __forceinline__ uint32_t bits_at_nb(const uint32_t* __restrict__ bits, int64_t bit0, int n) {
-  const int64_t wi = bit0 >> 5;
-  const int sh = (int)(bit0 & 31);
-  const uint64_t two = (uint64_t)bits[wi] | ((uint64_t)bits[wi + 1] << 32);
-  const uint32_t v = (uint32_t)(two >> sh);
-  return n >= 32 ? v : (v & ((1u << n) - 1u));
+// ---- K5: grid_array from the bitmap: per-cell counts, scan, ordered coordinate fill -------------
+// Cell `cell` of the gc cells per row: rows [y0, y0 + ch) x columns [x0, x0 + cw), clipped to the image.
+struct CellRect {
+  int y0, x0, ch, cw;
+};
+__device__ __forceinline__ CellRect cell_rect(int cell, int grid, int gc, int h, int w) {
+  const int cr = cell / gc, cc = cell - cr * gc;
+  const int y0 = cr * grid, x0 = cc * grid;
+  return CellRect{y0, x0, min(grid, h - y0), min(grid, w - x0)};
 }
 
-// ---- K5: grid_array from the bitmap: per-cell counts, scan, ordered coordinate fill -------------
 __global__ __launch_bounds__(NT) void k_cell_count(const uint32_t* __restrict__ d_bits, int64_t words_per_plane, int h,
                                                    int w, int grid, int gc, int n_cells,
                                                    int32_t* __restrict__ d_counts, unsigned long long* __restrict__ d_state,
@@ -1182,9 +1178,7 @@ __global__ __launch_bounds__(NT) void k_cell_count(const uint32_t* __restrict__ 
   if (d_state && cell < state_words) d_state[(int64_t)plane * state_words + cell] = 0ull;
   if (cell >= n_cells) return;
   const uint32_t* bits = d_bits + plane * words_per_plane;
-  const int cr = cell / gc, cc = cell - cr * gc;
-  const int y0 = cr * grid, x0 = cc * grid;
-  const int ch = min(grid, h - y0), cw = min(grid, w - x0);
+  const auto [y0, x0, ch, cw] = cell_rect(cell, grid, gc, h, w);
   int cnt = 0;
 #pragma unroll 5
   for (int r = 0; r < ch; ++r)  // (branch-free loads, five rows a trip: in flight together)
@@ -1293,9 +1287,7 @@ __global__ __launch_bounds__(NT) void k_cell_fill(const uint32_t* __restrict__ d
   const int cell = blockIdx.x * NT + threadIdx.x;
   if (cell >= n_cells) return;
   const uint32_t* bits = d_bits + plane * words_per_plane;
-  const int cr = cell / gc, cc = cell - cr * gc;
-  const int y0 = cr * grid, x0 = cc * grid;
-  const int ch = min(grid, h - y0), cw = min(grid, w - x0);
+  const auto [y0, x0, ch, cw] = cell_rect(cell, grid, gc, h, w);
   int2* out = reinterpret_cast<int2*>(d_coords + (int64_t)plane * coord_cap * 2);
   int64_t pos = d_starts[(int64_t)plane * n_cells + cell];
   for (int r = 0; r < ch; ++r)
@@ -1400,9 +1392,20 @@ __global__ __launch_bounds__(NT) void k_edge_angles(const uint8_t* __restrict__ 
   }
 }
 
+inline dim3 hysteresis_grid(int h, int w, int n_planes) { return dim3((w + TW - 1) / TW, (h + HTH - 1) / HTH, n_planes); }
+inline bool grid_ok(const dim3& g) { return g.y <= 65535 && g.z <= 65535; }
 inline dim3 tile_grid(int h, int w, int n_planes) { return dim3((w + TW - 1) / TW, (h + TH - 1) / TH, n_planes); }
 inline bool words_ok(int64_t words_per_plane, int h, int w) {
   return words_per_plane * 32 >= (((int64_t)h * w + 31) / 32) * 32 + 32;  // one spare word: bits_at reads wi + 1
+}
+
+// d_hist += the n_planes x slots packed histograms that the kernel before it on the stream left in d_partial.
+int launch_hist_reduce(const uint32_t* d_partial, int slots, int n_bins, int n_planes, uint32_t* d_hist,
+                       const uint32_t* d_skip_base, hipStream_t s) {
+  const dim3 g((n_bins / 2 + NT - 1) / NT, n_planes, (slots + HIST_SLOTS_PER_BLOCK - 1) / HIST_SLOTS_PER_BLOCK);
+  hipLaunchKernelGGL(k_hist_reduce, g, dim3(NT), 0, s, d_partial, slots, n_bins, d_hist, d_skip_base);
+  MG_CHECK_LAUNCH();
+  return MG_OK;
 }
 
 }  // namespace
@@ -1414,7 +1417,7 @@ extern "C" int mg_to_uint8_blur(const void* d_src, int dtype, int n_planes, int6
   if (!d_minmax && dtype != MG_U8) return MG_EINVAL;
   if (n_planes == 0 || h == 0 || w == 0) return MG_OK;
   const dim3 g = tile_grid(h, w, n_planes);
-  if (g.y > 65535 || g.z > 65535) return MG_EINVAL;
+  if (!grid_ok(g)) return MG_EINVAL;
   hipStream_t s = mg_stream(stream);
   return mg_dispatch_pixel(dtype, [&](auto t) {
     using T = decltype(t);
@@ -1439,7 +1442,7 @@ extern "C" int mg_scharr_hist(const uint8_t* d_blur, int n_planes, int h, int w,
   if (n_planes == 0 || h == 0 || w == 0) return MG_OK;
   const dim3 t = tile_grid(h, w, n_planes);
   const dim3 g(t.x, (t.y + HIST_TILES - 1) / HIST_TILES, t.z);
-  if (g.y > 65535 || g.z > 65535) return MG_EINVAL;
+  if (!grid_ok(g)) return MG_EINVAL;
   if (d_scratch && scratch_words < mg_scharr_hist_scratch_words(n_planes, h, w, mode)) return MG_EINVAL;
   const int n_bins = mode == 0 ? FINE + COARSE : FINE;
   const size_t lds = (size_t)(TH + 2) * LS + (size_t)n_bins * 2;
@@ -1461,13 +1464,8 @@ extern "C" int mg_scharr_hist(const uint8_t* d_blur, int n_planes, int h, int w,
   hipLaunchKernelGGL(k_scharr_hist<false>, t, dim3(NT), lds, mg_stream(stream), d_blur, h, w, mode, d_base, n_bins,
                      d_hist, d_scratch, split);
   MG_CHECK_LAUNCH();
-  if (d_scratch) {
-    const int slots = (int)(g.x * g.y);
-    hipLaunchKernelGGL(k_hist_reduce, dim3((n_bins / 2 + NT - 1) / NT, n_planes, (slots + HIST_SLOTS_PER_BLOCK - 1) / HIST_SLOTS_PER_BLOCK),
-                       dim3(NT), 0, mg_stream(stream), d_scratch, slots, n_bins, d_hist, mode == 1 ? d_base : nullptr);
-    MG_CHECK_LAUNCH();
-  }
-  return MG_OK;
+  if (!d_scratch) return MG_OK;
+  return launch_hist_reduce(d_scratch, (int)(g.x * g.y), n_bins, n_planes, d_hist, mode == 1 ? d_base : nullptr, mg_stream(stream));
 }
 
 // to_uint8 + blur + combined histogram: one pass where the fused kernel applies (integer input, no un-blurred
@@ -1500,7 +1498,7 @@ extern "C" int mg_to_uint8_blur_hist(const void* d_src, int dtype, int n_planes,
     return mg_scharr_hist(d_blur, n_planes, h, w, 0, nullptr, d_hist, d_scratch, scratch_words, stream);
   }
   const dim3 g((w + FW - 1) / FW, (h + FH - 1) / FH, n_planes);
-  if (g.y > 65535 || g.z > 65535) return MG_EINVAL;
+  if (!grid_ok(g)) return MG_EINVAL;
   hipStream_t s = mg_stream(stream);
   constexpr int n_bins = FINE + COARSE;
   if (dtype == MG_U8)
@@ -1510,11 +1508,7 @@ extern "C" int mg_to_uint8_blur_hist(const void* d_src, int dtype, int n_planes,
     hipLaunchKernelGGL((k_blur_hist<uint16_t>), g, dim3(NT), (size_t)n_bins * 2, s, (const uint16_t*)d_src, plane_stride, h,
                        w, row_stride, d_minmax, d_blur, d_scratch);
   MG_CHECK_LAUNCH();
-  const int slots = (int)(g.x * g.y);
-  hipLaunchKernelGGL(k_hist_reduce, dim3((n_bins / 2 + NT - 1) / NT, n_planes, (slots + HIST_SLOTS_PER_BLOCK - 1) / HIST_SLOTS_PER_BLOCK),
-                     dim3(NT), 0, s, d_scratch, slots, n_bins, d_hist, (const uint32_t*)nullptr);
-  MG_CHECK_LAUNCH();
-  return MG_OK;
+  return launch_hist_reduce(d_scratch, (int)(g.x * g.y), n_bins, n_planes, d_hist, nullptr, s);
 }
 
 extern "C" int mg_edge_thresholds(const uint32_t* d_hist, int n_planes, const int64_t* ranks4, float gamma_low,
@@ -1550,7 +1544,7 @@ extern "C" int mg_canny_nms(const uint8_t* d_blur, int n_planes, int h, int w, c
   if (n_planes == 0 || h == 0 || w == 0) return MG_OK;
   if (!words_ok(words_per_plane, h, w)) return MG_EINVAL;
   const dim3 g = tile_grid(h, w, n_planes);
-  if (g.y > 65535 || g.z > 65535) return MG_EINVAL;
+  if (!grid_ok(g)) return MG_EINVAL;
   hipStream_t s = mg_stream(stream);
   // w % 32 == 0: every bitmap word inside the image belongs to one lane group, which stores it whole -- nothing to
   // clear (the spare words behind the image are never written: the caller zeroes the buffers once, when it makes them)
@@ -1570,8 +1564,8 @@ extern "C" int mg_canny_hysteresis(const uint32_t* d_weak, uint32_t* d_strong, i
   if (!d_weak || !d_strong || !d_changed || n_planes < 0 || h < 0 || w < 0) return MG_EINVAL;
   if (n_planes == 0 || h == 0 || w == 0) return MG_OK;
   if (!words_ok(words_per_plane, h, w)) return MG_EINVAL;
-  const dim3 g((w + TW - 1) / TW, (h + HTH - 1) / HTH, n_planes);
-  if (g.y > 65535 || g.z > 65535) return MG_EINVAL;
+  const dim3 g = hysteresis_grid(h, w, n_planes);
+  if (!grid_ok(g)) return MG_EINVAL;
   hipLaunchKernelGGL(k_hysteresis, g, dim3(NT), 0, mg_stream(stream), d_weak, d_strong, words_per_plane, h, w,
                      d_changed, d_flags_in, d_flags_out);
   MG_CHECK_LAUNCH();
@@ -1580,8 +1574,9 @@ extern "C" int mg_canny_hysteresis(const uint32_t* d_weak, uint32_t* d_strong, i
 
 extern "C" int mg_hysteresis_tiles(int h, int w, int* tiles_x, int* tiles_y) {
   if (!tiles_x || !tiles_y) return MG_EINVAL;
-  *tiles_x = (w + TW - 1) / TW;
-  *tiles_y = (h + HTH - 1) / HTH;
+  const dim3 g = hysteresis_grid(h, w, 1);
+  *tiles_x = (int)g.x;
+  *tiles_y = (int)g.y;
   return MG_OK;
 }
 

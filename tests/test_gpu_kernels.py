@@ -228,13 +228,13 @@ def _edge_images():
     return np.stack(imgs)
 
 
-@pytest.mark.parametrize("quantiles", [(0.1, 0.9), (0.5, 0.99), (0.9, 0.1)])
-def test_edge_stage(hp, quantiles):
-    planes = _edge_images()
+def _check_edge_stage(hp, planes, quantiles, keep_u8=False):
+    """edge_stage of `planes` against the oracle, plane by plane: blur, quantiles, thresholds, weak map, edge bitmap and
+    its zero tail, the three orientation planes, angles, grid counts / starts / coordinates (and the un-blurred copy)."""
     p, h, w = planes.shape
     cf = hp.CircleFinder(p, h, w, 5, 14, 1000)
     cf.keep_debug_maps = True
-    n_edges = cf.edge_stage(dev(planes), None, *quantiles)
+    n_edges = cf.edge_stage(dev(planes), None, *quantiles, keep_u8=keep_u8)
     bits = cf.edge_bits.cpu().numpy().view(np.uint32)
     edges = cf.edges.cpu().numpy()
     angle = cf.angle.cpu().numpy()
@@ -242,6 +242,8 @@ def test_edge_stage(hp, quantiles):
     coords = cf.coords.cpu().numpy()
     for k in range(p):
         u8 = rn.to_uint8(planes[k])
+        if keep_u8:
+            np.testing.assert_array_equal(cf.u8[k].cpu().numpy(), u8)
         blur, dx, dy, want_edges, (lo, hi) = rp.edge_stage(u8, *quantiles)
         np.testing.assert_array_equal(cf.blur[k].cpu().numpy(), blur)
         assert (np.float32(lo), np.float32(hi)) == tuple(cf.quantiles[k])
@@ -290,6 +292,28 @@ def test_edge_stage(hp, quantiles):
         np.testing.assert_array_equal(counts[k].reshape(gcounts.shape), gcounts)
         np.testing.assert_array_equal(starts[k].reshape(gstarts.shape), gstarts)
         np.testing.assert_array_equal(coords[k, : len(gcoords)], gcoords)
+
+
+@pytest.mark.parametrize("quantiles", [(0.1, 0.9), (0.5, 0.99), (0.9, 0.1)])
+def test_edge_stage(hp, quantiles):
+    _check_edge_stage(hp, _edge_images(), quantiles)
+
+
+@pytest.mark.parametrize("dtype,shape,keep_u8", [
+    # odd width: the two-pass route, every histogram tile staged, ragged last lanes, NMS words by atomicOr, the
+    # row_word loader of the hysteresis
+    (np.uint16, (1, 70, 113), False),
+    # w % 32 == 0 over 3 x 5 stencil tiles and two hysteresis tile rows: the one-pass blur + histogram, whole-word NMS
+    # stores, the whole-word hysteresis loader across tile borders
+    (np.uint16, (2, 300, 544), False),
+    # float input: k_u8_blur<float>, the register-direct histogram for tile columns 0 and 1, the staged launch for 2
+    (np.float32, (1, 200, 520), False),
+    # one tile at the left and the right image edge at once in the register-direct histogram; the un-blurred copy
+    (np.uint16, (1, 64, 256), True),
+])
+def test_edge_stage_shapes(hp, dtype, shape, keep_u8):
+    planes = np.stack([noisy_bead_image(30 + k, shape[1:], 2 + k, r_lo=4, r_hi=7)[0] for k in range(shape[0])])
+    _check_edge_stage(hp, planes.astype(dtype), (0.1, 0.9), keep_u8=keep_u8)
 
 
 def test_edge_stage_empty_and_tiny(hp):
