@@ -123,6 +123,26 @@ int mg_plane_minmax(const void* d_src, int dtype, int n_planes, int64_t plane_st
                     int64_t row_stride, double* d_minmax, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * rotate (preprocess.py:54-59; the disabled body there: dask_image.ndinterp.rotate(order=1, reshape=False))
+ * ---------------------------------------------------------------------------------- */
+
+/* Bilinear 2 x 2 affine resampling of n_planes contiguous (h, w) planes of `dtype`, d_src -> d_dst (distinct buffers
+ * of the same size and type), with the semantics of scipy.ndimage.affine_transform(order=1, mode="constant", cval=0):
+ * `matrix` (4 doubles, row-major) and `offset` (2 doubles) are HOST pointers, read before the call returns.  All
+ * arithmetic is float64, every operation rounded on its own (no fused multiply-add), in this order, for output pixel
+ * (oy, ox):
+ *   cy = (offset[0] + oy * matrix[0]) + ox * matrix[1],  cx = (offset[1] + oy * matrix[2]) + ox * matrix[3];
+ *   cy < 0, cy > h - 1, cx < 0 or cx > w - 1: the value is 0 (no interpolation across the border); otherwise
+ *   fy = floor(cy), ty = cy - fy, y0 = fy, y1 = min(y0 + 1, h - 1), and the same for x;
+ *   v = (((p00 * (1 - ty)) * (1 - tx) + (p01 * (1 - ty)) * tx) + (p10 * ty) * (1 - tx)) + (p11 * ty) * tx;
+ *   written as floor(v + 0.5) for MG_U8 / MG_U16, (float)v for MG_F32, v for MG_F64.
+ * d_minmax (optional, double[n_planes][2] pre-initialised to {+inf, -inf}) receives the per-plane min/max of the
+ * values written, as for mg_flatfield_apply_stitch.  MG_EINVAL: a null or misaligned pointer, d_src == d_dst, a
+ * negative size, an unknown dtype, a non-finite matrix or offset; MG_OK without a launch when there is no pixel. */
+int mg_affine_bilinear(const void* d_src, void* d_dst, int dtype, int64_t n_planes, int h, int w,
+                       const double* matrix, const double* offset, double* d_minmax, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Shading model (BaSiC, Peng et al. 2017): fit of a flat- and a dark-field from training tiles and its apply fused
  * with the stitch crop (DESIGN.md §4 "shading"; oracle tests/ref_shading.py).  The fit's state lives in one device
  * workspace of mg_shading_workspace_bytes(n, w) bytes (n images, w x w working grid, 1 <= w <= 128), 256-byte aligned;

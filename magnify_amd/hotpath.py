@@ -297,6 +297,46 @@ def plane_minmax(planes: torch.Tensor) -> torch.Tensor:
 
 
 # --------------------------------------------------------------------------------------
+# rotate: bilinear resampling of the stitched image about its centre
+# --------------------------------------------------------------------------------------
+
+
+def rotation_matrix_offset(angle_degrees: float, h: int, w: int):
+    """(matrix (2, 2), offset (2,)) float64 of ``scipy.ndimage.rotate(..., reshape=False)`` on an (h, w) plane, built
+    the way scipy builds them: output pixel o samples the input at ``matrix @ o + offset``."""
+    from scipy import special  # cosdg / sindg are exact at the multiples of 90 degrees
+
+    c, s = special.cosdg(angle_degrees), special.sindg(angle_degrees)
+    m = np.array([[c, s], [-s, c]], dtype=np.float64)
+    ctr = np.array([(h - 1) / 2, (w - 1) / 2], dtype=np.float64)
+    return m, ctr - m @ ctr
+
+
+def rotate_image(image: torch.Tensor, angle_degrees: float, want_minmax=True):
+    """image (C, T, H, W) -> (every plane rotated by ``angle_degrees`` about its centre, per-plane min/max (C*T, 2) or
+    None): ``scipy.ndimage.rotate(plane, angle, axes=(-1, -2), reshape=False, order=1, mode="constant", cval=0)`` on
+    every plane, one launch of mg_affine_bilinear for all of them."""
+    require_gpu()
+    if image.dim() != 4:
+        raise ValueError(f"rotate_image takes a (channel, time, y, x) image, got {tuple(image.shape)}")
+    angle = float(angle_degrees)
+    if not math.isfinite(angle):
+        raise ValueError(f"rotation must be finite, got {angle_degrees!r}")
+    c, t, h, w = image.shape
+    image = image.contiguous()
+    m, off = rotation_matrix_offset(angle, h, w)
+    m = np.ascontiguousarray(m, dtype=np.float64)
+    off = np.ascontiguousarray(off, dtype=np.float64)
+    out = torch.empty_like(image)
+    minmax = _minmax_init(c * t, image.device).clone() if want_minmax else None
+    if image.numel() == 0:
+        return out, minmax
+    _call("mg_affine_bilinear", image.data_ptr(), out.data_ptr(), nat.dtype_code(image.dtype), c * t, h, w,
+          m.ctypes.data, off.ctypes.data, _ptr(minmax), _stream())
+    return out, minmax
+
+
+# --------------------------------------------------------------------------------------
 # np.quantile on the float32 gradient magnitude, from the integer histogram
 # --------------------------------------------------------------------------------------
 

@@ -1,8 +1,9 @@
 """standardize_format and flatfield_correct (reference: src/magnify/preprocess.py:11-41, 62-88),
-plus the trivial view components that keep their registry names (rotate is a no-op in the
-reference as well, preprocess.py:54-59)."""
+plus the trivial view components that keep their registry names and ``rotate`` (a stub in the reference,
+preprocess.py:54-59; here it does what its disabled body did)."""
 from __future__ import annotations
 
+import math
 import os
 
 import numpy as np
@@ -82,7 +83,25 @@ def rename_labels(xp, **coords):
 
 @registry.component("rotate")
 def rotate(xp, rotation=0):
-    return xp  # no-op in the reference too (preprocess.py:54-59)
+    """Rotate every plane of the stitched ``image`` by ``rotation`` degrees about its centre, keeping its size: the
+    disabled body of the reference's stub (preprocess.py:54-59, ``ndinterp.rotate(..., reshape=False)``) with bilinear
+    interpolation, ``scipy.ndimage.rotate(plane, rotation, axes=(-1, -2), reshape=False, order=1)`` per plane
+    (deliberate differences).  A whole number of turns returns the dataset untouched."""
+    rotation = float(rotation)
+    if not math.isfinite(rotation):
+        raise ValueError(f"rotation must be a finite number of degrees, got {rotation!r}")
+    if rotation % 360 == 0:
+        return xp
+    if "image" not in xp:
+        raise AttributeError("Dataset must contain 'image' data variable.")
+    v = xp.data_vars["image"].transpose("channel", "time", "im_y", "im_x")
+    data = v.data
+    if not isinstance(data, torch.Tensor) or not data.is_cuda:
+        data = to_device(data)
+    image, minmax = hotpath.rotate_image(data, rotation)
+    xp["image"] = DataArray(image, ("channel", "time", "im_y", "im_x"))
+    xp._cache["image_minmax"] = (image.data_ptr(), minmax)  # (find._plane_minmax: the finders skip their own pass)
+    return xp
 
 
 class LazyFlatfield:
