@@ -1,14 +1,17 @@
-// A8-A11: RANSAC circle candidates (utils.py:295-344), filter_circles steps 4-6
-// (utils.py:149-199), mean_grad scoring (utils.py:225-251) and the greedy claim-grid
-// suppression of filter_neighbors (utils.py:254-292), re-formulated for a GPU:
+// A8-A11: RANSAC circle candidates (utils.py:295-344), filter_circles steps 4-6 (utils.py:149-199), mean_grad scoring
+// (utils.py:225-251) and the greedy suppression of filter_neighbors (utils.py:254-292).  A circle's score depends only
+// on (row, col, r), so candidates are de-duplicated before they are scored.  What this file holds:
 //
-//   candidates -> integer circles -> de-duplication in a bitmap (a circle's score depends
-//   only on (row, col, r)) -> ordered compaction (= sort by r, row, col without sorting)
-//   -> one thread per unique circle scores it with the reference's sequential float64 sum
-//   -> parallel rounds of min-priority claims on the reference's own claim grid.
-//
-// Roofline: gather/latency bound (random reads of the angle map from L2 / Infinity Cache);
-// reported separately from the HBM-streaming stages.
+//   candidates   k_candidates_tab (bisectors from an LDS table; the keyed product path) and k_candidates<FAST> (every
+//                other shape, and the bitmap path); both end in circle_from_bisectors / candidate_key
+//   unique list  keyed: k_tile_dedup -- a workgroup per tile pair collects its 32-bit keys (mg_common.h: mg_key_*) in
+//                LDS layers and emits them sorted;  bitmap: global atomicOr, then k_layer_count / _scan / _emit
+//   scoring      k_score_tiles: a workgroup per centre tile, its edge window in LDS as bits, count-only prefilter, then
+//                the reference's sequential float64 sum for the survivors (the second product path; the
+//                keyed path scores with mg_score.hip and shares mg_alignment_term / mg_score_floor / mg_emit_alive)
+//   suppression  k_nms_sparse: a plane decided in one workgroup from the circles alone;  k_nms<PHASE>: parallel rounds
+//                of min-priority claims on the reference's own claim grid, for the planes the former cannot take
+//   collection   k_collect_list / k_collect_rank: the kept circles in the reference's order
 #include <math.h>
 #include <stdlib.h>
 
@@ -18,20 +21,8 @@ namespace {
 
 constexpr int NT = 256;
 
-// ---- RNG: splitmix64 finaliser, top 32 bits -------------------------------------------------
-__device__ __forceinline__ uint32_t draw32(uint64_t seed, uint64_t it, uint32_t k) {
-  uint64_t z = seed + (it * 3ull + k + 1ull) * 0x9E3779B97F4A7C15ull;
-  z ^= z >> 30;
-  z *= 0xBF58476D1CE4E5B9ull;
-  z ^= z >> 27;
-  z *= 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return (uint32_t)(z >> 32);
-}
-
-// The finaliser alone: draw32(seed, it, k) == mix_top32(seed + (3 it + k + 1) * golden).
+// ---- RNG: splitmix64 finaliser; draw k of iteration `it` is the top half of mix64(seed + (3 it + k + 1) * golden) ----
 constexpr uint64_t GOLDEN = 0x9E3779B97F4A7C15ull;
-constexpr uint32_t MG_NO_KEY = 0xFFFFFFFFu;  // candidate rejected by the radius / on-image filter
 __device__ __forceinline__ uint64_t mix64(uint64_t z) {
   z ^= z >> 30;
   z *= 0xBF58476D1CE4E5B9ull;
@@ -66,6 +57,65 @@ __device__ __forceinline__ uint64_t div_u64(uint64_t n, uint64_t d, double inv_d
   return q;
 }
 
+// ---- the candidate tail shared by k_candidates<> and k_candidates_tab --------------------------------
+// Perpendicular bisector of p0 and p0 + (d_row, d_col) in p0-centred coordinates (utils.py:326-334), float64: (slope,
+// intercept).  The slope's numerator is negated as an integer (as the reference does), so a zero stays +0.0.
+constexpr double BISECTOR_EPS = (double)1e-20f;
+__device__ __forceinline__ double2 bisector(int d_row, int d_col) {
+  const double m = (double)(-d_col) / ((double)d_row + BISECTOR_EPS);
+  return make_double2(m, 0.5 * (double)d_row - m * (0.5 * (double)d_col));
+}
+
+// The one general division of a candidate: `/`, or the same sequence without its range scaling (k_candidates_tab).
+struct DivFull {
+  __device__ __forceinline__ double operator()(double num, double den) const { return num / den; }
+};
+struct DivUnscaled {
+  __device__ __forceinline__ double operator()(double num, double den) const {
+    if (!(fabs(den) > 0.0 && fabs(den) < 1.0e300)) return num / den;  // 0, inf, NaN: the full sequence
+    double y = __builtin_amdgcn_rcp(den);
+    double e = fma(-den, y, 1.0);
+    y = fma(y, e, y);
+    e = fma(-den, y, 1.0);
+    y = fma(y, e, y);
+    double q = num * y;
+    const double r = fma(-den, q, num);
+    return fma(r, y, q);
+  }
+};
+
+// Intersection of two bisectors, each store rounds to float32 (utils.py:337-342): (row, col, radius) in image coordinates.
+template <class Div>
+__device__ __forceinline__ float3 circle_from_bisectors(double2 l1, double2 l2, int p0r, int p0c, Div div) {
+  const float c_col = (float)div(l1.y - l2.y, l2.x - l1.x + BISECTOR_EPS);
+  const float c_row = (float)(l1.x * (double)c_col + l1.y);
+  const float rad = sqrtf(c_row * c_row + c_col * c_col);
+  return make_float3((float)((double)c_row + (double)p0r), (float)((double)c_col + (double)p0c), rad);
+}
+
+__device__ __forceinline__ void store_raw(float* __restrict__ d_raw, int64_t index, float3 c) {
+  if (!d_raw) return;
+  float* o = d_raw + index * 3;
+  o[0] = c.x;
+  o[1] = c.y;
+  o[2] = c.z;
+}
+
+// filter_circles step 4 (utils.py:157-166): the radius range, then the rounded circle has to touch the image.  What
+// passes goes to its cell of the tile-major de-duplication -- emit(tile, layer, row, col): 64 x 64 tiles of the centre
+// grid padded by max_r, one 4096-bit layer per (tile, radius) -- as a key (mg_key_pack) or as a bit of the global
+// bitmap, which has layers for any number of tiles and radii.
+template <class Emit>
+__device__ __forceinline__ void candidate_cell(float3 c, int h, int w, int min_r, int max_r, int ntc, Emit&& emit) {
+  if (!(c.z >= (float)min_r && c.z <= (float)max_r)) return;
+  const float rr = rintf(c.x), rc = rintf(c.y);
+  if (!(fabsf(rr) < 1.0e9f && fabsf(rc) < 1.0e9f)) return;  // cannot be on the image (and NaN)
+  const int ir = (int)rr, ic = (int)rc, irad = (int)rintf(c.z);
+  if (ir + irad < 0 || ic + irad < 0 || ir - irad >= h || ic - irad >= w) return;
+  const int pr = ir + max_r, pc = ic + max_r;
+  emit((pr >> 6) * ntc + (pc >> 6), irad - min_r, pr & 63, pc & 63);
+}
+
 // ---- K7: candidate circles --------------------------------------------------------------------
 // FAST: num_iter < 2^31 and h, w <= 65536 and grid > 1 (checked by the launcher).
 template <bool FAST>
@@ -87,22 +137,20 @@ __global__ __launch_bounds__(NT) void k_candidates(const int32_t* __restrict__ d
   const int ntc = (w + 2 * max_r + 63) >> 6, nr = max_r - min_r + 1;
   uint32_t* bitmap = d_bitmap ? d_bitmap + (int64_t)plane * bitmap_words : nullptr;
   uint32_t* keys = d_keys ? d_keys + (int64_t)plane * num_iter : nullptr;
-  const double eps = (double)1e-20f;
   const double inv_iter = 1.0 / (double)num_iter;
-  // strength-reduced bookkeeping (same values as draw32 / floor(it E / K), fewer quarter-rate
+  // strength-reduced bookkeeping (same values as mix64(seed + ...) / floor(it E / K), fewer quarter-rate
   // integer multiplies): the RNG counter advances by a constant per loop trip; E = eq K + er splits
   // the stratum bound into a 32-bit product and a float64 quotient; cells by a magic multiply
   const int64_t it0 = (int64_t)blockIdx.x * NT + threadIdx.x, stride = (int64_t)gridDim.x * NT;
   uint64_t zbase = seed + ((uint64_t)it0 * 3ull + 1ull) * GOLDEN;
   const uint64_t zstep = (uint64_t)stride * 3ull * GOLDEN;
-  constexpr bool small = FAST, gfast = FAST;
-  const uint32_t eq = small ? n_edges / (uint32_t)num_iter : 0u;
-  const double er = small ? (double)(n_edges - eq * (uint32_t)num_iter) : 0.0, dk = (double)num_iter;
+  const uint32_t eq = FAST ? n_edges / (uint32_t)num_iter : 0u;
+  const double er = FAST ? (double)(n_edges - eq * (uint32_t)num_iter) : 0.0, dk = (double)num_iter;
   const uint32_t gmagic = grid > 1 ? 0xFFFFFFFFu / (uint32_t)grid + 1u : 0u;  // exact for operands < 2^16
   for (int64_t it = it0; it < num_iter; it += stride, zbase += zstep) {
     // jittered stratified p0: iteration it owns the slice [a, b) of the cell-major edge list
     uint64_t sa, sb;
-    if (small) {
+    if (FAST) {
       const double x = (double)(uint32_t)it * er;  // exact: < 2^52
       sa = (uint64_t)((uint32_t)it * eq + div_f64(x, dk, inv_iter));
       sb = (uint64_t)(((uint32_t)it + 1u) * eq + div_f64(x + er, dk, inv_iter));
@@ -113,54 +161,27 @@ __global__ __launch_bounds__(NT) void k_candidates(const int32_t* __restrict__ d
     const uint64_t width = sb > sa ? sb - sa : 1;
     const uint32_t u0 = (uint32_t)(sa + (((uint64_t)mix_top32(zbase) * width) >> 32));
     const int p0r = coords[2 * (int64_t)u0], p0c = coords[2 * (int64_t)u0 + 1];
-    const int cell = gfast ? (int)(__umulhi((uint32_t)p0r, gmagic) * (uint32_t)gc + __umulhi((uint32_t)p0c, gmagic))
+    const int cell = FAST ? (int)(__umulhi((uint32_t)p0r, gmagic) * (uint32_t)gc + __umulhi((uint32_t)p0c, gmagic))
                            : (p0r / grid) * gc + (p0c / grid);
     const uint32_t cnt = (uint32_t)counts[cell];
     const int64_t base = starts[cell];
     const uint64_t z12 = mix64(zbase + GOLDEN);
     const int64_t i1 = base + (int64_t)__umulhi((uint32_t)(z12 >> 32), cnt);
     const int64_t i2 = base + (int64_t)__umulhi((uint32_t)z12, cnt);
-    // p0-centred integer coordinates (utils.py:319-321); the slope numerator is negated as an
-    // integer (as the reference does), so a zero stays +0.0
-    const int d1r = coords[2 * i1] - p0r, d1c = coords[2 * i1 + 1] - p0c;
-    const int d2r = coords[2 * i2] - p0r, d2c = coords[2 * i2 + 1] - p0c;
-    const double q1r = (double)d1r, q1c = (double)d1c, q2r = (double)d2r, q2c = (double)d2c;
-    // perpendicular bisectors (utils.py:326-334), float64
-    const double m1 = (double)(-d1c) / (q1r + eps);
-    const double m2 = (double)(-d2c) / (q2r + eps);
-    const double b1 = 0.5 * q1r - m1 * (0.5 * q1c);
-    const double b2 = 0.5 * q2r - m2 * (0.5 * q2c);
-    // intersection, each store rounds to float32 (utils.py:337-342)
-    const float c_col = (float)((b1 - b2) / (m2 - m1 + eps));
-    const float c_row = (float)(m1 * (double)c_col + b1);
-    const float rad = sqrtf(c_row * c_row + c_col * c_col);
-    const float f_row = (float)((double)c_row + (double)p0r);
-    const float f_col = (float)((double)c_col + (double)p0c);
-    if (d_raw) {
-      float* o = d_raw + ((int64_t)plane * num_iter + it) * 3;
-      o[0] = f_row;
-      o[1] = f_col;
-      o[2] = rad;
-    }
-    // filter_circles step 4 (utils.py:157-166)
+    // p0-centred integer coordinates (utils.py:319-321)
+    const double2 l1 = bisector(coords[2 * i1] - p0r, coords[2 * i1 + 1] - p0c);
+    const double2 l2 = bisector(coords[2 * i2] - p0r, coords[2 * i2 + 1] - p0c);
+    const float3 c = circle_from_bisectors(l1, l2, p0r, p0c, DivFull{});
+    store_raw(d_raw, (int64_t)plane * num_iter + it, c);
     uint32_t key = MG_NO_KEY;
-    do {
-      if (!(rad >= (float)min_r && rad <= (float)max_r)) break;
-      const float rr = rintf(f_row), rc = rintf(f_col);
-      if (!(fabsf(rr) < 1.0e9f && fabsf(rc) < 1.0e9f)) break;  // cannot be on the image (and NaN)
-      const int ir = (int)rr, ic = (int)rc, irad = (int)rintf(rad);
-      if (ir + irad < 0 || ic + irad < 0 || ir - irad >= h || ic - irad >= w) break;
-      // tile-major de-duplication: 64 x 64 tiles of the padded centre grid, one 4096-bit layer per
-      // (tile, radius); the ordered compaction then emits circles grouped by tile
-      const int pr = ir + max_r, pc = ic + max_r;
-      const int tile = (pr >> 6) * ntc + (pc >> 6);
+    candidate_cell(c, h, w, min_r, max_r, ntc, [&](int tile, int layer, int row, int col) {
       if (keys) {
-        key = ((uint32_t)tile << 17) | ((uint32_t)(irad - min_r) << 12) | (uint32_t)(((pr & 63) << 6) + (pc & 63));
+        key = mg_key_pack(tile, layer, row, col);
       } else {
-        const int64_t bit = (((int64_t)tile * nr + (irad - min_r)) << 12) + ((pr & 63) << 6) + (pc & 63);
+        const int64_t bit = (((int64_t)tile * nr + layer) << 12) + (row << 6) + col;
         atomicOr(&bitmap[bit >> 5], 1u << (bit & 31));
       }
-    } while (false);
+    });
     if (keys) keys[it] = key;  // coalesced plain store; k_tile_dedup builds the bitmap tile by tile in LDS
   }
 }
@@ -180,22 +201,11 @@ __global__ __launch_bounds__(NT) void k_candidates(const int32_t* __restrict__ d
 //    (quotient, remainder) pairs -- integer adds and compares instead of two float64 quotients with corrections;
 //  * when the stratum holds one edge (E <= K: the usual case) p0 IS that edge and the first hash is not drawn at all
 //    (its product with a width of 1 is 0 whatever the hash).
-// Bit-identical to k_candidates<true> (tests/test_gpu_kernels.py compares the raw float32 triples with the oracle's,
-// NaN / inf included, and both kernels with each other).
+// Bit-identical to k_candidates<> (test_candidates_degenerate_triplets compares the raw float32 triples and the keys of
+// all three kernels -- grid 20: this one, grid 40: k_candidates<true>, grid 1: k_candidates<false> -- with the
+// oracle's, NaN / inf included).
 constexpr int CT = 1024;
 constexpr int MAX_TAB_GRID = 32;  // (2 * 32 - 1)^2 * 16 B = 63.5 KB of LDS
-
-__device__ __forceinline__ double div_unscaled(double num, double den) {
-  if (!(fabs(den) > 0.0 && fabs(den) < 1.0e300)) return num / den;  // 0, inf, NaN: the full sequence
-  double y = __builtin_amdgcn_rcp(den);
-  double e = fma(-den, y, 1.0);
-  y = fma(y, e, y);
-  e = fma(-den, y, 1.0);
-  y = fma(y, e, y);
-  double q = num * y;
-  const double r = fma(-den, q, num);
-  return fma(r, y, q);
-}
 
 __global__ __launch_bounds__(CT) void k_candidates_tab(const int32_t* __restrict__ d_coords, int64_t coord_cap,
                                                        const int32_t* __restrict__ d_starts,
@@ -208,14 +218,8 @@ __global__ __launch_bounds__(CT) void k_candidates_tab(const int32_t* __restrict
   const int plane = blockIdx.y;
   const uint32_t n_edges = (uint32_t)d_num_edges[plane];
   if (n_edges == 0) return;
-  const double eps = (double)1e-20f;
   const int g1 = grid - 1, span = 2 * grid - 1;
-  for (int i = threadIdx.x; i < span * span; i += CT) {
-    const int dr = i / span - g1, dc = i - (i / span) * span - g1;
-    const double m = (double)(-dc) / ((double)dr + eps);
-    const double b = 0.5 * (double)dr - m * (0.5 * (double)dc);
-    s_tab[i] = make_double2(m, b);
-  }
+  for (int i = threadIdx.x; i < span * span; i += CT) s_tab[i] = bisector(i / span - g1, i - (i / span) * span - g1);
   __syncthreads();
   const int32_t* coords = d_coords + (int64_t)plane * coord_cap * 2;
   const int32_t* starts = d_starts + (int64_t)plane * n_cells;
@@ -259,41 +263,17 @@ __global__ __launch_bounds__(CT) void k_candidates_tab(const int32_t* __restrict
     const uint32_t i2 = base + __umulhi((uint32_t)z12, cnt);
     const int2 p1 = reinterpret_cast<const int2*>(coords)[i1], p2 = reinterpret_cast<const int2*>(coords)[i2];
     const int d1r = p1.x - p0r, d1c = p1.y - p0c, d2r = p2.x - p0r, d2c = p2.y - p0c;
-    double m1, b1, m2, b2;
+    double2 l1, l2;
     if ((uint32_t)(d1r + g1) < (uint32_t)span && (uint32_t)(d1c + g1) < (uint32_t)span &&
         (uint32_t)(d2r + g1) < (uint32_t)span && (uint32_t)(d2c + g1) < (uint32_t)span) {
-      const double2 t1 = s_tab[(d1r + g1) * span + d1c + g1], t2 = s_tab[(d2r + g1) * span + d2c + g1];
-      m1 = t1.x, b1 = t1.y, m2 = t2.x, b2 = t2.y;
+      l1 = s_tab[(d1r + g1) * span + d1c + g1], l2 = s_tab[(d2r + g1) * span + d2c + g1];
     } else {  // (cannot happen with a cell-major list made by mg_edge_grid; kept so that no list can index beyond the table)
-      m1 = (double)(-d1c) / ((double)d1r + eps);
-      m2 = (double)(-d2c) / ((double)d2r + eps);
-      b1 = 0.5 * (double)d1r - m1 * (0.5 * (double)d1c);
-      b2 = 0.5 * (double)d2r - m2 * (0.5 * (double)d2c);
+      l1 = bisector(d1r, d1c), l2 = bisector(d2r, d2c);
     }
-    // intersection, each store rounds to float32 (utils.py:337-342)
-    const float c_col = (float)div_unscaled(b1 - b2, m2 - m1 + eps);
-    const float c_row = (float)(m1 * (double)c_col + b1);
-    const float rad = sqrtf(c_row * c_row + c_col * c_col);
-    const float f_row = (float)((double)c_row + (double)p0r);
-    const float f_col = (float)((double)c_col + (double)p0c);
-    if (d_raw) {
-      float* o = d_raw + ((int64_t)plane * num_iter + it) * 3;
-      o[0] = f_row;
-      o[1] = f_col;
-      o[2] = rad;
-    }
-    // filter_circles step 4 (utils.py:157-166)
+    const float3 c = circle_from_bisectors(l1, l2, p0r, p0c, DivUnscaled{});
+    store_raw(d_raw, ((int64_t)plane * num_iter + it), c);
     uint32_t key = MG_NO_KEY;
-    do {
-      if (!(rad >= (float)min_r && rad <= (float)max_r)) break;
-      const float rr = rintf(f_row), rc = rintf(f_col);
-      if (!(fabsf(rr) < 1.0e9f && fabsf(rc) < 1.0e9f)) break;  // cannot be on the image (and NaN)
-      const int ir = (int)rr, ic = (int)rc, irad = (int)rintf(rad);
-      if (ir + irad < 0 || ic + irad < 0 || ir - irad >= h || ic - irad >= w) break;
-      const int pr = ir + max_r, pc = ic + max_r;
-      const int tile = (pr >> 6) * ntc + (pc >> 6);
-      key = ((uint32_t)tile << 17) | ((uint32_t)(irad - min_r) << 12) | (uint32_t)(((pr & 63) << 6) + (pc & 63));
-    } while (false);
+    candidate_cell(c, h, w, min_r, max_r, ntc, [&](int tile, int layer, int row, int col) { key = mg_key_pack(tile, layer, row, col); });
     if (keys) keys[it] = key;
   }
 }
@@ -317,7 +297,7 @@ __global__ __launch_bounds__(NT) void k_layer_count(const uint32_t* __restrict__
 }
 
 // Keyed de-duplication (no global atomics): candidates were written as 32-bit keys
-// (tile << 17 | radius layer << 12 | position in the 64 x 64 tile) in iteration order.  p0 is a
+// (mg_common.h: tile | radius layer | position in the 64 x 64 tile) in iteration order.  p0 is a
 // stratified draw over the cell-major edge list, so the iterations that can put a centre into a
 // given tile are a handful of contiguous iteration ranges -- one per cell row within reach of the
 // tile.  One workgroup per tile scans those ranges, sets the bits of its own keys in an LDS copy of
@@ -398,14 +378,14 @@ __global__ __launch_bounds__(NT) void k_tile_dedup(const uint32_t* __restrict__ 
 #pragma unroll
       for (int u = 0; u < KB; ++u) {
         const uint32_t key = kv[u];
-        const uint32_t t = (key >> 17) - (uint32_t)tile0;  // wraps for foreign (and rejected) keys
-        if (t < (uint32_t)ntx) atomicOr(&lbits[t * words + ((key & 0x1FFFFu) >> 5)], 1u << (key & 31u));
+        const uint32_t t = mg_key_tile(key) - (uint32_t)tile0;  // wraps for foreign (and rejected) keys
+        if (t < (uint32_t)ntx) atomicOr(&lbits[t * words + (mg_key_low17(key) >> 5)], 1u << (key & 31u));
       }
     }
   }
   __syncthreads();
   // Ordered emission straight from LDS.  The bit index inside a tile IS the low 17 bits of the key
-  // ((r << 12) | (row << 6) | col), so walking the tile's words in order yields its keys in ascending order.
+  // (layer | row | col), so walking the tile's words in order yields its keys in ascending order.
   // Every thread owns a run of consecutive words: count its bits, one block-wide exclusive scan of the counts
   // (its entries at the layer boundaries are the per-(tile, radius) starts), reserve the group's slice of the
   // plane's list with one atomicAdd (d_num_circles is the cursor), then every thread stores the keys of its run.
@@ -454,7 +434,7 @@ __global__ __launch_bounds__(NT) void k_tile_dedup(const uint32_t* __restrict__ 
 #pragma unroll
     for (int k = 1; k < TX; ++k)
       if (rem >= words) rem -= words, ++t;
-    const uint32_t hi = ((uint32_t)(tile0 + t) << 17) | ((uint32_t)rem << 5);
+    const uint32_t hi = mg_key_from_low17(tile0 + t, (uint32_t)rem << 5);
     while (bits) {
       const int b = __ffs(bits) - 1;
       bits &= bits - 1;
@@ -543,6 +523,12 @@ __device__ __forceinline__ uint32_t bits_at(const uint32_t* __restrict__ bits, i
   return n >= 32 ? v : (v & ((1u << n) - 1u));
 }
 
+// Entry of k_score_tiles' perimeter table in LDS: (dr << 16) | (quarter << 14) | (dc & 0x3FFF).
+__device__ __forceinline__ int32_t per_pack(int dr, int quarter, int dc) { return (dr << 16) | (quarter << 14) | (dc & 0x3FFF); }
+__device__ __forceinline__ int per_dr(int32_t v) { return v >> 16; }
+__device__ __forceinline__ int per_dc(int32_t v) { return ((int)((uint32_t)v << 18)) >> 18; }
+__device__ __forceinline__ int per_quarter(int32_t v) { return (v >> 14) & 3; }
+
 constexpr int CHUNK = 1024;        // capacity of the LDS survivor list of one prefilter/exact round
 constexpr int SURV_IDX_BITS = 20;  // list entry: circle index within the round | hits << 20 (perimeters < 2048 points)
 
@@ -623,42 +609,31 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(96))) void k_sco
     }
   }
   for (int i = threadIdx.x; i < per_total; i += NT) {
-    // (dr << 16) | (quarter << 14) | (dc & 0x3FFF); the quarter of theta = atan2(dr, dc) mod pi by the same
+    // the quarter of theta = atan2(dr, dc) mod pi by the same
     // integer rule as the pixels' classes (on a boundary either side is valid, but the prefilter's
     // count and the exact pass must use the same window)
     const int dr = d_per_rc[2 * i], dc = d_per_rc[2 * i + 1];
     const int ay = abs(dr), ax = abs(dc);
     const int quarter = ((dr ^ dc) < 0) ? (ay > ax ? 2 : 3) : (ay < ax ? 0 : 1);
-    tab[i] = (dr << 16) | (quarter << 14) | (dc & 0x3FFF);
+    tab[i] = per_pack(dr, quarter, dc);
   }
   __syncthreads();
-#define MG_TAB_DR(v) ((v) >> 16)
-#define MG_TAB_DC(v) (((int)((uint32_t)(v) << 18)) >> 18)
-#define MG_TAB_Q(v) (((v) >> 14) & 3)
   int32_t* circles = d_circles + (int64_t)plane * circle_cap * 3;
   const uint32_t* ukeys = KEYED ? d_ukeys + (int64_t)plane * circle_cap : nullptr;
   const int trow0 = (tile / ntc) * TS - max_r, tcol0 = (tile % ntc) * TS - max_r;  // centre of tile position (0, 0)
-#define MG_CIRCLE(i, row, col, rad)                                         \
-  int row, col, rad;                                                        \
-  if (KEYED) {                                                              \
-    const uint32_t key_ = ukeys[i];                                         \
-    row = trow0 + (int)((key_ >> 6) & 63u);                                 \
-    col = tcol0 + (int)(key_ & 63u);                                        \
-    rad = min_r + (int)((key_ >> 12) & 31u);                                \
-  } else {                                                                  \
-    row = circles[3 * (i)], col = circles[3 * (i) + 1], rad = circles[3 * (i) + 2]; \
-  }
-#define MG_PASS(i, row, col, rad)                                                        \
-  {                                                                                      \
-    const int k_ = atomicAdd(&d_num_alive[plane], 1);                                    \
-    d_alive[(int64_t)plane * circle_cap + k_] = (int32_t)(i);                            \
-    if (KEYED) circles[3 * (i)] = (row), circles[3 * (i) + 1] = (col), circles[3 * (i) + 2] = (rad); \
-    atomicMax(&d_max_rc[2 * plane], (row));                                              \
-    atomicMax(&d_max_rc[2 * plane + 1], (col));                                          \
-  }
+  struct Circle {
+    int row, col, rad;
+  };
+  auto load_circle = [&](int64_t i) -> Circle {
+    if constexpr (KEYED) {
+      const uint32_t key = ukeys[i];
+      return {trow0 + mg_key_row(key), tcol0 + mg_key_col(key), min_r + mg_key_layer(key)};
+    } else {
+      return {circles[3 * i], circles[3 * i + 1], circles[3 * i + 2]};
+    }
+  };
   const float* ang = d_angle + (int64_t)plane * h * w;
   float* scores = d_scores + (int64_t)plane * circle_cap;
-  const double PI = 3.141592653589793, INV_PI = 1.0 / 3.141592653589793;
   // Rounds: prefilter batches of BATCH circles until the survivor list is nearly full (or the tile is
   // done), then the exact pass over the list -- with few survivors per batch the exact pass would
   // otherwise run on mostly idle waves.
@@ -673,36 +648,34 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(96))) void k_sco
     int64_t pos = chunk;
     for (;;) {
     for (int64_t i = pos + threadIdx.x; i < min(pos + BATCH, last); i += NT) {
-      MG_CIRCLE(i, row, col, rad)
+      const auto [row, col, rad] = load_circle(i);
       const int p0 = d_per_starts[rad - min_r], p1 = d_per_starts[rad - min_r + 1];
-      const int len = p1 - p0;
-      // need: hits >= min_roundness * len - 1e-3 (margin far above any rounding of the real sum)
-      const int need = (int)ceil((double)min_roundness * len - 1e-3);
+      const int need = (int)ceil(mg_score_floor(min_roundness, p1 - p0));  // every term is <= 1: hits >= the sum's floor
       const int by = row - wy0, bx = col - wx0;
-#define MG_BIT(k, yy, xx) \
-  ((win[(k) * slot + ((by + (yy)) << wsh) + ((bx + (xx)) >> 5)] >> ((bx + (xx)) & 31)) & 1u)
+      // bit (by + yy, bx + xx) of window ww = win + k * slot (an immediate offset where the slot size is WS)
+      auto bit = [&](const uint32_t* ww, int yy, int xx) -> uint32_t {
+        return (ww[((by + yy) << wsh) + ((bx + xx) >> 5)] >> ((bx + xx) & 31)) & 1u;
+      };
+      const uint32_t *w0 = win, *w1 = win + slot, *w2 = win + 2 * slot, *w3 = win + 3 * slot;
       // The midpoint circle is emitted as 4 axis points, groups of 8 symmetric points sharing one
       // (x, y), and possibly 4 diagonal points (utils.py:441-464): one table read per group.
       // Axis points (quarters by the table's rule): theta = pi, pi/2, 0, pi/2.
-      int hits = MG_BIT(3, 0, -rad) + MG_BIT(2, -rad, 0) + MG_BIT(0, 0, rad) + MG_BIT(1, rad, 0);
+      int hits = bit(w3, 0, -rad) + bit(w2, -rad, 0) + bit(w0, 0, rad) + bit(w1, rad, 0);
       int p = p0 + 4;
       for (; p + 8 <= p1; p += 8) {
         const int v = tab[p];
-        const int x = MG_TAB_DR(v), y = MG_TAB_DC(v);  // entry (dr, dc) = (x, y), x > 0 > y, x < -y
-        hits += MG_BIT(3, x, y) + MG_BIT(2, y, x) + MG_BIT(0, -x, y) + MG_BIT(1, -y, x) + MG_BIT(0, x, -y) +
-                MG_BIT(1, y, -x) + MG_BIT(3, -x, -y) + MG_BIT(2, -y, -x);
+        const int x = per_dr(v), y = per_dc(v);  // entry (dr, dc) = (x, y), x > 0 > y, x < -y
+        hits += bit(w3, x, y) + bit(w2, y, x) + bit(w0, -x, y) + bit(w1, -y, x) + bit(w0, x, -y) +
+                bit(w1, y, -x) + bit(w3, -x, -y) + bit(w2, -y, -x);
         // (no early exit: a wave runs as long as its slowest lane anyway, and the test cost more than it saved)
       }
       if (p + 4 == p1) {  // diagonal points: theta = pi/4 (quarter 1) where dr, dc have the same sign, else 3 pi/4 (3)
         const int v = tab[p];
-        const int x = MG_TAB_DR(v), y = MG_TAB_DC(v);
+        const int x = per_dr(v), y = per_dc(v);
         const uint32_t* wa = win + (((x ^ y) < 0) ? 3 : 1) * slot;  // (x, y), (-x, -y)
         const uint32_t* wb = win + (((x ^ y) < 0) ? 1 : 3) * slot;  // (-x, y), (x, -y)
-#define MG_BITW(ww, yy, xx) ((ww[((by + (yy)) << wsh) + ((bx + (xx)) >> 5)] >> ((bx + (xx)) & 31)) & 1u)
-        hits += MG_BITW(wa, x, y) + MG_BITW(wa, -x, -y) + MG_BITW(wb, -x, y) + MG_BITW(wb, x, -y);
-#undef MG_BITW
+        hits += bit(wa, x, y) + bit(wa, -x, -y) + bit(wb, -x, y) + bit(wb, x, -y);
       }
-#undef MG_BIT
       if (hits >= need) {
         list[atomicAdd(&n_surv, 1)] = (int32_t)(i - chunk) | (hits << SURV_IDX_BITS);
       } else if (write_skipped) {
@@ -719,16 +692,16 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(96))) void k_sco
     if (threadIdx.x == 0 && d_num_scored) atomicAdd(&d_num_scored[plane], ns);
     for (int a = threadIdx.x; a < ns; a += NT) {
       const int64_t i = chunk + (list[a] & ((1 << SURV_IDX_BITS) - 1));
-      MG_CIRCLE(i, row, col, rad)
+      const auto [row, col, rad] = load_circle(i);
       const int p0 = d_per_starts[rad - min_r], p1 = d_per_starts[rad - min_r + 1];
       const int by = row - wy0, bx = col - wx0;
       double acc = 0.0;
       // Early abort (exact): every remaining counted pixel adds at most 1, so once
-      // acc + remaining < min_roundness * len - 1e-3 the circle cannot pass any more.  Most circles
+      // acc + remaining < mg_score_floor the circle cannot pass any more.  Most circles
       // that survive the count-only prefilter sit just above it and their terms average ~0 (noise
       // edges point anywhere): they are ruled out after a handful of terms.
       double left = (double)(list[a] >> SURV_IDX_BITS);  // prefilter hits on the perimeter not yet summed
-      const double floor_sum = (double)min_roundness * (double)(p1 - p0) - 1e-3;
+      const double floor_sum = mg_score_floor(min_roundness, p1 - p0);
       bool dead = false;
       // 32 perimeter points at a time: hit mask from LDS, then only the hits (in perimeter order)
       // pay for the angle gather and the float64 arithmetic
@@ -737,10 +710,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(96))) void k_sco
         const int cnt = min(32, p1 - base);
         for (int j = 0; j < cnt; ++j) {
           const int v = tab[base + j];
-          const int y = by + MG_TAB_DR(v), x = bx + MG_TAB_DC(v);
+          const int y = by + per_dr(v), x = bx + per_dc(v);
           const int wi = (y << wsh) + (x >> 5);  // every edge pixel is in W_0 or in W_2
           mask |= (((win[wi] | win[2 * slot + wi]) >> (x & 31)) & 1u) << j;
-          counted |= ((win[MG_TAB_Q(v) * slot + wi] >> (x & 31)) & 1u) << j;
+          counted |= ((win[per_quarter(v) * slot + wi] >> (x & 31)) & 1u) << j;
         }
         // The gathers of up to PF hits are issued together (their latency, not the arithmetic, is what
         // a lane waits for), then summed in perimeter order.
@@ -756,22 +729,14 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(96))) void k_sco
             if (jj[u] >= 0) {
               const int v = tab[base + jj[u]];
               // hits lie inside the image: 24-bit multiply (h, w < 2^24 guaranteed by the launcher)
-              an[u] = ang[(int64_t)(__umul24(row + MG_TAB_DR(v), w) + (col + MG_TAB_DC(v)))];
+              an[u] = ang[(int64_t)(__umul24(row + per_dr(v), w) + (col + per_dc(v)))];
             }
           }
 #pragma unroll
           for (int u = 0; u < PF; ++u) {
             if (jj[u] < 0 || dead) continue;
             const int p = base + jj[u];
-            double d = fabs((double)an[u] - d_per_expected[p]);
-            if (d > PI) d = d - PI;
-            // x / pi, correctly rounded without the division (Markstein: y = RN(1/pi), q0 = RN(x y),
-            // r = x - q0 pi exactly by FMA, q = RN(q0 + r y) == RN(x / pi) because pi's significand is
-            // not all ones; verified against x / pi on 1e9 operands of exactly this form)
-            const double x4 = 4.0 * fabs(d - PI / 2.0);
-            const double q0 = x4 * INV_PI;
-            const double q = fma(fma(-q0, PI, x4), INV_PI, q0);
-            acc += q - 1.0;
+            acc += mg_alignment_term(an[u], d_per_expected[p]);
             // `left` = the prefilter's hits still to come; the other edge pixels (perpendicular class)
             // add <= 0 (+6e-8 at worst when exactly pi/4 off radial: inside the 1e-3 margin)
             left -= (double)((counted >> jj[u]) & 1u);
@@ -790,9 +755,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(96))) void k_sco
         if (slot < PASS_CAP) {
           list[CHUNK - 1 - 3 * slot] = (int32_t)(i - first);
           list[CHUNK - 2 - 3 * slot] = __float_as_int(score);
-          list[CHUNK - 3 - 3 * slot] = (rad << 12) | ((row - trow0) << 6) | (col - tcol0);
+          list[CHUNK - 3 - 3 * slot] = (int32_t)mg_key_pack(0, rad, row - trow0, col - tcol0);  // (the radius itself: any nr)
         } else {  // no room (or no de-duplication wanted): straight to the plane's list
-          MG_PASS(i, row, col, rad)
+          mg_emit_alive<KEYED>(d_num_alive, d_alive, d_max_rc, plane, circle_cap, circles, i, row, col, rad);
         }
       }
     }
@@ -811,31 +776,27 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(96))) void k_sco
     for (int b = 0; b < np; ++b) {
       const int code_b = list[CHUNK - 3 - 3 * b];
       const float score_b = __int_as_float(list[CHUNK - 2 - 3 * b]);
-      if (((code ^ code_b) & 0xFFF) == 0 && (score_b > score || (score_b == score && code_b < code))) first_at_centre = false;
+      if (((code ^ code_b) & MG_KEY_CENTRE_MASK) == 0 && (score_b > score || (score_b == score && code_b < code))) first_at_centre = false;
     }
     if (first_at_centre) {
       const int64_t i = first + list[CHUNK - 1 - 3 * a];
-      MG_PASS(i, trow0 + ((code >> 6) & 63), tcol0 + (code & 63), code >> 12)
+      mg_emit_alive<KEYED>(d_num_alive, d_alive, d_max_rc, plane, circle_cap, circles, i, trow0 + mg_key_row(code),
+                           tcol0 + mg_key_col(code), code >> MG_KEY_LAYER_SHIFT);
     }
   }
 }
-
-#undef MG_TAB_DR
-#undef MG_TAB_DC
-#undef MG_TAB_Q
-#undef MG_CIRCLE
-#undef MG_PASS
 
 // ---- K10: greedy suppression in parallel rounds ------------------------------------------------------
 // Priority key: smaller = earlier in the reference's score-descending order; ties broken by the
 // canonical (tile, r, row, col) order -- the circle's 32-bit de-duplication key on the keyed path
 // (list positions are arrival-ordered there), its list index otherwise.  The score field of a real
 // key is never 0, which leaves (0, tie) as the mark a kept circle puts on its ring cells.
-__device__ __forceinline__ uint64_t nms_key(float score, uint32_t idx) {
+__device__ __forceinline__ uint32_t nms_sort_bits(float score) {  // the score half of the key: smaller = higher score
   uint32_t b = __float_as_uint(score);
   b = (b & 0x80000000u) ? ~b : (b | 0x80000000u);  // ascending-sortable
-  return ((uint64_t)(~b) << 32) | idx;             // descending score
+  return ~b;                                       // descending score
 }
+__device__ __forceinline__ uint64_t nms_key(float score, uint32_t idx) { return ((uint64_t)nms_sort_bits(score) << 32) | idx; }
 
 // Python's v % n for n > 0.  Ring coordinates are at most one period outside [0, n) in practice, so
 // the integer division (~30 instructions, twice per ring pixel) is kept off the common path.
@@ -851,6 +812,12 @@ __device__ __forceinline__ int wrap(int v, int n) {
     }
   }
   return v;
+}
+
+// The claim-grid cell of ring offset (dr, dc) around centre (row, col): the reference's padded, wrapping index
+// (utils.py:271).
+__device__ __forceinline__ uint64_t* ring_cell(uint64_t* grid, int n_rows, int n_cols, int pad, int row, int col, int dr, int dc) {
+  return &grid[(int64_t)wrap(dr + row + pad, n_rows) * n_cols + wrap(dc + col + pad, n_cols)];
 }
 
 // PHASE 0 (bid), 1 (decide), 2 (cleanup): the lanes of a wave work on the ring cells of one circle together -- its
@@ -899,7 +866,7 @@ __global__ __launch_bounds__(NT) void k_nms(const int32_t* __restrict__ d_circle
       // later one rejected without ever claiming (utils.py:254-292): only that first one enters the rounds.  One
       // bid on the centre's own cell (3), the losers marked rejected (4), the cell restored (5): three tiny
       // launches instead of a ring of bids, loads and withdrawals per duplicate.
-      uint64_t* cell = &grid[(int64_t)wrap(row + pad, n_rows) * n_cols + wrap(col + pad, n_cols)];
+      uint64_t* cell = ring_cell(grid, n_rows, n_cols, pad, row, col, 0, 0);
       if (PHASE == 3) atomicMin(reinterpret_cast<unsigned long long*>(cell), (unsigned long long)key);
       else if (PHASE == 4) { if (*cell != key) state[idx] = 2; }
       else *cell = ~0ull;
@@ -955,7 +922,7 @@ __global__ __launch_bounds__(NT) void k_nms(const int32_t* __restrict__ d_circle
         uint64_t* cell[NU];
 #pragma unroll
         for (int u = 0; u < NU; ++u)
-          cell[u] = &grid[(int64_t)wrap(dr + row[u] + pad, n_rows) * n_cols + wrap(dc + col[u] + pad, n_cols)];
+          cell[u] = ring_cell(grid, n_rows, n_cols, pad, row[u], col[u], dr, dc);
         if (PHASE == 2) {  // cleanup (after convergence): restore the all-ones grid under every ring
 #pragma unroll
           for (int u = 0; u < NU; ++u)
@@ -984,7 +951,7 @@ __global__ __launch_bounds__(NT) void k_nms(const int32_t* __restrict__ d_circle
           uint64_t g[NU];
 #pragma unroll
           for (int u = 0; u < NU; ++u)
-            g[u] = u < cnt ? grid[(int64_t)wrap(dr + row[u] + pad, n_rows) * n_cols + wrap(dc + col[u] + pad, n_cols)] : key[u];
+            g[u] = u < cnt ? *ring_cell(grid, n_rows, n_cols, pad, row[u], col[u], dr, dc) : key[u];
 #pragma unroll
           for (int u = 0; u < NU; ++u)
             if (g[u] != key[u]) {
@@ -1001,14 +968,14 @@ __global__ __launch_bounds__(NT) void k_nms(const int32_t* __restrict__ d_circle
             // mark the ring as kept: (0, tie) is below every real key, so no later bid replaces it
             for (int j = lane; j < ring_len; j += 64)
               atomicMin(reinterpret_cast<unsigned long long*>(
-                            &grid[(int64_t)wrap(d_ring_rc[2 * j] + row[u] + pad, n_rows) * n_cols + wrap(d_ring_rc[2 * j + 1] + col[u] + pad, n_cols)]),
+                            ring_cell(grid, n_rows, n_cols, pad, row[u], col[u], d_ring_rc[2 * j], d_ring_rc[2 * j + 1])),
                         (unsigned long long)tk[u]);
           } else if (hit_kept) {
             if (lane == 0) state[idx[u]] = 2;
             // withdraw this circle's bids so that later circles can win these pixels
             for (int j = lane; j < ring_len; j += 64)
               atomicCAS(reinterpret_cast<unsigned long long*>(
-                            &grid[(int64_t)wrap(d_ring_rc[2 * j] + row[u] + pad, n_rows) * n_cols + wrap(d_ring_rc[2 * j + 1] + col[u] + pad, n_cols)]),
+                            ring_cell(grid, n_rows, n_cols, pad, row[u], col[u], d_ring_rc[2 * j], d_ring_rc[2 * j + 1])),
                         (unsigned long long)key[u], ~0ull);
           } else {
             any_undecided = true;
@@ -1098,10 +1065,8 @@ __global__ __launch_bounds__(SP_NT) void k_nms_sparse(const int32_t* __restrict_
       if (row[u] < -(min_dist + 1) || col[u] < -(min_dist + 1) || row[u] > max_row || col[u] > max_col) {
         bad = true;
       } else {
-        uint32_t b = __float_as_uint(sc[u]);
-        b = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
         pos[a] = ((uint32_t)(row[u] + SP_BIAS) << 16) | (uint32_t)(col[u] + SP_BIAS);
-        skey[a] = ~b;
+        skey[a] = nms_sort_bits(sc[u]);
         st[a] = 0;
         bkt[u] = ((row[u] + SP_BIAS) >> SP_SHIFT_R) * nbc + ((col[u] + SP_BIAS) >> SP_SHIFT_C);
         // entry bkt + 1 counts the bucket (16-bit halves of a word: a 32-bit atomic on the half's word; n < 65536: no carry)
@@ -1310,16 +1275,16 @@ int launch_candidates(const int32_t* d_coords, int64_t coord_cap, const int32_t*
   if (n_planes < 0 || n_planes > 65535 || h <= 0 || w <= 0 || grid <= 0 || num_iter < 0 || min_r < 0 || max_r < min_r)
     return MG_EINVAL;
   if ((double)num_iter * (double)h * (double)w >= 4.0e15) return MG_EINVAL;  // exact-division range of the strata
-  int ntr_, ntc_;
-  int64_t n_layers_, need_words_;
-  if (mg_dedup_layout(h, w, min_r, max_r, &ntr_, &ntc_, &n_layers_, &need_words_) != MG_OK) return MG_EINVAL;
-  if (d_bitmap && bitmap_words < need_words_) return MG_EINVAL;
-  if (d_keys && ((int64_t)ntr_ * ntc_ >= 32768 || max_r - min_r + 1 > 32)) return MG_EINVAL;  // key fields
+  int ntr, ntc, nr;
+  int64_t n_layers, need_words;
+  if (d_keys && mg_key_layout(h, w, min_r, max_r, &ntr, &ntc, &nr) != MG_OK) return MG_EINVAL;
+  if (d_bitmap && (mg_dedup_layout(h, w, min_r, max_r, &ntr, &ntc, &n_layers, &need_words) != MG_OK || bitmap_words < need_words))
+    return MG_EINVAL;
   if (n_planes == 0 || num_iter == 0) return MG_OK;
   const int gr = (h + grid - 1) / grid, gc = (w + grid - 1) / grid;
   const bool fast = num_iter < (1ll << 31) && grid > 1 && h <= 65536 && w <= 65536;
-  // keys from the table kernel (round 4) unless MG_CANDIDATES_V1 is set (the tests compare the two) or the shape is
-  // outside its ranges: a grid cell above 32 (table size), a coordinate list of 2^31 entries
+  // keys from the table kernel (round 4) unless MG_CANDIDATES_V1 is set or the shape is outside its ranges: a grid cell
+  // above 32 (table size; test_candidates_degenerate_triplets[40-*] takes that way), a coordinate list of 2^31 entries
   static const bool v1 = getenv("MG_CANDIDATES_V1") != nullptr;
   if (fast && !v1 && d_keys && !d_bitmap && grid <= MAX_TAB_GRID && coord_cap < (1ll << 31)) {
     // workgroups of 1024 that run ~32 iterations per lane (the table costs each lane 1.5 entries once), but at least
@@ -1412,11 +1377,8 @@ extern "C" int mg_keys_to_circles(const uint32_t* d_keys, int64_t num_iter, cons
   if (!d_keys || !d_cell_starts || !d_cell_counts || !d_num_edges || !d_unique_keys || !d_tile_ranges ||
       !d_num_circles || n_planes < 0 || n_planes > 65535 || circle_cap < 0 || num_iter < 0 || grid <= 0)
     return MG_EINVAL;
-  int ntr, ntc;
-  int64_t n_layers, need_words;
-  if (mg_dedup_layout(h, w, min_r, max_r, &ntr, &ntc, &n_layers, &need_words) != MG_OK) return MG_EINVAL;
-  const int nr = max_r - min_r + 1;
-  if ((int64_t)ntr * ntc >= 32768 || nr > 32) return MG_EINVAL;  // the 32-bit key: 15 + 5 + 12 bits
+  int ntr, ntc, nr;
+  if (mg_key_layout(h, w, min_r, max_r, &ntr, &ntc, &nr) != MG_OK) return MG_EINVAL;
   if ((TS + 2 * (max_r + 2)) / grid + 2 > MAX_RANGES || num_iter >= (1ll << 31)) return MG_EINVAL;
   if (n_planes == 0) return MG_OK;
   const int gr = (h + grid - 1) / grid, gc = (w + grid - 1) / grid;
@@ -1451,10 +1413,11 @@ extern "C" int mg_score_circles(const float* d_angle, const uint32_t* d_edge_bit
   const bool keyed = d_unique_keys != nullptr;
   if (keyed ? !d_tile_ranges : !d_layer_offsets) return MG_EINVAL;
   if (n_planes < 0 || n_planes > 65535 || per_total <= 0 || max_r > 8000) return MG_EINVAL;
-  int ntr, ntc;
+  int ntr, ntc, nr = max_r - min_r + 1;
   int64_t n_layers, words;
-  if (mg_dedup_layout(h, w, min_r, max_r, &ntr, &ntc, &n_layers, &words) != MG_OK) return MG_EINVAL;
-  if (keyed && ((int64_t)ntr * ntc >= 32768 || max_r - min_r + 1 > 32)) return MG_EINVAL;
+  if ((keyed ? mg_key_layout(h, w, min_r, max_r, &ntr, &ntc, &nr)
+             : mg_dedup_layout(h, w, min_r, max_r, &ntr, &ntc, &n_layers, &words)) != MG_OK)
+    return MG_EINVAL;
   if (n_planes == 0 || circle_cap == 0) return MG_OK;
   const int side = TS + 2 * max_r;
   int wpr = 1;
@@ -1475,7 +1438,7 @@ extern "C" int mg_score_circles(const float* d_angle, const uint32_t* d_edge_bit
   }
   hipLaunchKernelGGL(kernel, dim3(ntr * ntc, n_planes), dim3(NT), lds_bytes, mg_stream(stream), d_angle, d_edge_bits,
                      d_class_bits, words_per_plane, h, w, d_circles, circle_cap, d_layer_offsets, d_unique_keys,
-                     d_tile_ranges, ntr * ntc, (int)n_layers, max_r - min_r + 1, ntc, min_r, max_r, d_per_rc, per_total,
+                     d_tile_ranges, ntr * ntc, (int)((int64_t)ntr * ntc * nr), nr, ntc, min_r, max_r, d_per_rc, per_total,
                      d_per_expected, d_per_starts, min_roundness, write_skipped, dedup_centres, d_scores, d_alive,
                      d_num_alive,
                      d_max_rc, d_num_scored);
@@ -1484,11 +1447,54 @@ extern "C" int mg_score_circles(const float* d_angle, const uint32_t* d_edge_bit
 }
 
 namespace {
-// circles a wave of the suppression rounds looks up at once: 64 when the batch has many (late rounds are then a
-// coalesced look at the state bytes), fewer when it has few (their rings are worked through one trip after another)
-inline int nms_circles_per_wave(int64_t alive_bound, int n_planes) {
-  const int64_t total = alive_bound * std::max(n_planes, 1);
-  return total >= 262144 ? 64 : total >= 32768 ? 16 : 4;
+// One call of the claim-grid kernels: the entry point's arguments, and what nms_prepare derives from them.
+struct NmsArgs {
+  const int32_t* d_circles;
+  int64_t circle_cap;
+  const float* d_scores;
+  const int32_t *d_alive, *d_num_alive, *d_max_rc;
+  int n_planes, min_dist;
+  const int32_t* d_ring_rc;  // null, ring_len 0: the entry point walks no ring (phases 3-5, a thread per circle)
+  int ring_len;
+  uint64_t* d_grid;
+  int64_t grid_cap;
+  uint8_t* d_state;
+  const uint32_t* d_tie;
+  int64_t max_alive;
+  const int32_t* d_skip;
+  void* stream;
+  int32_t* d_undecided = nullptr;  // phase 1 only: the round's flags
+  bool empty = false;              // nothing to launch
+  int cpw = 64;                    // circles a wave looks up at once
+  dim3 grid;
+};
+
+// Pointers and ranges (with_ring: the ring is required too), then the launch shape.  The kernels walk d_alive with a
+// grid-stride loop: max_alive (> 0: the caller's upper bound of d_num_alive) only sizes the grid -- an all-capacity grid
+// of empty blocks costs ~0.1 ms per launch.  Ring phases: 64 circles per wave when the batch has many (late rounds are
+// then a coalesced look at the state bytes), fewer when it has few (their rings are worked through one trip after
+// another).
+int nms_prepare(NmsArgs& a, bool with_ring) {
+  if (!a.d_circles || !a.d_scores || !a.d_alive || !a.d_num_alive || !a.d_max_rc || !a.d_grid || !a.d_state) return MG_EINVAL;
+  if (a.n_planes < 0 || a.n_planes > 65535 || a.min_dist <= 0) return MG_EINVAL;
+  if (with_ring && (!a.d_ring_rc || a.ring_len <= 0)) return MG_EINVAL;
+  a.empty = a.n_planes == 0 || a.circle_cap == 0;
+  const int64_t bound = a.max_alive > 0 ? std::min(a.max_alive, a.circle_cap) : a.circle_cap;
+  if (with_ring) {
+    const int64_t total = bound * std::max(a.n_planes, 1);
+    a.cpw = total >= 262144 ? 64 : total >= 32768 ? 16 : 4;
+  }
+  a.grid = dim3(grid_x(bound * (64 / a.cpw)), a.n_planes);
+  return MG_OK;
+}
+
+template <int PHASE>
+int launch_nms(const NmsArgs& a) {
+  hipLaunchKernelGGL((k_nms<PHASE>), a.grid, dim3(NT), 0, mg_stream(a.stream), a.d_circles, a.circle_cap, a.d_scores,
+                     a.d_alive, a.d_num_alive, a.d_max_rc, a.min_dist, a.d_ring_rc, a.ring_len, a.d_grid, a.grid_cap,
+                     a.d_state, a.d_undecided, a.d_tie, a.cpw, a.d_skip);
+  MG_CHECK_LAUNCH();
+  return MG_OK;
 }
 }  // namespace
 
@@ -1498,27 +1504,15 @@ extern "C" int mg_nms_rounds(const int32_t* d_circles, int64_t circle_cap, const
                              uint8_t* d_state, int32_t* d_undecided, int64_t undecided_stride, int n_rounds,
                              int counters_clear, const uint32_t* d_tie_keys, int64_t max_alive, const int32_t* d_skip,
                              void* stream) {
-  if (!d_circles || !d_scores || !d_alive || !d_num_alive || !d_max_rc || !d_ring_rc || !d_grid || !d_state ||
-      !d_undecided)
-    return MG_EINVAL;
-  if (n_planes < 0 || n_planes > 65535 || min_dist <= 0 || ring_len <= 0 || n_rounds < 0) return MG_EINVAL;
+  NmsArgs a{d_circles, circle_cap, d_scores, d_alive, d_num_alive, d_max_rc, n_planes, min_dist, d_ring_rc, ring_len,
+            d_grid, grid_cap, d_state, d_tie_keys, max_alive, d_skip, stream};
+  if (nms_prepare(a, true) != MG_OK || !d_undecided || n_rounds < 0) return MG_EINVAL;
   if (n_rounds > 1 && undecided_stride < n_planes) return MG_EINVAL;
-  if (n_planes == 0 || circle_cap == 0) return MG_OK;
-  hipStream_t s = mg_stream(stream);
-  // the kernels walk d_alive with a grid-stride loop: max_alive (> 0: the caller's upper bound of
-  // d_num_alive) only sizes the grid -- an all-capacity grid of empty blocks costs ~0.1 ms per launch
-  const int64_t bound = max_alive > 0 ? std::min(max_alive, circle_cap) : circle_cap;
-  const int cpw = nms_circles_per_wave(bound, n_planes);
-  const dim3 g(grid_x(bound * (64 / cpw)), n_planes);
+  if (a.empty) return MG_OK;
   for (int k = 0; k < n_rounds; ++k) {
-    int32_t* und = d_undecided + (int64_t)k * undecided_stride;
-    if (!counters_clear && mg_zero_async(und, sizeof(int32_t) * n_planes, s) != hipSuccess) return MG_ELAUNCH;
-    hipLaunchKernelGGL((k_nms<0>), g, dim3(NT), 0, s, d_circles, circle_cap, d_scores, d_alive, d_num_alive, d_max_rc,
-                       min_dist, d_ring_rc, ring_len, d_grid, grid_cap, d_state, und, d_tie_keys, cpw, d_skip);
-    MG_CHECK_LAUNCH();
-    hipLaunchKernelGGL((k_nms<1>), g, dim3(NT), 0, s, d_circles, circle_cap, d_scores, d_alive, d_num_alive, d_max_rc,
-                       min_dist, d_ring_rc, ring_len, d_grid, grid_cap, d_state, und, d_tie_keys, cpw, d_skip);
-    MG_CHECK_LAUNCH();
+    a.d_undecided = d_undecided + (int64_t)k * undecided_stride;
+    if (!counters_clear && mg_zero_async(a.d_undecided, sizeof(int32_t) * n_planes, mg_stream(stream)) != hipSuccess) return MG_ELAUNCH;
+    if (launch_nms<0>(a) != MG_OK || launch_nms<1>(a) != MG_OK) return MG_ELAUNCH;
   }
   return MG_OK;
 }
@@ -1527,20 +1521,11 @@ extern "C" int mg_nms_same_centre(const int32_t* d_circles, int64_t circle_cap, 
                                   const int32_t* d_alive, const int32_t* d_num_alive, const int32_t* d_max_rc, int n_planes,
                                   int min_dist, uint64_t* d_grid, int64_t grid_cap, uint8_t* d_state,
                                   const uint32_t* d_tie_keys, int64_t max_alive, const int32_t* d_skip, void* stream) {
-  if (!d_circles || !d_scores || !d_alive || !d_num_alive || !d_max_rc || !d_grid || !d_state) return MG_EINVAL;
-  if (n_planes < 0 || n_planes > 65535 || min_dist <= 0) return MG_EINVAL;
-  if (n_planes == 0 || circle_cap == 0) return MG_OK;
-  hipStream_t s = mg_stream(stream);
-  const dim3 g(grid_x(max_alive > 0 ? std::min(max_alive, circle_cap) : circle_cap), n_planes);
-  hipLaunchKernelGGL((k_nms<3>), g, dim3(NT), 0, s, d_circles, circle_cap, d_scores, d_alive, d_num_alive, d_max_rc,
-                     min_dist, (const int32_t*)nullptr, 0, d_grid, grid_cap, d_state, (int32_t*)nullptr, d_tie_keys, 64, d_skip);
-  MG_CHECK_LAUNCH();
-  hipLaunchKernelGGL((k_nms<4>), g, dim3(NT), 0, s, d_circles, circle_cap, d_scores, d_alive, d_num_alive, d_max_rc,
-                     min_dist, (const int32_t*)nullptr, 0, d_grid, grid_cap, d_state, (int32_t*)nullptr, d_tie_keys, 64, d_skip);
-  MG_CHECK_LAUNCH();
-  hipLaunchKernelGGL((k_nms<5>), g, dim3(NT), 0, s, d_circles, circle_cap, d_scores, d_alive, d_num_alive, d_max_rc,
-                     min_dist, (const int32_t*)nullptr, 0, d_grid, grid_cap, d_state, (int32_t*)nullptr, d_tie_keys, 64, d_skip);
-  MG_CHECK_LAUNCH();
+  NmsArgs a{d_circles, circle_cap, d_scores, d_alive, d_num_alive, d_max_rc, n_planes, min_dist, nullptr, 0,
+            d_grid, grid_cap, d_state, d_tie_keys, max_alive, d_skip, stream};
+  if (nms_prepare(a, false) != MG_OK) return MG_EINVAL;
+  if (a.empty) return MG_OK;
+  if (launch_nms<3>(a) != MG_OK || launch_nms<4>(a) != MG_OK || launch_nms<5>(a) != MG_OK) return MG_ELAUNCH;
   return MG_OK;
 }
 
@@ -1548,18 +1533,10 @@ extern "C" int mg_nms_cleanup(const int32_t* d_circles, int64_t circle_cap, cons
                               const int32_t* d_alive, const int32_t* d_num_alive, const int32_t* d_max_rc, int n_planes,
                               int min_dist, const int32_t* d_ring_rc, int ring_len, uint64_t* d_grid, int64_t grid_cap,
                               uint8_t* d_state, int64_t max_alive, const int32_t* d_skip, void* stream) {
-  if (!d_circles || !d_scores || !d_alive || !d_num_alive || !d_max_rc || !d_ring_rc || !d_grid || !d_state)
-    return MG_EINVAL;
-  if (n_planes < 0 || n_planes > 65535 || min_dist <= 0 || ring_len <= 0) return MG_EINVAL;
-  if (n_planes == 0 || circle_cap == 0) return MG_OK;
-  const int64_t bound = max_alive > 0 ? std::min(max_alive, circle_cap) : circle_cap;
-  const int cpw = nms_circles_per_wave(bound, n_planes);
-  hipLaunchKernelGGL((k_nms<2>), dim3(grid_x(bound * (64 / cpw)), n_planes),
-                     dim3(NT), 0, mg_stream(stream), d_circles,
-                     circle_cap, d_scores, d_alive, d_num_alive, d_max_rc, min_dist, d_ring_rc, ring_len, d_grid,
-                     grid_cap, d_state, (int32_t*)nullptr, (const uint32_t*)nullptr, cpw, d_skip);
-  MG_CHECK_LAUNCH();
-  return MG_OK;
+  NmsArgs a{d_circles, circle_cap, d_scores, d_alive, d_num_alive, d_max_rc, n_planes, min_dist, d_ring_rc, ring_len,
+            d_grid, grid_cap, d_state, nullptr, max_alive, d_skip, stream};
+  if (nms_prepare(a, true) != MG_OK) return MG_EINVAL;
+  return a.empty ? MG_OK : launch_nms<2>(a);
 }
 
 extern "C" int mg_nms_sparse(const int32_t* d_circles, int64_t circle_cap, const float* d_scores, const int32_t* d_alive,

@@ -21,6 +21,35 @@
 #define MG_SCORE_MAX_PAIRS 80
 #define MG_SCORE_WSTRIDE (MG_SCORE_TILE * MG_SCORE_SUBX + 2 * MG_SCORE_MAX_R)
 
+// The 32-bit circle key of the keyed path: tile << 17 | radius layer << 12 | row << 6 | col, where (row, col) is the
+// position of the centre in its 64 x 64 tile of the grid padded by max_r on every side and layer = r - min_r.
+// Ascending keys = the build's canonical (tile, r, row, col) order; the low 17 bits are the circle's bit index in the
+// tile's de-duplication layers.  15 + 5 + 12 bits: mg_key_layout refuses what does not fit.
+constexpr int MG_KEY_ROW_SHIFT = 6, MG_KEY_LAYER_SHIFT = 12, MG_KEY_TILE_SHIFT = 17;
+constexpr uint32_t MG_KEY_POS_MASK = 63u, MG_KEY_LAYER_MASK = 31u;
+constexpr uint32_t MG_KEY_CENTRE_MASK = (1u << MG_KEY_LAYER_SHIFT) - 1u, MG_KEY_LOW17_MASK = (1u << MG_KEY_TILE_SHIFT) - 1u;
+constexpr uint32_t MG_NO_KEY = 0xFFFFFFFFu;  // candidate rejected by the radius / on-image filter
+constexpr int MG_KEY_MAX_TILES = 1 << (32 - MG_KEY_TILE_SHIFT), MG_KEY_MAX_LAYERS = 1 << (MG_KEY_TILE_SHIFT - MG_KEY_LAYER_SHIFT);
+__host__ __device__ __forceinline__ uint32_t mg_key_pack(int tile, int layer, int row, int col) {
+  return ((uint32_t)tile << MG_KEY_TILE_SHIFT) | ((uint32_t)layer << MG_KEY_LAYER_SHIFT) |
+         (uint32_t)((row << MG_KEY_ROW_SHIFT) + col);
+}
+__host__ __device__ __forceinline__ uint32_t mg_key_from_low17(int tile, uint32_t low17) {
+  return ((uint32_t)tile << MG_KEY_TILE_SHIFT) | low17;
+}
+__host__ __device__ __forceinline__ uint32_t mg_key_tile(uint32_t key) { return key >> MG_KEY_TILE_SHIFT; }
+__host__ __device__ __forceinline__ uint32_t mg_key_low17(uint32_t key) { return key & MG_KEY_LOW17_MASK; }
+__host__ __device__ __forceinline__ int mg_key_layer(uint32_t key) { return (int)((key >> MG_KEY_LAYER_SHIFT) & MG_KEY_LAYER_MASK); }
+__host__ __device__ __forceinline__ int mg_key_row(uint32_t key) { return (int)((key >> MG_KEY_ROW_SHIFT) & MG_KEY_POS_MASK); }
+__host__ __device__ __forceinline__ int mg_key_col(uint32_t key) { return (int)(key & MG_KEY_POS_MASK); }
+// mg_dedup_layout for a launcher that takes keys: MG_EINVAL also where a tile or a radius layer has no key.
+static inline int mg_key_layout(int h, int w, int min_r, int max_r, int* ntr, int* ntc, int* nr) {
+  int64_t n_layers, words;
+  if (mg_dedup_layout(h, w, min_r, max_r, ntr, ntc, &n_layers, &words) != MG_OK) return MG_EINVAL;
+  *nr = max_r - min_r + 1;
+  return ((int64_t)*ntr * *ntc >= MG_KEY_MAX_TILES || *nr > MG_KEY_MAX_LAYERS) ? MG_EINVAL : MG_OK;
+}
+
 #define MG_CHECK_LAUNCH()                          \
   do {                                             \
     hipError_t e_ = hipGetLastError();             \
@@ -285,4 +314,35 @@ __device__ __forceinline__ float mg_edge_angle(const uint8_t* __restrict__ pb, i
   const int dx = 3 * (c - a) + 10 * (f - d) + 3 * (ii - g);
   const int dy = 3 * (g - a) + 10 * (hh - b) + 3 * (ii - c);
   return (float)atan2((double)dy, (double)dx);
+}
+
+// ---- the scoring tail shared by k_score_tiles (mg_circles.hip) and k_prefilter / k_exact (mg_score.hip) ----
+// One term of mean_grad (utils.py:225-251): |angle - expected| folded to [0, pi], then 4 |d - pi/2| / pi - 1.
+// x / pi is correctly rounded without the division (Markstein: y = RN(1/pi), q0 = RN(x y), r = x - q0 pi exactly by
+// FMA, q = RN(q0 + r y) == RN(x / pi) because pi's significand is not all ones; verified against x / pi on 1e9
+// operands of exactly this form).
+__device__ __forceinline__ double mg_alignment_term(float angle, double expected) {
+  const double PI = 3.141592653589793, INV_PI = 1.0 / 3.141592653589793;
+  double d = fabs((double)angle - expected);
+  if (d > PI) d = d - PI;
+  const double x4 = 4.0 * fabs(d - PI / 2.0);
+  const double q0 = x4 * INV_PI;
+  return fma(fma(-q0, PI, x4), INV_PI, q0) - 1.0;
+}
+// What the sum of a perimeter of `len` points has to reach: a circle passes with sum / len >= min_roundness in float32;
+// the 1e-3 margin is far above any rounding of the real sum.
+__device__ __forceinline__ double mg_score_floor(float min_roundness, int len) {
+  return (double)min_roundness * (double)len - 1e-3;
+}
+// Circle i of the plane's list passed the threshold: onto the alive list, its centre into the plane's maxima (the
+// extent of the claim grid).  WRITE: (row, col, r) is not in `circles` yet (keyed lists hold keys until here).
+template <bool WRITE>
+__device__ __forceinline__ void mg_emit_alive(int32_t* __restrict__ d_num_alive, int32_t* __restrict__ d_alive,
+                                              int32_t* __restrict__ d_max_rc, int plane, int64_t circle_cap,
+                                              int32_t* __restrict__ circles, int64_t i, int row, int col, int rad) {
+  const int k = atomicAdd(&d_num_alive[plane], 1);
+  d_alive[(int64_t)plane * circle_cap + k] = (int32_t)i;
+  if (WRITE) circles[3 * i] = row, circles[3 * i + 1] = col, circles[3 * i + 2] = rad;
+  atomicMax(&d_max_rc[2 * plane], row);
+  atomicMax(&d_max_rc[2 * plane + 1], col);
 }

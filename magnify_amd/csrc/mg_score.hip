@@ -46,15 +46,6 @@ static_assert(WBASE >= BIAS && WBASE % 16 == 0, "window base");
 static_assert(STX + 2 * MAXR <= WSTR && (WSTR % 4) == 0 && ((WSTR / 4) & 1) == 1, "window stride");
 static_assert(2 * BIAS < 65536, "DS immediates are 16 bits");
 
-__device__ __forceinline__ uint32_t bits_at(const uint32_t* __restrict__ bits, int64_t bit0, int n) {
-  const int64_t wi = bit0 >> 5;
-  const int sh = (int)(bit0 & 31);
-  uint64_t two = bits[wi];
-  if (sh + n > 32) two |= (uint64_t)bits[wi + 1] << 32;
-  const uint32_t v = (uint32_t)(two >> sh);
-  return n >= 32 ? v : (v & ((1u << n) - 1u));
-}
-
 // First point (dr, dc) of every pair of opposite perimeter points of radius R, in the order of
 // mg_score_pair_table (mg_tables.hip: score_pairs) -- the reference's midpoint walk, utils.py:433-465.
 template <int R>
@@ -154,9 +145,8 @@ __global__ __launch_bounds__(NP) void k_prefilter(const uint32_t* __restrict__ d
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int i = threadIdx.x; i < nr; i += NP) {
     const int len = d_per_starts[i + 1] - d_per_starts[i];
-    // a circle can only pass with sum(terms) >= min_roundness * len - 1e-3 (margin far above any rounding of the
-    // real sum), and sum(terms) <= sum(bounds) / 64
-    need[i] = (int)ceil(64.0 * ((double)min_roundness * len - 1e-3));
+    // a circle can only pass with sum(terms) >= mg_score_floor, and sum(terms) <= sum(bounds) / 64
+    need[i] = (int)ceil(64.0 * mg_score_floor(min_roundness, len));
   }
   const int wgroups = (side_x + 31) >> 5;  // 32-pixel groups per window row
   for (int64_t st = blockIdx.x; st < total_st; st += gridDim.x) {
@@ -274,7 +264,7 @@ __global__ __launch_bounds__(NP) void k_prefilter(const uint32_t* __restrict__ d
       const bool valid = valid_n;
       const uint32_t key = valid ? key_n : 0u;
       have = fetch();
-      const int wrow = (s / SUBX) * TS + (int)((key >> 6) & 63u) + max_r, wcol = (s % SUBX) * TS + (int)(key & 63u) + max_r;
+      const int wrow = (s / SUBX) * TS + mg_key_row(key) + max_r, wcol = (s % SUBX) * TS + mg_key_col(key) + max_r;
       const int vaddr = WBASE + wrow * WSTR + wcol - BIAS;
       int sum = 0;
       const int need_rho = need[rho];
@@ -363,8 +353,7 @@ __global__ __launch_bounds__(NT) void k_exact(const uint8_t* __restrict__ d_blur
   const uint8_t* blur = d_blur + (int64_t)plane * h * w;
   const float* ang = d_angle ? d_angle + (int64_t)plane * h * w : nullptr;
   float* scores = d_scores + (int64_t)plane * circle_cap;
-  const double PI = 3.141592653589793, INV_PI = 1.0 / 3.141592653589793;
-  const int t = threadIdx.x, lane = t & 63;
+  const int t = threadIdx.x;
   const int64_t rounds = (n + (int64_t)gridDim.x * XS - 1) / ((int64_t)gridDim.x * XS);
   for (int64_t rd = 0; rd < rounds; ++rd) {
     __syncthreads();  // tables in place / the previous round's lists are no longer read
@@ -381,13 +370,13 @@ __global__ __launch_bounds__(NT) void k_exact(const uint8_t* __restrict__ d_blur
       const int2 rec = active ? reinterpret_cast<const int2*>(d_surv)[(int64_t)plane * surv_cap + k] : make_int2(0, 0);
       ci = rec.x;
       const uint32_t key = (uint32_t)rec.y;
-      const int tile = (int)(key >> 17);
-      rad = min_r + (int)((key >> 12) & 31u);
-      s_row[t] = (tile / ntc) * TS - max_r + (int)((key >> 6) & 63u);
-      s_col[t] = (tile % ntc) * TS - max_r + (int)(key & 63u);
+      const int tile = (int)mg_key_tile(key);
+      rad = min_r + mg_key_layer(key);
+      s_row[t] = (tile / ntc) * TS - max_r + mg_key_row(key);
+      s_col[t] = (tile % ntc) * TS - max_r + mg_key_col(key);
       s_p0[t] = starts[rad - min_r];
       s_p1[t] = active ? starts[rad - min_r + 1] : s_p0[t];
-      floor_sum = (double)min_roundness * (double)(s_p1[t] - s_p0[t]) - 1e-3;
+      floor_sum = mg_score_floor(min_roundness, s_p1[t] - s_p0[t]);
     }
     for (int i = t; i < XS * (XPMAX / 32); i += NT) (&s_mask[0][0])[i] = 0u;
     __syncthreads();
@@ -448,14 +437,7 @@ __global__ __launch_bounds__(NT) void k_exact(const uint8_t* __restrict__ d_blur
           const int v = tab[p];
           const int y = s_row[s] + (v >> 16), x = s_col[s] + (int)(int16_t)(v & 0xFFFF);
           const float a = ang ? ang[(int64_t)y * w + x] : mg_edge_angle(blur, h, w, y, x);
-          double d = fabs((double)a - d_per_expected[p]);
-          if (d > PI) d = d - PI;
-          // x / pi, correctly rounded without the division (Markstein: y = RN(1/pi), q0 = RN(x y),
-          // r = x - q0 pi exactly by FMA, q = RN(q0 + r y) == RN(x / pi); verified against x / pi on 1e9
-          // operands of exactly this form)
-          const double x4 = 4.0 * fabs(d - PI / 2.0);
-          const double q0 = x4 * INV_PI;
-          s_term[s][j] = fma(fma(-q0, PI, x4), INV_PI, q0) - 1.0;
+          s_term[s][j] = mg_alignment_term(a, d_per_expected[p]);
         }
       }
       __syncthreads();
@@ -484,17 +466,11 @@ __global__ __launch_bounds__(NT) void k_exact(const uint8_t* __restrict__ d_blur
       } else {
         const float score = (float)acc / (float)(s_p1[t] - s_p0[t]);
         scores[ci] = score;
-        if (score >= min_roundness) {
-          const int k_ = atomicAdd(&d_num_alive[plane], 1);
-          d_alive[(int64_t)plane * circle_cap + k_] = (int32_t)ci;
-          circles[3 * ci] = s_row[t], circles[3 * ci + 1] = s_col[t], circles[3 * ci + 2] = rad;
-          atomicMax(&d_max_rc[2 * plane], s_row[t]);
-          atomicMax(&d_max_rc[2 * plane + 1], s_col[t]);
-        }
+        if (score >= min_roundness)
+          mg_emit_alive<true>(d_num_alive, d_alive, d_max_rc, plane, circle_cap, circles, ci, s_row[t], s_col[t], rad);
       }
     }
   }
-  (void)lane;
 }
 
 }  // namespace
@@ -519,11 +495,8 @@ extern "C" int mg_score_circles_keyed(const uint8_t* d_blur, const float* d_angl
   if (n_planes < 0 || n_planes > 65535 || per_total <= 0 || surv_cap < circle_cap) return MG_EINVAL;  // (a survivor per circle)
   if (mg_score_keyed_supported(min_r, max_r) != 1) return MG_EINVAL;
   if (h <= 0 || w <= 0 || h >= (1 << 24) || w >= (1 << 24) || (int64_t)h * w >= (1LL << 31)) return MG_EINVAL;
-  const int nr = max_r - min_r + 1;
-  int ntr, ntc;
-  int64_t n_layers, words;
-  if (mg_dedup_layout(h, w, min_r, max_r, &ntr, &ntc, &n_layers, &words) != MG_OK) return MG_EINVAL;
-  if ((int64_t)ntr * ntc >= 32768) return MG_EINVAL;  // the 32-bit key
+  int ntr, ntc, nr;
+  if (mg_key_layout(h, w, min_r, max_r, &ntr, &ntc, &nr) != MG_OK) return MG_EINVAL;
   if ((size_t)per_total * 12 > 48 * 1024 || NSUB * (nr + 1) > NP) return MG_EINVAL;
   hipStream_t s = mg_stream(stream);
   if (!counters_clear && mg_zero_async(d_num_surv, (size_t)std::max(n_planes, 1) * sizeof(int32_t), s) != hipSuccess)

@@ -1109,17 +1109,22 @@ def test_graph_survives_regrown_buffers(hp):
 
 
 @pytest.mark.parametrize("num_iter", [3000, 200000])
-def test_candidates_degenerate_triplets(hp, num_iter):
+@pytest.mark.parametrize("grid", [20, 40, 1])
+def test_candidates_degenerate_triplets(hp, grid, num_iter):
     """mg_candidate_keys on edge maps made of exactly the triplets that stress its arithmetic (VERDICT r3 item 3a;
     utils.py:319-342): lone pixels (p1 = p2 = p0: 0 / eps), horizontal runs (d_row = 0: slopes of 1e20), vertical runs
     (both slopes 0: the divisor is eps itself), diagonals (collinear: equal slopes, centres at 1e20 and beyond float32),
     two-pixel cells, and a dense block where general triplets mix with all of these.  The round-4 kernel reads slope
     and intercept from a per-workgroup LDS table and divides without range scaling; the raw float32 triples must equal
     the oracle's BIT FOR BIT, NaN and infinities included, with fewer edges than iterations (strata of one edge: the
-    first hash is never drawn) and with more (num_iter 3000 < edges), and the keys must be those of the triples."""
+    first hash is never drawn) and with more (num_iter 3000 < edges), and the keys must be those of the triples.
+    The three candidate kernels end in one shared tail; every one of them is held to the same bits: grid 20 takes
+    k_candidates_tab, grid 40 (above the table's largest cell) k_candidates<true> with key output, grid 1 (not a fast
+    shape) k_candidates<false>.  With a grid of 1 a cell holds one pixel, p1 = p2 = p0: every radius is 0 and every
+    key MG_NO_KEY."""
     from magnify_amd import _native as nat
 
-    h, w, grid, min_r, max_r = 200, 260, 20, 5, 14
+    h, w, min_r, max_r = 200, 260, 5, 14
     e = np.zeros((3, h, w), dtype=np.uint8)
     e[0, 10::40, 10::40] = 1                      # lone pixels
     e[0, 5, 60:80] = 1                            # a horizontal run inside one cell row
@@ -1171,9 +1176,12 @@ def test_candidates_degenerate_triplets(hp, num_iter):
         pr, pc = c[:, 0] + max_r, c[:, 1] + max_r
         key = (((pr >> 6) * ntc + (pc >> 6)) << 17) | ((c[:, 2] - min_r) << 12) | ((pr & 63) << 6) | (pc & 63)
         np.testing.assert_array_equal(got_keys[k], np.where(ok, key, 0xFFFFFFFF).astype(np.uint32), err_msg=f"keys of plane {k}")
-        if k == 2:
+        if grid == 1:
+            assert (got_keys[k] == 0xFFFFFFFF).all()
+        elif k == 2:
             assert ok.sum() > num_iter // 50  # the circles are found
-    assert {"zero radius", "huge"} <= kinds and ("nan" in kinds or "inf" in kinds), kinds
+    if grid > 1:
+        assert {"zero radius", "huge"} <= kinds and ("nan" in kinds or "inf" in kinds), kinds
 
 
 @pytest.mark.parametrize("L,time_major", [(100, False), (40, False), (64, True)])
