@@ -117,6 +117,19 @@ int mg_flatfield_apply_stitch_planes(const void* d_tiles, int dtype, int64_t n_p
                                      double flat, const void* d_flat, int flat_dtype,
                                      const double* d_max2, void* d_image, double* d_minmax, void* stream);
 
+/* Pass 2 with linear overlap blending of the tile seams: the operands, layouts and the image shape of
+ * mg_flatfield_apply_stitch.  Inside the band of `overlap` pixels around every inner seam a pixel is the linear mix of
+ * the values the plain pass would write for the two tiles that cover it (four where a row band and a column band
+ * cross): position k of a band weighs the later tile (k + 0.5) / overlap.  Integer pixels: (sum of ny nx value +
+ * D / 2) / D with D = (2 overlap)^2 in 64-bit integers; float pixels: float64, x first, then y, then the cast.  Outer
+ * borders stay cropped.  d_minmax receives the min/max of the BLENDED values.  MG_EINVAL also for
+ * 2 * overlap > min(ty, tx): a pixel would lie in two bands of one axis. */
+int mg_flatfield_apply_stitch_blend(const void* d_tiles, int dtype, int64_t n_planes, int n_tile_rows, int n_tile_cols,
+                                    int ty, int tx, int overlap, int apply_flatfield, int planes_per_group,
+                                    double dark, const void* d_dark, int dark_dtype,
+                                    double flat, const void* d_flat, int flat_dtype,
+                                    const double* d_max2, void* d_image, double* d_minmax, void* stream);
+
 /* Per-plane min/max (utils.py:24-25) of strided planes.  d_minmax double[n_planes][2],
  * pre-initialised to {+inf, -inf}.  Strides are in elements. */
 int mg_plane_minmax(const void* d_src, int dtype, int n_planes, int64_t plane_stride, int h, int w,
@@ -182,6 +195,11 @@ int mg_shading_upsample(const double* d_flat_w, const double* d_dark_w, int w, i
 int mg_shading_apply_stitch(const void* d_tiles, int dtype, int n_fields, int64_t planes_per_field, int n_tile_rows,
                             int n_tile_cols, int ty, int tx, int overlap, const float* d_flat, const float* d_dark,
                             void* d_image, double* d_minmax, void* stream);
+/* mg_shading_apply_stitch with the seams blended as in mg_flatfield_apply_stitch_blend (the values mixed are those
+ * mg_shading_apply_stitch writes). */
+int mg_shading_apply_stitch_blend(const void* d_tiles, int dtype, int n_fields, int64_t planes_per_field,
+                                  int n_tile_rows, int n_tile_cols, int ty, int tx, int overlap, const float* d_flat,
+                                  const float* d_dark, void* d_image, double* d_minmax, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * A3-A6 edge stage of find_circles (utils.py:20-27, 115-142)

@@ -51,6 +51,35 @@ __device__ __forceinline__ double exact_quotient(double t, double fl, double m1,
   return e;
 }
 
+template <typename T>
+struct IsIntegral {
+  static constexpr bool value = false;
+};
+template <>
+struct IsIntegral<uint8_t> {
+  static constexpr bool value = true;
+};
+template <>
+struct IsIntegral<uint16_t> {
+  static constexpr bool value = true;
+};
+
+// out = trunc(((t / fl) * m1) / m2) for an integer output type.  With r = refined_rcp(fl) != 0 and
+// k = m1 / m2, v = t * r * k agrees with the reference's three roundings to ~1e-15 relative, so the
+// truncation is the same unless v lies within 1e-6 of an integer -- those (rare) pixels, and every
+// non-integer output type, take the exact two-division path.
+template <typename T>
+__device__ __forceinline__ T correct_pixel(double t, double fl, double r, double m1, double m2, double k, bool fast_ok) {
+  if (IsIntegral<T>::value && fast_ok && r != 0.0) {
+    if (t == 0.0) return (T)0;  // 0 / fl * m1 / m2 == 0 exactly (m1, m2 finite and positive here)
+    const double v = t * r * k;
+    const double fv = floor(v);
+    const double fr = v - fv;
+    if (fr > 1e-6 && fr < 1.0 - 1e-6 && v < 4.0e9) return (T)(unsigned int)fv;
+  }
+  return cast_trunc<T>(exact_quotient(t, fl, m1, m2));
+}
+
 // k = M1 / M2 of a group; whether the fast path holds for these maxima
 __device__ __forceinline__ bool group_quotient(double m1, double m2, double& kk) {
   kk = m1 / m2;

@@ -7,50 +7,9 @@
 
 #include "mg_common.h"
 #include "mg_flatcorr.h"
+#include "mg_stitch.h"
 
 namespace {
-
-template <typename T>
-struct VecOf;
-template <>
-struct VecOf<uint8_t> {
-  static constexpr int N = 16;
-};
-template <>
-struct VecOf<uint16_t> {
-  static constexpr int N = 8;
-};
-template <>
-struct VecOf<float> {
-  static constexpr int N = 4;
-};
-template <>
-struct VecOf<double> {
-  static constexpr int N = 2;
-};
-
-// Load N consecutive elements; one 16-byte load when the address is aligned.
-template <typename T, int N>
-__device__ __forceinline__ void load_vec(const T* p, T (&v)[N]) {
-  if ((reinterpret_cast<uintptr_t>(p) & 15) == 0) {
-    const uint4 raw = *reinterpret_cast<const uint4*>(p);
-    __builtin_memcpy(v, &raw, 16);
-  } else {
-#pragma unroll
-    for (int j = 0; j < N; ++j) v[j] = p[j];
-  }
-}
-template <typename T, int N>
-__device__ __forceinline__ void store_vec(T* p, const T (&v)[N]) {
-  if ((reinterpret_cast<uintptr_t>(p) & 15) == 0) {
-    uint4 raw;
-    __builtin_memcpy(&raw, v, 16);
-    *reinterpret_cast<uint4*>(p) = raw;
-  } else {
-#pragma unroll
-    for (int j = 0; j < N; ++j) p[j] = v[j];
-  }
-}
 
 // 16-byte accesses at addresses the caller knows to be aligned; `nt`: nontemporal (streamed once, not kept in cache)
 typedef uint32_t mg_u32x4 __attribute__((ext_vector_type(4)));
@@ -68,19 +27,6 @@ __device__ __forceinline__ void store_vec16(T* p, const T (&v)[N], bool nt) {
   if (nt) __builtin_nontemporal_store(raw, q);
   else *q = raw;
 }
-
-template <typename T>
-struct IsIntegral {
-  static constexpr bool value = false;
-};
-template <>
-struct IsIntegral<uint8_t> {
-  static constexpr bool value = true;
-};
-template <>
-struct IsIntegral<uint16_t> {
-  static constexpr bool value = true;
-};
 
 __device__ __forceinline__ void block_atomic_max2(double m1, double m2, double* out) {
   __shared__ double s1[16], s2[16];
@@ -119,35 +65,6 @@ __device__ __forceinline__ void max_step(double t, double fl, bool fast_m2, doub
     if (m2 == m2 && qa < m2 * (1.0 - 1e-6)) return;  // provably below the running maximum
   }
   m2 = mg_nanmax(m2, t / fl);
-}
-
-// N consecutive dark/flat operands as float64 (image of float32/float64, or the scalar).
-template <int N>
-__device__ __forceinline__ void load_field(const void* __restrict__ img, int dt, int64_t p, double scalar,
-                                           double (&out)[N]) {
-  if (!img) {
-#pragma unroll
-    for (int j = 0; j < N; ++j) out[j] = scalar;
-  } else if (dt == MG_F32) {
-    const float* f = (const float*)img + p;
-    if ((N % 4) == 0 && (reinterpret_cast<uintptr_t>(f) & 15) == 0) {
-#pragma unroll
-      for (int q = 0; q < N / 4; ++q) {
-        const float4 v = reinterpret_cast<const float4*>(f)[q];
-        out[4 * q] = v.x;
-        out[4 * q + 1] = v.y;
-        out[4 * q + 2] = v.z;
-        out[4 * q + 3] = v.w;
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < N; ++j) out[j] = f[j];
-    }
-  } else {
-    const double* d = (const double*)img + p;
-#pragma unroll
-    for (int j = 0; j < N; ++j) out[j] = d[j];
-  }
 }
 
 // Thread = one chunk of N pixels of the tile grid; it walks over the tiles of its group, so the
@@ -426,26 +343,6 @@ __global__ __launch_bounds__(256) void k_flatfield_max_lean(const T* __restrict_
 }
 
 // ---- pass 2: apply + stitch (+ output min/max) ----------------------------------------
-constexpr int ROWS_PER_BLOCK = 32;  // rows of a workgroup at large batches; fewer when the grid would not fill the chip
-
-// out = trunc(((t / fl) * m1) / m2) for an integer output type.  With r = refined_rcp(fl) != 0 and
-// k = m1 / m2, v = t * r * k agrees with the reference's three roundings to ~1e-15 relative, so the
-// truncation is the same unless v lies within 1e-6 of an integer -- those (rare) pixels, and every
-// non-integer output type, take the exact two-division path.
-template <typename T>
-__device__ __forceinline__ T correct_pixel(double t, double fl, double r, double m1, double m2, double k, bool fast_ok) {
-  if (IsIntegral<T>::value && fast_ok && r != 0.0) {
-    if (t == 0.0) return (T)0;  // 0 / fl * m1 / m2 == 0 exactly (m1, m2 finite and positive here)
-    const double v = t * r * k;
-    const double fv = floor(v);
-    const double fr = v - fv;
-    if (fr > 1e-6 && fr < 1.0 - 1e-6 && v < 4.0e9) return (T)(unsigned int)fv;
-  }
-  return cast_trunc<T>(exact_quotient(t, fl, m1, m2));
-}
-
-constexpr int PLANES_PER_BLOCK = 8;
-
 // Selected planes of every group (mg_flatfield_apply_stitch_planes): bit c of `mask` selects plane c of each group of
 // planes_per_group planes; the s-th selected plane of the stack is plane (s / n_sel) * planes_per_group + the
 // (s % n_sel)-th set bit.  A workgroup takes PLANES_PER_BLOCK consecutive SELECTED planes; without a selection
@@ -827,16 +724,8 @@ int launch_apply(const void* d_tiles, int64_t n_planes, int n_tr, int n_tc, int 
   // a selection (plane_mask != 0, apply only): from here on n_planes counts the selected planes, the kernels map them
   const PlaneSel sel{plane_mask, __builtin_popcount(plane_mask)};
   if (plane_mask) n_planes = n_planes / planes_per_group * sel.n_sel;
-  // rows per workgroup: 32 when that still gives ~8 workgroups per CU, down to 2 for a single assay
-  int rows = ROWS_PER_BLOCK;
-  const int64_t cols_planes = (int64_t)((w_out + 256 * N - 1) / (256 * N)) * ((n_planes + PLANES_PER_BLOCK - 1) / PLANES_PER_BLOCK);
-  while (rows > 2 && cols_planes * ((h_out + rows - 1) / rows) < 2048) rows /= 2;
-  // ... and at most ~1024 workgroups per plane group walk them (each ends with min/max atomics on the plane's one
-  // cache line: 2048 workgroups finishing together took 100 us over them)
-  int y_blocks = (h_out + rows - 1) / rows;
-  if (rows < ROWS_PER_BLOCK) y_blocks = (int)std::min<int64_t>(y_blocks, std::max<int64_t>(1, 1024 / std::max<int64_t>(1, cols_planes)));
-  dim3 grid((w_out + 256 * N - 1) / (256 * N), y_blocks,
-            (unsigned)((n_planes + PLANES_PER_BLOCK - 1) / PLANES_PER_BLOCK));
+  int rows;
+  const dim3 grid = stitch_grid<N>(h_out, w_out, n_planes, rows);
   if (grid.y > 65535 || grid.z > 65535) return MG_EINVAL;
   const bool aligned = IsIntegral<T>::value && hx % N == 0 && tx % N == 0 && clip % N == 0 &&
                        (reinterpret_cast<uintptr_t>(d_tiles) & 15) == 0 && (reinterpret_cast<uintptr_t>(d_image) & 15) == 0 &&

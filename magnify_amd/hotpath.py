@@ -193,18 +193,46 @@ def stitch_geometry(ty: int, tx: int, overlap: int):
     return clip, ty - 2 * clip - rem, tx - 2 * clip - rem
 
 
+BLEND_MODES = (None, "linear")
+
+
+def check_blend(blend, overlap=None, ty=None, tx=None):
+    """``blend`` as ``stitch`` takes it: None (crop and butt, the reference) or "linear"; with the tile size, also that
+    a "linear" band fits: 2 * overlap <= min(ty, tx), so that a pixel lies in at most one band per axis."""
+    if blend not in BLEND_MODES:
+        raise ValueError(f"blend must be one of {BLEND_MODES}, got {blend!r}")
+    if blend is not None and overlap is not None and 2 * overlap > min(ty, tx):
+        raise ValueError(f"blend={blend!r} needs 2 * overlap <= tile size: overlap {overlap}, tiles {ty}x{tx}")
+    return blend
+
+
+def blend_bands(n: int, t: int, overlap: int):
+    """The bands of ``blend="linear"`` along one axis of ``n`` tiles of length ``t``: [(start, stop)] in canvas
+    coordinates, one per inner seam -- the seam at i * h (h the kept length of ``stitch_geometry``) has the band
+    [i * h - clip, i * h + clip + overlap % 2), ``overlap`` pixels in which the weight of tile i rises from
+    0.5 / overlap to 1 - 0.5 / overlap (mg_blend.hip)."""
+    clip, h, _ = stitch_geometry(t, t, overlap)
+    if overlap == 0:
+        return []
+    return [(i * h - clip, i * h + clip + overlap % 2) for i in range(1, n)]
+
+
 def flatfield_stitch(tiles: torch.Tensor, overlap: int, flatfield=1.0, darkfield=0.0, apply_flatfield=True,
                      max2: torch.Tensor | None = None, want_minmax=True, out: torch.Tensor | None = None,
-                     minmax_out: torch.Tensor | None = None, n_groups=1):
+                     minmax_out: torch.Tensor | None = None, n_groups=1, blend=None):
     """tiles (C, T, R, Cc, ty, tx) -> image (C, T, R*hy, Cc*hx) and per-plane min/max (C*T, 2).
 
-    ``max2`` lets a multi-GPU caller supply all-reduced maxima."""
+    ``max2`` lets a multi-GPU caller supply all-reduced maxima.  ``blend="linear"``: the same image
+    with the bands around the inner seams (``blend_bands``) mixed from the tiles that cover them
+    (mg_flatfield_apply_stitch_blend); the min/max is that of the blended image."""
+    check_blend(blend)
     require_gpu()
     if overlap < 0:
         raise ValueError("Overlap must be non-negative.")
     c, t, nr, nc, ty, tx = tiles.shape
     if overlap >= ty or overlap >= tx:
         raise ValueError(f"Overlap ({overlap}) must be smaller than tile size ({ty}x{tx}).")
+    check_blend(blend, overlap, ty, tx)
     tiles = tiles.contiguous()
     _, hy, hx = stitch_geometry(ty, tx, overlap)
     dk, dkt, dkc = _df_operand(darkfield, ty, tx, tiles.device)
@@ -228,10 +256,9 @@ def flatfield_stitch(tiles: torch.Tensor, overlap: int, flatfield=1.0, darkfield
             minmax = minmax_out
             assert minmax.is_contiguous() and minmax.numel() == c * t * 2 and minmax.dtype == torch.float64
         minmax.view(-1, 2).copy_(_minmax_init(c * t, tiles.device))  # (+inf, -inf) rows: one copy, not two fills
-    _call("mg_flatfield_apply_stitch", tiles.data_ptr(), nat.dtype_code(tiles.dtype), c * t, nr, nc, ty, tx,
-                                                  overlap, int(bool(apply_flatfield)), (c * t) // n_groups, dk, _ptr(dkt), dkc, fl,
-                                                  _ptr(flt), flc, _ptr(max2), image.data_ptr(), _ptr(minmax),
-                                                  _stream())
+    _call("mg_flatfield_apply_stitch" if blend is None else "mg_flatfield_apply_stitch_blend", tiles.data_ptr(),
+          nat.dtype_code(tiles.dtype), c * t, nr, nc, ty, tx, overlap, int(bool(apply_flatfield)), (c * t) // n_groups, dk,
+          _ptr(dkt), dkc, fl, _ptr(flt), flc, _ptr(max2), image.data_ptr(), _ptr(minmax), _stream())
     return image, minmax
 
 

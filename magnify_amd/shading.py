@@ -55,13 +55,16 @@ class Shading:
 
 
 def apply_stitch(tiles: torch.Tensor, overlap: int, flats: torch.Tensor, darks: torch.Tensor, want_minmax=True,
-                 out: torch.Tensor | None = None):
+                 out: torch.Tensor | None = None, blend=None):
     """tiles (C, T, R, Cc, ty, tx) -> image (C, T, R*hy, Cc*hx) with (x - dark[c]) / flat[c] applied, and the
-    per-plane min / max (C*T, 2) -- one launch for all channels (flats, darks: (C, ty, tx) float32)."""
+    per-plane min / max (C*T, 2) -- one launch for all channels (flats, darks: (C, ty, tx) float32).
+    ``blend="linear"``: the seams blended as in ``hotpath.flatfield_stitch`` (mg_shading_apply_stitch_blend)."""
+    hotpath.check_blend(blend)
     hotpath.require_gpu()
     c, t, nr, nc, ty, tx = tiles.shape
     if overlap < 0 or overlap >= ty or overlap >= tx:
         raise ValueError(f"Overlap ({overlap}) must be non-negative and smaller than tile size ({ty}x{tx}).")
+    hotpath.check_blend(blend, overlap, ty, tx)
     if tuple(flats.shape) != (c, ty, tx) or tuple(darks.shape) != (c, ty, tx):
         raise ValueError("one (ty, tx) flat and dark field per channel")
     tiles = tiles.contiguous()
@@ -72,8 +75,8 @@ def apply_stitch(tiles: torch.Tensor, overlap: int, flats: torch.Tensor, darks: 
     minmax = None
     if want_minmax:
         minmax = hotpath._minmax_init(c * t, tiles.device).clone()
-    hotpath._call("mg_shading_apply_stitch", tiles.data_ptr(), nat.dtype_code(tiles.dtype), c, t, nr, nc, ty, tx,
-                  overlap, flats.data_ptr(), darks.data_ptr(), image.data_ptr(), hotpath._ptr(minmax),
+    hotpath._call("mg_shading_apply_stitch" if blend is None else "mg_shading_apply_stitch_blend", tiles.data_ptr(),
+                  nat.dtype_code(tiles.dtype), c, t, nr, nc, ty, tx, overlap, flats.data_ptr(), darks.data_ptr(), image.data_ptr(), hotpath._ptr(minmax),
                   hotpath._stream())
     return image, minmax
 

@@ -32,10 +32,12 @@ class StackProcessor:
     def __init__(self, n_t, n_c, h, w, dtype=torch.uint16, min_bead_diameter=10, max_bead_diameter=50,
                  low_edge_quantile=0.1, high_edge_quantile=0.9, num_iter=5_000_000, min_roundness=0.3,
                  roi_length=None, search_channels=(0,), mode="P", plane_batch=None, device="cuda", n_streams=1,
-                 sub_batches=None, tile_grid=None, overlap=0):
+                 sub_batches=None, tile_grid=None, overlap=0, blend=None):
         """``h, w``: the size of the (stitched) image.  ``tile_grid=(rows, cols, tile_y, tile_x)`` + ``overlap``:
         the input stack is (T, C, rows, cols, tile_y, tile_x) and the flat-field pass also crops and joins the
-        tiles (stitch.py:22-39); ``h, w`` must then be the stitched size (``stitched_shape``)."""
+        tiles (stitch.py:22-39); ``h, w`` must then be the stitched size (``stitched_shape``).  ``blend``: as
+        ``Stitcher``'s -- "linear" blends the seams in that pass (the image's size does not depend on it)."""
+        hp.check_blend(blend)
         hp.require_gpu()
         if min_bead_diameter > max_bead_diameter:
             raise ValueError("min_bead_diameter must be <= max_bead_diameter.")
@@ -47,6 +49,8 @@ class StackProcessor:
         if stitched_shape(*self.tile_grid, self.overlap) != (h, w):
             raise ValueError(f"tile_grid {self.tile_grid} with overlap {overlap} stitches to "
                              f"{stitched_shape(*self.tile_grid, self.overlap)}, not to {(h, w)}")
+        # (the stitch launch is never inside the finder's captured chain: the mode changes no graph key)
+        self.blend = hp.check_blend(blend, self.overlap, *self.tile_grid[2:])
         self.min_r = math.floor(min_bead_diameter / 2)  # find.py:461-467
         self.max_r = math.ceil(max_bead_diameter / 2)
         self.L = roi_length if roi_length is not None else 2 * max_bead_diameter
@@ -173,7 +177,7 @@ class StackProcessor:
         # mode P: every time slice is its own assay -> its own pair of maxima (n_groups = T);
         # mode R: single assay, the maxima span the whole stack (preprocess.py:84,86)
         hp.flatfield_stitch(tiles, self.overlap, flatfield, darkfield, out=self._image, minmax_out=self._minmax, max2=max2,
-                            n_groups=T if self.mode == "P" else 1)
+                            n_groups=T if self.mode == "P" else 1, blend=self.blend)
         return self._image
 
     def detect(self, seed=0):
@@ -231,7 +235,7 @@ class StackProcessor:
                             self.stage.view(stack.shape)[lo:hi].copy_(stack[lo:hi], non_blocking=True)
                         if tiles is not None:
                             hp.flatfield_stitch(tiles[lo * C : hi * C], self.overlap, flatfield, darkfield, out=self._image[lo:hi],
-                                                minmax_out=self._minmax[lo:hi], n_groups=hi - lo)
+                                                minmax_out=self._minmax[lo:hi], n_groups=hi - lo, blend=self.blend)
                         for j, ch in enumerate(self.search_channels):
                             planes = self._image[lo:hi, ch]
                             mm = self._minmax[lo:hi, ch].contiguous()
@@ -440,10 +444,11 @@ def stitched_shape(rows, cols, tile_y, tile_x, overlap):
 
 
 def process_stream(chunks, flatfield=1.0, darkfield=0.0, seed=0, want_roi=False, prefetch=2, overlap=0, sink=None,
-                   first_timepoint=None, **processor_kwargs):
+                   first_timepoint=None, blend=None, **processor_kwargs):
     """Mode-P processing of a time series that arrives chunk by chunk (config C5: ``reader.iter_time_chunks``
     or any iterator of (T_chunk, C, H, W) blocks -- or TILED blocks (T_chunk, C, rows, cols, tile_y, tile_x), which the
-    flat-field pass crops and joins with ``overlap`` on the device, so the stitched assay never exists on the host --
+    flat-field pass crops and joins with ``overlap`` on the device (``blend="linear"``: and blends their seams, as
+    ``Stitcher``), so the stitched assay never exists on the host --
     optionally wrapped as (time_values, channels, block)).
     A reader thread keeps ``prefetch`` chunks ahead, so decoding files overlaps the GPU's work on the chunk
     before; inside a chunk the upload overlaps compute when ``n_streams > 1`` is passed on.  Every
@@ -467,6 +472,7 @@ def process_stream(chunks, flatfield=1.0, darkfield=0.0, seed=0, want_roi=False,
     import queue
     import threading
 
+    hp.check_blend(blend)
     prefetch = max(1, int(prefetch))
     ring = getattr(chunks, "ring", None)
     if ring is not None and ring < prefetch + 2:
@@ -523,7 +529,7 @@ def process_stream(chunks, flatfield=1.0, darkfield=0.0, seed=0, want_roi=False,
                     t, c = block.shape[:2]
                     h, w = stitched_shape(*block.shape[2:], overlap)
                     procs[key] = StackProcessor(t, c, h, w, dtype=block.dtype, mode="P", tile_grid=tuple(block.shape[2:]),
-                                                overlap=overlap, **processor_kwargs)
+                                                overlap=overlap, blend=blend, **processor_kwargs)
                 else:
                     t, c, h, w = block.shape
                     procs[key] = StackProcessor(t, c, h, w, dtype=block.dtype, mode="P", **processor_kwargs)
