@@ -130,6 +130,45 @@ int mg_flatfield_apply_stitch_blend(const void* d_tiles, int dtype, int64_t n_pl
                                     double flat, const void* d_flat, int flat_dtype,
                                     const double* d_max2, void* d_image, double* d_minmax, void* stream);
 
+/* Pass 2 on tiles moved by one integer shift each (tile registration): the operands, layouts and the image
+ * of mg_flatfield_apply_stitch (blend = 0) or mg_flatfield_apply_stitch_blend (blend = 1) applied to
+ *   tile'[r, c][y, x] = value[r, c][clamp(y - ey, 0, ty - 1), clamp(x - ex, 0, tx - 1)],
+ * value: what the plain pass writes for that pixel of the tile, (ey, ex) = d_shift[table][r][c] (device int32,
+ * (n_tables, n_tile_rows, n_tile_cols, 2)); the table of plane p is 0 when n_tables == 1, else p % n_time
+ * (n_tables == n_time: one table per timepoint of (channel, time) planes).  d_minmax as there.  The tables are read
+ * back and checked before the launch: the call copies them to the host and waits for the stream, so it must not be
+ * made while the stream is being captured into a graph (the kernel itself clamps every read into the tile, so no table
+ * can make it read out of bounds).  MG_EINVAL for an entry outside
+ * [-overlap / 2, overlap / 2], for n_tables not in {1, n_time}, for blend not in {0, 1}, and for what the plain
+ * (blend = 0) or the blended (blend = 1) entry refuses. */
+int mg_flatfield_apply_stitch_shift(const void* d_tiles, int dtype, int64_t n_planes, int n_tile_rows, int n_tile_cols,
+                                    int ty, int tx, int overlap, int apply_flatfield, int planes_per_group,
+                                    double dark, const void* d_dark, int dark_dtype,
+                                    double flat, const void* d_flat, int flat_dtype,
+                                    const double* d_max2, void* d_image, double* d_minmax,
+                                    const int32_t* d_shift, int n_tables, int n_time, int blend, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Tile registration: the sums of the zero-mean normalised cross-correlation of every seam's overlap strips
+ * ---------------------------------------------------------------------------------- */
+
+/* d_planes: (n_planes, n_tile_rows, n_tile_cols, ty, tx) of `dtype`.  Seams in this order: (r, c) | (r, c + 1) at
+ * index r (n_tile_cols - 1) + c, then (r, c) | (r + 1, c) at n_tile_rows (n_tile_cols - 1) + r n_tile_cols + c; A is
+ * the first tile of the pair, B the second.  With v = overlap, m = max_shift the patch of B is q in
+ * [m, ty - m) x [m, v - m) with offset o = (0, tx - v) for the first kind and [m, v - m) x [m, tx - m) with
+ * o = (ty - v, 0) for the second; B[q] meets A[q + o + delta] for delta in [-m, m]^2.
+ *   d_fixed (n_planes, n_seams, 3): n, sum B, sum B^2;
+ *   d_sums  (n_planes, n_seams, 2m + 1, 2m + 1, 3): sum A, sum A^2, sum A B at [delta_y + m][delta_x + m];
+ * int64 (exact) for MG_U8 / MG_U16, float64 for MG_F32 / MG_F64 -- the same bits on every run (partial sums per strip
+ * in d_scratch, added in strip order; no atomics).  d_scratch: mg_seam_sums_scratch_bytes(...) bytes, 8-byte aligned.
+ * MG_EINVAL / -1: max_shift < 1, 4 max_shift > overlap, max_shift > 32, overlap > min(ty, tx), more than 65535
+ * planes or seams, a null pointer or too little scratch.  A 1 x 1 grid has no seams: MG_OK, nothing written. */
+int64_t mg_seam_sums_scratch_bytes(int64_t n_planes, int n_tile_rows, int n_tile_cols, int ty, int tx, int overlap,
+                                   int max_shift);
+int mg_seam_sums(const void* d_planes, int dtype, int64_t n_planes, int n_tile_rows, int n_tile_cols, int ty, int tx,
+                 int overlap, int max_shift, void* d_sums, void* d_fixed, void* d_scratch, int64_t scratch_bytes,
+                 void* stream);
+
 /* Per-plane min/max (utils.py:24-25) of strided planes.  d_minmax double[n_planes][2],
  * pre-initialised to {+inf, -inf}.  Strides are in elements. */
 int mg_plane_minmax(const void* d_src, int dtype, int n_planes, int64_t plane_stride, int h, int w,
@@ -200,6 +239,13 @@ int mg_shading_apply_stitch(const void* d_tiles, int dtype, int n_fields, int64_
 int mg_shading_apply_stitch_blend(const void* d_tiles, int dtype, int n_fields, int64_t planes_per_field,
                                   int n_tile_rows, int n_tile_cols, int ty, int tx, int overlap, const float* d_flat,
                                   const float* d_dark, void* d_image, double* d_minmax, void* stream);
+
+/* mg_shading_apply_stitch on tiles moved by one integer shift each, blended or not: the shift arguments and their
+ * checks are those of mg_flatfield_apply_stitch_shift (planes: n_fields * planes_per_field). */
+int mg_shading_apply_stitch_shift(const void* d_tiles, int dtype, int n_fields, int64_t planes_per_field,
+                                  int n_tile_rows, int n_tile_cols, int ty, int tx, int overlap, const float* d_flat,
+                                  const float* d_dark, void* d_image, double* d_minmax, const int32_t* d_shift,
+                                  int n_tables, int n_time, int blend, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * A3-A6 edge stage of find_circles (utils.py:20-27, 115-142)

@@ -219,12 +219,15 @@ def blend_bands(n: int, t: int, overlap: int):
 
 def flatfield_stitch(tiles: torch.Tensor, overlap: int, flatfield=1.0, darkfield=0.0, apply_flatfield=True,
                      max2: torch.Tensor | None = None, want_minmax=True, out: torch.Tensor | None = None,
-                     minmax_out: torch.Tensor | None = None, n_groups=1, blend=None):
+                     minmax_out: torch.Tensor | None = None, n_groups=1, blend=None, shifts=None):
     """tiles (C, T, R, Cc, ty, tx) -> image (C, T, R*hy, Cc*hx) and per-plane min/max (C*T, 2).
 
     ``max2`` lets a multi-GPU caller supply all-reduced maxima.  ``blend="linear"``: the same image
     with the bands around the inner seams (``blend_bands``) mixed from the tiles that cover them
-    (mg_flatfield_apply_stitch_blend); the min/max is that of the blended image."""
+    (mg_flatfield_apply_stitch_blend); the min/max is that of the blended image.  ``shifts``: int32 (R, Cc, 2) for
+    every plane or (T, R, Cc, 2) per timepoint, entries within [-overlap // 2, overlap // 2] -- every tile is first
+    moved by its (ey, ex) with edge replication, ``tile'[y, x] = value[clamp(y - ey), clamp(x - ex)]``, then stitched
+    as above (mg_flatfield_apply_stitch_shift); None: the passes above, untouched."""
     check_blend(blend)
     require_gpu()
     if overlap < 0:
@@ -256,10 +259,37 @@ def flatfield_stitch(tiles: torch.Tensor, overlap: int, flatfield=1.0, darkfield
             minmax = minmax_out
             assert minmax.is_contiguous() and minmax.numel() == c * t * 2 and minmax.dtype == torch.float64
         minmax.view(-1, 2).copy_(_minmax_init(c * t, tiles.device))  # (+inf, -inf) rows: one copy, not two fills
+    if shifts is not None:
+        table = shift_tables(shifts, t, nr, nc, overlap, tiles.device)
+        _call("mg_flatfield_apply_stitch_shift", tiles.data_ptr(), nat.dtype_code(tiles.dtype), c * t, nr, nc, ty, tx, overlap,
+              int(bool(apply_flatfield)), (c * t) // n_groups, dk, _ptr(dkt), dkc, fl, _ptr(flt), flc, _ptr(max2),
+              image.data_ptr(), _ptr(minmax), table.data_ptr(), table.shape[0], t, int(blend is not None), _stream())
+        return image, minmax
     _call("mg_flatfield_apply_stitch" if blend is None else "mg_flatfield_apply_stitch_blend", tiles.data_ptr(),
           nat.dtype_code(tiles.dtype), c * t, nr, nc, ty, tx, overlap, int(bool(apply_flatfield)), (c * t) // n_groups, dk,
           _ptr(dkt), dkc, fl, _ptr(flt), flc, _ptr(max2), image.data_ptr(), _ptr(minmax), _stream())
     return image, minmax
+
+
+def shift_tables(shifts, n_time, nr, nc, overlap, device):
+    """The per-tile shifts of a registered stitch as the contiguous int32 device tensor (n_tables, R, Cc, 2) the
+    kernels read: (R, Cc, 2) is one table for every plane, (T, R, Cc, 2) one per timepoint; every entry lies within
+    [-overlap // 2, overlap // 2].  A tensor that already has that form is handed on as it is."""
+    if (isinstance(shifts, torch.Tensor) and shifts.is_cuda and shifts.dtype == torch.int32 and shifts.is_contiguous()
+            and shifts.dim() == 4 and tuple(shifts.shape[1:]) == (nr, nc, 2) and shifts.shape[0] in (1, n_time)):
+        return shifts  # already what the kernels read: no upload; the entry point checks the range itself
+    host = shifts.cpu().numpy() if isinstance(shifts, torch.Tensor) else np.asarray(shifts)
+    if host.dtype.kind not in "iu":
+        raise ValueError(f"shifts must be integers, got {host.dtype}")
+    if host.ndim == 3:
+        host = host[None]
+    if host.ndim != 4 or host.shape[1:] != (nr, nc, 2) or host.shape[0] not in (1, n_time):
+        raise ValueError(f"shifts must have the shape (R, Cc, 2) or (T, R, Cc, 2) = ({n_time}, {nr}, {nc}, 2), "
+                         f"got {tuple(np.shape(shifts))}")
+    clip = overlap // 2
+    if host.size and (host.min() < -clip or host.max() > clip):
+        raise ValueError(f"shifts must lie within [-{clip}, {clip}] (overlap // 2)")
+    return torch.from_numpy(np.ascontiguousarray(host, dtype=np.int32)).to(device)
 
 
 def flatfield_apply_planes(tiles: torch.Tensor, overlap: int, flatfield, darkfield, max2: torch.Tensor, plane_mask: int,

@@ -86,8 +86,10 @@ def microfluidic_chip(data, shape=(8, 8), pinlist=None, blank=None, overlap=102,
                       chamber_diameter=60, top_chamber=None, left_chamber=None, low_edge_quantile=0.1,
                       high_edge_quantile=0.9, num_iter=5000000, min_roundness=0.2, cluster_penalty=50, roi_length=None,
                       progress_bar=False, search_timestep=0, search_channel=None, roi_only=False, drop_tiles=True,
-                      interactive=False, blend=None):
-    """registry.py:32-110 (``blend``: ``stitch``'s overlap blending, not in the reference)."""
+                      interactive=False, blend=None,
+                      register=None, max_shift=8, register_channel=None):
+    """registry.py:32-110 (``blend``: ``stitch``'s overlap blending; ``register``, ``max_shift``, ``register_channel``:
+    its tile registration -- neither is in the reference)."""
     kw = dict(locals())
     kw.pop("data")
     return microfluidic_chip_pipe(**kw)(data=data)
@@ -98,7 +100,8 @@ def microfluidic_chip_pipe(shape=(8, 8), pinlist=None, blank=None, overlap=102, 
                            chamber_diameter=60, top_chamber=None, left_chamber=None, low_edge_quantile=0.1,
                            high_edge_quantile=0.9, num_iter=5000000, min_roundness=0.2, cluster_penalty=50,
                            roi_length=None, progress_bar=False, search_timestep=0, search_channel=None,
-                           roi_only=False, drop_tiles=True, interactive=False, blend=None):
+                           roi_only=False, drop_tiles=True, interactive=False, blend=None,
+                           register=None, max_shift=8, register_channel=None):
     """registry.py:196-271."""
     if chip_type is not None:
         if chip_type == "minichip":
@@ -112,7 +115,8 @@ def microfluidic_chip_pipe(shape=(8, 8), pinlist=None, blank=None, overlap=102, 
     pipe = Pipeline("read")
     pipe.add_pipe("standardize_format")
     pipe.add_pipe("identify_buttons", shape=shape, pinlist=pinlist, blank=blank)
-    pipe.add_pipe("stitch", overlap=overlap, blend=blend)
+    pipe.add_pipe("stitch", overlap=overlap, blend=blend, register=register, max_shift=max_shift,
+                  register_channel=register_channel)
     pipe.add_pipe("rotate", rotation=rotation)
     pipe.add_pipe("find_buttons", row_dist=row_dist, col_dist=col_dist, min_button_diameter=min_button_diameter,
                   max_button_diameter=max_button_diameter, chamber_diameter=chamber_diameter, top_chamber=top_chamber,
@@ -127,7 +131,8 @@ def microfluidic_chip_pipe(shape=(8, 8), pinlist=None, blank=None, overlap=102, 
 
 def mrbles(data, spectra, codes, flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=10, max_bead_diameter=50,
            low_edge_quantile=0.1, high_edge_quantile=0.9, num_iter=5000000, min_roundness=0.3, roi_length=None,
-           search_channel=None, reference="eu", roi_only=False, drop_tiles=True, interactive=False, blend=None):
+           search_channel=None, reference="eu", roi_only=False, drop_tiles=True, interactive=False, blend=None,
+           register=None, max_shift=8, register_channel=None):
     """registry.py:274-399."""
     kw = dict(locals())
     kw.pop("data")
@@ -136,12 +141,14 @@ def mrbles(data, spectra, codes, flatfield=1.0, darkfield=0.0, overlap=102, min_
 
 def mrbles_pipe(spectra, codes, flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=10, max_bead_diameter=50,
                 low_edge_quantile=0.1, high_edge_quantile=0.9, num_iter=5000000, min_roundness=0.3, roi_length=None,
-                search_channel=None, reference="eu", roi_only=False, drop_tiles=True, interactive=False, blend=None):
+                search_channel=None, reference="eu", roi_only=False, drop_tiles=True, interactive=False, blend=None,
+                register=None, max_shift=8, register_channel=None):
     """registry.py:402-451."""
     pipe = Pipeline("read")
     pipe.add_pipe("standardize_format")
     pipe.add_pipe("flatfield_correct", flatfield=flatfield, darkfield=darkfield)
-    pipe.add_pipe("stitch", overlap=overlap, blend=blend)
+    pipe.add_pipe("stitch", overlap=overlap, blend=blend, register=register, max_shift=max_shift,
+                  register_channel=register_channel)
     pipe.add_pipe("find_beads", min_bead_diameter=min_bead_diameter, max_bead_diameter=max_bead_diameter,
                   low_edge_quantile=low_edge_quantile, high_edge_quantile=high_edge_quantile, num_iter=num_iter,
                   min_roundness=min_roundness, roi_length=roi_length, search_channel=search_channel,
@@ -154,7 +161,8 @@ def mrbles_pipe(spectra, codes, flatfield=1.0, darkfield=0.0, overlap=102, min_b
 
 def beads(data, flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=10, max_bead_diameter=50,
           low_edge_quantile=0.1, high_edge_quantile=0.9, num_iter=5000000, min_roundness=0.3, roi_length=None,
-          search_channel=None, roi_only=False, drop_tiles=True, interactive=False, blend=None):
+          search_channel=None, roi_only=False, drop_tiles=True, interactive=False, blend=None,
+          register=None, max_shift=8, register_channel=None):
     """registry.py:454-565."""
     kw = dict(locals())
     kw.pop("data")
@@ -163,12 +171,14 @@ def beads(data, flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=10,
 
 def beads_pipe(flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=5, max_bead_diameter=25,
                low_edge_quantile=0.1, high_edge_quantile=0.9, num_iter=5000000, min_roundness=0.3, roi_length=None,
-               search_channel=None, roi_only=False, drop_tiles=True, interactive=False, blend=None):
+               search_channel=None, roi_only=False, drop_tiles=True, interactive=False, blend=None,
+               register=None, max_shift=8, register_channel=None):
     """registry.py:568-612 (note the 5/25 defaults here versus 10/50 in ``beads``)."""
     pipe = Pipeline("read")
     pipe.add_pipe("standardize_format")
     pipe.add_pipe("flatfield_correct", flatfield=flatfield, darkfield=darkfield)
-    pipe.add_pipe("stitch", overlap=overlap, blend=blend)
+    pipe.add_pipe("stitch", overlap=overlap, blend=blend, register=register, max_shift=max_shift,
+                  register_channel=register_channel)
     pipe.add_pipe("find_beads", min_bead_diameter=min_bead_diameter, max_bead_diameter=max_bead_diameter,
                   low_edge_quantile=low_edge_quantile, high_edge_quantile=high_edge_quantile, num_iter=num_iter,
                   min_roundness=min_roundness, roi_length=roi_length, search_channel=search_channel,
@@ -178,16 +188,20 @@ def beads_pipe(flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=5, m
     return pipe
 
 
-def image(data, overlap=102, rotation=0, roi_only=False, drop_tiles=True, blend=None):
+def image(data, overlap=102, rotation=0, roi_only=False, drop_tiles=True, blend=None,
+          register=None, max_shift=8, register_channel=None):
     """registry.py:615-669."""
-    return image_pipe(overlap=overlap, rotation=rotation, roi_only=roi_only, drop_tiles=drop_tiles, blend=blend)(data=data)
+    return image_pipe(overlap=overlap, rotation=rotation, roi_only=roi_only, drop_tiles=drop_tiles, blend=blend,
+                      register=register, max_shift=max_shift, register_channel=register_channel)(data=data)
 
 
-def image_pipe(overlap=102, rotation=0, roi_only=False, drop_tiles=True, blend=None):
+def image_pipe(overlap=102, rotation=0, roi_only=False, drop_tiles=True, blend=None,
+               register=None, max_shift=8, register_channel=None):
     """registry.py:672-693."""
     pipe = Pipeline("read")
     pipe.add_pipe("standardize_format")
-    pipe.add_pipe("stitch", overlap=overlap, blend=blend)
+    pipe.add_pipe("stitch", overlap=overlap, blend=blend, register=register, max_shift=max_shift,
+                  register_channel=register_channel)
     pipe.add_pipe("rotate", rotation=rotation)
     pipe.add_pipe("drop", roi_only=roi_only, drop_tiles=drop_tiles)
     pipe.add_pipe("restore_format")

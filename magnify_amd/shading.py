@@ -55,10 +55,11 @@ class Shading:
 
 
 def apply_stitch(tiles: torch.Tensor, overlap: int, flats: torch.Tensor, darks: torch.Tensor, want_minmax=True,
-                 out: torch.Tensor | None = None, blend=None):
+                 out: torch.Tensor | None = None, blend=None, shifts=None):
     """tiles (C, T, R, Cc, ty, tx) -> image (C, T, R*hy, Cc*hx) with (x - dark[c]) / flat[c] applied, and the
     per-plane min / max (C*T, 2) -- one launch for all channels (flats, darks: (C, ty, tx) float32).
-    ``blend="linear"``: the seams blended as in ``hotpath.flatfield_stitch`` (mg_shading_apply_stitch_blend)."""
+    ``blend="linear"``: the seams blended as in ``hotpath.flatfield_stitch`` (mg_shading_apply_stitch_blend).
+    ``shifts``: per-tile shifts as in ``hotpath.flatfield_stitch`` (mg_shading_apply_stitch_shift)."""
     hotpath.check_blend(blend)
     hotpath.require_gpu()
     c, t, nr, nc, ty, tx = tiles.shape
@@ -75,6 +76,12 @@ def apply_stitch(tiles: torch.Tensor, overlap: int, flats: torch.Tensor, darks: 
     minmax = None
     if want_minmax:
         minmax = hotpath._minmax_init(c * t, tiles.device).clone()
+    if shifts is not None:
+        table = hotpath.shift_tables(shifts, t, nr, nc, overlap, tiles.device)
+        hotpath._call("mg_shading_apply_stitch_shift", tiles.data_ptr(), nat.dtype_code(tiles.dtype), c, t, nr, nc, ty, tx,
+                      overlap, flats.data_ptr(), darks.data_ptr(), image.data_ptr(), hotpath._ptr(minmax),
+                      table.data_ptr(), table.shape[0], t, int(blend is not None), hotpath._stream())
+        return image, minmax
     hotpath._call("mg_shading_apply_stitch" if blend is None else "mg_shading_apply_stitch_blend", tiles.data_ptr(),
                   nat.dtype_code(tiles.dtype), c, t, nr, nc, ty, tx, overlap, flats.data_ptr(), darks.data_ptr(), image.data_ptr(), hotpath._ptr(minmax),
                   hotpath._stream())
