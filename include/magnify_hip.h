@@ -455,9 +455,10 @@ int mg_score_circles(const float* d_angle, const uint32_t* d_edge_bits, const ui
 /* The keyed path's scoring (same scores and same passing set as mg_score_circles input (a), which remains for
  * radii outside mg_score_keyed_supported): two kernels.
  * Prefilter: a workgroup per super-tile of 2 x 4 centre tiles (128 x 256 positions) with the edge window in LDS as one byte per
- * pixel (the gradient-orientation bin of mg_canny_nms' class planes, 0x0C = no edge); a lane per circle, all
- * circles of a wave of one radius, the perimeter walked as straight-line code per radius.  For every pair of
- * opposite perimeter points the two window bytes select, in one byte permute, UPPER BOUNDS of the two pixels'
+ * pixel position (low nibble: the gradient-orientation bin of mg_canny_nms' class planes, 0xC = no edge; high nibble:
+ * the same for the pixel to the right, so one byte read returns two adjacent perimeter points of a row); a lane per
+ * circle, all circles of a wave of one radius, the perimeter walked as straight-line code per radius.  For every pair of
+ * opposite perimeter points the two window nibbles select, in one byte permute, UPPER BOUNDS of the two pixels'
  * terms 4 |d - pi/2| / pi - 1 (utils.py:244-249) from the pair's table (mg_score_pair_table: the distance
  * between the points' radial direction and the pixel's orientation bin bounds the term); the bounds are summed
  * in 1/64 (rounded up) and a circle whose bound is below min_roundness * P - 1e-3 is dropped -- exact: every
@@ -475,6 +476,9 @@ int mg_score_keyed_supported(int min_r, int max_r); /* 1: 2 <= min_r, max_r <= 2
 int mg_score_pair_table(uint64_t* out_entries, int cap);
 /* first point (dr, dc) of every pair of radius r, in table order; returns the number of pairs */
 int mg_score_pairs(int r, int32_t* out_rc, int cap);
+/* LDS byte reads of the prefilter's walk of radius r (two adjacent perimeter points of a row come with one read):
+ * taken from the structure the kernel is instantiated from; 0 for r outside 2..26 */
+int mg_score_walk_reads(int r);
 int mg_score_circles_keyed(const uint8_t* d_blur, const float* d_angle, const uint32_t* d_edge_bits,
                            const uint32_t* d_class_bits, int64_t words_per_plane, int n_planes, int h, int w,
                            int32_t* d_circles, int64_t circle_cap, const uint32_t* d_unique_keys,

@@ -12,8 +12,9 @@
 #define MG_WAVE 64
 
 // Keyed scoring prefilter (mg_score.hip): super-tiles of MG_SCORE_SUBY x MG_SCORE_SUBX centre tiles (128 x 256
-// positions) with their edge window as bytes in LDS, row stride 308 B = 77 dwords (odd: rows rotate through the
-// banks); radii up to MG_SCORE_MAX_R (window 180 x 308), perimeters up to 2 * MG_SCORE_MAX_PAIRS points.
+// positions) with their edge window as bytes in LDS (a pixel's orientation bin | its right neighbour's << 4), row
+// stride 308 B = 77 dwords (odd: rows rotate through the banks); radii up to MG_SCORE_MAX_R (window 180 x 308),
+// perimeters up to 2 * MG_SCORE_MAX_PAIRS points.
 #define MG_SCORE_TILE 64
 #define MG_SCORE_SUBY 2
 #define MG_SCORE_SUBX 4

@@ -4,19 +4,23 @@
 //   k_prefilter  exact rejection of the circles that cannot reach min_roundness -- 99.6 % of them on noisy images.
 //                A (persistent, 768-thread) workgroup owns a super-tile of MG_SCORE_SUBY x MG_SCORE_SUBX = 2 x 4 centre
 //                tiles (128 x 256 positions); its window of the edge map lives in LDS as
-//                ONE BYTE per pixel: the pixel's gradient-orientation bin (eighths of pi, decided exactly on the
-//                integer gradient by mg_canny_nms) or 0x0C for "no edge".  A lane owns a circle; all 64 circles of
-//                a wave have the SAME radius (the keys of a tile are sorted by radius: the block cuts the eight key
-//                lists at the radius boundaries and deals 64-circle chunks of one radius to its waves), so the
-//                perimeter walk is straight-line code per radius (template <R>, the midpoint circle evaluated at
-//                compile time): the offset of a perimeter point is the immediate of its ds_read_u8 and the bound
-//                table of the point sits in scalar registers.  Opposite points (p, -p) have the same radial
-//                direction mod pi and share a table: their two bytes form the selector of ONE v_perm_b32, which
-//                looks both up in the 8 signed bytes of the table (0x0C selects the constant 0), and one
-//                v_dot4_i32_i8 adds both to the lane's sum.  A table byte is an upper bound, in 1/64, of the term
-//                a pixel of that bin can contribute to the reference's sum; a circle whose bounds add up to less
-//                than min_roundness * P cannot pass (every term <= its bound) and is dropped.  Survivors are
-//                appended to a per-plane list.  Bounding roofline: LDS (one byte read per perimeter point).
+//                ONE BYTE per pixel position: the low nibble is the pixel's gradient-orientation bin (eighths of pi,
+//                decided exactly on the integer gradient by mg_canny_nms) or 0xC for "no edge", the high nibble the
+//                same for the pixel to its RIGHT (0xC beyond the window's last column or the image).  A lane owns a
+//                circle; all 64 circles of a wave have the SAME radius (the keys of a tile are sorted by radius: the
+//                block cuts the eight key lists at the radius boundaries and deals 64-circle chunks of one radius to
+//                its waves), so the perimeter walk is straight-line code per radius (template <R>, the midpoint
+//                circle evaluated at compile time and matched into read groups, Walk<R>): the offset of a read is the
+//                immediate of its ds_read_u8 and the bound tables sit in scalar registers.  Two horizontally adjacent
+//                perimeter points come with ONE byte read, at any start column: the horizontal runs of the perimeter
+//                cost ceil(L / 2) reads, 15-23 % fewer reads per radius.  Opposite points (p, -p) have the same radial
+//                direction mod pi and share a table: the nibbles of a byte and of the byte at the mirrored position
+//                form the selector of a v_perm_b32 per table, which looks them up in the 8 signed bytes of the table
+//                (0x0C selects the constant 0), and a v_dot4_i32_i8 per table adds the two it owns to the lane's sum.
+//                A table byte is an upper bound, in 1/64, of the term a pixel of that bin can contribute to the
+//                reference's sum; a circle whose bounds add up to less than min_roundness * P cannot pass (every
+//                term <= its bound) and is dropped.  Survivors are appended to a per-plane list.  Bounding roofline:
+//                LDS (mg_score_walk_reads(r) byte reads per circle).
 //   k_exact      the survivors' reference sum (float64, sequential in perimeter order) in workgroup-level phases over
 //                XS = 64 (16 at small batches) survivors: NT / XS lanes per survivor find the edge pixels on its
 //                perimeter, a lane lists them in order, all lanes evaluate (survivor, hit) terms -- gradient angles
@@ -32,7 +36,7 @@
 namespace {
 
 constexpr int NT = 256;
-constexpr int NP = 768;  // prefilter block: 8 waves share a window (4 blocks per CU by LDS: 32 waves per CU)
+constexpr int NP = 768;  // prefilter block: 12 waves share a window (2 blocks per CU by LDS, up to 63.6 KB each: 24 waves per CU)
 constexpr int TS = MG_SCORE_TILE;
 constexpr int SUBY = MG_SCORE_SUBY, SUBX = MG_SCORE_SUBX, NSUB = SUBY * SUBX;  // centre tiles per super-tile
 constexpr int STY = SUBY * TS, STX = SUBX * TS;
@@ -80,11 +84,69 @@ struct Pairs {
   }
 };
 
+// Read groups of the walk of radius R.  A window byte holds its own pixel's bin in the low nibble and the right
+// neighbour's in the high one, so ONE byte read returns two horizontally adjacent perimeter points.  The 2 * P.n points
+// (the first points of Pairs<R> and their opposites) are matched row by row: the rows above the centre are cut into
+// maximal runs of consecutive columns and a run is paired from its left end; the mirrored run (row -dr) is thereby
+// paired from its right end, and the opposite of every pair is a pair.  A group is
+//   a quad    the points (dr, dc), (dr, dc + 1) and their opposites: byte reads at (dr, dc) and (-dr, -dc - 1);
+//   a single  what a run of odd length leaves over, and (0, -R): the point and its opposite, a byte read each.
+// A run may mix first points and opposites (the top run through (-R, 0)): every point carries the index of its pair
+// for the bound table.
+template <int R>
+struct Walk {
+  int n;                   // groups: two byte reads each
+  int off[MAXP];           // dr * WSTR + dc of the group's (left) point
+  int k1[MAXP], k2[MAXP];  // pair index of the left point; of its right neighbour, -1 in a single
+  int pts[MAXP];           // perimeter points added up to and including the group
+  constexpr Walk() : n(0), off{}, k1{}, k2{}, pts{} {
+    const Pairs<R> P{};
+    for (int row = -R; row <= 0; ++row) {
+      int at[2 * R + 2] = {};  // pair index + 1 of the perimeter point in column c - R of this row
+      for (int k = 0; k < P.n; ++k)
+        for (int sg = -1; sg <= 1; sg += 2) {
+          const int dr = sg * P.dr[k], dc = sg * P.dc[k];
+          if (dr == row && (row < 0 || dc < 0)) at[dc + R] = k + 1;
+        }
+      for (int c = 0; c <= 2 * R;) {
+        if (!at[c]) {
+          ++c;
+          continue;
+        }
+        const bool quad = at[c + 1] != 0;
+        off[n] = row * WSTR + (c - R);
+        k1[n] = at[c] - 1;
+        k2[n] = quad ? at[c + 1] - 1 : -1;
+        ++n;
+        c += quad ? 2 : 1;
+      }
+    }
+    // in the order of the tables (a quad: of its lower index), which the scalar loads then fetch in blocks
+    for (int i = 1; i < n; ++i)
+      for (int j = i; j > 0 && key(j) < key(j - 1); --j) {
+        swap(off[j], off[j - 1]);
+        swap(k1[j], k1[j - 1]);
+        swap(k2[j], k2[j - 1]);
+      }
+    for (int g = 0; g < n; ++g) pts[g] = (g ? pts[g - 1] : 0) + (k2[g] >= 0 ? 4 : 2);
+  }
+  constexpr int key(int g) const { return k2[g] >= 0 && k2[g] < k1[g] ? k2[g] : k1[g]; }
+  static constexpr void swap(int& a, int& b) {
+    const int t = a;
+    a = b;
+    b = t;
+  }
+};
+
 typedef unsigned short us2 __attribute__((ext_vector_type(2)));
 
 // Sum of the bounds over the perimeter of the circle whose centre byte sits at lds[vaddr + BIAS].
+// Per group the two bytes A (at the left point, low half) and B (at the mirrored left point, high half) are split
+// into the nibbles [A.lo, A.hi, B.lo, B.hi] = the selector of a v_perm_b32 per table: A.lo and B.hi are the left
+// point and its opposite (table k1), A.hi and B.lo the right point and its opposite (table k2); a v_dot4 per table
+// adds the two bounds it owns.  A single masks the high nibbles (pixels that are not on the perimeter) away.
 // `need`: what the sum has to reach (wave-uniform: a wave's circles share the radius).  A bound is at most 64 per
-// point, so after k of n pairs a circle with sum + 128 (n - k) < need cannot reach it whatever the rest holds; when
+// point, so a circle with sum + 64 (points not yet added) < need cannot reach it whatever the rest holds; when
 // that is true of ALL 64 circles of the wave -- four checks in the last quarter of the walk: a wave of noise circles
 // (81 % of the waves hold no survivor) is out at ~85 % of its perimeter -- the rest is not read.  The sums returned
 // then are below `need` like the full ones would be: the same circles are dropped.
@@ -92,20 +154,30 @@ template <int R>
 __device__ __forceinline__ int score_r(const uint8_t* lds, int vaddr, const uint2* __restrict__ tabs, int need = -(1 << 30),
                                        bool valid = true) {
   constexpr Pairs<R> P{};
+  constexpr Walk<R> W{};
   static_assert(P.n <= MAXP, "perimeter too long");
+  static_assert(W.pts[W.n - 1] == 2 * P.n, "the perimeter points are distinct and every one is in a group");
   int sum = 0;
 #pragma unroll
-  for (int k = 0; k < P.n; ++k) {
-    const uint2 t = tabs[R * MAXP + k];  // uniform address: scalar loads
-    const int off = P.dr[k] * WSTR + P.dc[k];
+  for (int g = 0; g < W.n; ++g) {
+    const bool quad = W.k2[g] >= 0;
     us2 s;
-    s.x = lds[vaddr + (BIAS + off)];
-    s.y = lds[vaddr + (BIAS - off)];
-    const uint32_t q = __builtin_amdgcn_perm(t.y, t.x, __builtin_bit_cast(uint32_t, s));  // bytes 0 and 2: the two bounds
-    sum = __builtin_amdgcn_sdot4((int)q, 0x00010001, sum, false);
-    const int done = k + 1;
-    if (P.n >= 16 && done < P.n && (done == (P.n * 12) / 16 || done == (P.n * 13) / 16 || done == (P.n * 14) / 16 || done == (P.n * 15) / 16)) {
-      if (__ballot(valid && sum + 128 * (P.n - done) >= need) == 0) return sum;
+    s.x = lds[vaddr + (BIAS + W.off[g])];
+    s.y = lds[vaddr + (BIAS - W.off[g] - (quad ? 1 : 0))];
+    const uint32_t v = __builtin_bit_cast(uint32_t, s);
+    const uint2 t1 = tabs[R * MAXP + W.k1[g]];  // uniform address: scalar loads
+    if (quad) {
+      const uint2 t2 = tabs[R * MAXP + W.k2[g]];
+      const uint32_t sel = (v | (v << 4)) & 0x0F0F0F0Fu;
+      sum = __builtin_amdgcn_sdot4((int)__builtin_amdgcn_perm(t1.y, t1.x, sel), 0x01000001, sum, false);
+      sum = __builtin_amdgcn_sdot4((int)__builtin_amdgcn_perm(t2.y, t2.x, sel), 0x00010100, sum, false);
+    } else {
+      const uint32_t q = __builtin_amdgcn_perm(t1.y, t1.x, v & 0x000F000Fu);  // bytes 0 and 2: the two bounds
+      sum = __builtin_amdgcn_sdot4((int)q, 0x00010001, sum, false);
+    }
+    const int done = g + 1;
+    if (P.n >= 16 && done < W.n && (done == (W.n * 12) / 16 || done == (W.n * 13) / 16 || done == (W.n * 14) / 16 || done == (W.n * 15) / 16)) {
+      if (__ballot(valid && sum + 64 * (2 * P.n - W.pts[g]) >= need) == 0) return sum;
     }
   }
   return sum;
@@ -176,7 +248,7 @@ __global__ __launch_bounds__(NP) void k_prefilter(const uint32_t* __restrict__ d
         const int i = threadIdx.x + it * NP;
         const int j = i / wgroups, k = i - j * wgroups;
         const int y = wy0 + j, xs = wx0 + 32 * k;
-        const int x_lo = max(xs, 0), x_hi = min(min(xs + 32, wx0 + side_x), w);
+        const int x_lo = max(xs, 0), x_hi = min(min(xs + 33, wx0 + side_x), w);  // (33: the last pixel's right neighbour)
         const bool live = i < side_y * wgroups && y >= 0 && y < h && x_lo < x_hi;
         const int64_t wi = live ? ((int64_t)y * w + x_lo) >> 5 : 0;
 #pragma unroll
@@ -191,24 +263,37 @@ __global__ __launch_bounds__(NP) void k_prefilter(const uint32_t* __restrict__ d
         if (i >= side_y * wgroups) break;
         const int j = i / wgroups, k = i - j * wgroups;
         const int y = wy0 + j, xs = wx0 + 32 * k;
-        const int x_lo = max(xs, 0), x_hi = min(min(xs + 32, wx0 + side_x), w);
-        uint32_t pv[4] = {0u, 0u, 0u, 0u};  // edge bit, c0, c1, c2 of the group's 32 pixels
+        const int x_lo = max(xs, 0), x_hi = min(min(xs + 33, wx0 + side_x), w);
+        // edge bit, c0, c1, c2 of the group's 32 pixels and (nb) of the pixel to their right: a pixel beyond the
+        // window's last column or outside the image is "no edge" as a neighbour too
+        uint32_t pv[4] = {0u, 0u, 0u, 0u}, nb[4] = {0u, 0u, 0u, 0u};
         if (y >= 0 && y < h && x_lo < x_hi) {
-          const int sh = (int)(((int64_t)y * w + x_lo) & 31), n = x_hi - x_lo;
-          const uint32_t keep = n >= 32 ? 0xFFFFFFFFu : ((1u << n) - 1u);
+          const int sh = (int)(((int64_t)y * w + x_lo) & 31), n = x_hi - x_lo;  // 1 <= n <= 33
+          const uint64_t keep = (1ull << n) - 1ull;
 #pragma unroll
-          for (int c = 0; c < 4; ++c)
-            pv[c] = ((uint32_t)(((((uint64_t)hi[it][c]) << 32) | lo[it][c]) >> sh) & keep) << (x_lo - xs);
+          for (int c = 0; c < 4; ++c) {
+            const uint64_t v = ((((((uint64_t)hi[it][c]) << 32) | lo[it][c]) >> sh) & keep) << (x_lo - xs);
+            pv[c] = (uint32_t)v;
+            nb[c] = (uint32_t)(v >> 32);
+          }
         }
         uint32_t* rowp = reinterpret_cast<uint32_t*>(win + j * WSTR) + 8 * k;
         const int nd = min(8, (WSTR >> 2) - 8 * k);  // dwords of this group inside the row
+        // four pixels -> four bytes: bin = 4 c1 + 2 c0 + c2 where the pixel is an edge, else 0x0C
+        auto bins4 = [](uint32_t e, uint32_t c0, uint32_t c1, uint32_t c2) -> uint32_t {
+          const uint32_t m = spread4(e) * 0xFFu;
+          return ((4u * spread4(c1) + 2u * spread4(c0) + spread4(c2)) & m) | (0x0C0C0C0Cu & ~m);
+        };
+        uint32_t own = bins4(pv[0], pv[1], pv[2], pv[3]);
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
           if (q >= nd) break;
-          // four pixels -> four bytes: bin = 4 c1 + 2 c0 + c2 where the pixel is an edge, else 0x0C
-          const uint32_t bins = 4u * spread4(pv[2] >> (4 * q)) + 2u * spread4(pv[1] >> (4 * q)) + spread4(pv[3] >> (4 * q));
-          const uint32_t m = spread4(pv[0] >> (4 * q)) * 0xFFu;
-          rowp[q] = (bins & m) | (0x0C0C0C0Cu & ~m);
+          // (dword 8: only its first byte, the neighbour pixel, is used)
+          const uint32_t nxt = q < 7 ? bins4(pv[0] >> (4 * q + 4), pv[1] >> (4 * q + 4), pv[2] >> (4 * q + 4), pv[3] >> (4 * q + 4))
+                                     : bins4(nb[0], nb[1], nb[2], nb[3]);
+          // byte = own bin | right neighbour's bin << 4 (bins are <= 0x0C: nothing crosses a byte)
+          rowp[q] = own | (__builtin_amdgcn_alignbyte(nxt, own, 1) << 4);
+          own = nxt;
         }
       }
     }
@@ -474,6 +559,17 @@ __global__ __launch_bounds__(NT) void k_exact(const uint8_t* __restrict__ d_blur
 }
 
 }  // namespace
+
+extern "C" int mg_score_walk_reads(int r) {
+  switch (r) {
+#define MG_CASE(R) case R: return 2 * Walk<R>{}.n;
+    MG_CASE(2) MG_CASE(3) MG_CASE(4) MG_CASE(5) MG_CASE(6) MG_CASE(7) MG_CASE(8) MG_CASE(9) MG_CASE(10)
+    MG_CASE(11) MG_CASE(12) MG_CASE(13) MG_CASE(14) MG_CASE(15) MG_CASE(16) MG_CASE(17) MG_CASE(18)
+    MG_CASE(19) MG_CASE(20) MG_CASE(21) MG_CASE(22) MG_CASE(23) MG_CASE(24) MG_CASE(25) MG_CASE(26)
+#undef MG_CASE
+    default: return 0;
+  }
+}
 
 extern "C" int mg_score_keyed_supported(int min_r, int max_r) {
   return (min_r >= 2 && max_r >= min_r && max_r <= MG_SCORE_MAX_R && max_r - min_r + 1 <= 32) ? 1 : 0;

@@ -11,7 +11,9 @@ extern "C" int mg_dedup_layout(int, int, int, int, int*, int*, int64_t*, int64_t
 template <int R>
 __global__ __launch_bounds__(512) void kb(const int* __restrict__ centres, const uint2* __restrict__ tabs, int n_iter, int* out) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-  for (int i = threadIdx.x; i < 8192 + 180 * 180; i += 512) lds[i] = (uint8_t)((i * 7) % 13 > 8 ? (i & 7) : 0x0C);
+  // the window's encoding: a pixel's bin (0x0C: no edge) | its right neighbour's << 4
+  auto bin = [](int i) { return (i * 7) % 13 > 8 ? (i & 7) : 0x0C; };
+  for (int i = threadIdx.x; i < WBASE + 180 * WSTR; i += 512) lds[i] = (uint8_t)(bin(i) | bin(i + 1) << 4);
   __syncthreads();
   int c = centres[blockIdx.x * 512 + threadIdx.x];
   int acc = 0;
@@ -57,14 +59,15 @@ int main() {
     float ms = 0;
     for (int rep = 0; rep < 2; ++rep) {
       hipEventRecord(e0);
-      hipLaunchKernelGGL(kb<14>, dim3(blocks), dim3(512), 8192 + 180 * 180, 0, d_c, d_tabs, n_iter, d_out);
+      hipLaunchKernelGGL(kb<14>, dim3(blocks), dim3(512), WBASE + 180 * WSTR, 0, d_c, d_tabs, n_iter, d_out);
       hipEventRecord(e1);
       hipEventSynchronize(e1);
       hipEventElapsedTime(&ms, e0, e1);
     }
-    const double wave_reads = (double)blocks * 8 * n_iter * 80;  // r = 14: 80 points
-    printf("%-60s %.3f ms, %.2f ns per wave-read per CU (%.1f cycles at 2.4 GHz)\n", names[pat], ms, ms * 1e6 / (wave_reads / 256),
-           ms * 1e6 / (wave_reads / 256) * 2.4);
+    const int reads = mg_score_walk_reads(14);  // r = 14: 80 points
+    const double waves = (double)blocks * 8 * n_iter;  // 64 circles each, over 256 CUs
+    printf("%-60s %.3f ms, %.0f cycles per 64 circles per CU, %d reads: %.1f cycles per wave-read (2.4 GHz)\n", names[pat], ms,
+           ms * 1e6 / (waves / 256) * 2.4, reads, ms * 1e6 / (waves * reads / 256) * 2.4);
   }
   return 0;
 }

@@ -16,7 +16,8 @@ extern "C" int mg_dedup_layout(int, int, int, int, int*, int*, int64_t*, int64_t
 template <int R>
 __global__ __launch_bounds__(512) void kb(const int* __restrict__ centres, const uint2* __restrict__ tabs, int n_iter, int* out) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-  for (int i = threadIdx.x; i < WBASE + 180 * WSTR; i += 512) lds[i] = (uint8_t)((i * 7) % 13 > 8 ? (i & 7) : 0x0C);
+  auto bin = [](int i) { return (i * 7) % 13 > 8 ? (i & 7) : 0x0C; };  // own bin | right neighbour's << 4
+  for (int i = threadIdx.x; i < WBASE + 180 * WSTR; i += 512) lds[i] = (uint8_t)(bin(i) | bin(i + 1) << 4);
   __syncthreads();
   int c[4];
   for (int q = 0; q < 4; ++q) c[q] = centres[(blockIdx.x * 512 + threadIdx.x) * 4 + q];
@@ -69,7 +70,7 @@ int main() {
       hipEventSynchronize(e1);
       hipEventElapsedTime(&ms, e0, e1);
     }
-    const double wave_reads = (double)blocks * 8 * n_iter * 4 * 80;  // r = 14: 80 points
+    const double wave_reads = (double)blocks * 8 * n_iter * 4 * mg_score_walk_reads(14);  // r = 14: 80 points
     printf("%-48s %.3f ms, %.2f ns per wave-read per CU (%.1f cycles at 2.4 GHz)\n", names[pat], ms, ms * 1e6 / (wave_reads / 256),
            ms * 1e6 / (wave_reads / 256) * 2.4);
   }

@@ -22,7 +22,6 @@ STEPS=3
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $RAW/fetch -- python3 $ROOT/bench.py --steps $STEPS --warmup 1 --full --no-cpu > /dev/null 2> $OUT/${TAG}_pmc_fetch.log
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $RAW/write -- python3 $ROOT/bench.py --steps $STEPS --warmup 1 --full --no-cpu > /dev/null 2> $OUT/${TAG}_pmc_write.log
 echo pmc done
-rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES --kernel-trace --output-format csv -d $RAW/sq -- python3 $ROOT/bench.py --steps 2 --warmup 1 --full --no-cpu > /dev/null 2> $OUT/${TAG}_sq.log || \
 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES --output-format csv -d $RAW/sq -- python3 $ROOT/bench.py --steps 2 --warmup 1 --full --no-cpu > /dev/null 2> $OUT/${TAG}_sq.log
 echo sq done
 cd $ROOT

@@ -22,6 +22,11 @@ print("circles per radius (plane 0):", cnt.sum(axis=0).tolist())
 print("perimeter lengths:", per.tolist())
 tot = cnt.sum()
 print("weighted mean perimeter:", float((cnt.sum(axis=0) * per).sum() / tot))
+# LDS byte reads of the prefilter's walk per radius (two adjacent points of a row come with one read) against points
+reads = np.array([nat.lib().mg_score_walk_reads(r) for r in range(f.min_r, f.max_r + 1)])
+print("walk reads per radius:", reads.tolist())
+print("expected LDS reads / perimeter points, weighted with the circles per radius:",
+      float((cnt.sum(axis=0) * reads).sum() / (cnt.sum(axis=0) * per).sum()))
 c4 = cnt.reshape(ntr, ntc, -1)
 for name, (a, b) in {"64x64": (1, 1), "128x128": (2, 2), "128x256": (2, 4), "256x256": (4, 4)}.items():
     pr, pc = (-ntr) % a, (-ntc) % b
