@@ -7,9 +7,11 @@
 //                ONE BYTE per pixel position: the low nibble is the pixel's gradient-orientation bin (eighths of pi,
 //                decided exactly on the integer gradient by mg_canny_nms) or 0xC for "no edge", the high nibble the
 //                same for the pixel to its RIGHT (0xC beyond the window's last column or the image).  A lane owns a
-//                circle; all 64 circles of a wave have the SAME radius (the keys of a tile are sorted by radius: the
-//                block cuts the eight key lists at the radius boundaries and deals 64-circle chunks of one radius to
-//                its waves), so the perimeter walk is straight-line code per radius (template <R>, the midpoint
+//                circle, or two; all circles of a wave have the SAME radius (the keys of a tile are sorted by radius:
+//                the block cuts the eight key lists at the radius boundaries and deals tickets of one radius to its
+//                waves: 128 consecutive positions, two circles per lane walked together, while a radius has 128 left,
+//                then chunks of up to 64; a position finds its key through a per-radius prefix table of the eight
+//                sub-tiles, `locate`), so the perimeter walk is straight-line code per radius (template <R>, the midpoint
 //                circle evaluated at compile time and matched into read groups, Walk<R>): the offset of a read is the
 //                immediate of its ds_read_u8 and the bound tables sit in scalar registers.  Two horizontally adjacent
 //                perimeter points come with ONE byte read, at any start column: the horizontal runs of the perimeter
@@ -140,46 +142,67 @@ struct Walk {
 
 typedef unsigned short us2 __attribute__((ext_vector_type(2)));
 
-// Sum of the bounds over the perimeter of the circle whose centre byte sits at lds[vaddr + BIAS].
+// Sum of the bounds over the perimeter of the circle whose centre byte sits at lds[va + BIAS]; with TWO, also of a
+// second circle of the same radius at vb: the two walks share the scalar table loads and the v_mov that brings a
+// table half to the v_perm (one SGPR operand per VOP3), and their LDS reads overlap.
 // Per group the two bytes A (at the left point, low half) and B (at the mirrored left point, high half) are split
 // into the nibbles [A.lo, A.hi, B.lo, B.hi] = the selector of a v_perm_b32 per table: A.lo and B.hi are the left
 // point and its opposite (table k1), A.hi and B.lo the right point and its opposite (table k2); a v_dot4 per table
 // adds the two bounds it owns.  A single masks the high nibbles (pixels that are not on the perimeter) away.
 // `need`: what the sum has to reach (wave-uniform: a wave's circles share the radius).  A bound is at most 64 per
 // point, so a circle with sum + 64 (points not yet added) < need cannot reach it whatever the rest holds; when
-// that is true of ALL 64 circles of the wave -- four checks in the last quarter of the walk: a wave of noise circles
+// that is true of ALL circles of the wave (both of a lane) -- four checks in the last quarter of the walk: a wave of noise circles
 // (81 % of the waves hold no survivor) is out at ~85 % of its perimeter -- the rest is not read.  The sums returned
 // then are below `need` like the full ones would be: the same circles are dropped.
-template <int R>
-__device__ __forceinline__ int score_r(const uint8_t* lds, int vaddr, const uint2* __restrict__ tabs, int need = -(1 << 30),
-                                       bool valid = true) {
+template <int R, bool TWO>
+__device__ __forceinline__ void score_walk(const uint8_t* lds, int va, int vb, const uint2* __restrict__ tabs, int need, bool valid,
+                                           int& sum_a, int& sum_b) {
   constexpr Pairs<R> P{};
   constexpr Walk<R> W{};
   static_assert(P.n <= MAXP, "perimeter too long");
   static_assert(W.pts[W.n - 1] == 2 * P.n, "the perimeter points are distinct and every one is in a group");
-  int sum = 0;
-#pragma unroll
-  for (int g = 0; g < W.n; ++g) {
+  // one group of one circle: two byte reads, the selector, a perm and a dot4 per table
+  auto add = [&](int vaddr, int g, const uint2 t1, const uint2 t2, int sum) -> int {
     const bool quad = W.k2[g] >= 0;
     us2 s;
     s.x = lds[vaddr + (BIAS + W.off[g])];
     s.y = lds[vaddr + (BIAS - W.off[g] - (quad ? 1 : 0))];
     const uint32_t v = __builtin_bit_cast(uint32_t, s);
-    const uint2 t1 = tabs[R * MAXP + W.k1[g]];  // uniform address: scalar loads
     if (quad) {
-      const uint2 t2 = tabs[R * MAXP + W.k2[g]];
       const uint32_t sel = (v | (v << 4)) & 0x0F0F0F0Fu;
       sum = __builtin_amdgcn_sdot4((int)__builtin_amdgcn_perm(t1.y, t1.x, sel), 0x01000001, sum, false);
-      sum = __builtin_amdgcn_sdot4((int)__builtin_amdgcn_perm(t2.y, t2.x, sel), 0x00010100, sum, false);
-    } else {
-      const uint32_t q = __builtin_amdgcn_perm(t1.y, t1.x, v & 0x000F000Fu);  // bytes 0 and 2: the two bounds
-      sum = __builtin_amdgcn_sdot4((int)q, 0x00010001, sum, false);
+      return __builtin_amdgcn_sdot4((int)__builtin_amdgcn_perm(t2.y, t2.x, sel), 0x00010100, sum, false);
     }
+    const uint32_t q = __builtin_amdgcn_perm(t1.y, t1.x, v & 0x000F000Fu);  // bytes 0 and 2: the two bounds
+    return __builtin_amdgcn_sdot4((int)q, 0x00010001, sum, false);
+  };
+  int sa = 0, sb = 0;
+#pragma unroll
+  for (int g = 0; g < W.n; ++g) {
+    const uint2 t1 = tabs[R * MAXP + W.k1[g]];  // uniform address: scalar loads
+    const uint2 t2 = tabs[R * MAXP + (W.k2[g] >= 0 ? W.k2[g] : W.k1[g])];
+    sa = add(va, g, t1, t2, sa);
+    if (TWO) sb = add(vb, g, t1, t2, sb);
     const int done = g + 1;
     if (P.n >= 16 && done < W.n && (done == (W.n * 12) / 16 || done == (W.n * 13) / 16 || done == (W.n * 14) / 16 || done == (W.n * 15) / 16)) {
-      if (__ballot(valid && sum + 64 * (2 * P.n - W.pts[g]) >= need) == 0) return sum;
+      const int rest = 64 * (2 * P.n - W.pts[g]);
+      if (__ballot((valid && sa + rest >= need) || (TWO && sb + rest >= need)) == 0) {
+        sum_a = sa;
+        sum_b = sb;
+        return;
+      }
     }
   }
+  sum_a = sa;
+  sum_b = sb;
+}
+
+// (one circle per lane, no early exit: the form the micro-benchmarks of the walk use)
+template <int R>
+__device__ __forceinline__ int score_r(const uint8_t* lds, int vaddr, const uint2* __restrict__ tabs, int need = -(1 << 30),
+                                       bool valid = true) {
+  int sum, unused;
+  score_walk<R, false>(lds, vaddr, vaddr, tabs, need, valid, sum, unused);
   return sum;
 }
 
@@ -188,13 +211,37 @@ __device__ __forceinline__ int score_r(const uint8_t* lds, int vaddr, const uint
 // Survivors are collected per super-tile in LDS and appended to the plane's list with ONE global atomic: a returning
 // atomic per wave-with-survivors (~9 000 per plane, all on one address, while only one or two planes are being
 // worked on at any time) cost as much as the perimeter walks of a single plane.
-constexpr int SURV_OFF = 2048, SURV_LDS = (WBASE - SURV_OFF) / 8;
-static_assert((NSUB * SEGW + SEGW + 32 + 8) * 4 <= SURV_OFF, "small tables");
+constexpr int MAP_OFF = (NSUB * SEGW + SEGW + 32 + 3) * 4, MAP_BYTES = 32 * 4 * 16;
+constexpr int SURV_OFF = 3584, SURV_LDS = (WBASE - SURV_OFF) / 8;
+static_assert(MAP_OFF % 16 == 0 && MAP_OFF + MAP_BYTES <= SURV_OFF && NSUB == 8, "small tables");
+
+// Position -> key of one radius in a super-tile.  The circles of radius rho are the concatenation of the eight
+// sub-tiles' segments of the sorted key lists; map[rho] holds, as four int4 a wave reads with four broadcast
+// ds_read_b128, {count, pre[1..7]} (pre[s]: positions before sub-tile s; pre[0] = 0 gives its slot to the count)
+// and {first key of segment s - pre[s]}.  Position m lies in the LAST sub-tile with pre[s] <= m (an empty sub-tile
+// shares its successor's pre and is never the last): seven compare-selects give the key's index m + dlt[s] and the
+// window offset of the sub-tile's corner.
+struct KeyAt {
+  int i, wo;
+};
+__device__ __forceinline__ KeyAt locate(int m, const int4 p0, const int4 p1, const int4 d0, const int4 d1) {
+  int d = d0.x, wo = 0;
+#define MG_STEP(P, D, S)                                    \
+  {                                                         \
+    const bool c = m >= (P);                                \
+    d = c ? (D) : d;                                        \
+    wo = c ? ((S) / SUBX) * TS * WSTR + ((S) % SUBX) * TS : wo; \
+  }
+  MG_STEP(p0.y, d0.y, 1) MG_STEP(p0.z, d0.z, 2) MG_STEP(p0.w, d0.w, 3) MG_STEP(p1.x, d1.x, 4)
+  MG_STEP(p1.y, d1.y, 5) MG_STEP(p1.z, d1.z, 6) MG_STEP(p1.w, d1.w, 7)
+#undef MG_STEP
+  return {m + d, wo};
+}
 
 // bits 0..3 of x -> bit 0 of bytes 0..3
 __device__ __forceinline__ uint32_t spread4(uint32_t x) { return ((x & 0xFu) * 0x00204081u) & 0x01010101u; }
 
-__global__ __launch_bounds__(NP) void k_prefilter(const uint32_t* __restrict__ d_bits, const uint32_t* __restrict__ d_class,
+__global__ __launch_bounds__(NP) __attribute__((amdgpu_waves_per_eu(6))) void k_prefilter(const uint32_t* __restrict__ d_bits, const uint32_t* __restrict__ d_class,
                                                   int64_t words_per_plane, int h, int w,
                                                   const uint32_t* __restrict__ d_ukeys, int64_t circle_cap,
                                                   const int32_t* __restrict__ d_layer_starts, int n_tiles, int ntr, int ntc,
@@ -206,11 +253,12 @@ __global__ __launch_bounds__(NP) void k_prefilter(const uint32_t* __restrict__ d
                                                   int32_t* __restrict__ d_num_surv) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   int32_t* seg = reinterpret_cast<int32_t*>(lds);  // [NSUB][SEGW]: index of the first key of radius rho in sub-tile s
-  int32_t* chunk0 = seg + NSUB * SEGW;             // [nr + 1]: first chunk of radius rho
+  int32_t* chunk0 = seg + NSUB * SEGW;             // [nr + 1]: first ticket of radius rho
   int32_t* need = chunk0 + SEGW;                   // [nr]: threshold on the sum of bounds (1/64)
-  int32_t* next = need + 32;                       // the block's chunk counter
+  int32_t* next = need + 32;                       // the block's ticket counter
   int32_t* n_held = next + 1;                      // survivors of this super-tile held in LDS (may count past SURV_LDS)
   int32_t* g_base = next + 2;                      // where they go in the plane's list
+  int4* map = reinterpret_cast<int4*>(lds + MAP_OFF);    // [nr][4]: position -> key of radius rho (locate)
   int2* held = reinterpret_cast<int2*>(lds + SURV_OFF);  // [SURV_LDS] (index in the key list, key)
   uint8_t* win = lds + WBASE;
   const int side_y = STY + 2 * max_r, side_x = STX + 2 * max_r;
@@ -220,17 +268,21 @@ __global__ __launch_bounds__(NP) void k_prefilter(const uint32_t* __restrict__ d
     // a circle can only pass with sum(terms) >= mg_score_floor, and sum(terms) <= sum(bounds) / 64
     need[i] = (int)ceil(64.0 * mg_score_floor(min_roundness, len));
   }
-  const int wgroups = (side_x + 31) >> 5;  // 32-pixel groups per window row
+  const int wgroups_all = (side_x + 31) >> 5;  // 32-pixel groups per window row
   for (int64_t st = blockIdx.x; st < total_st; st += gridDim.x) {
     const int plane = (int)(st / n_st), sidx = (int)(st - (int64_t)plane * n_st);
     const int sr = sidx / nsc, sc = sidx - sr * nsc;
     __syncthreads();  // the previous super-tile's window and tables are no longer read
+    // (opaque: what a thread derives from its index for the tables and the window -- rows, columns, addresses -- is
+    // worked out again for every super-tile instead of being kept in ~20 registers through the walks, which need them)
+    int tid = threadIdx.x, wgroups = wgroups_all, nr1 = nr + 1;
+    asm volatile("" : "+v"(tid), "+s"(wgroups), "+s"(nr1));
     // ---- segment table: first key of every radius in the sub-tiles' sorted lists (mg_keys_to_circles) ----
-    if ((int)threadIdx.x < NSUB * (nr + 1)) {
-      const int s = threadIdx.x / (nr + 1), q = threadIdx.x - s * (nr + 1);
+    if (tid < NSUB * nr1) {
+      const int s = tid / nr1, q = tid - s * nr1;
       const int tr = SUBY * sr + s / SUBX, tc = SUBX * sc + s % SUBX;
       int v = 0;
-      if (tr < ntr && tc < ntc) v = d_layer_starts[((int64_t)plane * n_tiles + tr * ntc + tc) * (nr + 1) + q];
+      if (tr < ntr && tc < ntc) v = d_layer_starts[((int64_t)plane * n_tiles + tr * ntc + tc) * nr1 + q];
       seg[s * SEGW + q] = v;  // a sub-tile beyond the grid: all zero = empty
     }
     if (threadIdx.x == 0) *next = 0, *n_held = 0;
@@ -245,7 +297,7 @@ __global__ __launch_bounds__(NP) void k_prefilter(const uint32_t* __restrict__ d
       uint32_t lo[WI][4], hi[WI][4];
 #pragma unroll
       for (int it = 0; it < WI; ++it) {
-        const int i = threadIdx.x + it * NP;
+        const int i = tid + it * NP;
         const int j = i / wgroups, k = i - j * wgroups;
         const int y = wy0 + j, xs = wx0 + 32 * k;
         const int x_lo = max(xs, 0), x_hi = min(min(xs + 33, wx0 + side_x), w);  // (33: the last pixel's right neighbour)
@@ -259,7 +311,7 @@ __global__ __launch_bounds__(NP) void k_prefilter(const uint32_t* __restrict__ d
       }
 #pragma unroll
       for (int it = 0; it < WI; ++it) {
-        const int i = threadIdx.x + it * NP;
+        const int i = tid + it * NP;
         if (i >= side_y * wgroups) break;
         const int j = i / wgroups, k = i - j * wgroups;
         const int y = wy0 + j, xs = wx0 + 32 * k;
@@ -299,69 +351,62 @@ __global__ __launch_bounds__(NP) void k_prefilter(const uint32_t* __restrict__ d
     }
     const uint32_t* ukeys = d_ukeys + (int64_t)plane * circle_cap;
     __syncthreads();
-    if (wave == 0) {  // chunks of 64 circles per radius
+    if (wave == 0) {  // the radii's position maps and tickets: 128 circles each while 128 are left, then 64 (or fewer)
       int cnt = 0;
-      if (lane < nr)
-        for (int s = 0; s < NSUB; ++s) cnt += seg[s * SEGW + lane + 1] - seg[s * SEGW + lane];
-      const int chunks = (cnt + 63) >> 6;
-      const int incl = mg_wave_scan_incl_i32(chunks);
-      if (lane < nr) chunk0[lane] = incl - chunks;
+      if (lane < nr) {
+        int pre[NSUB], dlt[NSUB];
+#pragma unroll
+        for (int s = 0; s < NSUB; ++s) {
+          const int a = seg[s * SEGW + lane];
+          pre[s] = cnt;
+          dlt[s] = a - cnt;
+          cnt += seg[s * SEGW + lane + 1] - a;
+        }
+        map[4 * lane + 0] = make_int4(cnt, pre[1], pre[2], pre[3]);
+        map[4 * lane + 1] = make_int4(pre[4], pre[5], pre[6], pre[7]);
+        map[4 * lane + 2] = make_int4(dlt[0], dlt[1], dlt[2], dlt[3]);
+        map[4 * lane + 3] = make_int4(dlt[4], dlt[5], dlt[6], dlt[7]);
+      }
+      const int tickets = (cnt >> 7) + (((cnt & 127) + 63) >> 6);
+      const int incl = mg_wave_scan_incl_i32(tickets);
+      if (lane < nr) chunk0[lane] = incl - tickets;
       if (lane == nr - 1) chunk0[nr] = incl;
     }
     __syncthreads();
-    const int total_chunks = chunk0[nr];
-    // Chunk loop, software-pipelined: the keys of the NEXT chunk are requested before the current chunk is
-    // scored (a wave's chunks are otherwise one global round trip each).
-    int rho_n = 0, s_n = 0;
-    int64_t i_n = 0;
-    bool valid_n = false;
-    uint32_t key_n = 0;
+    const int total_tickets = chunk0[nr];
+    // Ticket loop, software-pipelined: the keys of the NEXT ticket are requested before the current one is scored
+    // (a wave's tickets are otherwise one global round trip each).  A ticket is 64 positions of one radius, a
+    // circle per lane (A), or 128, two per lane (A: position m, B: m + 64), walked together: the two circles share
+    // the ticket, the radius decode, the map, the switch and the walk's scalar table loads.
+    int rho_n = 0;
+    bool two_n = false, valid_n = false;
+    KeyAt a_n = {0, 0}, b_n = {0, 0};
+    uint32_t key_an = 0, key_bn = 0;
     auto fetch = [&]() -> bool {
       int c = 0;
       if (lane == 0) c = atomicAdd(next, 1);
       c = __builtin_amdgcn_readfirstlane(c);
-      if (c >= total_chunks) return false;
-      // the chunk's radius: the last rho with chunk0[rho] <= c (empty radii share their successor's start)
+      if (c >= total_tickets) return false;
+      // the ticket's radius: the last rho with chunk0[rho] <= c (empty radii share their successor's start)
       rho_n = __builtin_popcountll(__ballot(lane < nr && chunk0[lane] <= c)) - 1;
-      int m = 64 * (c - chunk0[rho_n]) + lane;  // position in the concatenation of the sub-tiles' segments of rho
-      s_n = -1;
-#pragma unroll
-      for (int s = 0; s < NSUB; ++s) {
-        const int a = seg[s * SEGW + rho_n], cnt = seg[s * SEGW + rho_n + 1] - a;
-        if (s_n < 0) {
-          if (m < cnt) {
-            s_n = s;
-            i_n = (int64_t)a + m;
-          } else {
-            m -= cnt;
-          }
-        }
+      const int4 p0 = map[4 * rho_n], p1 = map[4 * rho_n + 1], d0 = map[4 * rho_n + 2], d1 = map[4 * rho_n + 3];
+      const int cnt = __builtin_amdgcn_readfirstlane(p0.x), t = c - __builtin_amdgcn_readfirstlane(chunk0[rho_n]);
+      const int nd = cnt >> 7;  // double tickets of this radius; then singles
+      two_n = t < nd;
+      const int m = 64 * (t + min(t, nd)) + lane;
+      valid_n = m < cnt;
+      a_n = locate(m, p0, p1, d0, d1);
+      if (!valid_n) a_n.i = 0;
+      key_an = ukeys[a_n.i];  // (an idle lane reads a valid address: no branch around the load)
+      if (two_n) {            // (all 128 positions exist)
+        b_n = locate(m + 64, p0, p1, d0, d1);
+        key_bn = ukeys[b_n.i];
       }
-      valid_n = s_n >= 0;
-      if (!valid_n) s_n = 0, i_n = 0;
-      key_n = ukeys[i_n];  // (an idle lane reads a valid address: no branch around the load)
       return true;
     };
-    bool have = fetch();
-    while (have) {
-      const int rho = rho_n, s = s_n;
-      const int64_t i = i_n;
-      const bool valid = valid_n;
-      const uint32_t key = valid ? key_n : 0u;
-      have = fetch();
-      const int wrow = (s / SUBX) * TS + mg_key_row(key) + max_r, wcol = (s % SUBX) * TS + mg_key_col(key) + max_r;
-      const int vaddr = WBASE + wrow * WSTR + wcol - BIAS;
-      int sum = 0;
-      const int need_rho = need[rho];
-      switch (rho + min_r) {
-#define MG_CASE(R) case R: sum = score_r<R>(lds, vaddr, d_tabs, need_rho, valid); break;
-          MG_CASE(2) MG_CASE(3) MG_CASE(4) MG_CASE(5) MG_CASE(6) MG_CASE(7) MG_CASE(8) MG_CASE(9) MG_CASE(10)
-          MG_CASE(11) MG_CASE(12) MG_CASE(13) MG_CASE(14) MG_CASE(15) MG_CASE(16) MG_CASE(17) MG_CASE(18)
-          MG_CASE(19) MG_CASE(20) MG_CASE(21) MG_CASE(22) MG_CASE(23) MG_CASE(24) MG_CASE(25) MG_CASE(26)
-#undef MG_CASE
-          default: break;
-        }
-      const bool pass = valid && sum >= need[rho];
+    // sum against need -> the survivors of a chunk to the block's list
+    auto hand_over = [&](bool valid, int sum, int need_rho, int i, uint32_t key) {
+      const bool pass = valid && sum >= need_rho;
       if (write_skipped && valid && !pass) d_scores[(int64_t)plane * circle_cap + i] = MG_SCORE_SKIPPED;
       const uint64_t pm = __ballot(pass);
       if (pm) {  // rare: hold the survivors in LDS until the super-tile is done
@@ -380,6 +425,40 @@ __global__ __launch_bounds__(NP) void k_prefilter(const uint32_t* __restrict__ d
             reinterpret_cast<int2*>(d_surv)[(int64_t)plane * surv_cap + sbase + rank] = make_int2((int32_t)i, (int32_t)key);
         }
       }
+    };
+    const int corner = WBASE - BIAS + max_r * (WSTR + 1);  // window byte of a sub-tile's position (0, 0), less BIAS
+    bool have = fetch();
+    while (have) {
+      const int rho = rho_n;
+      const bool two = two_n, valid = valid_n;
+      const KeyAt a = a_n, b = b_n;
+      const uint32_t key_a = valid ? key_an : 0u, key_b = key_bn;
+      have = fetch();
+      const int va = corner + a.wo + mg_key_row(key_a) * WSTR + mg_key_col(key_a);
+      int sum_a = 0, sum_b = 0;
+      const int need_rho = need[rho];
+      if (two) {
+        const int vb = corner + b.wo + mg_key_row(key_b) * WSTR + mg_key_col(key_b);
+        switch (rho + min_r) {
+#define MG_CASE(R) case R: score_walk<R, true>(lds, va, vb, d_tabs, need_rho, true, sum_a, sum_b); break;
+          MG_CASE(2) MG_CASE(3) MG_CASE(4) MG_CASE(5) MG_CASE(6) MG_CASE(7) MG_CASE(8) MG_CASE(9) MG_CASE(10)
+          MG_CASE(11) MG_CASE(12) MG_CASE(13) MG_CASE(14) MG_CASE(15) MG_CASE(16) MG_CASE(17) MG_CASE(18)
+          MG_CASE(19) MG_CASE(20) MG_CASE(21) MG_CASE(22) MG_CASE(23) MG_CASE(24) MG_CASE(25) MG_CASE(26)
+#undef MG_CASE
+          default: break;
+        }
+      } else {
+        switch (rho + min_r) {
+#define MG_CASE(R) case R: score_walk<R, false>(lds, va, va, d_tabs, need_rho, valid, sum_a, sum_b); break;
+          MG_CASE(2) MG_CASE(3) MG_CASE(4) MG_CASE(5) MG_CASE(6) MG_CASE(7) MG_CASE(8) MG_CASE(9) MG_CASE(10)
+          MG_CASE(11) MG_CASE(12) MG_CASE(13) MG_CASE(14) MG_CASE(15) MG_CASE(16) MG_CASE(17) MG_CASE(18)
+          MG_CASE(19) MG_CASE(20) MG_CASE(21) MG_CASE(22) MG_CASE(23) MG_CASE(24) MG_CASE(25) MG_CASE(26)
+#undef MG_CASE
+          default: break;
+        }
+      }
+      hand_over(valid, sum_a, need_rho, a.i, key_a);
+      if (two) hand_over(true, sum_b, need_rho, b.i, key_b);
     }
     // ---- the super-tile's survivors -> the plane's list ----
     __syncthreads();
