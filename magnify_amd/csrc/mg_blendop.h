@@ -1,15 +1,15 @@
 // The per-pixel pieces of the blended stitch, once: which tiles cover a canvas coordinate and with what numerators
-// (Axis, axis_term), what the plain pass writes for one pixel of one tile (BlendSrc, tile_value) and the mix of up to
-// four such values (mix_tiles).  mg_blend.hip (the blended stitch) and mg_register.hip (the stitch of shifted tiles)
-// call the same functions, so their pixels agree by construction.
+// (Axis, axis_term), what the plain pass writes for one pixel of one tile (tile_value, from the StitchSrc of
+// mg_stitch.h) and the mix of up to four such values (mix_tiles).  The generic kernel (mg_stitch_kernel.h, blended in
+// mg_blend.hip) and mg_register.hip (the stitch of shifted tiles) call the same functions, so their pixels agree by
+// construction.
 #pragma once
 #include "mg_common.h"
 #include "mg_flatcorr.h"
 #include "mg_shadeop.h"
+#include "mg_stitch.h"
 
 namespace {
-
-enum { BL_COPY, BL_FLAT, BL_SHADE };  // the value of a tile's pixel: raw, flat-field corrected, shading corrected
 
 struct Axis {
   int v, clip, rem, h, n;
@@ -28,25 +28,10 @@ __device__ __forceinline__ void axis_term(const Axis& a, int i, int j, int& othe
   }
 }
 
-// The operands of the pass (those of mg_flatfield_apply_stitch; BL_SHADE: d_dark / d_flat are the float32 fields,
-// one per group of planes_per_group planes).
-template <typename T>
-struct BlendSrc {
-  const T* tiles;
-  int n_tr, n_tc, ty, tx, planes_per_group;
-  double dark;
-  const void* d_dark;
-  int dark_dt;
-  double flat;
-  const void* d_flat;
-  int flat_dt;
-  const double* d_max2;
-};
-
 // What the plain pass writes for pixel (y, x) of tile (tr, tc) of `plane`.
 template <typename T, int MODE>
-__device__ __forceinline__ T tile_value(const BlendSrc<T>& s, int plane, int tr, int tc, int y, int x, double m1,
-                                        double m2, double kk, bool fast_ok) {
+__device__ __forceinline__ T tile_value(const StitchSrc<T>& s, int plane, int tr, int tc, int y, int x,
+                                        const GroupMax& g) {
   const int64_t tile_elems = (int64_t)s.ty * s.tx, pix = (int64_t)y * s.tx + x;
   const T px = s.tiles[(((int64_t)plane * s.n_tr + tr) * s.n_tc + tc) * tile_elems + pix];
   if (MODE == BL_COPY) return px;
@@ -58,7 +43,7 @@ __device__ __forceinline__ T tile_value(const BlendSrc<T>& s, int plane, int tr,
   const double fl = s.d_flat ? mg_load_f64(s.d_flat, s.flat_dt, pix) : s.flat;
   double t = (double)px - dk;
   t = t < 0.0 ? 0.0 : t;
-  return correct_pixel<T>(t, fl, IsIntegral<T>::value ? refined_rcp(fl) : 0.0, m1, m2, kk, fast_ok);
+  return correct_pixel<T>(t, fl, IsIntegral<T>::value ? refined_rcp(fl) : 0.0, g.m1, g.m2, g.kk, g.fast_ok);
 }
 
 // The mix of the owner's value c00 with the x neighbour's c01, the y neighbour's c10 and the diagonal tile's c11

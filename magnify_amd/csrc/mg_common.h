@@ -174,13 +174,12 @@ __device__ __forceinline__ void mg_atomic_nanmin(double* addr, double v) {
 // registers and saw one, the integer pair (a kernel instance uses one of the two; the other stays at its identity).
 constexpr int MG_MINMAX_WAVES = 4;
 template <int PB, class I>
-__device__ __forceinline__ void mg_block_minmax(double* vmin, double* vmax, const uint32_t* imin, const uint32_t* imax,
-                                                int np, double* d_minmax, I plane0) {
+__device__ __forceinline__ void mg_block_minmax_f64(const double* vmin, const double* vmax, int np, double* d_minmax,
+                                                    I plane0) {
   __shared__ double s_min[PB][MG_MINMAX_WAVES], s_max[PB][MG_MINMAX_WAVES];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int b = 0; b < PB; ++b) {
-    if (imin[b] <= imax[b]) vmin[b] = (double)imin[b], vmax[b] = (double)imax[b];
     const double a = mg_wave_nanmin(vmin[b]), c = mg_wave_nanmax(vmax[b]);
     if (lane == 0) {
       s_min[b][wave] = a;
@@ -200,6 +199,15 @@ __device__ __forceinline__ void mg_block_minmax(double* vmin, double* vmax, cons
       mg_atomic_nanmax(d_minmax + 2 * (plane0 + b) + 1, c);
     }
   }
+}
+// (a kernel that keeps both pairs: the integer one, where it saw a pixel, takes the place of the float64 one)
+template <int PB, class I>
+__device__ __forceinline__ void mg_block_minmax(double* vmin, double* vmax, const uint32_t* imin, const uint32_t* imax,
+                                                int np, double* d_minmax, I plane0) {
+#pragma unroll
+  for (int b = 0; b < PB; ++b)
+    if (imin[b] <= imax[b]) vmin[b] = (double)imin[b], vmax[b] = (double)imax[b];
+  mg_block_minmax_f64<PB>(vmin, vmax, np, d_minmax, plane0);
 }
 // The same for integer pixels kept as uint32 (no NaN; the identity is min > max).
 template <int PB, class I>

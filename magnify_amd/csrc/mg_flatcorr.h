@@ -32,6 +32,8 @@ __device__ __forceinline__ double cast_trunc<double>(double v) {
 
 // the range of flat values the reciprocal paths are valid in
 __device__ __forceinline__ bool flat_in_range(double fl) { return fl > 1e-30 && fl < 1e30; }
+// the same test on a float32 flat value (the float32 filters of pass 1)
+__device__ __forceinline__ bool flat_in_range_f32(float fl) { return fl > 1e-30f && fl < 1e30f; }
 
 // Newton-refined reciprocal of a flat-field value (float32 seed, two steps in float64: ~1e-16).
 // Returns 0 when the value is outside the range in which the fast path is valid.

@@ -8,6 +8,7 @@
 #include "mg_common.h"
 #include "mg_flatcorr.h"
 #include "mg_stitch.h"
+#include "mg_stitch_kernel.h"
 
 namespace {
 
@@ -147,6 +148,19 @@ __global__ __launch_bounds__(256) void k_flatfield_max_int(const T* __restrict__
   block_atomic_max2(m1, m1 / flat, out);
 }
 
+// One pixel of the fast paths below: can it beat the running maximum of t / flat?  The test runs in float32 against
+// the lane's own threshold `thr` and an extra one, `gthr`; a pixel that passes pays for the exact float64 division and
+// raises m2 and thr.  rc: the float32 reciprocal of fl.
+__device__ __forceinline__ void max2_step(uint32_t xi, float dk_f, double dark, float fl, float rc, float gthr, double& m2,
+                                          float& thr) {
+  const float t_f = fmaxf((float)xi - dk_f, 0.0f);
+  if (flat_in_range_f32(fl) && t_f * rc <= fmaxf(thr, gthr)) return;  // provably below the running maximum
+  double t = (double)xi - dark;
+  t = t < 0.0 ? 0.0 : t;
+  m2 = mg_nanmax(m2, t / (double)fl);
+  thr = (m2 == m2 && m2 < 1e30) ? (float)m2 * (1.0f - 1e-5f) : -INFINITY;
+}
+
 // Fast path of pass 1 for integer pixels, scalar dark and a float32 flat image: the test "can this
 // pixel beat the running maximum of t / flat?" runs in float32 (reciprocal + multiply, error
 // < 1e-6 relative against a 1e-5 margin); only pixels that pass pay for the exact float64 division,
@@ -169,11 +183,7 @@ __global__ __launch_bounds__(256) void k_flatfield_max_fast(const T* __restrict_
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += stride) {
     float fl[N], rc[N];
-#pragma unroll
-    for (int q = 0; q < N / 4; ++q) {
-      const float4 f = reinterpret_cast<const float4*>(d_flat + v * N)[q];
-      fl[4 * q] = f.x, fl[4 * q + 1] = f.y, fl[4 * q + 2] = f.z, fl[4 * q + 3] = f.w;
-    }
+    load_f32<N>(d_flat + v * N, fl);
 #pragma unroll
     for (int j = 0; j < N; ++j) rc[j] = __builtin_amdgcn_rcpf(fl[j]);
     any = true;
@@ -195,21 +205,12 @@ __global__ __launch_bounds__(256) void k_flatfield_max_fast(const T* __restrict_
           const uint32_t xi = (uint32_t)x4[q][j];
           xmax = max(xmax, xi);
           const float t_f = fmaxf((float)xi - dk_f, 0.0f);
-          const bool in_range = fl[j] > 1e-30f && fl[j] < 1e30f;
-          cand |= !(in_range && t_f * rc[j] <= thr);
+          cand |= !(flat_in_range_f32(fl[j]) && t_f * rc[j] <= thr);
         }
         if (!cand) continue;
 #pragma unroll
-        for (int j = 0; j < N; ++j) {
-          const uint32_t xi = (uint32_t)x4[q][j];
-          const float t_f = fmaxf((float)xi - dk_f, 0.0f);
-          const bool in_range = fl[j] > 1e-30f && fl[j] < 1e30f;
-          if (in_range && t_f * rc[j] <= thr) continue;  // provably below the running maximum
-          double t = (double)xi - dark;
-          t = t < 0.0 ? 0.0 : t;
-          m2 = mg_nanmax(m2, t / (double)fl[j]);
-          thr = (m2 == m2 && m2 < 1e30) ? (float)m2 * (1.0f - 1e-5f) : -INFINITY;
-        }
+        // (gthr = -inf: no threshold besides the lane's own)
+        for (int j = 0; j < N; ++j) max2_step((uint32_t)x4[q][j], dk_f, dark, fl[j], rc[j], -INFINITY, m2, thr);
       }
     }
   }
@@ -229,17 +230,13 @@ __global__ __launch_bounds__(256) void k_flatfield_max_fast(const T* __restrict_
 template <int N>
 __global__ __launch_bounds__(256) void k_flat_rcmax(const float* __restrict__ d_flat, int64_t nvec, float* __restrict__ d_rcmax) {
   for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (int64_t)gridDim.x * blockDim.x) {
-    float m = 0.0f;
+    float m = 0.0f, fl[N];
     bool ok = true;
+    load_f32<N>(d_flat + v * N, fl);
 #pragma unroll
-    for (int q = 0; q < N / 4; ++q) {
-      const float4 f = reinterpret_cast<const float4*>(d_flat + v * N)[q];
-      const float fl[4] = {f.x, f.y, f.z, f.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        ok = ok && fl[j] > 1e-30f && fl[j] < 1e30f;
-        m = fmaxf(m, __builtin_amdgcn_rcpf(fl[j]));
-      }
+    for (int j = 0; j < N; ++j) {
+      ok = ok && flat_in_range_f32(fl[j]);
+      m = fmaxf(m, __builtin_amdgcn_rcpf(fl[j]));
     }
     d_rcmax[v] = ok ? m : -1.0f;
   }
@@ -309,22 +306,10 @@ __global__ __launch_bounds__(256) void k_flatfield_max_lean(const T* __restrict_
           const float tf = fmaxf((float)cm - dk_f, 0.0f);
           if (rcm[u] >= 0.0f && tf * rcm[u] <= fmaxf(thr, gthr)) continue;
           float fl[N];
+          load_f32<N>(d_flat + v * N, fl);
 #pragma unroll
-          for (int k4 = 0; k4 < N / 4; ++k4) {
-            const float4 f = reinterpret_cast<const float4*>(d_flat + v * N)[k4];
-            fl[4 * k4] = f.x, fl[4 * k4 + 1] = f.y, fl[4 * k4 + 2] = f.z, fl[4 * k4 + 3] = f.w;
-          }
-#pragma unroll
-          for (int j = 0; j < N; ++j) {
-            const uint32_t xi = (uint32_t)x4[u][q][j];
-            const float t_f = fmaxf((float)xi - dk_f, 0.0f);
-            const bool in_range = fl[j] > 1e-30f && fl[j] < 1e30f;
-            if (in_range && t_f * __builtin_amdgcn_rcpf(fl[j]) <= fmaxf(thr, gthr)) continue;  // provably below the running maximum
-            double t = (double)xi - dark;
-            t = t < 0.0 ? 0.0 : t;
-            m2 = mg_nanmax(m2, t / (double)fl[j]);
-            thr = (m2 == m2 && m2 < 1e30) ? (float)m2 * (1.0f - 1e-5f) : -INFINITY;
-          }
+          for (int j = 0; j < N; ++j)
+            max2_step((uint32_t)x4[u][q][j], dk_f, dark, fl[j], __builtin_amdgcn_rcpf(fl[j]), gthr, m2, thr);
         }
       }
     }
@@ -343,147 +328,8 @@ __global__ __launch_bounds__(256) void k_flatfield_max_lean(const T* __restrict_
 }
 
 // ---- pass 2: apply + stitch (+ output min/max) ----------------------------------------
-// Selected planes of every group (mg_flatfield_apply_stitch_planes): bit c of `mask` selects plane c of each group of
-// planes_per_group planes; the s-th selected plane of the stack is plane (s / n_sel) * planes_per_group + the
-// (s % n_sel)-th set bit.  A workgroup takes PLANES_PER_BLOCK consecutive SELECTED planes; without a selection
-// (SUBSET false) plane s is plane s.
-struct PlaneSel {
-  uint32_t mask;
-  int n_sel;
-};
-template <bool SUBSET>
-__device__ __forceinline__ int sel_plane(int s, int planes_per_group, PlaneSel sel) {
-  if (!SUBSET) return s;
-  const int g = s / sel.n_sel;
-  uint32_t m = sel.mask;
-  for (int k = s - g * sel.n_sel; k > 0; --k) m &= m - 1u;  // without its k lowest set bits
-  return g * planes_per_group + __builtin_ctz(m);
-}
-// plane0 of mg_block_minmax for a selection: `base + b` is the plane the workgroup's b-th running pair belongs to
-struct SelBase {
-  int s0, planes_per_group;
-  PlaneSel sel;
-  __device__ __forceinline__ int operator+(int b) const { return sel_plane<true>(s0 + b, planes_per_group, sel); }
-};
-
-// Block = 256 lanes x N pixels of ROWS_PER_BLOCK output rows, for PLANES_PER_BLOCK consecutive
-// planes: the dark/flat operands of a pixel chunk are loaded once and reused across those planes.
-template <typename T, bool APPLY, bool SUBSET = false>
-__global__ __launch_bounds__(256) void k_apply_stitch(const T* __restrict__ tiles, int n_planes, int n_tr, int n_tc,
-                                                       int ty, int tx, int clip, int hy, int hx, int planes_per_group,
-                                                       double dark, const void* __restrict__ d_dark, int dark_dt,
-                                                       double flat, const void* __restrict__ d_flat, int flat_dt,
-                                                       const double* __restrict__ d_max2, T* __restrict__ image,
-                                                       double* __restrict__ d_minmax, int rows_per_block, PlaneSel sel) {
-  constexpr int N = VecOf<T>::N;
-  constexpr int PB = PLANES_PER_BLOCK;
-  const int plane0 = blockIdx.z * PB;  // (SUBSET: n_planes, plane0 count SELECTED planes; pl[b] is the plane itself)
-  const int np = min(PB, n_planes - plane0);
-  const int h_out = n_tr * hy, w_out = n_tc * hx;
-  const int ox0 = (blockIdx.x * blockDim.x + threadIdx.x) * N;
-  int pl[PB];
-#pragma unroll
-  for (int b = 0; b < PB; ++b) pl[b] = (!SUBSET || b < np) ? sel_plane<SUBSET>(plane0 + b, planes_per_group, sel) : 0;
-  double m1[PB], m2[PB], kk[PB];
-  bool fast_ok[PB];
-#pragma unroll
-  for (int b = 0; b < PB; ++b) {
-    m1[b] = 0.0, m2[b] = 1.0, kk[b] = 1.0, fast_ok[b] = false;
-    if (APPLY && b < np) {
-      const int group = pl[b] / planes_per_group;
-      m1[b] = d_max2[2 * group];
-      m2[b] = d_max2[2 * group + 1];
-      fast_ok[b] = group_quotient(m1[b], m2[b], kk[b]);
-    }
-  }
-  double vmin[PB], vmax[PB];
-  uint32_t imin[PB], imax[PB];  // integer outputs: min/max in integer registers
-#pragma unroll
-  for (int b = 0; b < PB; ++b) vmin[b] = INFINITY, vmax[b] = -INFINITY, imin[b] = 0xFFFFFFFFu, imax[b] = 0u;
-  const int64_t tile_elems = (int64_t)ty * tx;
-  // a workgroup takes the row groups blockIdx.y, blockIdx.y + gridDim.y, ...: one set of min/max atomics per
-  // workgroup however short the row groups are
-  if (ox0 < w_out)
-  for (int yg = blockIdx.y; yg * rows_per_block < h_out; yg += gridDim.y) {
-    const int row_end = min((yg + 1) * rows_per_block, h_out);
-    const int tc0 = ox0 / hx;
-    const int x0 = ox0 - tc0 * hx + clip;
-    const bool one_tile = (ox0 + N <= w_out) && (x0 - clip + N <= hx);
-    for (int oy = yg * rows_per_block; oy < row_end; ++oy) {
-      const int tr = oy / hy;
-      const int y = oy - tr * hy + clip;
-      int64_t pix[N], toff[N];  // pixel index inside the tile, element offset of the tile in a plane
-      const int cnt = one_tile ? N : min(N, w_out - ox0);
-#pragma unroll
-      for (int j = 0; j < N; ++j) {
-        const int ox = ox0 + (one_tile ? j : min(j, cnt - 1));
-        const int tc = one_tile ? tc0 : ox / hx;
-        const int xx = one_tile ? x0 + j : ox - tc * hx + clip;
-        pix[j] = (int64_t)y * tx + xx;
-        toff[j] = ((int64_t)tr * n_tc + tc) * tile_elems;
-      }
-      double dk[N], fl[N], rr[N];
-      if (APPLY) {
-        if (one_tile) {
-          load_field<N>(d_dark, dark_dt, pix[0], dark, dk);
-          load_field<N>(d_flat, flat_dt, pix[0], flat, fl);
-        } else {
-#pragma unroll
-          for (int j = 0; j < N; ++j) {
-            dk[j] = d_dark ? mg_load_f64(d_dark, dark_dt, pix[j]) : dark;
-            fl[j] = d_flat ? mg_load_f64(d_flat, flat_dt, pix[j]) : flat;
-          }
-        }
-        // the refined reciprocal of flat is shared by all planes of the block
-#pragma unroll
-        for (int j = 0; j < N; ++j) rr[j] = IsIntegral<T>::value ? refined_rcp(fl[j]) : 0.0;
-      }
-#pragma unroll
-      for (int b = 0; b < PB; ++b) {
-        if (b >= np) break;
-        const int64_t plane_base = (int64_t)pl[b] * n_tr * n_tc * tile_elems;
-        T x[N], o[N];
-        if (one_tile) {
-          load_vec<T, N>(tiles + plane_base + toff[0] + pix[0], x);
-        } else {
-#pragma unroll
-          for (int j = 0; j < N; ++j) x[j] = tiles[plane_base + toff[j] + pix[j]];
-        }
-#pragma unroll
-        for (int j = 0; j < N; ++j) {
-          if (APPLY) {
-            double t = (double)x[j] - dk[j];
-            t = t < 0.0 ? 0.0 : t;
-            o[j] = correct_pixel<T>(t, fl[j], rr[j], m1[b], m2[b], kk[b], fast_ok[b]);
-          } else {
-            o[j] = x[j];
-          }
-          if (d_minmax && j < cnt) {
-            if (IsIntegral<T>::value) {
-              imin[b] = min(imin[b], (uint32_t)o[j]);
-              imax[b] = max(imax[b], (uint32_t)o[j]);
-            } else {
-              const double ov = (double)o[j];
-              vmin[b] = mg_nanmin(vmin[b], ov);
-              vmax[b] = mg_nanmax(vmax[b], ov);
-            }
-          }
-        }
-        T* dst = image + ((int64_t)pl[b] * h_out + oy) * w_out + ox0;
-        if (cnt == N) {
-          store_vec<T, N>(dst, o);
-        } else {
-          for (int j = 0; j < cnt; ++j) dst[j] = o[j];
-        }
-      }
-    }
-  }
-  if (d_minmax) {
-    if (SUBSET) mg_block_minmax<PB>(vmin, vmax, imin, imax, np, d_minmax, SelBase{plane0, planes_per_group, sel});
-    else mg_block_minmax<PB>(vmin, vmax, imin, imax, np, d_minmax, plane0);
-  }
-}
-
+// The generic pass is k_stitch<T, BL_COPY or BL_FLAT, false, SUBSET> (mg_stitch_kernel.h).
+//
 // Lean variant for the aligned case (hx % N == 0 and aligned bases: every N-pixel chunk lies
 // inside one tile and all accesses are 16-byte vectors); integer pixel types only.
 // Arithmetic of the correction, per pixel: the conversion, ONE float64 product with the position's factor, fract,
@@ -493,16 +339,12 @@ __global__ __launch_bounds__(256) void k_apply_stitch(const T* __restrict__ tile
 // at 64 the pass waits for memory, see the workgroup order below).  INT_DARK: an integer-valued scalar dark,
 // subtracted in the integer domain (two uint16 pixels per instruction).
 template <typename T, bool APPLY, bool INT_DARK, bool SUBSET = false>
-__global__ __launch_bounds__(256) void k_apply_stitch_aligned(const T* __restrict__ tiles, int n_planes, int n_tr,
-                                                               int n_tc, int ty, int tx, int clip, int hy, int hx,
-                                                               int planes_per_group, double dark,
-                                                               const void* __restrict__ d_dark, int dark_dt,
-                                                               double flat, const void* __restrict__ d_flat,
-                                                               int flat_dt, const double* __restrict__ d_max2,
+__global__ __launch_bounds__(256) void k_apply_stitch_aligned(StitchSrc<T> s, int n_planes, int clip, int hy, int hx,
                                                                T* __restrict__ image, double* __restrict__ d_minmax,
                                                                int rows_per_block, PlaneSel sel) {
   constexpr int N = VecOf<T>::N;
   constexpr int PB = PLANES_PER_BLOCK;
+  const int n_tr = s.n_tr, n_tc = s.n_tc, tx = s.tx, planes_per_group = s.planes_per_group;
   // Which part of the grid this workgroup is: the plane groups (z) of one (x, y) part read the same rows of the flat /
   // dark images -- 64 MB of float32 per plane group at 4096^2, 2 GB of the pass's 19 GB at 64 assays when the parts
   // are worked through plane group by plane group (the hardware's order: x, y, then z).  Workgroups are dealt to the
@@ -524,10 +366,8 @@ __global__ __launch_bounds__(256) void k_apply_stitch_aligned(const T* __restric
   int pl[PB];
 #pragma unroll
   for (int b = 0; b < PB; ++b) pl[b] = (!SUBSET || b < np) ? sel_plane<SUBSET>(plane0 + b, planes_per_group, sel) : 0;
-  uint32_t imin[PB], imax[PB];
-#pragma unroll
-  for (int b = 0; b < PB; ++b) imin[b] = 0xFFFFFFFFu, imax[b] = 0u;
-  const int64_t tile_elems = (int64_t)ty * tx, plane_elems = (int64_t)n_tr * n_tc * tile_elems;
+  PlaneMinMax<T, PB> mm;
+  const int64_t tile_elems = (int64_t)s.ty * tx, plane_elems = (int64_t)n_tr * n_tc * tile_elems;
   // per plane, once per workgroup (scalar registers): the quotient of the group's maxima and whether the fast path
   // holds for them (the maxima themselves are read again by the rare exact path: 16 more scalar registers spilled)
   double kka[PB];
@@ -537,7 +377,7 @@ __global__ __launch_bounds__(256) void k_apply_stitch_aligned(const T* __restric
     kka[b] = 1.0;
     if (APPLY && b < np) {
       const int group = pl[b] / planes_per_group;
-      const double m1 = d_max2[2 * group], m2 = d_max2[2 * group + 1];
+      const double m1 = s.d_max2[2 * group], m2 = s.d_max2[2 * group + 1];
       double kk;
       const bool ok = group_quotient(m1, m2, kk);
       kka[b] = uniform_f64(kk);
@@ -545,9 +385,9 @@ __global__ __launch_bounds__(256) void k_apply_stitch_aligned(const T* __restric
     }
   }
   ok_mask = __builtin_amdgcn_readfirstlane(ok_mask);
-  const uint32_t dark_i = INT_DARK ? (uint32_t)dark : 0u;
+  const uint32_t dark_i = INT_DARK ? (uint32_t)s.dark : 0u;
   if (ox0 < w_out)
-  for (int yg = by; yg * rows_per_block < h_out; yg += gridDim.y) {  // (as in k_apply_stitch)
+  for (int yg = by; yg * rows_per_block < h_out; yg += gridDim.y) {  // (as in k_stitch)
     const int row_end = min((yg + 1) * rows_per_block, h_out);
     const int tc0 = ox0 / hx;
     const int x0 = ox0 - tc0 * hx + clip;
@@ -558,8 +398,8 @@ __global__ __launch_bounds__(256) void k_apply_stitch_aligned(const T* __restric
       double dk[N], fl[N], rr[N];
       bool flat_bad = false;  // a flat value outside the range the reciprocal path is valid in
       if (APPLY) {
-        if (!INT_DARK) load_field<N>(d_dark, dark_dt, p0, dark, dk);
-        load_field<N>(d_flat, flat_dt, p0, flat, fl);
+        if (!INT_DARK) load_field<N>(s.d_dark, s.dark_dt, p0, s.dark, dk);
+        load_field<N>(s.d_flat, s.flat_dt, p0, s.flat, fl);
 #pragma unroll
         for (int j = 0; j < N; ++j) {
           rr[j] = refined_rcp(fl[j]);
@@ -570,7 +410,7 @@ __global__ __launch_bounds__(256) void k_apply_stitch_aligned(const T* __restric
       T xin[PB][N];
 #pragma unroll
       for (int b = 0; b < PB; ++b)
-        if (b < np) load_vec16<T, N>(tiles + (int64_t)pl[b] * plane_elems + src0, xin[b], false);
+        if (b < np) load_vec16<T, N>(s.tiles + (int64_t)pl[b] * plane_elems + src0, xin[b], false);
       double rk[N];
       double kk_of_rk = -1.0;  // the quotient rk was made with (planes of one group follow each other)
       bool rk_large = true;
@@ -585,25 +425,19 @@ __global__ __launch_bounds__(256) void k_apply_stitch_aligned(const T* __restric
             rk_large = chunk_factors<N>(rr, kk_of_rk, rk);
           }
           const bool rk_bad = rk_large || flat_bad || !((ok_mask >> b) & 1u);
-          correct_chunk_rk<T, N, INT_DARK>(x, dark_i, dk, fl, rk, rk_bad, d_max2, pl[b], planes_per_group, o);
+          correct_chunk_rk<T, N, INT_DARK>(x, dark_i, dk, fl, rk, rk_bad, s.d_max2, pl[b], planes_per_group, o);
         } else {
 #pragma unroll
           for (int j = 0; j < N; ++j) o[j] = x[j];
         }
-        if (d_minmax) {
-#pragma unroll
-          for (int j = 0; j < N; ++j) {
-            imin[b] = min(imin[b], (uint32_t)o[j]);
-            imax[b] = max(imax[b], (uint32_t)o[j]);
-          }
-        }
+        if (d_minmax) mm.add(b, o);
         store_vec16<T, N>(image + ((int64_t)pl[b] * h_out + oy) * w_out + ox0, o, false);
       }
     }
   }
   if (d_minmax) {
-    if (SUBSET) mg_block_minmax_u32<PB>(imin, imax, np, d_minmax, SelBase{plane0, planes_per_group, sel});
-    else mg_block_minmax_u32<PB>(imin, imax, np, d_minmax, plane0);
+    if constexpr (SUBSET) mm.flush(np, d_minmax, SelBase{plane0, planes_per_group, sel});
+    else mm.flush(np, d_minmax, plane0);
   }
 }
 
@@ -614,13 +448,12 @@ __global__ __launch_bounds__(256) void k_plane_minmax(const T* __restrict__ src,
   constexpr int N = VecOf<T>::N;
   const int plane = blockIdx.y;
   const T* base = src + (int64_t)plane * plane_stride;
-  double vmin = INFINITY, vmax = -INFINITY;
-  uint32_t imin = 0xFFFFFFFFu, imax = 0u;
+  PlaneMinMax<T, 1> mm;
   const int vec_per_row = (w + N - 1) / N;
   const int64_t total = (int64_t)h * vec_per_row;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (IsIntegral<T>::value && w % N == 0 && (reinterpret_cast<uintptr_t>(base) & 15) == 0 && (row_stride * (int64_t)sizeof(T)) % 16 == 0) {
+  if (IsIntegral<T>::value && w % N == 0 && aligned16(base) && (row_stride * (int64_t)sizeof(T)) % 16 == 0) {
     // integer pixels, rows of whole 16-byte vectors: integer min / max, four loads in flight per lane (one 4096^2
     // uint16 plane: 28 -> ~10 us; the float64 compares of the general loop kept the lanes busy, one load at a time)
     for (; i < total; i += 4 * stride) {
@@ -633,12 +466,7 @@ __global__ __launch_bounds__(256) void k_plane_minmax(const T* __restrict__ src,
         load_vec16<T, N>(base + (int64_t)r * row_stride + c0, x[q], false);
       }
 #pragma unroll
-      for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int j = 0; j < N; ++j) {
-          imin = min(imin, (uint32_t)x[q][j]);
-          imax = max(imax, (uint32_t)x[q][j]);
-        }
+      for (int q = 0; q < 4; ++q) mm.add(0, x[q]);
     }
     i = total;
   }
@@ -649,19 +477,12 @@ __global__ __launch_bounds__(256) void k_plane_minmax(const T* __restrict__ src,
     if (c0 + N <= w) {
       T x[N];
       load_vec<T, N>(p, x);
-#pragma unroll
-      for (int j = 0; j < N; ++j) {
-        vmin = mg_nanmin(vmin, (double)x[j]);
-        vmax = mg_nanmax(vmax, (double)x[j]);
-      }
+      mm.add(0, x);
     } else {
-      for (int j = 0; c0 + j < w; ++j) {
-        vmin = mg_nanmin(vmin, (double)p[j]);
-        vmax = mg_nanmax(vmax, (double)p[j]);
-      }
+      for (int j = 0; c0 + j < w; ++j) mm.add(0, p[j]);
     }
   }
-  mg_block_minmax<1>(&vmin, &vmax, &imin, &imax, 1, d_minmax, plane);
+  mm.flush(1, d_minmax, plane);
 }
 
 template <typename T>
@@ -669,43 +490,43 @@ int launch_max(const void* d_tiles, int64_t tiles_per_group, int n_groups, int64
                const void* d_dark, int dark_dt, double flat, const void* d_flat, int flat_dt, double* d_max2,
                float* d_scratch, int64_t scratch_floats, hipStream_t s) {
   if (tiles_per_group == 0 || n_groups == 0 || tile_elems == 0) return MG_OK;
-  const int64_t nvec = tile_elems / VecOf<T>::N + 1;
+  constexpr int N = VecOf<T>::N;
+  const int64_t nvec = tile_elems / N + 1;
   const int per_group = std::min(512, std::max(1, 4096 / n_groups));
   int blocks = (int)std::min<int64_t>((nvec + 255) / 256, per_group);
-  const int64_t group_elems = tiles_per_group * tile_elems;
-  if (IsIntegral<T>::value && !d_dark && !d_flat && flat > 0.0 && flat < 1e300 && fabs(dark) < 1e300 &&
-      (reinterpret_cast<uintptr_t>(d_tiles) & 15) == 0 && (group_elems * (int64_t)sizeof(T)) % 16 == 0) {
-    const int64_t gvec = group_elems / VecOf<T>::N;
-    // (every workgroup ends with two compare-and-swap maxima on the group's cache line: few, long-running workgroups)
-    const int gb = (int)std::max<int64_t>(1, std::min<int64_t>(gvec / 256, std::min(512, std::max(64, 2048 / n_groups))));
-    hipLaunchKernelGGL((k_flatfield_max_int<T>), dim3(gb, n_groups), dim3(256), 0, s, (const T*)d_tiles, group_elems, dark,
-                       flat, d_max2);
-    MG_CHECK_LAUNCH();
-    return MG_OK;
-  }
-  if (IsIntegral<T>::value && !d_dark && d_flat && flat_dt == MG_F32 && tile_elems % VecOf<T>::N == 0 &&
-      (reinterpret_cast<uintptr_t>(d_flat) & 15) == 0 && (reinterpret_cast<uintptr_t>(d_tiles) & 15) == 0 &&
-      fabs(dark) < 16777216.0 && (double)(float)dark == dark) {
-    constexpr int N = VecOf<T>::N;
-    if (d_scratch && scratch_floats >= tile_elems / N && (reinterpret_cast<uintptr_t>(d_scratch) & 3) == 0) {
-      const int64_t cvec = tile_elems / N;  // (d_scratch: the bound of this flat image, mg_flatfield_bound)
-      // one resident round of workgroups in all (74 VGPRs: 6 per CU), however many groups share them: every workgroup
-      // ends with two compare-and-swap maxima on its group's cache line
-      const int per = (int)std::max<int64_t>(1, std::min<int64_t>((cvec + 255) / 256, std::max(1, 1536 / n_groups)));
-      const int64_t chunks_per_lane = (cvec + (int64_t)per * 256 - 1) / ((int64_t)per * 256) * tiles_per_group;
-      if (chunks_per_lane < 512)
-        hipLaunchKernelGGL((k_flatfield_max_lean<T, true>), dim3(per, n_groups), dim3(256), 0, s, (const T*)d_tiles,
-                           tiles_per_group, tile_elems, dark, (const float*)d_flat, d_scratch, d_max2);
-      else
-        hipLaunchKernelGGL((k_flatfield_max_lean<T, false>), dim3(per, n_groups), dim3(256), 0, s, (const T*)d_tiles,
-                           tiles_per_group, tile_elems, dark, (const float*)d_flat, d_scratch, d_max2);
+  if constexpr (IsIntegral<T>::value) {  // (the integer-only kernels exist for integer pixels only)
+    const int64_t group_elems = tiles_per_group * tile_elems;
+    if (!d_dark && !d_flat && flat > 0.0 && flat < 1e300 && fabs(dark) < 1e300 && aligned16(d_tiles) &&
+        (group_elems * (int64_t)sizeof(T)) % 16 == 0) {
+      const int64_t gvec = group_elems / N;
+      // (every workgroup ends with two compare-and-swap maxima on the group's cache line: few, long-running workgroups)
+      const int gb = (int)std::max<int64_t>(1, std::min<int64_t>(gvec / 256, std::min(512, std::max(64, 2048 / n_groups))));
+      hipLaunchKernelGGL((k_flatfield_max_int<T>), dim3(gb, n_groups), dim3(256), 0, s, (const T*)d_tiles, group_elems, dark,
+                         flat, d_max2);
       MG_CHECK_LAUNCH();
       return MG_OK;
     }
-    hipLaunchKernelGGL((k_flatfield_max_fast<T>), dim3(blocks, n_groups), dim3(256), 0, s, (const T*)d_tiles,
-                       tiles_per_group, tile_elems, dark, (const float*)d_flat, d_max2);
-    MG_CHECK_LAUNCH();
-    return MG_OK;
+    if (!d_dark && d_flat && flat_dt == MG_F32 && tile_elems % N == 0 && aligned16(d_flat) && aligned16(d_tiles) &&
+        fabs(dark) < 16777216.0 && (double)(float)dark == dark) {
+      if (d_scratch && scratch_floats >= tile_elems / N && (reinterpret_cast<uintptr_t>(d_scratch) & 3) == 0) {
+        const int64_t cvec = tile_elems / N;  // (d_scratch: the bound of this flat image, mg_flatfield_bound)
+        // one resident round of workgroups in all (74 VGPRs: 6 per CU), however many groups share them: every workgroup
+        // ends with two compare-and-swap maxima on its group's cache line
+        const int per = (int)std::max<int64_t>(1, std::min<int64_t>((cvec + 255) / 256, std::max(1, 1536 / n_groups)));
+        const int64_t chunks_per_lane = (cvec + (int64_t)per * 256 - 1) / ((int64_t)per * 256) * tiles_per_group;
+        with_flag(chunks_per_lane < 512, [&](auto share) {
+          hipLaunchKernelGGL((k_flatfield_max_lean<T, decltype(share)::value>), dim3(per, n_groups), dim3(256), 0, s,
+                             (const T*)d_tiles, tiles_per_group, tile_elems, dark, (const float*)d_flat, d_scratch, d_max2);
+          return 0;
+        });
+        MG_CHECK_LAUNCH();
+        return MG_OK;
+      }
+      hipLaunchKernelGGL((k_flatfield_max_fast<T>), dim3(blocks, n_groups), dim3(256), 0, s, (const T*)d_tiles,
+                         tiles_per_group, tile_elems, dark, (const float*)d_flat, d_max2);
+      MG_CHECK_LAUNCH();
+      return MG_OK;
+    }
   }
   hipLaunchKernelGGL((k_flatfield_max<T>), dim3(blocks, n_groups), dim3(256), 0, s, (const T*)d_tiles, tiles_per_group,
                      tile_elems, dark, d_dark, dark_dt, flat, d_flat, flat_dt, d_max2);
@@ -713,59 +534,42 @@ int launch_max(const void* d_tiles, int64_t tiles_per_group, int n_groups, int64
   return MG_OK;
 }
 
+// Pass 2 for a source: the aligned kernel where it applies, else the generic one.  plane_mask != 0: a selection
+// (apply only).
 template <typename T>
-int launch_apply(const void* d_tiles, int64_t n_planes, int n_tr, int n_tc, int ty, int tx, int overlap, int apply,
-                 int planes_per_group, double dark, const void* d_dark, int dark_dt, double flat, const void* d_flat, int flat_dt,
-                 const double* d_max2, void* d_image, double* d_minmax, hipStream_t s, uint32_t plane_mask = 0) {
-  const auto [clip, hy, hx, h_out, w_out] = mg_stitch_geom(ty, tx, overlap, n_tr, n_tc);
-  if (n_planes == 0 || h_out == 0 || w_out == 0) return MG_OK;
+int launch_apply(const StitchSrc<T>& src, int64_t n_planes, int overlap, bool apply, void* d_image, double* d_minmax,
+                 hipStream_t s, uint32_t plane_mask = 0) {
+  const MgStitchGeom g = mg_stitch_geom(src.ty, src.tx, overlap, src.n_tr, src.n_tc);
+  if (n_planes == 0 || g.h_out == 0 || g.w_out == 0) return MG_OK;
   constexpr int N = VecOf<T>::N;
   if (n_planes > 0x7FFFFFF0) return MG_EINVAL;
-  // a selection (plane_mask != 0, apply only): from here on n_planes counts the selected planes, the kernels map them
+  // a selection: from here on n_planes counts the selected planes, the kernels map them
   const PlaneSel sel{plane_mask, __builtin_popcount(plane_mask)};
-  if (plane_mask) n_planes = n_planes / planes_per_group * sel.n_sel;
-  int rows;
-  const dim3 grid = stitch_grid<N>(h_out, w_out, n_planes, rows);
-  if (grid.y > 65535 || grid.z > 65535) return MG_EINVAL;
-  const bool aligned = IsIntegral<T>::value && hx % N == 0 && tx % N == 0 && clip % N == 0 &&
-                       (reinterpret_cast<uintptr_t>(d_tiles) & 15) == 0 && (reinterpret_cast<uintptr_t>(d_image) & 15) == 0 &&
-                       (!d_flat || (reinterpret_cast<uintptr_t>(d_flat) & 15) == 0) &&
-                       (!d_dark || (reinterpret_cast<uintptr_t>(d_dark) & 15) == 0);
-  if (aligned) {
-    // an integer-valued scalar dark inside the pixel range: subtracted in the integer domain
-    const bool int_dark = apply && dark_is_int(d_dark, dark);
-#define MG_ALIGNED(AP, ID, SUB) \
-    hipLaunchKernelGGL((k_apply_stitch_aligned<T, AP, ID, SUB>), grid, dim3(256), 0, s, (const T*)d_tiles, (int)n_planes, n_tr, \
-                       n_tc, ty, tx, clip, hy, hx, planes_per_group, dark, d_dark, dark_dt, flat, d_flat, flat_dt, \
-                       d_max2, (T*)d_image, d_minmax, rows, sel)
-    if (plane_mask && int_dark)
-      MG_ALIGNED(true, true, true);
-    else if (plane_mask)
-      MG_ALIGNED(true, false, true);
-    else if (!apply)
-      MG_ALIGNED(false, false, false);
-    else if (int_dark)
-      MG_ALIGNED(true, true, false);
-    else
-      MG_ALIGNED(true, false, false);
-#undef MG_ALIGNED
-    MG_CHECK_LAUNCH();
-    return MG_OK;
+  if (plane_mask) n_planes = n_planes / src.planes_per_group * sel.n_sel;
+  if constexpr (IsIntegral<T>::value) {
+    const bool aligned = g.hx % N == 0 && src.tx % N == 0 && g.clip % N == 0 && aligned16(src.tiles) && aligned16(d_image) &&
+                         (!src.d_flat || aligned16(src.d_flat)) && (!src.d_dark || aligned16(src.d_dark));
+    if (aligned) {
+      int rows;
+      const dim3 grid = stitch_grid<N>(g.h_out, g.w_out, n_planes, rows);
+      if (grid.y > 65535 || grid.z > 65535) return MG_EINVAL;
+      // an integer-valued scalar dark inside the pixel range: subtracted in the integer domain
+      const bool int_dark = apply && dark_is_int(src.d_dark, src.dark);
+      auto launch = [&](auto ap, auto id, auto sub) {
+        hipLaunchKernelGGL((k_apply_stitch_aligned<T, decltype(ap)::value, decltype(id)::value, decltype(sub)::value>), grid,
+                           dim3(256), 0, s, src, (int)n_planes, g.clip, g.hy, g.hx, (T*)d_image, d_minmax, rows, sel);
+        MG_CHECK_LAUNCH();
+        return (int)MG_OK;
+      };
+      if (!apply) return launch(std::false_type{}, std::false_type{}, std::false_type{});
+      return with_flag(int_dark, [&](auto id) {
+        return with_flag(plane_mask != 0, [&](auto sub) { return launch(std::true_type{}, id, sub); });
+      });
+    }
   }
-  if (plane_mask)
-    hipLaunchKernelGGL((k_apply_stitch<T, true, true>), grid, dim3(256), 0, s, (const T*)d_tiles, (int)n_planes, n_tr, n_tc,
-                       ty, tx, clip, hy, hx, planes_per_group, dark, d_dark, dark_dt, flat, d_flat, flat_dt, d_max2,
-                       (T*)d_image, d_minmax, rows, sel);
-  else if (apply)
-    hipLaunchKernelGGL((k_apply_stitch<T, true>), grid, dim3(256), 0, s, (const T*)d_tiles, (int)n_planes, n_tr, n_tc,
-                       ty, tx, clip, hy, hx, planes_per_group, dark, d_dark, dark_dt, flat, d_flat, flat_dt, d_max2,
-                       (T*)d_image, d_minmax, rows, sel);
-  else
-    hipLaunchKernelGGL((k_apply_stitch<T, false>), grid, dim3(256), 0, s, (const T*)d_tiles, (int)n_planes, n_tr, n_tc,
-                       ty, tx, clip, hy, hx, planes_per_group, dark, d_dark, dark_dt, flat, d_flat, flat_dt, d_max2,
-                       (T*)d_image, d_minmax, rows, sel);
-  MG_CHECK_LAUNCH();
-  return MG_OK;
+  if (plane_mask) return launch_stitch<BL_FLAT, false, true>(src, n_planes, overlap, sel, d_image, d_minmax, s);
+  if (apply) return launch_stitch<BL_FLAT, false, false>(src, n_planes, overlap, sel, d_image, d_minmax, s);
+  return launch_stitch<BL_COPY, false, false>(src, n_planes, overlap, sel, d_image, d_minmax, s);
 }
 
 template <typename T>
@@ -780,7 +584,11 @@ int launch_minmax(const void* d_src, int n_planes, int64_t plane_stride, int h, 
   return MG_OK;
 }
 
-bool df_dtype_ok(const void* p, int dt) { return p == nullptr || dt == MG_F32 || dt == MG_F64; }
+// The chunk of the flat image one entry of mg_flatfield_bound's scratch stands for: that of the integer fast path
+// of pass 1 (the only one that uses the scratch), 0 for the other pixel types.
+constexpr int bound_chunk(int dtype) {
+  return dtype == MG_U8 ? VecOf<uint8_t>::N : dtype == MG_U16 ? VecOf<uint16_t>::N : 0;
+}
 
 }  // namespace
 
@@ -788,7 +596,7 @@ extern "C" int mg_version(void) { return 1; }
 
 extern "C" int64_t mg_flatfield_max_scratch_floats(int dtype, int ty, int tx) {
   if (ty <= 0 || tx <= 0) return -1;
-  const int n = dtype == MG_U8 ? 16 : dtype == MG_U16 ? 8 : 0;  // (only the integer fast path uses the scratch)
+  const int n = bound_chunk(dtype);
   return n ? ((int64_t)ty * tx + n - 1) / n : 0;
 }
 
@@ -797,19 +605,23 @@ extern "C" int mg_flatfield_bound(const void* d_flat, int flat_dtype, int dtype,
   if (!d_flat || !d_scratch || ty <= 0 || tx <= 0 || flat_dtype != MG_F32) return MG_EINVAL;
   const int64_t need = mg_flatfield_max_scratch_floats(dtype, ty, tx);
   const int64_t tile_elems = (int64_t)ty * tx;
-  const int n = dtype == MG_U8 ? 16 : dtype == MG_U16 ? 8 : 0;
-  if (need <= 0 || scratch_floats < need || tile_elems % n || (reinterpret_cast<uintptr_t>(d_flat) & 15) ||
+  if (need <= 0 || scratch_floats < need || tile_elems % bound_chunk(dtype) || !aligned16(d_flat) ||
       (reinterpret_cast<uintptr_t>(d_scratch) & 3))
     return MG_EINVAL;
   hipStream_t s = mg_stream(stream);
-  const int64_t cvec = tile_elems / n;
-  const dim3 grid((unsigned)std::min<int64_t>((cvec + 255) / 256, 2048));
-  if (n == 16)
-    hipLaunchKernelGGL((k_flat_rcmax<16>), grid, dim3(256), 0, s, (const float*)d_flat, cvec, d_scratch);
-  else
-    hipLaunchKernelGGL((k_flat_rcmax<8>), grid, dim3(256), 0, s, (const float*)d_flat, cvec, d_scratch);
-  MG_CHECK_LAUNCH();
-  return MG_OK;
+  return mg_dispatch_pixel(dtype, [&](auto t) {
+    using T = decltype(t);
+    if constexpr (IsIntegral<T>::value) {  // (need > 0: an integer pixel type)
+      constexpr int N = VecOf<T>::N;
+      const int64_t cvec = tile_elems / N;
+      const dim3 grid((unsigned)std::min<int64_t>((cvec + 255) / 256, 2048));
+      hipLaunchKernelGGL((k_flat_rcmax<N>), grid, dim3(256), 0, s, (const float*)d_flat, cvec, d_scratch);
+      MG_CHECK_LAUNCH();
+      return (int)MG_OK;
+    } else {
+      return (int)MG_EINVAL;
+    }
+  });
 }
 
 extern "C" int mg_flatfield_max(const void* d_tiles, int dtype, int64_t n_tiles, int n_groups, int ty, int tx,
@@ -817,7 +629,7 @@ extern "C" int mg_flatfield_max(const void* d_tiles, int dtype, int64_t n_tiles,
                                 int flat_dtype, double* d_max2, float* d_scratch, int64_t scratch_floats, void* stream) {
   if (!d_tiles || !d_max2 || n_tiles < 0 || ty <= 0 || tx <= 0 || n_groups <= 0 || n_groups > 65535) return MG_EINVAL;
   if (n_tiles % n_groups) return MG_EINVAL;
-  if (!df_dtype_ok(d_dark, dark_dtype) || !df_dtype_ok(d_flat, flat_dtype)) return MG_EINVAL;
+  if (!field_dtype_ok(d_dark, dark_dtype) || !field_dtype_ok(d_flat, flat_dtype)) return MG_EINVAL;
   const int64_t tile_elems = (int64_t)ty * tx, tpg = n_tiles / n_groups;
   hipStream_t s = mg_stream(stream);
   return mg_dispatch_pixel(dtype, [&](auto t) {
@@ -835,22 +647,14 @@ extern "C" int mg_flatfield_apply_stitch(const void* d_tiles, int dtype, int64_t
                                          int planes_per_group, double dark, const void* d_dark, int dark_dtype,
                                          double flat, const void* d_flat, int flat_dtype, const double* d_max2,
                                          void* d_image, double* d_minmax, void* stream) {
-  if (!d_tiles || !d_image || n_planes < 0 || n_tile_rows <= 0 || n_tile_cols <= 0 || ty <= 0 || tx <= 0)
-    return MG_EINVAL;
+  if (n_tile_rows <= 0 || n_tile_cols <= 0 || ty <= 0 || tx <= 0) return MG_EINVAL;
   if (overlap < 0 || overlap >= ty || overlap >= tx) return MG_EINVAL;
-  // Integer pixels, dark 0 and flat 1 (the reference's defaults, preprocess.py:62): ((t / 1) * M1) / M2 with
-  // M2 = M1 / 1 is t itself -- the product of two integers below 2^16 is exact in float64 and so is its quotient by
-  // one of them; an all-zero group gives 0 either way (NaN -> 0).  Every pixel would otherwise take the exact
-  // two-division path (its fast result is an integer), 2.3x the time of a copy.
-  if (apply_flatfield && mg_flatfield_is_identity(dtype, dark, d_dark, flat, d_flat)) apply_flatfield = 0;
-  if (apply_flatfield && (!d_max2 || planes_per_group <= 0)) return MG_EINVAL;
-  if (!df_dtype_ok(d_dark, dark_dtype) || !df_dtype_ok(d_flat, flat_dtype)) return MG_EINVAL;
   hipStream_t s = mg_stream(stream);
-  return mg_dispatch_pixel(dtype, [&](auto t) {
-    return launch_apply<decltype(t)>(d_tiles, n_planes, n_tile_rows, n_tile_cols, ty, tx, overlap, apply_flatfield,
-                                     planes_per_group > 0 ? planes_per_group : 1, dark, d_dark, dark_dtype, flat, d_flat,
-                                     flat_dtype, d_max2, d_image, d_minmax, s);
-  });
+  return flatfield_stitch_entry(
+      d_tiles, dtype, n_planes, n_tile_rows, n_tile_cols, ty, tx, apply_flatfield, planes_per_group, dark, d_dark, dark_dtype,
+      flat, d_flat, flat_dtype, d_max2, d_image, [&](const auto& src, auto mode) {
+        return launch_apply(src, n_planes, overlap, decltype(mode)::value == BL_FLAT, d_image, d_minmax, s);
+      });
 }
 
 extern "C" int mg_flatfield_apply_stitch_planes(const void* d_tiles, int dtype, int64_t n_planes, int n_tile_rows,
@@ -864,15 +668,16 @@ extern "C" int mg_flatfield_apply_stitch_planes(const void* d_tiles, int dtype, 
   if (planes_per_group <= 0 || planes_per_group > 31 || n_planes % planes_per_group || plane_mask < 0 ||
       (plane_mask >> planes_per_group))
     return MG_EINVAL;
-  if (!df_dtype_ok(d_dark, dark_dtype) || !df_dtype_ok(d_flat, flat_dtype)) return MG_EINVAL;
+  if (!field_dtype_ok(d_dark, dark_dtype) || !field_dtype_ok(d_flat, flat_dtype)) return MG_EINVAL;
   if (plane_mask == 0) return MG_OK;  // nothing selected
   hipStream_t s = mg_stream(stream);
   // (no identity shortcut: the selected planes always go through the correction's arithmetic, whose result for the
   // identity operands is the pixel itself)
   return mg_dispatch_pixel(dtype, [&](auto t) {
-    return launch_apply<decltype(t)>(d_tiles, n_planes, n_tile_rows, n_tile_cols, ty, tx, overlap, 1, planes_per_group,
-                                     dark, d_dark, dark_dtype, flat, d_flat, flat_dtype, d_max2, d_image, d_minmax, s,
-                                     (uint32_t)plane_mask);
+    using T = decltype(t);
+    const StitchSrc<T> src{(const T*)d_tiles, n_tile_rows, n_tile_cols, ty, tx, planes_per_group,
+                           dark, d_dark, dark_dtype, flat, d_flat, flat_dtype, d_max2};
+    return launch_apply(src, n_planes, overlap, true, d_image, d_minmax, s, (uint32_t)plane_mask);
   });
 }
 

@@ -267,16 +267,16 @@ struct ShiftTable {
 
 // What the plain pass writes for pixel (y, x) of tile (tr, tc) moved by its shift: edge replication at the borders.
 template <typename T, int MODE>
-__device__ __forceinline__ T shifted_value(const BlendSrc<T>& s, const int32_t* __restrict__ table, int plane, int tr,
-                                           int tc, int y, int x, double m1, double m2, double kk, bool fast_ok) {
+__device__ __forceinline__ T shifted_value(const StitchSrc<T>& s, const int32_t* __restrict__ table, int plane, int tr,
+                                           int tc, int y, int x, const GroupMax& g) {
   const int32_t* e = table + 2 * (tr * s.n_tc + tc);
   const int yy = min(max(y - e[0], 0), s.ty - 1), xx = min(max(x - e[1], 0), s.tx - 1);
-  return tile_value<T, MODE>(s, plane, tr, tc, yy, xx, m1, m2, kk, fast_ok);
+  return tile_value<T, MODE>(s, plane, tr, tc, yy, xx, g);
 }
 
-// The grid and the chunks of k_blend_stitch (mg_blend.hip); every pixel of a chunk is fetched on its own.
+// The grid and the chunks of k_stitch (mg_stitch_kernel.h); every pixel of a chunk is fetched on its own.
 template <typename T, int MODE, bool BLEND>
-__global__ __launch_bounds__(256) void k_shift_stitch(BlendSrc<T> s, ShiftTable st, int n_planes, int v, int hy, int hx,
+__global__ __launch_bounds__(256) void k_shift_stitch(StitchSrc<T> s, ShiftTable st, int n_planes, int v, int hy, int hx,
                                                        T* __restrict__ image, double* __restrict__ d_minmax,
                                                        int rows_per_block) {
   constexpr int N = VecOf<T>::N;
@@ -287,10 +287,7 @@ __global__ __launch_bounds__(256) void k_shift_stitch(BlendSrc<T> s, ShiftTable 
   const int np = min(PB, n_planes - plane0);
   const int h_out = n_tr * hy, w_out = n_tc * hx;
   const int ox0 = (blockIdx.x * blockDim.x + threadIdx.x) * N;
-  double vmin[PB], vmax[PB];
-  uint32_t imin[PB], imax[PB];
-#pragma unroll
-  for (int b = 0; b < PB; ++b) vmin[b] = INFINITY, vmax[b] = -INFINITY, imin[b] = 0xFFFFFFFFu, imax[b] = 0u;
+  PlaneMinMax<T, PB> mm;
   if (ox0 < w_out) {
     const int cnt = min(N, w_out - ox0);
     for (int yg = blockIdx.y; yg * rows_per_block < h_out; yg += gridDim.y) {
@@ -303,96 +300,53 @@ __global__ __launch_bounds__(256) void k_shift_stitch(BlendSrc<T> s, ShiftTable 
 #pragma unroll 1
         for (int b = 0; b < np; ++b) {
           const int plane = plane0 + b;
-          double m1 = 0.0, m2 = 1.0, kk = 1.0;
-          bool fast_ok = false;
-          if (MODE == BL_FLAT) {
-            const int group = plane / s.planes_per_group;
-            m1 = s.d_max2[2 * group];
-            m2 = s.d_max2[2 * group + 1];
-            fast_ok = group_quotient(m1, m2, kk);
-          }
+          GroupMax g;
+          if (MODE == BL_FLAT) g = group_maxima(s.d_max2, plane, s.planes_per_group);
           const int32_t* table = st.shift + (st.n_tables == 1 ? 0 : (int64_t)(plane % st.n_time) * n_tr * n_tc * 2);
           T o[N];
 #pragma unroll
           for (int j = 0; j < N; ++j) {
             const int ox = ox0 + min(j, cnt - 1), tc = ox / hx, x = ox - tc * hx + clip;
-            T c00 = shifted_value<T, MODE>(s, table, plane, tr, tc, y, x, m1, m2, kk, fast_ok);
+            T c00 = shifted_value<T, MODE>(s, table, plane, tr, tc, y, x, g);
             if (BLEND) {
               int oth_x, nx;
               axis_term(ax, tc, x - clip, oth_x, nx);
               if (oth_x != 0 || oth_y != 0) {
                 const int tr1 = tr + oth_y, y1 = y - oth_y * hy, tc1 = tc + oth_x, x1 = x - oth_x * hx;
                 T c01 = (T)0, c10 = (T)0, c11 = (T)0;
-                if (oth_x != 0) c01 = shifted_value<T, MODE>(s, table, plane, tr, tc1, y, x1, m1, m2, kk, fast_ok);
-                if (oth_y != 0) c10 = shifted_value<T, MODE>(s, table, plane, tr1, tc, y1, x, m1, m2, kk, fast_ok);
-                if (oth_x != 0 && oth_y != 0)
-                  c11 = shifted_value<T, MODE>(s, table, plane, tr1, tc1, y1, x1, m1, m2, kk, fast_ok);
+                if (oth_x != 0) c01 = shifted_value<T, MODE>(s, table, plane, tr, tc1, y, x1, g);
+                if (oth_y != 0) c10 = shifted_value<T, MODE>(s, table, plane, tr1, tc, y1, x, g);
+                if (oth_x != 0 && oth_y != 0) c11 = shifted_value<T, MODE>(s, table, plane, tr1, tc1, y1, x1, g);
                 c00 = mix_tiles<T>(c00, c01, c10, c11, oth_x != 0, oth_y != 0, nx, ny, v);
               }
             }
             o[j] = c00;
           }
-          if (d_minmax) {
-            // the chunk's own min / max first, then into plane b's slot with selects (b is a loop variable: indexing
-            // the register arrays with it would move them to scratch memory)
-            double lo = INFINITY, hi = -INFINITY;
-            uint32_t ilo = 0xFFFFFFFFu, ihi = 0u;
-#pragma unroll
-            for (int j = 0; j < N; ++j) {
-              if (j >= cnt) break;
-              if (IsIntegral<T>::value) {
-                ilo = min(ilo, (uint32_t)o[j]);
-                ihi = max(ihi, (uint32_t)o[j]);
-              } else {
-                lo = mg_nanmin(lo, (double)o[j]);
-                hi = mg_nanmax(hi, (double)o[j]);
-              }
-            }
-#pragma unroll
-            for (int bb = 0; bb < PB; ++bb) {
-              if (bb != b) continue;
-              if (IsIntegral<T>::value) {
-                imin[bb] = min(imin[bb], ilo);
-                imax[bb] = max(imax[bb], ihi);
-              } else {
-                vmin[bb] = mg_nanmin(vmin[bb], lo);
-                vmax[bb] = mg_nanmax(vmax[bb], hi);
-              }
-            }
-          }
-          T* dst = image + ((int64_t)plane * h_out + oy) * w_out + ox0;
-          if (cnt == N) {
-            store_vec<T, N>(dst, o);
-          } else {
-            for (int j = 0; j < cnt; ++j) dst[j] = o[j];
-          }
+          if (d_minmax) mm.add_select(b, o, cnt);  // (b is a loop variable)
+          store_chunk<T, N>(image + ((int64_t)plane * h_out + oy) * w_out + ox0, o, cnt);
         }
       }
     }
   }
-  if (d_minmax) mg_block_minmax<PB>(vmin, vmax, imin, imax, np, d_minmax, plane0);
+  if (d_minmax) mm.flush(np, d_minmax, plane0);
 }
 
-template <typename T, int MODE>
-int launch_shift(const BlendSrc<T>& src, const ShiftTable& st, int64_t n_planes, int overlap, int blend, void* d_image,
+template <int MODE, typename T>
+int launch_shift(const StitchSrc<T>& src, const ShiftTable& st, int64_t n_planes, int overlap, int blend, void* d_image,
                  double* d_minmax, hipStream_t s) {
-  const auto [clip, hy, hx, h_out, w_out] = mg_stitch_geom(src.ty, src.tx, overlap, src.n_tr, src.n_tc);
-  (void)clip;
-  if (n_planes == 0 || h_out == 0 || w_out == 0) return MG_OK;
+  const MgStitchGeom g = mg_stitch_geom(src.ty, src.tx, overlap, src.n_tr, src.n_tc);
+  if (n_planes == 0 || g.h_out == 0 || g.w_out == 0) return MG_OK;
   int rows;
-  const dim3 grid = stitch_grid<VecOf<T>::N>(h_out, w_out, n_planes, rows);
+  const dim3 grid = stitch_grid<VecOf<T>::N>(g.h_out, g.w_out, n_planes, rows);
   if (grid.y > 65535 || grid.z > 65535) return MG_EINVAL;
-  if (blend)
-    hipLaunchKernelGGL((k_shift_stitch<T, MODE, true>), grid, dim3(256), 0, s, src, st, (int)n_planes, overlap, hy, hx,
-                       (T*)d_image, d_minmax, rows);
-  else
-    hipLaunchKernelGGL((k_shift_stitch<T, MODE, false>), grid, dim3(256), 0, s, src, st, (int)n_planes, overlap, hy, hx,
-                       (T*)d_image, d_minmax, rows);
-  MG_CHECK_LAUNCH();
-  return MG_OK;
+  return with_flag(blend, [&](auto bl) {
+    hipLaunchKernelGGL((k_shift_stitch<T, MODE, decltype(bl)::value>), grid, dim3(256), 0, s, src, st, (int)n_planes, overlap,
+                       g.hy, g.hx, (T*)d_image, d_minmax, rows);
+    MG_CHECK_LAUNCH();
+    return (int)MG_OK;
+  });
 }
 
-inline bool shift_field_dtype_ok(const void* p, int dt) { return p == nullptr || dt == MG_F32 || dt == MG_F64; }
 inline bool shift_shape_ok(int n_tr, int n_tc, int ty, int tx, int overlap, int blend) {
   // blend: 2 overlap <= tile, as mg_flatfield_apply_stitch_blend; else the plain pass's overlap < tile
   if (!(n_tr > 0 && n_tc > 0 && ty > 0 && tx > 0 && overlap >= 0 && (blend == 0 || blend == 1))) return false;
@@ -455,39 +409,32 @@ extern "C" int mg_flatfield_apply_stitch_shift(const void* d_tiles, int dtype, i
                                                double flat, const void* d_flat, int flat_dtype, const double* d_max2,
                                                void* d_image, double* d_minmax, const int32_t* d_shift, int n_tables,
                                                int n_time, int blend, void* stream) {
-  if (!d_tiles || !d_image || n_planes < 0 || !shift_shape_ok(n_tile_rows, n_tile_cols, ty, tx, overlap, blend))
-    return MG_EINVAL;
-  if (apply_flatfield && mg_flatfield_is_identity(dtype, dark, d_dark, flat, d_flat)) apply_flatfield = 0;
-  if (apply_flatfield && (!d_max2 || planes_per_group <= 0)) return MG_EINVAL;
-  if (!shift_field_dtype_ok(d_dark, dark_dtype) || !shift_field_dtype_ok(d_flat, flat_dtype)) return MG_EINVAL;
+  if (!shift_shape_ok(n_tile_rows, n_tile_cols, ty, tx, overlap, blend)) return MG_EINVAL;
   hipStream_t s = mg_stream(stream);
-  if (const int rc = shift_tables_ok(d_shift, n_tables, n_time, n_planes, n_tile_rows, n_tile_cols, overlap, s)) return rc;
   const ShiftTable st{d_shift, n_tables, n_time};
-  return mg_dispatch_pixel(dtype, [&](auto t) {
-    using T = decltype(t);
-    const BlendSrc<T> src{(const T*)d_tiles, n_tile_rows, n_tile_cols, ty, tx, planes_per_group > 0 ? planes_per_group : 1,
-                          dark, d_dark, dark_dtype, flat, d_flat, flat_dtype, d_max2};
-    return apply_flatfield ? launch_shift<T, BL_FLAT>(src, st, n_planes, overlap, blend, d_image, d_minmax, s)
-                           : launch_shift<T, BL_COPY>(src, st, n_planes, overlap, blend, d_image, d_minmax, s);
-  });
+  return flatfield_stitch_entry(
+      d_tiles, dtype, n_planes, n_tile_rows, n_tile_cols, ty, tx, apply_flatfield, planes_per_group, dark, d_dark, dark_dtype,
+      flat, d_flat, flat_dtype, d_max2, d_image, [&](const auto& src, auto mode) {
+        // (the tables are read back only for a call whose other arguments are in order)
+        if (const int rc = shift_tables_ok(d_shift, n_tables, n_time, n_planes, n_tile_rows, n_tile_cols, overlap, s)) return rc;
+        return launch_shift<decltype(mode)::value>(src, st, n_planes, overlap, blend, d_image, d_minmax, s);
+      });
 }
 
 extern "C" int mg_shading_apply_stitch_shift(const void* d_tiles, int dtype, int n_fields, int64_t planes_per_field,
                                              int n_tile_rows, int n_tile_cols, int ty, int tx, int overlap,
                                              const float* d_flat, const float* d_dark, void* d_image, double* d_minmax,
                                              const int32_t* d_shift, int n_tables, int n_time, int blend, void* stream) {
-  if (!d_tiles || !d_image || !d_flat || !d_dark || n_fields < 1 || planes_per_field < 0 || planes_per_field > 0x7FFFFFF0 ||
-      !shift_shape_ok(n_tile_rows, n_tile_cols, ty, tx, overlap, blend))
-    return MG_EINVAL;
+  if (!shift_shape_ok(n_tile_rows, n_tile_cols, ty, tx, overlap, blend)) return MG_EINVAL;
   hipStream_t s = mg_stream(stream);
-  const int64_t n_planes = (int64_t)n_fields * planes_per_field;
-  if (const int rc = shift_tables_ok(d_shift, n_tables, n_time, n_planes, n_tile_rows, n_tile_cols, overlap, s)) return rc;
-  if (planes_per_field == 0) return MG_OK;
   const ShiftTable st{d_shift, n_tables, n_time};
-  return mg_dispatch_pixel(dtype, [&](auto t) {
-    using T = decltype(t);
-    const BlendSrc<T> src{(const T*)d_tiles, n_tile_rows, n_tile_cols, ty, tx, (int)planes_per_field,
-                          0.0, d_dark, MG_F32, 1.0, d_flat, MG_F32, nullptr};
-    return launch_shift<T, BL_SHADE>(src, st, n_planes, overlap, blend, d_image, d_minmax, s);
-  });
+  return shading_stitch_entry(
+      d_tiles, dtype, n_fields, planes_per_field, n_tile_rows, n_tile_cols, ty, tx, d_flat, d_dark, d_image,
+      [&] {  // (after the argument checks, before an empty stack is answered: the tables, as the flat-field entry)
+        return shift_tables_ok(d_shift, n_tables, n_time, (int64_t)n_fields * planes_per_field, n_tile_rows, n_tile_cols,
+                               overlap, s);
+      },
+      [&](const auto& src, int64_t n_planes) {
+        return launch_shift<BL_SHADE>(src, st, n_planes, overlap, blend, d_image, d_minmax, s);
+      });
 }

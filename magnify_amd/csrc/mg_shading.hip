@@ -13,6 +13,7 @@
 
 #include "mg_common.h"
 #include "mg_shadeop.h"
+#include "mg_stitch.h"
 
 namespace {
 
@@ -457,8 +458,7 @@ __global__ __launch_bounds__(256) void k_shading_apply(const T* __restrict__ til
   const int h_out = n_tr * hy, w_out = n_tc * hx;
   T* dst_plane = image + plane * h_out * w_out;
   const int ox0 = (blockIdx.x * blockDim.x + threadIdx.x) * SH_APPLY_VEC;
-  uint32_t imin = 0xFFFFFFFFu, imax = 0u;
-  double vmin = INFINITY, vmax = -INFINITY;
+  PlaneMinMax<T, 1> mm;
   int64_t col_off[SH_APPLY_VEC];  // tile column offset + x inside the tile, per lane pixel
   int xin[SH_APPLY_VEC];          // x inside the tile
   int cnt = 0;
@@ -487,22 +487,14 @@ __global__ __launch_bounds__(256) void k_shading_apply(const T* __restrict__ til
         for (int j = 0; j < SH_APPLY_VEC; ++j) {
           if (j >= cnt) break;
           o[j] = ShadeOp<T>::apply(src[row_src + col_off[j]], dk[row_fld + xin[j]], fl[row_fld + xin[j]]);
-          if (d_minmax) {
-            if (ShadeOp<T>::kInt) {
-              imin = min(imin, (uint32_t)o[j]);
-              imax = max(imax, (uint32_t)o[j]);
-            } else {
-              vmin = mg_nanmin(vmin, (double)o[j]);
-              vmax = mg_nanmax(vmax, (double)o[j]);
-            }
-          }
+          if (d_minmax) mm.add(0, o[j]);
         }
         T* dst = dst_plane + (int64_t)oy * w_out + ox0;
         for (int j = 0; j < cnt; ++j) dst[j] = o[j];
       }
     }
   if (!d_minmax) return;
-  mg_block_minmax<1>(&vmin, &vmax, &imin, &imax, 1, d_minmax, plane);
+  mm.flush(1, d_minmax, plane);
 }
 
 template <typename T>

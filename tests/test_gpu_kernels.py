@@ -1024,6 +1024,63 @@ def test_flatfield_many_plane_groups(hp, dark):
             np.testing.assert_array_equal(mm[:, 1], want.max(axis=(-1, -2)))
 
 
+@pytest.mark.parametrize("shape,dtype,overlap", [((5, 4, 2, 2, 33, 47), np.uint16, 3), ((5, 4, 2, 2, 33, 47), np.float32, 3),
+                                                 ((5, 4, 2, 2, 64, 64), np.uint16, 16)])
+def test_flatfield_selected_planes_complete_the_full_pass(hp, shape, dtype, overlap):
+    """mg_flatfield_apply_stitch_planes through the generic kernel (odd tile widths) and through the aligned one (64 x 64,
+    overlap 16): planes 1, 2, 4 of every group of 5 -- 12 selected planes, one workgroup block of 8 and one of 4 -- land
+    in their place, everything else in `out` and `minmax_out` is left alone; the complementary selection then completes
+    both to what the full pass writes, byte for byte."""
+    rng = np.random.default_rng(41)
+    c, t, nr, nc, ty, tx = shape
+    tiles = rng.integers(0, 60000, size=shape).astype(dtype) if np.dtype(dtype).kind == "u" else (rng.random(shape) * 4000).astype(dtype)
+    flat = (0.6 + 0.8 * rng.random((ty, tx))).astype(np.float32)
+    dark, ppg, mask = 7.0, 5, 0b10110
+    d_tiles = dev(tiles)
+    max2 = hp.flatfield_max(d_tiles, flat, dark, n_groups=4)
+    want_img, want_mm = hp.flatfield_stitch(d_tiles, overlap, flat, dark, max2=max2, n_groups=4)
+    want_img, want_mm = want_img.cpu().numpy(), want_mm.cpu().numpy()
+    sentinel = 54321 if np.dtype(dtype).kind == "u" else -12345.0
+    out = torch.full(want_img.shape, sentinel, dtype=d_tiles.dtype, device="cuda")
+    minmax = torch.empty((c * t, 2), dtype=torch.float64, device="cuda")
+    hp.flatfield_apply_planes(d_tiles, overlap, flat, dark, max2, mask, ppg, out, minmax)
+    selected = np.array([(mask >> (p % ppg)) & 1 for p in range(c * t)], dtype=bool)
+    assert selected.sum() == 12
+    got, mm = out.cpu().numpy().reshape((c * t,) + want_img.shape[2:]), minmax.cpu().numpy()
+    want_planes = want_img.reshape(got.shape)
+    np.testing.assert_array_equal(got[selected], want_planes[selected])
+    np.testing.assert_array_equal(mm[selected], want_mm[selected])
+    assert (got[~selected] == sentinel).all()
+    assert (mm[~selected, 0] == np.inf).all() and (mm[~selected, 1] == -np.inf).all()
+    hp.flatfield_apply_planes(d_tiles, overlap, flat, dark, max2, (~mask) & 0b11111, ppg, out, minmax, init_minmax=False)
+    assert out.cpu().numpy().tobytes() == want_img.tobytes()
+    assert minmax.cpu().numpy().tobytes() == want_mm.tobytes()
+
+
+@pytest.mark.parametrize("dtype", [np.uint8, np.uint16])
+def test_flatfield_max_without_scratch(hp, dtype):
+    """Pass 1 as a C caller without scratch gets it (k_flatfield_max_fast): 3 groups of 5 tiles -- not a multiple of the
+    four tiles per trip --, a float32 flat image with a 0 and an inf (outside the reciprocal's range), scalar dark.  The
+    maxima are, bit for bit, those of hotpath.flatfield_max (which bounds the image first), and NumPy's."""
+    from magnify_amd import _native as nat
+
+    rng = np.random.default_rng(43)
+    tiles = rng.integers(0, 256 if dtype == np.uint8 else 60000, size=(3, 5, 1, 1, 40, 48)).astype(dtype)
+    flat = (0.6 + 0.8 * rng.random((40, 48))).astype(np.float32)
+    flat[7, 11], flat[30, 5] = 0.0, np.inf
+    d_tiles, d_flat = dev(tiles), dev(flat)
+    max2 = torch.full((3, 2), -np.inf, dtype=torch.float64, device="cuda")
+    nat.check(nat.lib().mg_flatfield_max(d_tiles.data_ptr(), nat.dtype_code(d_tiles.dtype), 15, 3, 40, 48, 100.0, 0, 0, 0.0,
+                                         d_flat.data_ptr(), nat.MG_F32, max2.data_ptr(), 0, 0, hp._stream()), "mg_flatfield_max")
+    got = max2.cpu().numpy()
+    lean = hp.flatfield_max(d_tiles, d_flat, 100.0, 3).cpu().numpy()
+    assert got.tobytes() == lean.tobytes(), (got, lean)
+    tt = np.maximum(tiles.astype(np.float64) - 100.0, 0.0).reshape(3, 5, 40, 48)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        want = np.stack([tt.max(axis=(1, 2, 3)), (tt / flat.astype(np.float64)).max(axis=(1, 2, 3))], axis=1)
+    np.testing.assert_array_equal(got, want)
+
+
 @pytest.mark.parametrize("dtype", [np.uint8, np.uint16, np.float32, np.float64])
 def test_masked_median_types_and_time_masks(hp, dtype):
     """mg_roi_masked_median (identify.py:76-80, filter.py:20-22, 74, 82): every roi dtype the path carries, a mask per
