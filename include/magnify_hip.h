@@ -169,6 +169,29 @@ int mg_seam_sums(const void* d_planes, int dtype, int64_t n_planes, int n_tile_r
                  int overlap, int max_shift, void* d_sums, void* d_fixed, void* d_scratch, int64_t scratch_bytes,
                  void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * find_beads: following beads through time (find.py:564-602 cuts every timepoint's ROI at the time-0 position,
+ * find.py:564: "TODO: Don't assume beads don't move across timesteps")
+ * ---------------------------------------------------------------------------------- */
+
+/* d_planes: the n_t planes (h, w) of ONE channel, plane t at d_planes + t * plane_stride elements of `dtype`.
+ * d_beads (m, 3): row, col, r.  With md = max_drift, W = 2 md + 1, per bead g and timepoint t:
+ *   patch: the pixels (y, x) with |y - row| <= half, |x - col| <= half, md <= y < h - md, md <= x < w - md (n of
+ *   them, possibly none); B = plane[t_ref] on the patch, A(y, x) = plane[t][y + dy, x + dx] for (dy, dx) in [-md, md]^2;
+ *   d_fixed (m, 3), optional: n, sum B, sum B^2;
+ *   d_sums (m, n_t, W, W, 3), optional: sum A, sum A^2, sum A B at [dy + md][dx + md] (row t_ref: A = B's plane);
+ *   int64 (exact) for MG_U8 / MG_U16, float64 for MG_F32 / MG_F64, the same bits on every call (no atomics);
+ *   z = (n sAB - sA sB) / sqrt((n sAA - sA^2) (n sBB - sB^2)) in float64, each operation rounded on its own, IEEE
+ *   division and square root; 0 where a variance term is <= 0 or z is not finite;
+ *   d_shift (m, n_t, 2), d_score (m, n_t): the (dy, dx) of the largest z -- ties to the smallest dy^2 + dx^2, then
+ *   the smallest dy, then the smallest dx -- and that z; row t_ref: (0, 0) and 1.0.
+ * MG_EINVAL unless 1 <= max_drift <= 16, 1 <= half, 2 half + 1 <= 95, 2 half + 1 + 2 max_drift <= 127,
+ * 0 <= t_ref < n_t, h, w > 0 (and m >= 0, m n_t < 2^31, no null pointer among planes, beads, shift, score); nothing
+ * is launched then.  m == 0: MG_OK, nothing to write.  One kernel launch; no allocation, no synchronisation. */
+int mg_track_beads(const void* d_planes, int dtype, int n_t, int64_t plane_stride, int h, int w, int t_ref,
+                   const int32_t* d_beads, int m, int half, int max_drift, int32_t* d_shift, double* d_score,
+                   void* d_sums, void* d_fixed, void* stream);
+
 /* Per-plane min/max (utils.py:24-25) of strided planes.  d_minmax double[n_planes][2],
  * pre-initialised to {+inf, -inf}.  Strides are in elements. */
 int mg_plane_minmax(const void* d_src, int dtype, int n_planes, int64_t plane_stride, int h, int w,

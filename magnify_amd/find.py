@@ -9,7 +9,7 @@ import math
 import numpy as np
 import torch
 
-from . import hotpath, preprocess, registry, utils
+from . import hotpath, preprocess, registry, track as tracking, utils
 from .stack import dedup_against
 from .xr_lite import DataArray
 
@@ -53,9 +53,27 @@ def _plane_minmax(assay, image, idx):
     return None
 
 
+def tracked_roi_pass(image, tables, L):
+    """Windows, masks and masked sums with a bead table per timepoint: image (C, T, H, W) on the device, tables
+    (T, M, 3) [row, col, r] -> roi (M, C, T, L, L), fg / bg (M, T, L, L) uint8, sums (M, C, T, 2), counts (M, T, 2).
+    The image is read where it lies, as C T single-plane assays of the ROI pass (mg_roi_segment_reduce, assay (c, t)
+    with the table of t); the pass's marker-major outputs are then permuted once into the (mark, channel, time) layout
+    ("find_beads: following beads through time", has what that costs)."""
+    n_c, n_t, h, w = image.shape
+    m = tables.shape[1]
+    out = hotpath.roi_gather_reduce(image.view(n_c * n_t, 1, 1, h, w), [tables[t] for _ in range(n_c) for t in range(n_t)],
+                                    L, None, disks=True)
+    per_time = lambda x: x[: n_t * m].view((n_t, m) + tuple(x.shape[1:])).transpose(0, 1).contiguous()  # noqa: E731
+    return {"roi": out["roi"].view(n_c, n_t, m, L, L).permute(2, 0, 1, 3, 4).contiguous(),
+            "sums": out["sums"].view(n_c, n_t, m, 2).permute(2, 0, 1, 3).contiguous(),
+            # masks and counts are the same for every channel: those of the first
+            "fg": per_time(out["fg"]), "bg": per_time(out["bg"]), "counts": per_time(out["counts"])}
+
+
 class BeadFinder:
     def __init__(self, min_bead_diameter, max_bead_diameter, low_edge_quantile, high_edge_quantile, num_iter,
-                 min_roundness, roi_length, search_channel, interactive):
+                 min_roundness, roi_length, search_channel, interactive, track=None, max_drift=8, track_min_score=0.5,
+                 track_channel=None, track_patch=None):
         if min_bead_diameter > max_bead_diameter:
             raise ValueError("min_bead_diameter must be <= max_bead_diameter.")
         if interactive:
@@ -68,6 +86,26 @@ class BeadFinder:
         self.min_roundness = min_roundness
         self.roi_length = roi_length if roi_length is not None else 2 * max_bead_diameter
         self.search_channels = utils.to_list(search_channel)
+        # following the beads through time (not in the reference: track.py); None: the time-0 geometry at every timepoint
+        self.track, self.max_drift, self.track_min_score = track, max_drift, track_min_score
+        self.track_channel, self.track_patch = track_channel, track_patch
+        tracking.check_track(track, max_drift)
+        if track is not None:
+            tracking.check_track(track, max_drift, self.max_bead_radius + 2 if track_patch is None else track_patch)
+
+    def _follow(self, assay, image, beads):
+        """``track="ncc"``: the beads of time 0 followed through the timepoints of the tracking channel
+        (track.track_beads), then windows, masks and sums per timepoint from that timepoint's bead table
+        (tracked_roi_pass)."""
+        h, w = image.shape[2:]
+        ch = _channel_index(assay, self.search_channels[0] if self.track_channel is None else self.track_channel)
+        half = self.max_bead_radius + 2 if self.track_patch is None else self.track_patch
+        res = tracking.track_beads(image[ch], beads, half, self.max_drift)
+        shift, score = res["shift"].cpu().numpy(), res["score"].cpu().numpy()
+        tables, followed = tracking.tracked_tables(beads, shift, score, self.track_min_score, h, w)
+        out = tracked_roi_pass(image, tables, self.roi_length)
+        out.update(tables=tables, followed=followed, shift=shift, score=score)
+        return out
 
     def __call__(self, assay):
         """find.py:471-605."""
@@ -79,7 +117,8 @@ class BeadFinder:
         beads = np.empty((0, 3), dtype=np.int32)
         finder = _finder(1, h, w, self.min_bead_radius, self.max_bead_radius, self.num_iter, image.device)
         m, L = None, self.roi_length
-        if len(self.search_channels) == 1:
+        followed = None
+        if len(self.search_channels) == 1 and self.track is None:
             # one search channel (nothing to de-duplicate across channels, find.py:490-500): the ROI pass reads the
             # bead table where the suppression left it on the device; the host copy of the table runs beside it
             ch = _channel_index(assay, self.search_channels[0])
@@ -101,36 +140,56 @@ class BeadFinder:
                 beads = np.concatenate([beads, b])
             # masks straight from the bead table (what utils.circle_labels + the == i / == -1 tests yield,
             # find.py:561-586) -- no label map is written or read
-            out = hotpath.roi_gather_reduce(image[None], [beads], L, None, disks=True)
+            if self.track is None:
+                out = hotpath.roi_gather_reduce(image[None], [beads], L, None, disks=True)
+            else:
+                out = followed = self._follow(assay, image, beads)
         m = len(beads)
         # the kernel writes 0 / 1 bytes: reinterpreted as bool, not converted (two passes over M L^2 bytes less)
-        fg = out["fg"].view(torch.bool)[:, None].expand(m, n_t, L, L)  # geometry replicated over time (find.py:585-586)
-        bg = out["bg"].view(torch.bool)[:, None].expand(m, n_t, L, L)
+        if followed is None:
+            fg = out["fg"].view(torch.bool)[:, None].expand(m, n_t, L, L)  # geometry replicated over time (find.py:585-586)
+            bg = out["bg"].view(torch.bool)[:, None].expand(m, n_t, L, L)
+        else:
+            fg, bg = out["fg"].view(torch.bool), out["bg"].view(torch.bool)  # (mark, time, L, L): every timepoint's own
         # the reference's chunk policy (find.py:506-531): every channel / timepoint of a marker together, markers per
         # chunk for >= 1 MB; recorded on the variables (xr_lite.DataArray.chunk: what to_xarray / mg.save go by)
         per = {"mark": utils.roi_mark_chunk(m, n_c, n_t, L)}
         assay["roi"] = DataArray(out["roi"], ("mark", "channel", "time", "roi_y", "roi_x")).chunk(per)
         xy = beads.astype(np.float64)
+        if followed is None:
+            x, y = np.repeat(xy[:, None, 1], n_t, axis=1), np.repeat(xy[:, None, 0], n_t, axis=1)
+            valid = np.ones((m, n_t), dtype=bool)
+        else:
+            x, y = followed["tables"][..., 1].T.astype(np.float64), followed["tables"][..., 0].T.astype(np.float64)
+            valid = followed["followed"]
         assay = assay.assign_coords(
             fg=DataArray(fg, ("mark", "time", "roi_y", "roi_x")).chunk(per),
             bg=DataArray(bg, ("mark", "time", "roi_y", "roi_x")).chunk(per),
-            x=(("mark", "time"), np.repeat(xy[:, None, 1], n_t, axis=1)),
-            y=(("mark", "time"), np.repeat(xy[:, None, 0], n_t, axis=1)),
-            valid=(("mark", "time"), np.ones((m, n_t), dtype=bool)),
+            x=(("mark", "time"), x),
+            y=(("mark", "time"), y),
+            valid=(("mark", "time"), valid),
         )
+        if followed is not None:
+            assay = assay.assign_coords(
+                track_shift_y=(("mark", "time"), np.ascontiguousarray(followed["shift"][..., 0])),
+                track_shift_x=(("mark", "time"), np.ascontiguousarray(followed["shift"][..., 1])),
+                track_score=(("mark", "time"), followed["score"]),
+            )
         # extras (not in the reference's schema): the fused masked reductions and the bead radii
         assay._cache["roi_sums"] = out["sums"]      # (mark, channel, time, {fg, bg}) float64
-        assay._cache["roi_counts"] = out["counts"]  # (mark, {fg, bg}) int32
+        assay._cache["roi_counts"] = out["counts"]  # (mark, {fg, bg}) int32; tracked: (mark, time, {fg, bg})
         assay._cache["radius"] = beads[:, 2].copy()
         return assay
 
     @registry.components.register("find_beads")
     def make(min_bead_diameter, max_bead_diameter, low_edge_quantile, high_edge_quantile, num_iter, min_roundness,
-             roi_length, search_channel, interactive):
+             roi_length, search_channel, interactive, track=None, max_drift=8, track_min_score=0.5, track_channel=None,
+             track_patch=None):
         return BeadFinder(min_bead_diameter=min_bead_diameter, max_bead_diameter=max_bead_diameter,
                           low_edge_quantile=low_edge_quantile, high_edge_quantile=high_edge_quantile,
                           num_iter=num_iter, min_roundness=min_roundness, roi_length=roi_length,
-                          search_channel=search_channel, interactive=interactive)
+                          search_channel=search_channel, interactive=interactive, track=track, max_drift=max_drift,
+                          track_min_score=track_min_score, track_channel=track_channel, track_patch=track_patch)
 
 
 # --------------------------------------------------------------------------------------

@@ -51,6 +51,8 @@ def counts(xp, mask="fg"):
     cached = xp._cache.get("roi_counts")
     n_t = xp.sizes.get("time", 1)
     if cached is not None and mask in ("fg", "bg") and "mark" in xp.sizes and cached.shape[0] == xp.sizes["mark"]:
+        if cached.dim() == 3:  # (mark, time, 2): beads followed through time have masks of their own per timepoint
+            return DataArray(cached[..., 0 if mask == "fg" else 1].to(torch.int64), ("mark", "time"))
         return DataArray(cached[:, 0 if mask == "fg" else 1].to(torch.int64)[:, None].expand(-1, n_t), ("mark", "time"))
     return DataArray(_sums_counts(xp, mask)[1], ("mark", "time"))
 

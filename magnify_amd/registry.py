@@ -132,7 +132,8 @@ def microfluidic_chip_pipe(shape=(8, 8), pinlist=None, blank=None, overlap=102, 
 def mrbles(data, spectra, codes, flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=10, max_bead_diameter=50,
            low_edge_quantile=0.1, high_edge_quantile=0.9, num_iter=5000000, min_roundness=0.3, roi_length=None,
            search_channel=None, reference="eu", roi_only=False, drop_tiles=True, interactive=False, blend=None,
-           register=None, max_shift=8, register_channel=None):
+           register=None, max_shift=8, register_channel=None,
+           track=None, max_drift=8, track_min_score=0.5, track_channel=None, track_patch=None):
     """registry.py:274-399."""
     kw = dict(locals())
     kw.pop("data")
@@ -142,7 +143,8 @@ def mrbles(data, spectra, codes, flatfield=1.0, darkfield=0.0, overlap=102, min_
 def mrbles_pipe(spectra, codes, flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=10, max_bead_diameter=50,
                 low_edge_quantile=0.1, high_edge_quantile=0.9, num_iter=5000000, min_roundness=0.3, roi_length=None,
                 search_channel=None, reference="eu", roi_only=False, drop_tiles=True, interactive=False, blend=None,
-                register=None, max_shift=8, register_channel=None):
+                register=None, max_shift=8, register_channel=None,
+                track=None, max_drift=8, track_min_score=0.5, track_channel=None, track_patch=None):
     """registry.py:402-451."""
     pipe = Pipeline("read")
     pipe.add_pipe("standardize_format")
@@ -152,7 +154,8 @@ def mrbles_pipe(spectra, codes, flatfield=1.0, darkfield=0.0, overlap=102, min_b
     pipe.add_pipe("find_beads", min_bead_diameter=min_bead_diameter, max_bead_diameter=max_bead_diameter,
                   low_edge_quantile=low_edge_quantile, high_edge_quantile=high_edge_quantile, num_iter=num_iter,
                   min_roundness=min_roundness, roi_length=roi_length, search_channel=search_channel,
-                  interactive=interactive)
+                  interactive=interactive, track=track, max_drift=max_drift, track_min_score=track_min_score,
+                  track_channel=track_channel, track_patch=track_patch)
     pipe.add_pipe("identify_mrbles", spectra=spectra, codes=codes, reference=reference)
     pipe.add_pipe("drop", roi_only=roi_only, drop_tiles=drop_tiles)
     pipe.add_pipe("restore_format")
@@ -162,7 +165,8 @@ def mrbles_pipe(spectra, codes, flatfield=1.0, darkfield=0.0, overlap=102, min_b
 def beads(data, flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=10, max_bead_diameter=50,
           low_edge_quantile=0.1, high_edge_quantile=0.9, num_iter=5000000, min_roundness=0.3, roi_length=None,
           search_channel=None, roi_only=False, drop_tiles=True, interactive=False, blend=None,
-          register=None, max_shift=8, register_channel=None):
+          register=None, max_shift=8, register_channel=None,
+          track=None, max_drift=8, track_min_score=0.5, track_channel=None, track_patch=None):
     """registry.py:454-565."""
     kw = dict(locals())
     kw.pop("data")
@@ -172,7 +176,8 @@ def beads(data, flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=10,
 def beads_pipe(flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=5, max_bead_diameter=25,
                low_edge_quantile=0.1, high_edge_quantile=0.9, num_iter=5000000, min_roundness=0.3, roi_length=None,
                search_channel=None, roi_only=False, drop_tiles=True, interactive=False, blend=None,
-               register=None, max_shift=8, register_channel=None):
+               register=None, max_shift=8, register_channel=None,
+               track=None, max_drift=8, track_min_score=0.5, track_channel=None, track_patch=None):
     """registry.py:568-612 (note the 5/25 defaults here versus 10/50 in ``beads``)."""
     pipe = Pipeline("read")
     pipe.add_pipe("standardize_format")
@@ -182,7 +187,8 @@ def beads_pipe(flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=5, m
     pipe.add_pipe("find_beads", min_bead_diameter=min_bead_diameter, max_bead_diameter=max_bead_diameter,
                   low_edge_quantile=low_edge_quantile, high_edge_quantile=high_edge_quantile, num_iter=num_iter,
                   min_roundness=min_roundness, roi_length=roi_length, search_channel=search_channel,
-                  interactive=interactive)
+                  interactive=interactive, track=track, max_drift=max_drift, track_min_score=track_min_score,
+                  track_channel=track_channel, track_patch=track_patch)
     pipe.add_pipe("drop", roi_only=roi_only, drop_tiles=drop_tiles)
     pipe.add_pipe("restore_format")
     return pipe
