@@ -192,6 +192,33 @@ int mg_track_beads(const void* d_planes, int dtype, int n_t, int64_t plane_strid
                    const int32_t* d_beads, int m, int half, int max_drift, int32_t* d_shift, double* d_score,
                    void* d_sums, void* d_fixed, void* stream);
 
+/* mg_track_beads around a per-timepoint base offset (find_beads(track="ncc", stage_drift=D): the stage moved, every
+ * bead of timepoint t with it).  d_base (n_t, 2): (by, bx) of every timepoint; row t_ref ignores its base.  The
+ * contract of mg_track_beads holds with these differences:
+ *   patch of (g, t): the pixels (y, x) with |y - row| <= half, |x - col| <= half, 0 <= y < h, 0 <= x < w,
+ *   md <= y + by < h - md, md <= x + bx < w - md -- the template and every displaced read inside the image; n now
+ *   depends on t.  The geometry is made in 64 bits: a base far outside the image gives an empty patch;
+ *   A(y, x) = plane[t][y + by + dy, x + bx + dx] for (dy, dx) in [-md, md]^2;
+ *   d_fixed (m, n_t, 3), optional: n, sum B, sum B^2 of the patch of (g, t); d_sums as for mg_track_beads;
+ *   d_shift[g, t] = (by + dy, bx + dx), the total displacement (the tie-breaks are on (dy, dx)); row t_ref: (0, 0)
+ *   and 1.0; an empty patch: (0, 0) and 0.
+ * With an all-zero base d_shift, d_score and d_sums equal those of mg_track_beads bit for bit and d_fixed[g, t] its
+ * d_fixed[g] for every t.  MG_EINVAL where mg_track_beads returns it, and for a null d_base; nothing is launched then.
+ * One kernel launch; no allocation, no synchronisation. */
+int mg_track_beads_based(const void* d_planes, int dtype, int n_t, int64_t plane_stride, int h, int w, int t_ref,
+                         const int32_t* d_beads, int m, int half, int max_drift, const int32_t* d_base,
+                         int32_t* d_shift, double* d_score, void* d_sums, void* d_fixed, void* stream);
+
+/* Binned planes (the coarse view of find_beads(stage_drift=D)).  d_planes: n_t planes (h, w) of `dtype`, plane t at
+ * d_planes + t * plane_stride elements.  d_out (n_t, hb, wb) contiguous float32, hb = h / bin, wb = w / bin:
+ * out[t, i, j] = the sum of the bin x bin block at (bin i, bin j) of plane t; the trailing h % bin rows and w % bin
+ * columns are not read.  MG_U8 / MG_U16: exact (64 * 65535 < 2^24).  MG_F32 / MG_F64: summed in float64 -- the
+ * block's rows from the top, each from the left -- and rounded to float32 once: the same bits on every call.  No
+ * atomics.  MG_EINVAL, with nothing launched: bin not in {2, 4, 8}, h < bin, w < bin, n_t < 1, an unknown dtype, a
+ * null pointer.  One kernel launch; no allocation, no synchronisation. */
+int mg_bin_planes(const void* d_planes, int dtype, int n_t, int64_t plane_stride, int h, int w, int bin,
+                  float* d_out, void* stream);
+
 /* Per-plane min/max (utils.py:24-25) of strided planes.  d_minmax double[n_planes][2],
  * pre-initialised to {+inf, -inf}.  Strides are in elements. */
 int mg_plane_minmax(const void* d_src, int dtype, int n_planes, int64_t plane_stride, int h, int w,

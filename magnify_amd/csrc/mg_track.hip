@@ -41,6 +41,15 @@
 // displacement are added in k order through LDS, the scores are made and the best one is picked with a total order
 // (so the reduction tree does not matter).
 //
+// mg_track_beads_based ("find_beads: following a stage that moved") is the same kernel, instantiated with
+// BASED: the search of timepoint t is centred on base[t] = (by, bx) -- the offset the whole stage moved by, found on
+// binned planes (mg_bin.hip, track.stage_drift).  The patch of (bead, t) is then also cut to the image itself and to
+// md <= y + by < h - md, md <= x + bx < w - md (in 64 bits: a base far outside the image leaves no pixel), so n and
+// `fixed` are per (bead, t); A(y, x) = plane[t][y + by + dy, x + bx + dx]; the shift written is (by + dy, bx + dx);
+// row t_ref ignores its base.  With an all-zero base every number is the plain instantiation's.  The plain
+// instantiation compiles to the resources it had before the flag (117 VGPRs, 112 for float64 pixels; no scratch),
+// the based one to 121 (117).
+//
 // Roofline: VALU (float64 FMA), not HBM: n W^2 multiply-adds per (bead, timepoint) against (pw + 2 md)^2 + pw^2
 // pixels read once (DESIGN.md has the measured rates).
 #include <math.h>
@@ -104,12 +113,15 @@ __device__ __forceinline__ bool trk_better(double za, int da, double zb, int db,
   return xa < xb;
 }
 
-// grid (bead * n_t + t)
-template <typename T>
+// grid (bead * n_t + t).  BASED (mg_track_beads_based): the search of timepoint t is centred on base[t] = (by, bx), the
+// patch is also cut to where the displaced reads stay inside the image (so n depends on t) and `fixed` has a row per
+// (bead, t); with an all-zero base every number is the one the plain instantiation makes.
+template <typename T, bool BASED>
 __global__ __launch_bounds__(256) void k_track(const T* __restrict__ planes, TrackGeom g, const int32_t* __restrict__ beads,
                                                int32_t* __restrict__ shift, double* __restrict__ score,
                                                typename TrackTypes<T>::Out* __restrict__ sums,
-                                               typename TrackTypes<T>::Out* __restrict__ fixed) {
+                                               typename TrackTypes<T>::Out* __restrict__ fixed,
+                                               const int32_t* __restrict__ base) {
   using L = typename TrackTypes<T>::L;
   using Out = typename TrackTypes<T>::Out;
   constexpr int R = TRK_R;
@@ -128,8 +140,18 @@ __global__ __launch_bounds__(256) void k_track(const T* __restrict__ planes, Tra
   }
   // the patch: rows [y0, y0 + ph), columns [x0, x0 + pw)
   const long long row = beads[3 * bead], col = beads[3 * bead + 1];
-  const long long y0l = max(row - g.half, (long long)md), y1l = min(row + g.half, (long long)g.h - md - 1);
-  const long long x0l = max(col - g.half, (long long)md), x1l = min(col + g.half, (long long)g.w - md - 1);
+  long long y0l = max(row - g.half, (long long)md), y1l = min(row + g.half, (long long)g.h - md - 1);
+  long long x0l = max(col - g.half, (long long)md), x1l = min(col + g.half, (long long)g.w - md - 1);
+  long long by = 0, bx = 0;
+  if constexpr (BASED) {
+    if (!is_ref) by = base[2 * t], bx = base[2 * t + 1];  // (row t_ref ignores its base)
+    // inside the image, and md <= y + by < h - md, md <= x + bx < w - md; in 64 bits: a base far outside the image
+    // leaves no pixel
+    y0l = max(max(row - g.half, 0LL), md - by), y1l = min(min(row + g.half, (long long)g.h - 1), (long long)g.h - md - 1 - by);
+    x0l = max(max(col - g.half, 0LL), md - bx), x1l = min(min(col + g.half, (long long)g.w - 1), (long long)g.w - md - 1 - bx);
+  }
+  // where `fixed` of this (bead, t) goes, if anywhere
+  Out* out_fixed = !fixed ? nullptr : BASED ? fixed + 3 * slot : is_ref ? fixed + 3 * (int64_t)bead : nullptr;
   const int ph = (int)max(0LL, y1l - y0l + 1), pw = (int)max(0LL, x1l - x0l + 1);
   const int n = ph * pw;
   Out* out_sums = sums ? sums + slot * D * 3 : nullptr;
@@ -138,11 +160,12 @@ __global__ __launch_bounds__(256) void k_track(const T* __restrict__ planes, Tra
       for (int e = tid; e < D * 3; e += 256) out_sums[e] = (Out)0;
     if (tid == 0) {
       shift[2 * slot] = 0, shift[2 * slot + 1] = 0, score[slot] = is_ref ? 1.0 : 0.0;
-      if (fixed && is_ref) fixed[3 * bead] = (Out)0, fixed[3 * bead + 1] = (Out)0, fixed[3 * bead + 2] = (Out)0;
+      if (out_fixed) out_fixed[0] = (Out)0, out_fixed[1] = (Out)0, out_fixed[2] = (Out)0;
     }
     return;
   }
   const int y0 = (int)y0l, x0 = (int)x0l;
+  const int ay0 = BASED ? (int)(y0l + by) : y0, ax0 = BASED ? (int)(x0l + bx) : x0;  // the patch in plane t: in [md, . - md)
   const int S = g.S, stride = g.stride, K = g.K, NR = g.NR;
   // LDS: the box-sum table (S + 2 md, W, 2) float64, the window strip, the template strip; after the last strip the
   // row groups' partial sums (K, W, NR R) float64 from the start
@@ -168,7 +191,7 @@ __global__ __launch_bounds__(256) void k_track(const T* __restrict__ planes, Tra
     __syncthreads();  // the strip before has been read
     for (int e = tid; e < a_rows * a_cols; e += 256) {
       const int i = e / a_cols, j = e - i * a_cols;
-      sA[i * stride + j] = (L)A[(int64_t)(y0 + s0 - md + i) * g.w + (x0 - md + j)];
+      sA[i * stride + j] = (L)A[(int64_t)(ay0 + s0 - md + i) * g.w + (ax0 - md + j)];
     }
     double pb = 0.0, pbb = 0.0;
     for (int e = tid; e < sh * pw; e += 256) {
@@ -297,10 +320,10 @@ __global__ __launch_bounds__(256) void k_track(const T* __restrict__ planes, Tra
     for (int i = 1; i < MG_MINMAX_WAVES; ++i)
       if (trk_better(s_best_z[i], s_best_d[i], best_z, best_d, W, md)) best_z = s_best_z[i], best_d = s_best_d[i];
     const int dy = best_d / W, dx = best_d - dy * W;
-    shift[2 * slot] = is_ref ? 0 : dy - md;
-    shift[2 * slot + 1] = is_ref ? 0 : dx - md;
+    shift[2 * slot] = is_ref ? 0 : (int)by + dy - md;
+    shift[2 * slot + 1] = is_ref ? 0 : (int)bx + dx - md;
     score[slot] = is_ref ? 1.0 : best_z;
-    if (fixed && is_ref) fixed[3 * bead] = (Out)n, fixed[3 * bead + 1] = (Out)fb, fixed[3 * bead + 2] = (Out)fbb;
+    if (out_fixed) out_fixed[0] = (Out)n, out_fixed[1] = (Out)fb, out_fixed[2] = (Out)fbb;
   }
 }
 
@@ -329,11 +352,10 @@ inline bool track_layout(int elem, TrackGeom& g, size_t& lds_bytes) {
   return true;
 }
 
-}  // namespace
-
-extern "C" int mg_track_beads(const void* d_planes, int dtype, int n_t, int64_t plane_stride, int h, int w, int t_ref,
-                              const int32_t* d_beads, int m, int half, int max_drift, int32_t* d_shift, double* d_score,
-                              void* d_sums, void* d_fixed, void* stream) {
+// both entries: d_base null is the plain search around (0, 0)
+int track_launch(const void* d_planes, int dtype, int n_t, int64_t plane_stride, int h, int w, int t_ref, const int32_t* d_beads,
+                 int m, int half, int max_drift, const int32_t* d_base, int32_t* d_shift, double* d_score, void* d_sums,
+                 void* d_fixed, void* stream) {
   // Exactness of the integer sums in float64 and of n * sum in the score's int64 reading: the largest term is
   // n * sum A B <= 9025 * (9025 * 65535^2) = 9025^2 * 65535^2 < 2^63, a single sum <= 9025 * 65535^2 < 2^46.
   if (!(max_drift >= 1 && max_drift <= TRK_MAX_DRIFT && half >= 1 && 2 * (int64_t)half + 1 <= TRK_MAX_SIDE &&
@@ -349,9 +371,31 @@ extern "C" int mg_track_beads(const void* d_planes, int dtype, int n_t, int64_t 
     TrackGeom g{n_t, h, w, t_ref, half, max_drift, plane_stride, 0, 0, 0, 0};
     size_t lds = 0;
     if (!track_layout((int)sizeof(typename TrackTypes<T>::L), g, lds)) return (int)MG_EINVAL;
-    hipLaunchKernelGGL((k_track<T>), dim3((unsigned)((int64_t)m * n_t)), dim3(256), lds, s, (const T*)d_planes, g, d_beads,
-                       d_shift, d_score, (Out*)d_sums, (Out*)d_fixed);
+    const dim3 grid((unsigned)((int64_t)m * n_t));
+    if (d_base)
+      hipLaunchKernelGGL((k_track<T, true>), grid, dim3(256), lds, s, (const T*)d_planes, g, d_beads, d_shift, d_score,
+                         (Out*)d_sums, (Out*)d_fixed, d_base);
+    else
+      hipLaunchKernelGGL((k_track<T, false>), grid, dim3(256), lds, s, (const T*)d_planes, g, d_beads, d_shift, d_score,
+                         (Out*)d_sums, (Out*)d_fixed, d_base);
     MG_CHECK_LAUNCH();
     return (int)MG_OK;
   });
+}
+
+}  // namespace
+
+extern "C" int mg_track_beads(const void* d_planes, int dtype, int n_t, int64_t plane_stride, int h, int w, int t_ref,
+                              const int32_t* d_beads, int m, int half, int max_drift, int32_t* d_shift, double* d_score,
+                              void* d_sums, void* d_fixed, void* stream) {
+  return track_launch(d_planes, dtype, n_t, plane_stride, h, w, t_ref, d_beads, m, half, max_drift, nullptr, d_shift, d_score,
+                      d_sums, d_fixed, stream);
+}
+
+extern "C" int mg_track_beads_based(const void* d_planes, int dtype, int n_t, int64_t plane_stride, int h, int w, int t_ref,
+                                    const int32_t* d_beads, int m, int half, int max_drift, const int32_t* d_base,
+                                    int32_t* d_shift, double* d_score, void* d_sums, void* d_fixed, void* stream) {
+  if (!d_base && m > 0) return MG_EINVAL;
+  return track_launch(d_planes, dtype, n_t, plane_stride, h, w, t_ref, d_beads, m, half, max_drift, d_base, d_shift, d_score,
+                      d_sums, d_fixed, stream);
 }

@@ -73,7 +73,7 @@ def tracked_roi_pass(image, tables, L):
 class BeadFinder:
     def __init__(self, min_bead_diameter, max_bead_diameter, low_edge_quantile, high_edge_quantile, num_iter,
                  min_roundness, roi_length, search_channel, interactive, track=None, max_drift=8, track_min_score=0.5,
-                 track_channel=None, track_patch=None):
+                 track_channel=None, track_patch=None, stage_drift=None):
         if min_bead_diameter > max_bead_diameter:
             raise ValueError("min_bead_diameter must be <= max_bead_diameter.")
         if interactive:
@@ -92,19 +92,28 @@ class BeadFinder:
         tracking.check_track(track, max_drift)
         if track is not None:
             tracking.check_track(track, max_drift, self.max_bead_radius + 2 if track_patch is None else track_patch)
+        # the stage moved by up to stage_drift pixels between time 0 and a timepoint: the per-bead search starts at the
+        # offset the timepoint's anchors vote for (track.stage_drift)
+        self.stage_drift = stage_drift
+        tracking.check_stage_drift(stage_drift, track, max_drift)
 
     def _follow(self, assay, image, beads):
         """``track="ncc"``: the beads of time 0 followed through the timepoints of the tracking channel
         (track.track_beads), then windows, masks and sums per timepoint from that timepoint's bead table
-        (tracked_roi_pass)."""
+        (tracked_roi_pass).  With ``stage_drift`` every timepoint's search is centred on the offset its anchors vote for
+        (track.stage_drift); the shifts are then the total displacements."""
         h, w = image.shape[2:]
         ch = _channel_index(assay, self.search_channels[0] if self.track_channel is None else self.track_channel)
         half = self.max_bead_radius + 2 if self.track_patch is None else self.track_patch
-        res = tracking.track_beads(image[ch], beads, half, self.max_drift)
+        stage = None
+        if self.stage_drift is not None:
+            tracking.check_stage_drift(self.stage_drift, self.track, self.max_drift, (h, w))
+            stage = tracking.stage_drift(image[ch], self.stage_drift, self.track_min_score)
+        res = tracking.track_beads(image[ch], beads, half, self.max_drift, base=None if stage is None else stage["shift"])
         shift, score = res["shift"].cpu().numpy(), res["score"].cpu().numpy()
         tables, followed = tracking.tracked_tables(beads, shift, score, self.track_min_score, h, w)
         out = tracked_roi_pass(image, tables, self.roi_length)
-        out.update(tables=tables, followed=followed, shift=shift, score=score)
+        out.update(tables=tables, followed=followed, shift=shift, score=score, stage=stage)
         return out
 
     def __call__(self, assay):
@@ -175,6 +184,12 @@ class BeadFinder:
                 track_shift_x=(("mark", "time"), np.ascontiguousarray(followed["shift"][..., 1])),
                 track_score=(("mark", "time"), followed["score"]),
             )
+            if followed["stage"] is not None:
+                assay = assay.assign_coords(
+                    stage_shift_y=(("time",), np.ascontiguousarray(followed["stage"]["shift"][:, 0])),
+                    stage_shift_x=(("time",), np.ascontiguousarray(followed["stage"]["shift"][:, 1])),
+                    stage_agree=(("time",), followed["stage"]["agree"]),
+                )
         # extras (not in the reference's schema): the fused masked reductions and the bead radii
         assay._cache["roi_sums"] = out["sums"]      # (mark, channel, time, {fg, bg}) float64
         assay._cache["roi_counts"] = out["counts"]  # (mark, {fg, bg}) int32; tracked: (mark, time, {fg, bg})
@@ -184,12 +199,13 @@ class BeadFinder:
     @registry.components.register("find_beads")
     def make(min_bead_diameter, max_bead_diameter, low_edge_quantile, high_edge_quantile, num_iter, min_roundness,
              roi_length, search_channel, interactive, track=None, max_drift=8, track_min_score=0.5, track_channel=None,
-             track_patch=None):
+             track_patch=None, stage_drift=None):
         return BeadFinder(min_bead_diameter=min_bead_diameter, max_bead_diameter=max_bead_diameter,
                           low_edge_quantile=low_edge_quantile, high_edge_quantile=high_edge_quantile,
                           num_iter=num_iter, min_roundness=min_roundness, roi_length=roi_length,
                           search_channel=search_channel, interactive=interactive, track=track, max_drift=max_drift,
-                          track_min_score=track_min_score, track_channel=track_channel, track_patch=track_patch)
+                          track_min_score=track_min_score, track_channel=track_channel, track_patch=track_patch,
+                          stage_drift=stage_drift)
 
 
 # --------------------------------------------------------------------------------------

@@ -133,7 +133,8 @@ def mrbles(data, spectra, codes, flatfield=1.0, darkfield=0.0, overlap=102, min_
            low_edge_quantile=0.1, high_edge_quantile=0.9, num_iter=5000000, min_roundness=0.3, roi_length=None,
            search_channel=None, reference="eu", roi_only=False, drop_tiles=True, interactive=False, blend=None,
            register=None, max_shift=8, register_channel=None,
-           track=None, max_drift=8, track_min_score=0.5, track_channel=None, track_patch=None):
+           track=None, max_drift=8, track_min_score=0.5, track_channel=None, track_patch=None,
+           stage_drift=None):
     """registry.py:274-399."""
     kw = dict(locals())
     kw.pop("data")
@@ -144,7 +145,8 @@ def mrbles_pipe(spectra, codes, flatfield=1.0, darkfield=0.0, overlap=102, min_b
                 low_edge_quantile=0.1, high_edge_quantile=0.9, num_iter=5000000, min_roundness=0.3, roi_length=None,
                 search_channel=None, reference="eu", roi_only=False, drop_tiles=True, interactive=False, blend=None,
                 register=None, max_shift=8, register_channel=None,
-                track=None, max_drift=8, track_min_score=0.5, track_channel=None, track_patch=None):
+                track=None, max_drift=8, track_min_score=0.5, track_channel=None, track_patch=None,
+                stage_drift=None):
     """registry.py:402-451."""
     pipe = Pipeline("read")
     pipe.add_pipe("standardize_format")
@@ -155,7 +157,7 @@ def mrbles_pipe(spectra, codes, flatfield=1.0, darkfield=0.0, overlap=102, min_b
                   low_edge_quantile=low_edge_quantile, high_edge_quantile=high_edge_quantile, num_iter=num_iter,
                   min_roundness=min_roundness, roi_length=roi_length, search_channel=search_channel,
                   interactive=interactive, track=track, max_drift=max_drift, track_min_score=track_min_score,
-                  track_channel=track_channel, track_patch=track_patch)
+                  track_channel=track_channel, track_patch=track_patch, stage_drift=stage_drift)
     pipe.add_pipe("identify_mrbles", spectra=spectra, codes=codes, reference=reference)
     pipe.add_pipe("drop", roi_only=roi_only, drop_tiles=drop_tiles)
     pipe.add_pipe("restore_format")
@@ -166,7 +168,8 @@ def beads(data, flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=10,
           low_edge_quantile=0.1, high_edge_quantile=0.9, num_iter=5000000, min_roundness=0.3, roi_length=None,
           search_channel=None, roi_only=False, drop_tiles=True, interactive=False, blend=None,
           register=None, max_shift=8, register_channel=None,
-          track=None, max_drift=8, track_min_score=0.5, track_channel=None, track_patch=None):
+          track=None, max_drift=8, track_min_score=0.5, track_channel=None, track_patch=None,
+          stage_drift=None):
     """registry.py:454-565."""
     kw = dict(locals())
     kw.pop("data")
@@ -177,7 +180,8 @@ def beads_pipe(flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=5, m
                low_edge_quantile=0.1, high_edge_quantile=0.9, num_iter=5000000, min_roundness=0.3, roi_length=None,
                search_channel=None, roi_only=False, drop_tiles=True, interactive=False, blend=None,
                register=None, max_shift=8, register_channel=None,
-               track=None, max_drift=8, track_min_score=0.5, track_channel=None, track_patch=None):
+               track=None, max_drift=8, track_min_score=0.5, track_channel=None, track_patch=None,
+               stage_drift=None):
     """registry.py:568-612 (note the 5/25 defaults here versus 10/50 in ``beads``)."""
     pipe = Pipeline("read")
     pipe.add_pipe("standardize_format")
@@ -188,7 +192,7 @@ def beads_pipe(flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=5, m
                   low_edge_quantile=low_edge_quantile, high_edge_quantile=high_edge_quantile, num_iter=num_iter,
                   min_roundness=min_roundness, roi_length=roi_length, search_channel=search_channel,
                   interactive=interactive, track=track, max_drift=max_drift, track_min_score=track_min_score,
-                  track_channel=track_channel, track_patch=track_patch)
+                  track_channel=track_channel, track_patch=track_patch, stage_drift=stage_drift)
     pipe.add_pipe("drop", roi_only=roi_only, drop_tiles=drop_tiles)
     pipe.add_pipe("restore_format")
     return pipe
