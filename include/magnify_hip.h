@@ -606,23 +606,18 @@ int mg_collect_circles(const int32_t* d_circles, int64_t circle_cap, const float
 
 /* circle_labels as a coverage count: d_labels[n_planes][h][w] int32 pre-set to -1;
  * beads d_beads[n_planes][bead_cap][3] (row, col, r), d_num_beads[n_planes];
- * d_halfwidths[(max_r+1)][2*max_r+1] from mg_disk_halfwidths (row r of the table).
- * reset != 0 writes -1 back under the same disks instead (the map is clean again for reuse). */
+ * d_halfwidths[(max_r+1)][2*max_r+1] from mg_disk_halfwidths (row r of the table). */
 int mg_circle_labels(const int32_t* d_beads, int64_t bead_cap, const int32_t* d_num_beads, int n_planes, int h,
-                     int w, const int32_t* d_halfwidths, int max_r, int32_t* d_labels, int reset, void* stream);
+                     int w, const int32_t* d_halfwidths, int max_r, int32_t* d_labels, void* stream);
 
-/* ROI gather + masks + reductions for one assay.  image (C, T, h, w) of dtype (u8/u16/f32);
+/* ROI gather + masks + reductions from a label map.  Every assay's image (C, T, h, w) of dtype (u8/u16/f32);
  * beads (m, 3) with labels from time 0; window = bounding_box(col, row, L, w, h).
+ * Marker g belongs to assay d_marker_assay[g] (image base + assay * assay_stride
+ * elements, labels base + assay * h * w) and owns label value d_marker_local[g].  Both index
+ * arrays may be NULL (single assay, local index = g).  d_beads is (m, 3) for all markers.
  * Outputs: roi (m, C, T, L, L) same dtype; fg, bg (m, L, L) uint8 {0,1};
  * sums double[m][C][T][2] = {sum over fg, sum over bg} (exact for integer dtypes below 2^53),
  * counts int32[m][2] = {|fg|, |bg|}.  Any output pointer may be NULL. */
-int mg_roi_gather_reduce(const void* d_image, int dtype, int n_c, int n_t, int h, int w, const int32_t* d_beads,
-                         int m, int roi_len, const int32_t* d_labels, void* d_roi, uint8_t* d_fg, uint8_t* d_bg,
-                         double* d_sums, int32_t* d_counts, void* stream);
-
-/* Batched form: marker g belongs to assay d_marker_assay[g] (image base + assay * assay_stride
- * elements, labels base + assay * h * w) and owns label value d_marker_local[g].  Both index
- * arrays may be NULL (single assay, local index = g).  d_beads is (m, 3) for all markers. */
 int mg_roi_gather_reduce_batched(const void* d_image, int dtype, int64_t assay_stride, int n_c, int n_t, int h, int w,
                                  const int32_t* d_beads, const int32_t* d_marker_assay,
                                  const int32_t* d_marker_local, int m, int roi_len, const int32_t* d_labels,
@@ -657,7 +652,7 @@ int mg_marker_table(const int32_t* d_beads, int64_t bead_stride, const int32_t* 
  * is still fetching them); the outputs are compact either way.  time_major != 0: every assay's image
  * block is stored (n_t, n_c, h, w) instead of (n_c, n_t, h, w) -- a time-sharded single assay is gathered
  * where the flat-field pass left it, without a transposing copy; the outputs stay (channel, time)-ordered.
- * Outputs as mg_roi_gather_reduce. */
+ * Outputs as mg_roi_gather_reduce_batched. */
 int mg_roi_segment_reduce(const void* d_image, int dtype, int64_t assay_stride, int n_c, int n_t, int h, int w,
                           int time_major, const int32_t* d_beads, int64_t bead_stride, const int32_t* d_assay_offsets,
                           int n_assays, int m, const int32_t* d_order, int roi_len, const int32_t* d_halfwidths, int max_r,
@@ -696,9 +691,6 @@ int mg_roi_window_order(const int32_t* d_beads, int64_t bead_stride, const int32
  * d_median double[m][C][T].  Exact: radix select on the order-preserving bit pattern of the values. */
 int mg_roi_masked_median(const void* d_roi, int dtype, const uint8_t* d_mask, int64_t mask_stride_m,
                          int64_t mask_stride_t, int m, int n_c, int n_t, int roi_len, double* d_median, void* stream);
-/* The same for uint16 rois under one mask (m, L, L) for all timepoints. */
-int mg_roi_masked_median_u16(const uint16_t* d_roi, const uint8_t* d_mask, int m, int n_c, int n_t, int roi_len,
-                             double* d_median, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * A16 / A17 ButtonFinder helpers (find.py:205-402, 632-677)

@@ -5,8 +5,6 @@
 // bytes (u16); the reductions ride along in registers (wavefront shuffles), 0 extra bytes.
 #include <math.h>
 
-#include <stdlib.h>
-
 #include "mg_common.h"
 #include "mg_flatcorr.h"
 
@@ -18,7 +16,7 @@ constexpr int NT = 256;
 __global__ __launch_bounds__(NT) void k_circle_labels(const int32_t* __restrict__ d_beads, int64_t bead_cap,
                                                       const int32_t* __restrict__ d_num_beads, int h, int w,
                                                       const int32_t* __restrict__ d_halfwidths, int max_r,
-                                                      int32_t* __restrict__ d_labels, int reset) {
+                                                      int32_t* __restrict__ d_labels) {
   const int plane = blockIdx.y;
   const int i = blockIdx.x;
   if (i >= d_num_beads[plane]) return;
@@ -34,10 +32,6 @@ __global__ __launch_bounds__(NT) void k_circle_labels(const int32_t* __restrict_
     const int y = row + dy, x = col + dx;
     if (y < 0 || y >= h || x < 0 || x >= w) continue;
     int32_t* cell = &lab[(int64_t)y * w + x];
-    if (reset) {  // restore the "nobody" value under this disk (lets the caller reuse the map)
-      *cell = -1;
-      continue;
-    }
     const int old = atomicCAS(cell, -1, i);
     if (old != -1 && old != i) *cell = -2;  // a second owner: contested
   }
@@ -360,7 +354,7 @@ __device__ __forceinline__ uint32_t roi_correct_dword(uint32_t d, uint32_t dark_
 // Registers: 62 VGPRs / 8 waves per SIMD without FUSE; the float64 correction brings the fused variants to 97 (4 waves)
 // when the compiler is left alone, 89 without scratch when asked for 5 -- asked for 6 it spills 11 registers.  The
 // hint leaves the plain variant's code as it was.
-template <int U, int CTB, bool PIPE, int FUSE = 0>
+template <int FUSE>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(5, 8))) void k_roi_u16_even(const uint16_t* __restrict__ d_image, int64_t assay_stride,
                                                      int n_c, int n_t, int h, int w,
                                                      const int32_t* __restrict__ d_beads,
@@ -375,6 +369,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(5, 8))) void
                                                      int32_t* __restrict__ d_counts, RoiRaw rw) {
   extern __shared__ __attribute__((aligned(4))) uint8_t smem[];  // three bit-row arrays of len x wpr words
   constexpr int WV = NT / 64;
+  constexpr int U = 2, CTB = 4;  // window rows per wave and (channel, time) planes per trip (alternatives: roi_dispatch)
   __shared__ uint32_t s_red[2][CTB][WV];
   __shared__ int s_cnt[2][WV];
   RoiMarker mk;  // one block per marker
@@ -487,9 +482,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(5, 8))) void
     float2 ff[U], fn[U];
     load_rows(wave, dd, ff);
     for (int r0 = wave; r0 < len; r0 += WV * U) {
-      if (PIPE) {
-        load_rows(r0 + WV * U, dn, fn);  // (rows beyond the window repeat its last row: no branch)
-      }
+      load_rows(r0 + WV * U, dn, fn);  // (rows beyond the window repeat its last row: no branch)
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int ry = r0 + u * WV;
@@ -520,17 +513,13 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(5, 8))) void
           }
         }
       }
-      if (PIPE) {
 #pragma unroll
-        for (int u = 0; u < U; ++u)
+      for (int u = 0; u < U; ++u)
 #pragma unroll
-          for (int c = 0; c < CTB; ++c) dd[u][c] = dn[u][c];
-        if (FUSE) {
+        for (int c = 0; c < CTB; ++c) dd[u][c] = dn[u][c];
+      if (FUSE) {
 #pragma unroll
-          for (int u = 0; u < U; ++u) ff[u] = fn[u];
-        }
-      } else if (r0 + WV * U < len) {
-        load_rows(r0 + WV * U, dd, ff);
+        for (int u = 0; u < U; ++u) ff[u] = fn[u];
       }
     }
     if (d_sums) {
@@ -556,314 +545,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(5, 8))) void
     }
   }
 }
-
-// ---- image-centric ROI pass (round 4): every image line is fetched once ----------------------------------------
-// The window-centric kernel above reads 200-byte window rows at arbitrary alignment: a row touches 2.56 lines of 128 B
-// (measured 15.7 GB fetched for 9.7 GB of window pixels at C4), and pixels shared by overlapping windows are fetched
-// again by each of them -- an L2 of 4 MB per XCD does not keep a line for the ~20 us until a neighbouring window of
-// another workgroup comes by.  Here a workgroup owns a TILE of RT_H x RT_W pixels of one assay: it loads the tile's
-// (channel, time) planes -- RT_CT at a time -- into LDS with full, aligned lines, finds the windows that reach into the
-// tile (a scan of the assay's bead table) and serves every one of them its FRAGMENT from LDS: roi pixels and mask
-// bytes to their places in the marker's outputs, masked sums and counts by atomic adds (integer sums below 2^53 are
-// exact in float64 whatever the order).  Masks as in the window kernel: fg = own disk and no other disk, bg = no disk
-// (utils.py:380-395 / find.py:571-586), from tile-wide any / multi bit maps.
-constexpr int RT_H = 16, RT_W = 384, RT_WPR = RT_W / 32;  // tile rows / pixels / words per bit row
-constexpr int RT_CT = 4;                                  // planes in LDS at a time (RT_CT * RT_H * RT_W * 2 B = 48 KB)
-constexpr int RT_F = 16;                                  // fragments per round (their mask rows are held in LDS)
-constexpr int RT_IDS = 2048;                              // beads per block of the window scan (one block unless an assay holds more)
-// (LDS per workgroup: 48 + 1.5 + 8 + 4 KB and ~2.5 KB of descriptors: two workgroups per CU -- one loads while the
-// other serves)
-constexpr int RTN = 512;                                  // threads of a tile workgroup (8 waves; two workgroups per CU)
-constexpr int RT_DISKS = 128;                             // disks reaching into one tile that are drawn row-parallel
-
-struct RtFrag {
-  int g;             // marker (row of the outputs)
-  int top, left;     // window origin in the image
-  int yj, xj, rj;    // its own disk
-  int r0, r1;        // tile rows [r0, r1) the window covers
-};
-
-__global__ __launch_bounds__(RTN) void k_roi_tiles_u16(const uint16_t* __restrict__ d_image, int64_t assay_stride, int n_c,
-                                                      int n_t, int h, int w, const int32_t* __restrict__ d_beads,
-                                                      int64_t bead_stride, const int32_t* __restrict__ d_assay_offsets,
-                                                      int time_major, int len, const int32_t* __restrict__ d_halfwidths,
-                                                      int max_r, uint16_t* __restrict__ d_roi, uint8_t* __restrict__ d_fg,
-                                                      uint8_t* __restrict__ d_bg, double* __restrict__ d_sums,
-                                                      int32_t* __restrict__ d_counts) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t rt_smem[];
-  uint32_t* s_tile = reinterpret_cast<uint32_t*>(rt_smem);                       // [RT_CT][RT_H][RT_W / 2] pixel pairs
-  uint32_t* s_any = s_tile + RT_CT * RT_H * (RT_W / 2);                          // [RT_H][RT_WPR]
-  uint32_t* s_multi = s_any + RT_H * RT_WPR;                                     // [RT_H][RT_WPR]
-  uint32_t* s_fg = s_multi + RT_H * RT_WPR;                                      // [RT_F][RT_H][4]
-  uint32_t* s_bg = s_fg + RT_F * RT_H * 4;                                       // [RT_F][RT_H][4]
-  uint16_t* s_ids = reinterpret_cast<uint16_t*>(s_bg + RT_F * RT_H * 4);         // [RT_IDS]
-  int32_t* s_hw = reinterpret_cast<int32_t*>(s_ids + RT_IDS);                    // [(max_r + 1)][2 max_r + 1] half widths
-  __shared__ int s_nfrag, s_ndisk;
-  __shared__ int s_disk[RT_DISKS][3];
-  __shared__ RtFrag s_frag[RT_F];
-  __shared__ int s_cnt[RT_F][2];
-  const int assay = blockIdx.z, tx0 = blockIdx.x * RT_W, ty0 = blockIdx.y * RT_H;
-  const int tw = min(RT_W, w - tx0), th = min(RT_H, h - ty0);
-  const int first = d_assay_offsets[assay], nb = d_assay_offsets[assay + 1] - first;
-  if (nb <= 0) return;
-  const int32_t* beads = d_beads + 3 * (bead_stride ? (int64_t)assay * bead_stride : (int64_t)first);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  constexpr int WV = RTN / 64;
-  for (int i = threadIdx.x; i < 2 * RT_H * RT_WPR; i += RTN) s_any[i] = 0u;  // (any and multi are adjacent)
-  for (int i = threadIdx.x; i < (max_r + 1) * (2 * max_r + 1); i += RTN) s_hw[i] = d_halfwidths[i];
-  if (threadIdx.x == 0) s_nfrag = 0, s_ndisk = 0;
-  __syncthreads();
-  // ---- 1. the assay's beads: whose window reaches into the tile, whose disk does ----
-  const int side = 2 * max_r + 1;
-  auto draw_row = [&](int r, int yj, int xj, int rj) {  // row r of the tile under the disk
-    const int dy = ty0 + r - yj;
-    if (dy < -rj || dy > rj) return;
-    const int hwid = s_hw[rj * side + dy + rj];
-    if (hwid < 0) return;
-    const int xa = max(xj - hwid, tx0) - tx0, xb = min(xj + hwid, tx0 + tw - 1) - tx0;
-    for (int wd = xa >> 5; xa <= xb && wd <= (xb >> 5); ++wd) {
-      const int lo = max(xa, 32 * wd) - 32 * wd, hi = min(xb, 32 * wd + 31) - 32 * wd;
-      const uint32_t bits = (hi - lo == 31) ? 0xFFFFFFFFu : (((1u << (hi - lo + 1)) - 1u) << lo);
-      const uint32_t old = atomicOr(&s_any[r * RT_WPR + wd], bits);
-      if (old & bits) atomicOr(&s_multi[r * RT_WPR + wd], old & bits);
-    }
-  };
-  constexpr int UB = 4;
-  for (int b0 = 0; b0 < nb; b0 += RTN * UB) {
-    int yy[UB], xx[UB], rr[UB];
-#pragma unroll
-    for (int u = 0; u < UB; ++u) {
-      const int j = b0 + u * RTN + (int)threadIdx.x;
-      yy[u] = xx[u] = 0;
-      rr[u] = -1;
-      if (j < nb) yy[u] = beads[3 * j], xx[u] = beads[3 * j + 1], rr[u] = beads[3 * j + 2];
-    }
-#pragma unroll
-    for (int u = 0; u < UB; ++u) {
-      const int j = b0 + u * RTN + (int)threadIdx.x;
-      if (j >= nb) continue;
-      const int yj = yy[u], xj = xx[u], rj = rr[u];
-      if (j < RT_IDS) {  // (the windows of the first RT_IDS beads: the block loop below scans the later ones itself)
-        int top, left;
-        window(yj, len, h, top);
-        window(xj, len, w, left);
-        if (top < ty0 + th && top + len > ty0 && left < tx0 + tw && left + len > tx0) s_ids[atomicAdd(&s_nfrag, 1)] = (uint16_t)j;
-      }
-      if (rj < 2 || rj > max_r) continue;  // undefined in the reference, no coverage (as k_circle_labels)
-      if (yj + rj < ty0 || yj - rj >= ty0 + th || xj + rj < tx0 || xj - rj >= tx0 + tw) continue;
-      const int k = atomicAdd(&s_ndisk, 1);
-      if (k < RT_DISKS) {
-        s_disk[k][0] = yj, s_disk[k][1] = xj, s_disk[k][2] = rj;
-      } else {  // an extremely crowded tile: this thread draws the whole disk itself
-        for (int r = max(yj - rj, ty0) - ty0; r <= min(yj + rj, ty0 + th - 1) - ty0; ++r) draw_row(r, yj, xj, rj);
-      }
-    }
-  }
-  __syncthreads();
-  if (nb <= RT_IDS && s_nfrag == 0) return;  // nobody wants this tile: it is not read at all
-  {
-    const int nd = min(s_ndisk, RT_DISKS);
-    for (int p = threadIdx.x; p < nd * RT_H; p += RTN) {
-      const int k = p / RT_H, r = p - k * RT_H;
-      if (r < th) draw_row(r, s_disk[k][0], s_disk[k][1], s_disk[k][2]);
-    }
-  }
-  __syncthreads();
-  // ---- 2. rounds of RT_F windows ----
-  const uint16_t* img = d_image + (int64_t)assay * assay_stride;
-  const int nct = n_c * n_t, half = len >> 1, n = len * len;
-  const int64_t plane_elems = (int64_t)h * w;
-  // this thread's 16-byte pieces of a tile plane: piece q = threadIdx.x + RTN * i, row q / (RT_W / 8), 8 pixels from column 8 (q % (RT_W / 8))
-  constexpr int PIECES = (RT_H * (RT_W / 8) + RTN - 1) / RTN;
-  auto fetch_planes = [&](int ct0, uint4 (&v)[RT_CT][PIECES]) {
-#pragma unroll
-    for (int c = 0; c < RT_CT; ++c) {
-      const int ct = min(ct0 + c, nct - 1);
-      const uint16_t* plane = img + (int64_t)(time_major ? (ct % n_t) * n_c + ct / n_t : ct) * plane_elems;
-#pragma unroll
-      for (int i = 0; i < PIECES; ++i) {
-        const int q = threadIdx.x + RTN * i, r = q / (RT_W / 8), c8 = q - r * (RT_W / 8);
-        v[c][i] = make_uint4(0u, 0u, 0u, 0u);
-        if (q < RT_H * (RT_W / 8) && r < th && 8 * c8 < tw) v[c][i] = *reinterpret_cast<const uint4*>(plane + (int64_t)(ty0 + r) * w + tx0 + 8 * c8);
-      }
-    }
-  };
-  auto stash_planes = [&](const uint4 (&v)[RT_CT][PIECES]) {
-#pragma unroll
-    for (int c = 0; c < RT_CT; ++c)
-#pragma unroll
-      for (int i = 0; i < PIECES; ++i) {
-        const int q = threadIdx.x + RTN * i;
-        if (q < RT_H * (RT_W / 8)) reinterpret_cast<uint4*>(s_tile + c * RT_H * (RT_W / 2))[q] = v[c][i];
-      }
-  };
-  // blocks of RT_IDS beads (one block unless an assay holds more): the windows of a block that reach into the tile
-  for (int blk = 0; blk < nb; blk += RT_IDS) {
-  if (blk > 0) {
-    __syncthreads();
-    if (threadIdx.x == 0) s_nfrag = 0;
-    __syncthreads();
-    for (int j = blk + threadIdx.x; j < min(blk + RT_IDS, nb); j += RTN) {
-      int top, left;
-      window(beads[3 * j], len, h, top);
-      window(beads[3 * j + 1], len, w, left);
-      if (top < ty0 + th && top + len > ty0 && left < tx0 + tw && left + len > tx0) s_ids[atomicAdd(&s_nfrag, 1)] = (uint16_t)(j - blk);
-    }
-    __syncthreads();
-  }
-  const int nfrag = s_nfrag;
-  for (int f0 = 0; f0 < nfrag; f0 += RT_F) {
-    const int nf = min(RT_F, nfrag - f0);
-    __syncthreads();  // the previous round's descriptors, masks and tile planes are no longer read
-    if ((int)threadIdx.x < nf) {
-      const int j = blk + s_ids[f0 + threadIdx.x];
-      RtFrag fr;
-      fr.g = first + j;
-      fr.yj = beads[3 * j], fr.xj = beads[3 * j + 1], fr.rj = beads[3 * j + 2];
-      window(fr.yj, len, h, fr.top);
-      window(fr.xj, len, w, fr.left);
-      fr.r0 = max(fr.top - ty0, 0);
-      fr.r1 = min(fr.top + len - ty0, th);
-      s_frag[threadIdx.x] = fr;
-      s_cnt[threadIdx.x][0] = s_cnt[threadIdx.x][1] = 0;
-    }
-    __syncthreads();
-    // mask rows: (fragment, tile row, 32-column word of the window) -> fg / bg bits of the pixels that lie in this tile
-    for (int it = threadIdx.x; it < nf * RT_H * 4; it += RTN) {
-      const int f = it / (RT_H * 4), r = (it >> 2) & (RT_H - 1), wd = it & 3;
-      const RtFrag fr = s_frag[f];
-      uint32_t fgb = 0u, bgb = 0u;
-      if (r >= fr.r0 && r < fr.r1 && 32 * wd < len) {
-        const int c0 = fr.left - tx0 + 32 * wd;  // tile column of the word's bit 0 (may be negative / beyond the tile)
-        // columns of the word that are window columns (< len) AND lie in the tile
-        const int lo = max(0, -c0), hi = min(min(32, len - 32 * wd), tw - c0);  // bits [lo, hi)
-        if (lo < hi) {
-          const uint32_t in = (hi - lo == 32) ? 0xFFFFFFFFu : (((1u << (hi - lo)) - 1u) << lo);
-          // any / multi bits of tile columns c0 .. c0 + 31
-          const int wi = c0 >> 5, sh = c0 & 31;  // (arithmetic shift: floor)
-          auto word_at = [&](const uint32_t* row, int k) { return (k >= 0 && k < RT_WPR) ? row[k] : 0u; };
-          const uint32_t* ar = s_any + r * RT_WPR;
-          const uint32_t* mr = s_multi + r * RT_WPR;
-          const uint64_t a2 = ((uint64_t)word_at(ar, wi + 1) << 32) | word_at(ar, wi);
-          const uint64_t m2 = ((uint64_t)word_at(mr, wi + 1) << 32) | word_at(mr, wi);
-          const uint32_t anyb = (uint32_t)(a2 >> sh), multib = (uint32_t)(m2 >> sh);
-          // the window's own disk in this row
-          uint32_t own = 0u;
-          const int dy = ty0 + r - fr.yj;
-          if (fr.rj >= 2 && fr.rj <= max_r && dy >= -fr.rj && dy <= fr.rj) {
-            const int hwid = s_hw[fr.rj * side + dy + fr.rj];
-            if (hwid >= 0) {
-              const int xa = max(fr.xj - hwid - fr.left - 32 * wd, 0), xb = min(fr.xj + hwid - fr.left - 32 * wd, 31);
-              if (xa <= xb) own = (xb - xa == 31) ? 0xFFFFFFFFu : (((1u << (xb - xa + 1)) - 1u) << xa);
-            }
-          }
-          fgb = own & ~multib & in;
-          bgb = ~anyb & in;
-        }
-      }
-      s_fg[(f * RT_H + r) * 4 + wd] = fgb;
-      s_bg[(f * RT_H + r) * 4 + wd] = bgb;
-      if (fgb) atomicAdd(&s_cnt[f][0], __popc(fgb));
-      if (bgb) atomicAdd(&s_cnt[f][1], __popc(bgb));
-    }
-    {
-      uint4 v[RT_CT][PIECES];
-      fetch_planes(0, v);  // (the first planes' loads are in flight while the masks settle)
-      stash_planes(v);
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < 2 * nf && d_counts) {
-      const int f = threadIdx.x >> 1, k = threadIdx.x & 1;
-      if (s_cnt[f][k]) atomicAdd(&d_counts[2 * (int64_t)s_frag[f].g + k], s_cnt[f][k]);
-    }
-    // per fragment (a wave each): lane l serves window columns 2 l, 2 l + 1
-    const int x = 2 * lane;
-    const bool act = lane < half;
-    const int mword = x >> 5, msh = x & 31;
-    for (int ct0 = 0; ct0 < nct; ct0 += RT_CT) {
-      if (ct0) {
-        uint4 v[RT_CT][PIECES];
-        fetch_planes(ct0, v);
-        __syncthreads();  // the planes before are served
-        stash_planes(v);
-        __syncthreads();
-      }
-      for (int f = wave; f < nf; f += WV) {
-        const RtFrag fr = s_frag[f];
-        const int odd = fr.left & 1;  // (tx0 is even: the parity of the window's first column inside the tile)
-        const uint32_t shift = odd ? 16u : 0u;
-        const int e2 = (fr.left - odd - tx0) >> 1;  // dword of the lane-0 pair's first source pixel (may be negative)
-        const int di = min(max(e2 + min(lane, half - 1 + odd), 0), RT_W / 2 - 1);
-        const int tc = fr.left - tx0 + x;
-        const bool in0 = act && tc >= 0 && tc < tw, in1 = act && tc + 1 >= 0 && tc + 1 < tw;
-        uint32_t sf[RT_CT], sb[RT_CT];
-#pragma unroll
-        for (int c = 0; c < RT_CT; ++c) sf[c] = 0u, sb[c] = 0u;
-        const bool masks_out = ct0 == 0 && (d_fg || d_bg);
-        auto serve_row = [&](int r, const uint32_t (&dd)[RT_CT]) {
-          const uint32_t fb = (s_fg[(f * RT_H + r) * 4 + mword] >> msh) & 3u, bb = (s_bg[(f * RT_H + r) * 4 + mword] >> msh) & 3u;
-          const uint32_t mf = roi_pair(fb), mb = roi_pair(bb);
-          const int ry = ty0 + r - fr.top;
-          const int64_t oi = (int64_t)ry * half + lane;  // dword of the window
-          if (masks_out) {  // the mask bytes of the fragment's pixels, once
-            const int64_t o = (int64_t)fr.g * n + ry * len + x;
-            if (in0 && in1) {
-              if (d_fg) *reinterpret_cast<uint16_t*>(&d_fg[o]) = (uint16_t)((fb & 1u) | ((fb & 2u) << 7));
-              if (d_bg) *reinterpret_cast<uint16_t*>(&d_bg[o]) = (uint16_t)((bb & 1u) | ((bb & 2u) << 7));
-            } else if (in0) {
-              if (d_fg) d_fg[o] = (uint8_t)(fb & 1u);
-              if (d_bg) d_bg[o] = (uint8_t)(bb & 1u);
-            } else if (in1) {
-              if (d_fg) d_fg[o + 1] = (uint8_t)(fb >> 1);
-              if (d_bg) d_bg[o + 1] = (uint8_t)(bb >> 1);
-            }
-          }
-#pragma unroll
-          for (int c = 0; c < RT_CT; ++c) {
-            if (ct0 + c >= nct) break;  // uniform
-            const uint32_t d = dd[c];
-            const uint32_t nx = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)d, 0x130, 0xF, 0xF, false);  // lane + 1
-            const uint32_t v = __builtin_amdgcn_alignbit(nx, d, shift);
-            if (d_roi) {
-              uint32_t* out = reinterpret_cast<uint32_t*>(d_roi + ((int64_t)fr.g * nct + ct0 + c) * n);
-              if (in0 && in1) out[oi] = v;
-              else if (in0) reinterpret_cast<uint16_t*>(out)[2 * oi] = (uint16_t)v;
-              else if (in1) reinterpret_cast<uint16_t*>(out)[2 * oi + 1] = (uint16_t)(v >> 16);
-            }
-            sf[c] = roi_dot2(v, mf, sf[c]);  // (pixels outside the tile carry mask 0)
-            sb[c] = roi_dot2(v, mb, sb[c]);
-          }
-        };
-        for (int r = fr.r0; r < fr.r1; r += 2) {  // two rows per trip: their LDS reads are in flight together
-          const int rb = min(r + 1, fr.r1 - 1);
-          uint32_t da[RT_CT], db[RT_CT];
-#pragma unroll
-          for (int c = 0; c < RT_CT; ++c) {
-            da[c] = s_tile[(c * RT_H + r) * (RT_W / 2) + di];
-            db[c] = s_tile[(c * RT_H + rb) * (RT_W / 2) + di];
-          }
-          serve_row(r, da);
-          if (r + 1 < fr.r1) serve_row(r + 1, db);  // wave-uniform
-        }
-        if (d_sums) {
-#pragma unroll
-          for (int c = 0; c < RT_CT; ++c) {
-            if (ct0 + c >= nct) break;
-            const uint32_t a = (uint32_t)mg_wave_scan_incl_i32((int)sf[c]), b = (uint32_t)mg_wave_scan_incl_i32((int)sb[c]);
-            if (lane == 63) {
-              double* o = d_sums + ((int64_t)fr.g * nct + ct0 + c) * 2;
-              if (a) atomicAdd(o, (double)a);
-              if (b) atomicAdd(o + 1, (double)b);
-            }
-          }
-        }
-      }
-    }
-  }
-  }
-}
-
-constexpr size_t RT_LDS = (size_t)RT_CT * RT_H * RT_W * 2 + 2 * RT_H * RT_WPR * 4 + 2 * RT_F * RT_H * 4 * 4 + RT_IDS * 2;  // + the half-width table
 
 // ---- masked median: byte-wise radix select in LDS -------------------------------------------------
 // Keys are the order-preserving unsigned images of the values: an unsigned integer is its own key, an IEEE float has
@@ -1023,44 +704,13 @@ inline bool aligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<u
 //   fast   (k_roi_u16_even)        image_align 4,  w_div 2, stride_div 2: every plane and row starts on a dword
 //   fused  (k_roi_u16_even, FUSE)  image_align 16, w_div 2, stride_div 8: every assay starts on 16 bytes, in the image
 //                                  block and in the raw stack alike (its other bases: roi_dispatch)
-//   tiles  (k_roi_tiles_u16)       image_align 16, w_div 8, stride_div 8: tile rows are fetched in 16-byte pieces
 bool roi_u16_even_ok(const RoiCall& c, int image_align, int w_div, int stride_div) {
   return c.dtype == MG_U16 && (c.len & 1) == 0 && c.len <= 126 && (c.w & (w_div - 1)) == 0 &&
          (c.assay_stride & (stride_div - 1)) == 0 && (int64_t)c.h * c.w < (1LL << 31) && aligned(c.d_image, image_align) &&
          aligned(c.d_roi, 4) && aligned(c.d_fg, 2) && aligned(c.d_bg, 2);
 }
 
-// MG_ROI_TILES=1 (looked at on every call: the tests switch it): the image-centric pass of round 4 -- masks from the
-// bead tables of whole assays, uint16, 16-byte aligned rows.  Measured at C4 (profiles/r4_roi_tiles.txt): 21.9 GB of
-// HBM traffic instead of 28.2 (fetches 15.7 -> 8.5 GB: every line once), but 7.05 ms against 4.37 -- 16 waves per CU
-// behind 68 KB of LDS and ten barriers per tile leave its latencies in the open.  Not the default.
-constexpr int RT_HW_MAX = 27 * 53 * 4 + 8192;  // bytes of the half-width table the tile kernel may be given in LDS
-bool roi_tiles_wanted(const RoiCall& c) {
-  const char* env = getenv("MG_ROI_TILES");
-  return env && env[0] == '1' && roi_u16_even_ok(c, 16, 8, 8) && c.d_halfwidths && c.d_assay_offsets && !c.d_labels &&
-         c.n_assays > 0 && c.n_assays <= 65535 && (c.bead_stride ? c.bead_stride : (int64_t)c.m) <= 65535 &&
-         c.max_r >= 2 && (c.max_r + 1) * (2 * c.max_r + 1) * 4 <= RT_HW_MAX;
-}
-int roi_launch_tiles(const RoiCall& c) {
-  const int nct = c.n_c * c.n_t;
-  if (c.d_sums && mg_zero_async(c.d_sums, (size_t)c.m * nct * 2 * sizeof(double), c.stream) != hipSuccess) return MG_ELAUNCH;
-  if (c.d_counts && mg_zero_async(c.d_counts, (size_t)c.m * 2 * sizeof(int32_t), c.stream) != hipSuccess) return MG_ELAUNCH;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_roi_tiles_u16), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)RT_LDS + RT_HW_MAX) != hipSuccess)
-      return MG_ELAUNCH;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(k_roi_tiles_u16, dim3((c.w + RT_W - 1) / RT_W, (c.h + RT_H - 1) / RT_H, c.n_assays), dim3(RTN),
-                     RT_LDS + (size_t)(c.max_r + 1) * (2 * c.max_r + 1) * 4, c.stream, (const uint16_t*)c.d_image,
-                     c.assay_stride, c.n_c, c.n_t, c.h, c.w, c.d_beads, c.bead_stride, c.d_assay_offsets, c.time_major, c.len,
-                     c.d_halfwidths, c.max_r, (uint16_t*)c.d_roi, c.d_fg, c.d_bg, c.d_sums, c.d_counts);
-  MG_CHECK_LAUNCH();
-  return MG_OK;
-}
-
-// Argument checks, then the first branch that takes the call: fused (`fuse` given: it or a refusal), tiles, fast, generic.
+// Argument checks, then the first branch that takes the call: fused (`fuse` given: it or a refusal), fast, generic.
 int roi_dispatch(const RoiCall& c, const RoiRaw* fuse = nullptr) {
   if (!c.d_image || !c.d_beads || c.m < 0 || c.len <= 0 || c.n_c <= 0 || c.n_t <= 0) return MG_EINVAL;
   // (the LDS bound is the generic kernel's; windows beyond it are refused whichever kernel would run)
@@ -1074,13 +724,12 @@ int roi_dispatch(const RoiCall& c, const RoiRaw* fuse = nullptr) {
         (fuse->chan_mask >> c.n_c) || fuse->planes_per_group <= 0 || fuse->planes_per_group % (c.n_c * c.n_t) ||
         !aligned(fuse->raw, 16) || !aligned(fuse->flat, 16) || !aligned(fuse->max2, 8))
       return MG_EINVAL;
-    if (dark_is_int(nullptr, fuse->dark)) return roi_launch<uint16_t>(k_roi_u16_even<2, 4, true, 1>, bit_rows, c, *fuse);
-    return roi_launch<uint16_t>(k_roi_u16_even<2, 4, true, 2>, bit_rows, c, *fuse);
+    if (dark_is_int(nullptr, fuse->dark)) return roi_launch<uint16_t>(k_roi_u16_even<1>, bit_rows, c, *fuse);
+    return roi_launch<uint16_t>(k_roi_u16_even<2>, bit_rows, c, *fuse);
   }
-  if (roi_tiles_wanted(c)) return roi_launch_tiles(c);
   // 2 rows x 4 planes per trip, next trip's loads in flight while this one is worked on (measured at 16 x 4 x 4096^2:
   // 1.14 ms; without the pipelining 1.22, one row per trip 1.22, 4 rows x 2 planes 1.20, 4 x 4 unpipelined 1.24)
-  if (roi_u16_even_ok(c, 4, 2, 2)) return roi_launch<uint16_t>(k_roi_u16_even<2, 4, true>, bit_rows, c, RoiRaw{});
+  if (roi_u16_even_ok(c, 4, 2, 2)) return roi_launch<uint16_t>(k_roi_u16_even<0>, bit_rows, c, RoiRaw{});
   return mg_dispatch_pixel(c.dtype, [&](auto t) {
     using T = decltype(t);
     return roi_launch<T>(k_roi<T, mg_acc_t<T>>, roi_lds_bytes(c.len, c.d_halfwidths != nullptr), c);
@@ -1091,13 +740,13 @@ int roi_dispatch(const RoiCall& c, const RoiRaw* fuse = nullptr) {
 
 extern "C" int mg_circle_labels(const int32_t* d_beads, int64_t bead_cap, const int32_t* d_num_beads, int n_planes,
                                 int h, int w, const int32_t* d_halfwidths, int max_r, int32_t* d_labels,
-                                int reset, void* stream) {
+                                void* stream) {
   if (!d_beads || !d_num_beads || !d_halfwidths || !d_labels || n_planes < 0 || n_planes > 65535 || bead_cap < 0 ||
       max_r < 0)
     return MG_EINVAL;
   if (n_planes == 0 || bead_cap == 0) return MG_OK;
   hipLaunchKernelGGL(k_circle_labels, dim3((unsigned)bead_cap, n_planes), dim3(NT), 0, mg_stream(stream), d_beads,
-                     bead_cap, d_num_beads, h, w, d_halfwidths, max_r, d_labels, reset);
+                     bead_cap, d_num_beads, h, w, d_halfwidths, max_r, d_labels);
   MG_CHECK_LAUNCH();
   return MG_OK;
 }
@@ -1294,13 +943,6 @@ extern "C" int mg_roi_segment_reduce_raw(const void* d_image, const void* d_raw,
                       &rw);
 }
 
-extern "C" int mg_roi_gather_reduce(const void* d_image, int dtype, int n_c, int n_t, int h, int w,
-                                    const int32_t* d_beads, int m, int roi_len, const int32_t* d_labels, void* d_roi,
-                                    uint8_t* d_fg, uint8_t* d_bg, double* d_sums, int32_t* d_counts, void* stream) {
-  return mg_roi_gather_reduce_batched(d_image, dtype, 0, n_c, n_t, h, w, d_beads, nullptr, nullptr, m, roi_len,
-                                      d_labels, d_roi, d_fg, d_bg, d_sums, d_counts, stream);
-}
-
 extern "C" int mg_roi_masked_median(const void* d_roi, int dtype, const uint8_t* d_mask, int64_t mask_stride_m,
                                     int64_t mask_stride_t, int m, int n_c, int n_t, int roi_len, double* d_median,
                                     void* stream) {
@@ -1311,9 +953,4 @@ extern "C" int mg_roi_masked_median(const void* d_roi, int dtype, const uint8_t*
   return mg_dispatch_pixel(dtype, [&](auto t) {
     return launch_median<decltype(t)>(d_roi, d_mask, mask_stride_m, mask_stride_t, m, n_c, n_t, roi_len, d_median, s);
   });
-}
-
-extern "C" int mg_roi_masked_median_u16(const uint16_t* d_roi, const uint8_t* d_mask, int m, int n_c, int n_t,
-                                        int roi_len, double* d_median, void* stream) {
-  return mg_roi_masked_median(d_roi, MG_U16, d_mask, (int64_t)roi_len * roi_len, 0, m, n_c, n_t, roi_len, d_median, stream);
 }

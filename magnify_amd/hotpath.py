@@ -1283,14 +1283,9 @@ def _halfwidth_table(max_r: int, device):
     return _HALF_CACHE[key]
 
 
-_LABEL_POOL = {}
-
-
-def circle_labels(beads_per_assay, h, w, device="cuda", reuse=False):
+def circle_labels(beads_per_assay, h, w, device="cuda"):
     """utils.circle_labels (utils.py:380-395) for a list of (M_a, 3) int bead arrays.
-    Returns labels (A, h, w) int32 on the device.  ``reuse=True`` hands out a pooled map that must
-    be given back with ``release_labels`` (which restores -1 under the disks instead of clearing
-    the whole map)."""
+    Returns labels (A, h, w) int32 on the device."""
     require_gpu()
     a = len(beads_per_assay)
     cap = max(1, max((len(b) for b in beads_per_assay), default=1))
@@ -1303,26 +1298,13 @@ def circle_labels(beads_per_assay, h, w, device="cuda", reuse=False):
         counts[k] = len(b)
         if len(b):
             max_r = max(max_r, int(b[:, 2].max()))
-    key = (a, h, w, str(device))
-    if reuse and key in _LABEL_POOL:
-        labels = _LABEL_POOL.pop(key)
-    else:
-        labels = torch.full((a, h, w), -1, dtype=torch.int32, device=device)
+    labels = torch.full((a, h, w), -1, dtype=torch.int32, device=device)
     d_beads = torch.from_numpy(host).to(device)
     d_counts = torch.from_numpy(counts).to(device)
     tab = _halfwidth_table(max_r, device)
     _call("mg_circle_labels", d_beads.data_ptr(), cap, d_counts.data_ptr(), a, h, w, tab.data_ptr(), max_r,
-          labels.data_ptr(), 0, _stream())
-    labels._mg_state = (d_beads, cap, d_counts, a, h, w, tab, max_r, key)
+          labels.data_ptr(), _stream())
     return labels
-
-
-def release_labels(labels):
-    """Give a label map back to the pool: -1 is restored under the disks that were drawn."""
-    d_beads, cap, d_counts, a, h, w, tab, max_r, key = labels._mg_state
-    _call("mg_circle_labels", d_beads.data_ptr(), cap, d_counts.data_ptr(), a, h, w, tab.data_ptr(), max_r,
-          labels.data_ptr(), 1, _stream(), stage="mg_circle_labels_reset")
-    _LABEL_POOL[key] = labels
 
 
 _STAGING = {}
@@ -1565,16 +1547,6 @@ def masked_median(roi: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
     if m == 0:
         return out
     _call("mg_roi_masked_median", roi.data_ptr(), nat.dtype_code(roi.dtype), mask.data_ptr(), sm, st, m, c, t, L,
-          out.data_ptr(), _stream())
-    return out
-
-
-def masked_median_u16(roi: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
-    """nanmedian of roi (M, C, T, L, L) uint16 under mask (M, L, L) -> (M, C, T) float64."""
-    require_gpu()
-    m, c, t, L, _ = roi.shape
-    out = torch.empty((m, c, t), dtype=torch.float64, device=roi.device)
-    _call("mg_roi_masked_median_u16", roi.contiguous().data_ptr(), mask.contiguous().data_ptr(), m, c, t, L,
           out.data_ptr(), _stream())
     return out
 

@@ -680,9 +680,9 @@ def test_roi_gather_reduce(hp, dtype):
     if dtype == np.uint16:
         np.testing.assert_array_equal(sums[..., 0], red["fg_sum"])  # exact integer sums
         np.testing.assert_array_equal(sums[..., 1], red["bg_sum"])
-        med = hp.masked_median_u16(res["roi"], res["fg"]).cpu().numpy()
+        med = hp.masked_median(res["roi"], res["fg"]).cpu().numpy()
         np.testing.assert_array_equal(med, red["fg_median"])
-        med = hp.masked_median_u16(res["roi"], res["bg"]).cpu().numpy()
+        med = hp.masked_median(res["roi"], res["bg"]).cpu().numpy()
         np.testing.assert_array_equal(med, red["bg_median"])
     else:
         np.testing.assert_allclose(sums[..., 0], red["fg_sum"], rtol=1e-12)  # float64 sums, other order
@@ -1121,8 +1121,6 @@ def test_masked_median_types_and_time_masks(hp, dtype):
     d_one = dev(one.view(np.uint8))
     for mask in (d_one[:, 0], d_one, d_one.expand(m, t, L, L), d_one.bool()):
         np.testing.assert_array_equal(hp.masked_median(d_roi, mask).cpu().numpy(), want)
-    if dtype == np.uint16:  # the round-1 entry point is the same kernel
-        np.testing.assert_array_equal(hp.masked_median_u16(d_roi, d_one[:, 0].contiguous()).cpu().numpy(), want)
     with pytest.raises(ValueError):
         hp.masked_median(d_roi, dev(fg[:, :2].view(np.uint8)))
     assert hp.masked_median(d_roi[:0], dev(fg[:0].view(np.uint8))).shape == (0, c, t)
@@ -1242,12 +1240,12 @@ def test_candidates_degenerate_triplets(hp, grid, num_iter):
 
 
 @pytest.mark.parametrize("L,time_major", [(100, False), (40, False), (64, True)])
-def test_roi_image_centric_pass_equals_window_pass(hp, monkeypatch, L, time_major):
-    """The image-centric ROI pass of round 4 (MG_ROI_TILES=1: a workgroup owns a 16 x 384 tile, loads its planes into
-    LDS once and serves every window's fragment -- roi pixels, mask bytes, sums and counts by atomic adds) against the
-    window-centric pass and against the masks of the oracle's circle_labels map: windows cut by tile borders in both
-    directions, shifted into the image at its edges, overlapping and contested disks, a crowded assay (hundreds of
-    windows per tile: several rounds), an empty one, 5 planes per assay (the second pass over the planes is partial)."""
+def test_roi_disk_pass_masks_and_windows_equal_oracle(hp, L, time_major):
+    """The ROI pass with masks from the bead tables (disk mode, padded device tables) against the masks of the oracle's
+    circle_labels map and the image's own windows: windows shifted into the image at its edges, at odd and even
+    offsets, overlapping and contested disks, a crowded assay (more disks in a window than are drawn row-parallel), an
+    empty one, 5 planes per assay (the second trip over the planes is partial), a time-major image block; and the
+    call for the reductions alone writes the sums and counts of the full call."""
     rng = np.random.default_rng(44)
     c, t, h, w = (5, 1, 150, 800) if not time_major else (2, 3, 150, 800)
     A = 3
@@ -1260,13 +1258,7 @@ def test_roi_image_centric_pass_equals_window_pass(hp, monkeypatch, L, time_majo
         tab[a, : len(beads)] = beads
     counts = [len(b) for b in assays]
     kw = dict(disks=True, device_tables=(dev(tab), counts, 25), time_major=time_major)
-    monkeypatch.delenv("MG_ROI_TILES", raising=False)
-    want = hp.roi_gather_reduce(dev(images), None, L, None, **kw)
-    monkeypatch.setenv("MG_ROI_TILES", "1")
     got = hp.roi_gather_reduce(dev(images), None, L, None, **kw)
-    monkeypatch.delenv("MG_ROI_TILES")
-    for key in ("roi", "fg", "bg", "sums", "counts"):
-        np.testing.assert_array_equal(got[key].cpu().numpy(), want[key].cpu().numpy(), err_msg=key)
     off = got["offsets"]
     lab = rn.circle_labels(assays[0][assays[0][:, 2] >= 2], h, w)  # (a radius below 2 covers nothing: undefined in the reference)
     for i, (row, col, r) in enumerate(assays[0]):
@@ -1279,11 +1271,9 @@ def test_roi_image_centric_pass_equals_window_pass(hp, monkeypatch, L, time_majo
         win = win.transpose(1, 0, 2, 3) if time_major else win
         np.testing.assert_array_equal(got["roi"][off[0] + i].cpu().numpy(), win)
     # only the reductions (no pixel stack, no mask bytes)
-    monkeypatch.setenv("MG_ROI_TILES", "1")
     light = hp.roi_gather_reduce(dev(images), None, L, None, want_roi=False, want_masks=False, **kw)
-    monkeypatch.delenv("MG_ROI_TILES")
-    np.testing.assert_array_equal(light["sums"].cpu().numpy(), want["sums"].cpu().numpy())
-    np.testing.assert_array_equal(light["counts"].cpu().numpy(), want["counts"].cpu().numpy())
+    np.testing.assert_array_equal(light["sums"].cpu().numpy(), got["sums"].cpu().numpy())
+    np.testing.assert_array_equal(light["counts"].cpu().numpy(), got["counts"].cpu().numpy())
 
 
 @pytest.mark.parametrize("device_counts", [False, True])
