@@ -610,8 +610,11 @@ int mg_collect_circles(const int32_t* d_circles, int64_t circle_cap, const float
 int mg_circle_labels(const int32_t* d_beads, int64_t bead_cap, const int32_t* d_num_beads, int n_planes, int h,
                      int w, const int32_t* d_halfwidths, int max_r, int32_t* d_labels, void* stream);
 
-/* ROI gather + masks + reductions from a label map.  Every assay's image (C, T, h, w) of dtype (u8/u16/f32);
- * beads (m, 3) with labels from time 0; window = bounding_box(col, row, L, w, h).
+/* ROI gather + masks + reductions from a label map.  Every assay's image (C, T, h, w) of dtype (u8/u16/f32/f64: the
+ * four are held to a NumPy restatement of the pass in tests/test_gpu_roi_edges.py, here and in mg_roi_segment_reduce);
+ * beads (m, 3) with labels from time 0; window = bounding_box(col, row, L, w, h), 0 < L <= min(h, w), its L * L flag
+ * bytes (+ 12 * L * ceil(L / 32) bytes of row masks in mg_roi_segment_reduce) within 60 000 bytes of LDS: L <= 244
+ * here, <= 206 there -- MG_EINVAL beyond, nothing written.
  * Marker g belongs to assay d_marker_assay[g] (image base + assay * assay_stride
  * elements, labels base + assay * h * w) and owns label value d_marker_local[g].  Both index
  * arrays may be NULL (single assay, local index = g).  d_beads is (m, 3) for all markers.
