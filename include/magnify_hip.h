@@ -252,8 +252,17 @@ int mg_affine_bilinear(const void* d_src, void* d_dst, int dtype, int64_t n_plan
  *   0 D, 1 E, 2 Y, 3 weight (float32 n x w^2); 4 W_hat, 5 F_w, 6 A_off, 7 M (scratch; mean_n XA before
  *   mg_shading_reweight), 8 T (scratch), 9 mean over images of D, 10 min over images of D (float64 w^2);
  *   11 DCT-II table C[k][x], 12 its transpose (float64 w^2); 13 coeff (float64 n); 14-16 partial sums (internal);
- *   17 Gram matrix D D^T (float64 n x n); 18 scalars (float64 x 32: 0 mu, 7 B1_offset); 19 flags (int32 x 8:
- *   0 done, 1 ALM iterations of the pass).
+ *   17 Gram matrix D D^T (float64 n x n); 18 scalars (float64 x 32); 19 flags (int32 x 8).
+ * Scalars: 0 mu, 1 mu_bar, 2 lambda_f, 3 lambda_d, 4 tol, 5 ||D||_F, 6 b_up (min of D), 7 B1_offset, 8 mean(F_w),
+ *   9 mean(A), 10 cbar (mean coeff of the images with coeff < 1), 11 mean(A1), 12 the stop ratio ||Z||_F / ||D||_F;
+ *   8-12 are those of the last iteration, 7, 10 and 11 of the last one whose darkfield step ran.
+ * Flags: 0 done, 1 ALM iterations of the pass, 2 max iterations, 3 skip-dark (no darkfield asked for, or no image with
+ *   coeff < 1 in the last iteration: its darkfield step was skipped).
+ * Region 14, the per-image totals of the last iteration (float64 n x 8): 0 sum of R = D - E, 1 the same over the
+ *   pixels with F_w > mean(F_w) - 1e-6 ("hi"), 2 over those with F_w < mean(F_w) + 1e-6 ("lo"), 3 sum of A,
+ *   4 sum of Z^2, 5 count of hi pixels, 6 count of lo pixels, 7 B1c = (R hi / count hi - R lo / count lo) / mean(A).
+ *   After a darkfield iteration region 7 (M) holds the shrunk DCT of the darkfield residual, otherwise the mean
+ *   over images of D - A - E + Y / mu.
  * -1 / MG_EINVAL for a bad argument.
  * ---------------------------------------------------------------------------------- */
 int64_t mg_shading_workspace_bytes(int n, int w);

@@ -44,9 +44,16 @@ def test_dct_matches_scipy(mg, w):
     x = rng.standard_normal((w, w))
     xin = torch.from_numpy(x).cuda()
     out = torch.empty_like(xin)
+    # the forward-error bound of test_gpu_shading_stages.py (two chained FMA dot products of w terms, and the table's
+    # own error on each side), plus 1e-13 for scipy's transform, in place of the first guess of 1e-5
+    c, cb = np.abs(f.cos_table()), rs.cos_table_bound(w)
     for inverse, ref in ((0, dctn), (1, idctn)):
         f._call("mg_shading_dct2", xin.data_ptr(), out.data_ptr(), inverse)
-        np.testing.assert_allclose(out.cpu().numpy(), ref(x, norm="ortho"), rtol=0, atol=1e-5)
+        left, lb = (c.T, cb.T) if inverse else (c, cb)
+        bound = (2.1 * w * 2.0**-53 * (left @ np.abs(x) @ left.T) + lb @ np.abs(x) @ left.T + left @ np.abs(x) @ lb.T
+                 + 1e-13)
+        assert bound.max() < 1e-10  # (the table term grows with the argument, up to about pi w)
+        assert np.all(np.abs(out.cpu().numpy() - ref(x, norm="ortho")) <= bound)
 
 
 def _rel(got, want):
