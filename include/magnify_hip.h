@@ -758,6 +758,42 @@ int mg_host_read_runs(const int32_t* fds, const int64_t* offsets, const int64_t*
 int mg_host_write_runs(const int32_t* fds, const int64_t* offsets, const int64_t* nbytes, void* const* srcs, int n,
                        int n_threads, int64_t* failed);
 
+/* ------------------------------------------------------------------------------------
+ * plot.overview (plot/image.py:52-168: the pixel work of imshow -- pyramid, one additive colour per channel, the
+ * label map of the foreground masks -- as an RGB picture made on the device; tests/plot_ref.py restates both entries)
+ * Below s = 2^level, hk = ceil(h / s), wk = ceil(w / s).
+ * ---------------------------------------------------------------------------------- */
+#define MG_OVERVIEW_MAX_LEVEL 6
+#define MG_OVERVIEW_MAX_CHANNELS 16
+
+/* Label map of the foreground masks in image coordinates (roi_to_image_labels, plot/image.py:157-168).  The mask of
+ * marker g at timepoint t is the roi_len x roi_len bytes at d_fg + g * mask_stride_m + t * mask_stride_t (elements;
+ * mask_stride_t = 0: one mask for all timepoints), its window's origin d_origin[g][t] = (top, left), int32 (m, n_t, 2).
+ * d_labels int32 (n_t, hk, wk), zeroed by the caller: every set mask pixel (ry, rx) claims
+ * labels[t, (top + ry) >> level, (left + rx) >> level] with g + 1 and the largest claim wins (atomicMax: the same bits
+ * on every call); at level 0 that is the reference's overwrite with g ascending.  Claims outside the image are
+ * dropped.  m = 0 is legal and launches nothing.  MG_EINVAL, with nothing launched: m < 0, n_t / roi_len / h / w < 1,
+ * level outside 0 .. MG_OVERVIEW_MAX_LEVEL, a negative stride, a null pointer.  One kernel launch. */
+int mg_roi_image_labels(const uint8_t* d_fg, int64_t mask_stride_m, int64_t mask_stride_t, const int32_t* d_origin, int m,
+                        int n_t, int roi_len, int level, int h, int w, int32_t* d_labels, void* stream);
+
+/* The composite.  d_image: plane (c, t) of `dtype`, (h, w) contiguous, at d_image + c * chan_stride + t * time_stride
+ * elements.  limits double[n_c][2] = (lo, hi), colors double[n_c][3] in [0, 1]: HOST pointers, read during the call.
+ * d_out uint8 (n_t, hk, wk, 3).  Per output pixel, in float64, one operation at a time: per channel the sum of the
+ * in-image pixels of its s x s block (exact for MG_U8 / MG_U16; float pixels row by row from the top, each row from the
+ * left), mean = sum / n, u = (mean - lo) / (hi - lo), u = 0 where hi <= lo, u is NaN or u < 0, u = 1 where u > 1,
+ * acc[j] = min(acc[j] + u * colors[c][j], 1) with the channels ascending; then the overlay from d_labels (the map of
+ * the same level; NULL with overlay 0) and d_table uint8 (n_marks, n_t, 3), the colour of marker g at timepoint t:
+ * overlay 2 ("fill"): where 0 < lab <= n_marks, acc = (1 - alpha) * acc + alpha * table[lab - 1, t] / 255; overlay 1
+ * ("outline"): the same with alpha = 1, only where one of the four neighbours in the label map holds another label
+ * (0 outside the picture); overlay 0: none.  byte = floor(255 * acc + 0.5).  MG_EINVAL, with nothing launched: a null
+ * image / output / limits / colors, an unknown dtype, n_c outside 1 .. MG_OVERVIEW_MAX_CHANNELS, n_t / h / w < 1, level
+ * outside 0 .. MG_OVERVIEW_MAX_LEVEL, a negative stride, an unknown overlay, alpha or a colour outside [0, 1], an
+ * overlay without labels, table or markers.  One kernel launch; no allocation, no synchronisation. */
+int mg_render_overview(const void* d_image, int dtype, int64_t chan_stride, int64_t time_stride, int n_c, int n_t, int h,
+                       int w, int level, const double* limits, const double* colors, const int32_t* d_labels,
+                       const uint8_t* d_table, int n_marks, int overlay, double alpha, uint8_t* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,7 +27,8 @@ from .utils import seed  # noqa: F401
 from .file import load, save  # noqa: F401
 from . import sink  # noqa: F401,E402
 from .sink import HostSink, SaveSink  # noqa: F401,E402
+from . import plot  # noqa: F401,E402
 
 __all__ = ["component", "microfluidic_chip", "microfluidic_chip_pipe", "mrbles", "mrbles_pipe", "beads", "beads_pipe",
            "image", "image_pipe", "save", "load", "Pipeline", "DataArray", "Dataset", "seed", "find", "identify", "postprocess",
-           "preprocess", "reader", "shading", "stitch", "reduce", "utils", "xr_lite", "filter"]
+           "preprocess", "reader", "shading", "stitch", "reduce", "utils", "xr_lite", "filter", "plot"]

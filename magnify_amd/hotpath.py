@@ -1552,6 +1552,65 @@ def masked_median(roi: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
 
 
 # --------------------------------------------------------------------------------------
+# plot.overview: the label map of the fg masks in image coordinates and the composite picture
+# --------------------------------------------------------------------------------------
+
+OVERVIEW_MAX_LEVEL, OVERVIEW_MAX_CHANNELS = 6, 16  # MG_OVERVIEW_MAX_LEVEL, MG_OVERVIEW_MAX_CHANNELS
+OVERLAYS = {None: 0, "none": 0, "outline": 1, "fill": 2}
+
+
+def image_labels(fg: torch.Tensor, origin: torch.Tensor, level: int, h: int, w: int) -> torch.Tensor:
+    """fg (M, T, L, L) bool / uint8 (a broadcast view with time stride 0 is read in place), origin int32 (M, T, 2) =
+    (top, left) of every window -> int32 (T, hk, wk): marker i + 1 where a set pixel of fg[i, t] falls, the largest
+    index where several do (mg_roi_image_labels; at level 0 ``roi_to_image_labels``, plot/image.py:157-168)."""
+    require_gpu()
+    m, t, L, _ = fg.shape
+    s = 1 << int(level)
+    labels = torch.zeros((t, -(h // -s), -(w // -s)), dtype=torch.int32, device=fg.device if fg.is_cuda else "cuda")
+    if m == 0:
+        return labels
+    if fg.dtype == torch.bool:
+        fg = fg.view(torch.uint8)
+    if fg.stride(3) != 1 or fg.stride(2) != L or (m > 1 and fg.stride(0) < L * L) or (t > 1 and 0 < fg.stride(1) < L * L):
+        fg = fg.contiguous()
+    origin = torch.as_tensor(origin).to(device=labels.device, dtype=torch.int32).contiguous()
+    assert tuple(origin.shape) == (m, t, 2) and fg.is_cuda
+    _call("mg_roi_image_labels", fg.data_ptr(), fg.stride(0) if m > 1 else 0, fg.stride(1) if t > 1 else 0,
+          origin.data_ptr(), m, t, L, int(level), int(h), int(w), labels.data_ptr(), _stream())
+    return labels
+
+
+def render_overview(image: torch.Tensor, level: int, limits, colors, labels: torch.Tensor | None = None,
+                    table: torch.Tensor | None = None, overlay=None, alpha: float = 0.7) -> torch.Tensor:
+    """image (C, T, H, W) on the device, read where it lies (any channel / time strides, planes contiguous) -> uint8
+    (T, hk, wk, 3): block means at 2**level, ``limits`` (C, 2) and ``colors`` (C, 3) on the host, the overlay from
+    ``labels`` (T, hk, wk) int32 and ``table`` (M, T, 3) uint8 (mg_render_overview; tests/plot_ref.py)."""
+    require_gpu()
+    c, t, h, w = image.shape
+    if image.stride(3) != 1 and w > 1 or image.stride(2) != w and h > 1:
+        image = image.contiguous()
+    s = 1 << int(level)
+    hk, wk = -(h // -s), -(w // -s)
+    limits = np.ascontiguousarray(limits, dtype=np.float64).reshape(c, 2)
+    colors = np.ascontiguousarray(colors, dtype=np.float64).reshape(c, 3)
+    mode = OVERLAYS[overlay]
+    if mode and (labels is None or table is None or table.shape[0] == 0):
+        mode = 0
+    n_marks = 0
+    if mode:
+        labels, table = labels.contiguous(), table.contiguous()
+        n_marks = int(table.shape[0])
+        assert tuple(labels.shape) == (t, hk, wk) and labels.dtype == torch.int32
+        assert tuple(table.shape) == (n_marks, t, 3) and table.dtype == torch.uint8
+    out = torch.empty((t, hk, wk, 3), dtype=torch.uint8, device=image.device)
+    _call("mg_render_overview", image.data_ptr(), nat.dtype_code(image.dtype), image.stride(0) if c > 1 else 0,
+          image.stride(1) if t > 1 else 0, c, t, h, w, int(level), limits.ctypes.data, colors.ctypes.data,
+          labels.data_ptr() if mode else 0, table.data_ptr() if mode else 0, n_marks, mode, float(alpha), out.data_ptr(),
+          _stream())
+    return out
+
+
+# --------------------------------------------------------------------------------------
 # A16 / A17: ButtonFinder helpers
 # --------------------------------------------------------------------------------------
 
