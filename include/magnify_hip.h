@@ -794,6 +794,53 @@ int mg_render_overview(const void* d_image, int dtype, int64_t chan_stride, int6
                        int w, int level, const double* limits, const double* colors, const int32_t* d_labels,
                        const uint8_t* d_table, int n_marks, int overlay, double alpha, uint8_t* d_out, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * plot.roishow and plot.percentile_limits (plot/image.py:14-49: the montage of every marker's window, bg in red and fg
+ * in green on top; exact percentiles of a resident stack as contrast limits; tests/roishow_ref.py restates both)
+ * ---------------------------------------------------------------------------------- */
+#define MG_PERCENTILE_MAX_PREFIXES 4
+#define MG_PERCENTILE_MAX_BITS 11
+
+/* One read-once histogram pass of the radix selection of order statistics (hotpath.percentiles picks the bins between
+ * passes).  Data: n0 * n1 units of unit_len contiguous elements of `dtype`, unit (i0, i1) at d_data + i0 * stride0 +
+ * i1 * stride1 (elements; 0 is legal: a broadcast view).  The key of a value: the value for u8 (8 bits) and u16 (16
+ * bits); for f32, and f64 rounded to f32, the 32 bits with the sign bit flipped (positive) or all bits flipped
+ * (negative), -0 as +0; NaN has no key and is never counted.  n_prefixes = 0, the first pass: shift + bits = key bits,
+ * every key is counted at d_hist[key >> shift].  n_prefixes in 1 .. MG_PERCENTILE_MAX_PREFIXES, a refinement:
+ * prefix_shift = shift + bits, the prefixes (a host array, distinct, each below 2^(key bits - prefix_shift)) name the
+ * leading bits selected so far; a key with key >> prefix_shift == prefixes[q] is counted at d_hist[q * 2^bits + ((key
+ * >> shift) & (2^bits - 1))], every other key nowhere.  d_hist: uint64 counters, max(n_prefixes, 1) * 2^bits of
+ * them, zeroed by the caller; the pass adds to them (LDS tables per workgroup, equal keys of a wave gathered before the
+ * atomic, one uint64 atomic per non-empty bin and workgroup).  n0, n1 or unit_len = 0 is legal and launches nothing.
+ * MG_EINVAL, with nothing launched: an unknown dtype, a null pointer, a negative count or stride, bits outside 1 ..
+ * MG_PERCENTILE_MAX_BITS, shift < 0, shift + bits beyond the key, a first pass that leaves leading bits out, a
+ * prefix_shift other than shift + bits, a prefix out of range or named twice, a stack so large that one workgroup's
+ * share of it could pass the 2^32 of its uint32 bins (2048 workgroups: beyond 8e12 elements).  One kernel launch; no
+ * allocation, no synchronisation. */
+int mg_percentile_histogram(const void* d_data, int dtype, int n0, int64_t stride0, int n1, int64_t stride1,
+                            int64_t unit_len, int shift, int bits, int prefix_shift, const uint32_t* prefixes,
+                            int n_prefixes, uint64_t* d_hist, void* stream);
+
+/* The montage.  Window (g, c, t) of `dtype`, roi_len x roi_len contiguous, at d_roi + g * stride_m + c * stride_c + t *
+ * stride_t (elements).  d_layout int32 [rows][cols] on the device: the marker of every cell, < 0 (or >= n_marks) for an
+ * empty one.  d_out uint8 [n_t][rows * lk][cols * lk][3] with s = 2^level, lk = ceil(roi_len / s); every byte is
+ * written once.  Per pixel of a cell: steps 1-4 of mg_render_overview on the window's s x s block (limits double
+ * [n_c][2], colors double [n_c][3], host arrays); then the masks, bg with (255, 0, 0) first and fg with (0, 255, 0) on
+ * top -- mask (g, t) is roi_len^2 bytes at d + g * stride_m + t * stride_t (0 is legal, as in mg_roi_image_labels), a
+ * null mask is skipped; a block is on where any mask byte in it is non-zero; overlay 2 ("fill"): where on, acc = (1 -
+ * alpha) * acc + (alpha * rgb) / 255; overlay 1 ("outline"): the same with alpha = 1, only where the block is on and
+ * one of its four neighbours in the cell is off (outside the cell is off); overlay 0: none.  byte = floor(255 * acc +
+ * 0.5); an empty cell is 0.  rows * cols = 0 is legal and launches nothing.  MG_EINVAL, with nothing launched: a null
+ * roi / layout / output (where there are cells) / limits / colors, an unknown dtype, n_c outside 1 ..
+ * MG_OVERVIEW_MAX_CHANNELS, n_t < 1, roi_len outside 1 .. 32767, level outside 0 .. MG_OVERVIEW_MAX_LEVEL, n_marks < 1
+ * where there are cells, a negative count or stride, an unknown overlay, alpha or a colour outside [0, 1].  One kernel
+ * launch; no allocation, no synchronisation. */
+int mg_render_roi_montage(const void* d_roi, int dtype, int64_t stride_m, int64_t stride_c, int64_t stride_t, int n_marks,
+                          int n_c, int n_t, int roi_len, int level, const int32_t* d_layout, int rows, int cols,
+                          const double* limits, const double* colors, const uint8_t* d_bg, int64_t bg_stride_m,
+                          int64_t bg_stride_t, const uint8_t* d_fg, int64_t fg_stride_m, int64_t fg_stride_t, int overlay,
+                          double alpha, uint8_t* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1611,6 +1611,145 @@ def render_overview(image: torch.Tensor, level: int, limits, colors, labels: tor
 
 
 # --------------------------------------------------------------------------------------
+# plot.percentile_limits / plot.roishow: exact order statistics of a resident stack, the montage of the ROI windows
+# --------------------------------------------------------------------------------------
+
+PERCENTILE_MAX_PREFIXES = 4  # MG_PERCENTILE_MAX_PREFIXES
+# (shift, bits) of every read pass over the key, coarse to fine (bits <= MG_PERCENTILE_MAX_BITS)
+_KEY_PASSES = {"uint8": ((0, 8),), "uint16": ((5, 11), (0, 5)), "float32": ((21, 11), (10, 11), (0, 10)),
+               "float64": ((21, 11), (10, 11), (0, 10))}
+
+
+def percentile_rank(n: int, q) -> int:
+    """Index into the ``n`` sorted values of the ``q``-th percentile, the lower order statistic: ``q`` in thousandths of
+    a percent, ``(n - 1) * qm // 100000`` in Python integers (no float, no int32 on the way)."""
+    qm = round(float(q) * 1000)
+    if not 0 <= qm <= 100000:
+        raise ValueError(f"a percentile must lie in [0, 100], got {q!r}")
+    n = int(n)
+    if n < 1:
+        raise ValueError("percentile of an empty population")
+    return (n - 1) * qm // 100000
+
+
+def _key_value(key: int, dtype_name: str) -> float:
+    if dtype_name in ("uint8", "uint16"):
+        return float(key)
+    bits = key ^ 0x80000000 if key & 0x80000000 else ~key & 0xFFFFFFFF
+    return float(np.array([bits], dtype=np.uint32).view(np.float32)[0])
+
+
+def _units(view: torch.Tensor):
+    """(tensor, n0, stride0, n1, stride1, unit_len): the view as at most two strided dimensions over contiguous units
+    (its longest contiguous tail); a view that is not of that form is copied."""
+    dims = [(n, s) for n, s in zip(view.shape, view.stride()) if n != 1]
+    unit = 1
+    while dims and dims[-1][1] == unit:
+        unit *= dims.pop()[0]
+    if len(dims) > 2:
+        return view.contiguous(), 1, 0, 1, 0, view.numel()
+    dims = [(1, 0)] * (2 - len(dims)) + dims
+    return view, dims[0][0], dims[0][1], dims[1][0], dims[1][1], unit
+
+
+def percentiles(view: torch.Tensor, qs) -> np.ndarray:
+    """The ``qs``-th percentiles (lower order statistic at ``percentile_rank``) of the non-NaN values of a device
+    tensor, float64 (len(qs),): exact for uint8 / uint16 / float32; float64 values are rounded to float32 first.  The
+    view is read where it lies -- e.g. the (time, y, x) planes of a channel, the (mark, time, y, x) windows of one --
+    once per pass (mg_percentile_histogram): one pass for uint8, two for uint16, three for floats; the host picks the
+    bin of every rank between the passes.  ValueError where no value is left."""
+    require_gpu()
+    name = str(view.dtype).replace("torch.", "")
+    code = nat.dtype_code(view.dtype)
+    qs = [float(q) for q in qs]
+    for q in qs:
+        percentile_rank(1, q)
+    if view.numel() == 0:
+        raise ValueError("percentiles: no values")
+    if not view.is_cuda:
+        view = view.cuda()
+    view, n0, s0, n1, s1, unit = _units(view)
+    passes = _KEY_PASSES[name]
+
+    def run(shift, bits, prefix_shift, prefixes):
+        hist = torch.zeros((max(len(prefixes), 1), 1 << bits), dtype=torch.int64, device=view.device)
+        pre = np.asarray(prefixes, dtype=np.uint32)
+        _call("mg_percentile_histogram", view.data_ptr(), code, n0, s0, n1, s1, unit, shift, bits, prefix_shift,
+              pre.ctypes.data if len(prefixes) else 0, len(prefixes), hist.data_ptr(), _stream())
+        return hist.cpu().numpy()
+
+    def pick(counts, k):
+        """(bin that holds rank k of the counted values, rank inside that bin)"""
+        cum = np.cumsum(counts)
+        b = int(np.searchsorted(cum, k, side="right"))
+        return b, k - (int(cum[b - 1]) if b else 0)
+
+    shift, bits = passes[0]
+    first = run(shift, bits, 0, [])[0]
+    n = int(first.sum())
+    if n == 0:
+        raise ValueError("percentiles: every value is NaN")
+    state = [pick(first, percentile_rank(n, q)) for q in qs]  # per q: (leading key bits so far, rank among them)
+    for shift, bits in passes[1:]:
+        wanted = sorted({p for p, _ in state})
+        tables = {}
+        for g in range(0, len(wanted), PERCENTILE_MAX_PREFIXES):
+            group = wanted[g:g + PERCENTILE_MAX_PREFIXES]
+            for p, h in zip(group, run(shift, bits, shift + bits, group)):
+                tables[p] = h
+        nxt = []
+        for p, k in state:
+            b, k2 = pick(tables[p], k)
+            nxt.append(((p << bits) | b, k2))
+        state = nxt
+    return np.array([_key_value(p, name) for p, _ in state], dtype=np.float64)
+
+
+def render_roi_montage(roi: torch.Tensor, layout, level: int, limits, colors, fg: torch.Tensor | None = None,
+                       bg: torch.Tensor | None = None, overlay=None, alpha: float = 0.7) -> torch.Tensor:
+    """roi (M, C, T, L, L) on the device, read where it lies (any mark / channel / time strides, windows contiguous),
+    ``layout`` (rows, cols) int32 marker of every cell (-1: empty) -> uint8 (T, rows * lk, cols * lk, 3) with lk =
+    ceil(L / 2**level): the windows side by side, block means at 2**level, ``limits`` (C, 2) and ``colors`` (C, 3) on
+    the host, ``bg`` in red and ``fg`` in green on top (bool / uint8 (M, T, L, L); a time stride of 0 is read in place)
+    (mg_render_roi_montage; tests/roishow_ref.py)."""
+    require_gpu()
+    m, c, t, L, _ = roi.shape
+    assert roi.shape[4] == L
+    layout = np.ascontiguousarray(layout, dtype=np.int32)
+    rows, cols = layout.shape
+    assert layout.size == 0 or (-1 <= layout.min() and layout.max() < m)
+    s = 1 << int(level)
+    lk = -(L // -s)
+    limits = np.ascontiguousarray(limits, dtype=np.float64).reshape(c, 2)
+    colors = np.ascontiguousarray(colors, dtype=np.float64).reshape(c, 3)
+    out = torch.empty((t, rows * lk, cols * lk, 3), dtype=torch.uint8, device=roi.device)
+    if out.numel() == 0:
+        return out
+    if L > 1 and (roi.stride(4) != 1 or roi.stride(3) != L):
+        roi = roi.contiguous()
+    mode = OVERLAYS[overlay]
+
+    def mask(a):
+        if a is None or not mode:
+            return None, 0, 0
+        if a.dtype == torch.bool:
+            a = a.view(torch.uint8)
+        assert tuple(a.shape) == (m, t, L, L) and a.dtype == torch.uint8 and a.is_cuda
+        if (L > 1 and (a.stride(3) != 1 or a.stride(2) != L)) or (m > 1 and a.stride(0) < L * L) or \
+                (t > 1 and 0 < a.stride(1) < L * L):
+            a = a.contiguous()
+        return a, a.stride(0) if m > 1 else 0, a.stride(1) if t > 1 else 0
+
+    (bg, bg_m, bg_t), (fg, fg_m, fg_t) = mask(bg), mask(fg)
+    d_layout = torch.from_numpy(layout).to(roi.device)
+    _call("mg_render_roi_montage", roi.data_ptr(), nat.dtype_code(roi.dtype), roi.stride(0) if m > 1 else 0,
+          roi.stride(1) if c > 1 else 0, roi.stride(2) if t > 1 else 0, m, c, t, L, int(level), d_layout.data_ptr(), rows,
+          cols, limits.ctypes.data, colors.ctypes.data, _ptr(bg), bg_m, bg_t, _ptr(fg), fg_m, fg_t, mode, float(alpha),
+          out.data_ptr(), _stream())
+    return out
+
+
+# --------------------------------------------------------------------------------------
 # A16 / A17: ButtonFinder helpers
 # --------------------------------------------------------------------------------------
 

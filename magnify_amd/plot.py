@@ -9,9 +9,18 @@ contract in NumPy; the kernels match it bit for bit.
 
     rgb = mg.plot.overview(xp)                        # uint8 (time, y, x, rgb), device-resident
     mg.plot.write_png("t0.png", rgb[0].values)
+
+``roishow`` is the other half of the reference's package (plot/image.py:14-49): every marker's ROI window side by side,
+grouped by tag, ``bg`` in red and ``fg`` in green on top (csrc/mg_montage.hip); ``percentile_limits`` gives exact
+percentiles of a resident stack as contrast limits (csrc/mg_percentile.hip).  tests/roishow_ref.py restates both
+(DESIGN.md, section 19).
+
+    lim = mg.plot.percentile_limits(xp, 1, 99.8, source="roi")
+    rgb = mg.plot.roishow(xp, contrast_limits=lim)    # rgb.attrs["marks"]: the mark of every cell
 """
 from __future__ import annotations
 
+import math
 import struct
 import zlib
 
@@ -238,3 +247,178 @@ def write_png(path, rgb):
     with open(path, "wb") as f:
         f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0))
                 + chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)) + chunk(b"IEND", b""))
+
+
+# ---- roishow: every marker's window side by side; percentile contrast limits ------------------------------------------
+
+percentile_rank = hotpath.percentile_rank
+SOURCES = ("image", "roi")
+
+
+def _roi(xp):
+    """The dataset and its ``roi`` as a (M, C, T, L, L) device view, marks stacked as ``_marker_var`` stacks them; a
+    missing ``channel`` / ``time`` counts as size 1; a host block is moved to the device."""
+    xp = xr_lite.from_any(xp)
+    if isinstance(xp, DataArray) or "roi" not in xp.data_vars:
+        raise AttributeError("Dataset must contain 'roi' data variable.")
+    has_channel = "channel" in xp.data_vars["roi"].dims
+    data = _marker_var(xp, "roi", ("channel", "roi_y", "roi_x"))  # (mark, time, [channel,] roi_y, roi_x)
+    if not isinstance(data, torch.Tensor) or not data.is_cuda:
+        data = preprocess.to_device(data)
+    data = data.permute(0, 2, 1, 3, 4) if has_channel else data.unsqueeze(1)
+    if data.shape[3] != data.shape[4]:
+        raise ValueError(f"plot: roi windows must be square, got {tuple(data.shape[3:])}")
+    return xp, data
+
+
+def _check_percentiles(lo, hi, source):
+    lo, hi = float(lo), float(hi)
+    if not (0.0 <= lo <= 100.0 and 0.0 <= hi <= 100.0) or lo > hi:
+        raise ValueError(f"percentiles must satisfy 0 <= lo <= hi <= 100, got lo={lo!r}, hi={hi!r}")
+    if source not in SOURCES:
+        raise ValueError(f"source must be one of {SOURCES}, got {source!r}")
+    return lo, hi
+
+
+def percentile_limits(xp, lo=1.0, hi=99.8, source="image"):
+    """Per channel the ``lo``-th and ``hi``-th percentile of its pixels over all timepoints (``source="roi"``: of its
+    window pixels over all marks and timepoints), float64 ``(channel, 2)`` on the host: what ``contrast_limits=`` of
+    ``overview`` and ``roishow`` takes.  Exact order statistics of the non-NaN values: ``sorted(values)[k]`` with ``k =
+    percentile_rank(N, q)``, the lower one where a percentile falls between two values; float64 pixels are rounded to
+    float32 first.  The stack is read where it lies, once per pass (``hotpath.percentiles``)."""
+    lo, hi = _check_percentiles(lo, hi, source)
+    if source == "image":
+        xp, image = _image(xp)
+        views = [image[c] for c in range(image.shape[0])]
+    else:
+        xp, roi = _roi(xp)
+        views = [roi[:, c] for c in range(roi.shape[1])]
+    out = np.empty((len(views), 2), dtype=np.float64)
+    for c, view in enumerate(views):
+        try:
+            out[c] = hotpath.percentiles(view, (lo, hi))
+        except ValueError as e:
+            raise ValueError(f"plot.percentile_limits: channel {c} of {source!r} has no value that is not NaN") from e
+    return out
+
+
+def montage_layout(tags, m, columns=None):
+    """int32 ``(rows, cols)``: the mark shown in every cell of the montage, -1 for an empty one.  With ``tags`` (one per
+    mark): the reference's grid (plot/image.py:16-23) -- one column per ``np.unique`` tag in that order, the marks of a
+    tag from the top in ascending order, as many rows as the largest group.  ``tags=None``: mark order, row-major, over
+    ``columns`` columns (None: ``ceil(sqrt(m))``)."""
+    m = int(m)
+    if tags is not None:
+        tags = np.asarray(tags).reshape(-1)
+        if len(tags) != m:
+            raise ValueError(f"montage_layout: {len(tags)} tags for {m} marks")
+        if m == 0:
+            return np.zeros((0, 0), dtype=np.int32)
+        names, inverse, counts = np.unique(tags, return_inverse=True, return_counts=True)
+        layout = np.full((int(counts.max()), len(names)), -1, dtype=np.int32)
+        for j in range(len(names)):
+            marks = np.nonzero(inverse.reshape(-1) == j)[0]
+            layout[:len(marks), j] = marks
+        return layout
+    if columns is not None and (isinstance(columns, bool) or not isinstance(columns, (int, np.integer)) or columns < 1):
+        raise ValueError(f"columns must be an integer >= 1, got {columns!r}")
+    if m == 0:
+        return np.zeros((0, 0), dtype=np.int32)
+    if columns is None:
+        columns = math.isqrt(m - 1) + 1  # ceil(sqrt(m))
+    columns = int(columns)
+    layout = np.full(-(m // -columns) * columns, -1, dtype=np.int32)
+    layout[:m] = np.arange(m, dtype=np.int32)
+    return layout.reshape(-1, columns)
+
+
+def montage_level(rows, cols, L):
+    """The smallest level in 0 .. 6 at which the montage has at most 1024**2 pixels per timepoint; 6 if none has."""
+    for level in range(MAX_LEVEL + 1):
+        lk = -(L // -(1 << level))
+        if rows * lk * cols * lk <= 1024 ** 2:
+            return level
+    return MAX_LEVEL
+
+
+def _mask(xp, name, m, n_t, L, device):
+    """Coordinate ``name`` as a (M, T, L, L) device view (stride 0 along a time of size 1), or None without it."""
+    if name not in xp:
+        return None
+    a = _marker_var(xp, name, ("roi_y", "roi_x"))
+    if not isinstance(a, torch.Tensor):
+        a = torch.from_numpy(np.ascontiguousarray(np.asarray(a), dtype=np.bool_))
+    if not a.is_cuda:
+        a = a.to(device)
+    if a.dtype not in (torch.bool, torch.uint8):
+        a = a != 0
+    if tuple(a.shape[2:]) != (L, L) or a.shape[0] != m or a.shape[1] not in (1, n_t):
+        raise ValueError(f"plot: {name} of shape {tuple(a.shape)} does not match {m} marks, {n_t} timepoints, L = {L}")
+    return a.expand(m, n_t, L, L)
+
+
+def roishow(xp, level=None, contrast_limits=None, colors=None, overlay="fill", alpha=0.7, group_by="tag", columns=None):
+    """Every marker's ROI window side by side, uint8 ``(time, y, x, rgb)`` on the device: the picture the reference's
+    ``roishow`` (plot/image.py:14-49) hands to a viewer.
+
+    With ``group_by="tag"`` and a ``tag`` coordinate there is one column per tag (sorted) and the marks of a tag run
+    from the top (``montage_layout``); otherwise the marks fill a grid of ``columns`` columns in mark order.  A cell
+    is the window at ``2**level`` (block means; ``level=None``: the smallest level whose montage has at most 1024**2
+    pixels), scaled and coloured per channel as in ``overview`` (``contrast_limits=None``: the min / max of the
+    channel's windows), with the ``bg`` mask in red and the ``fg`` mask in green on top, each timepoint with its own
+    masks: ``overlay="fill"`` blends with weight ``alpha``, ``"outline"`` paints the rim, ``"none"`` / None leaves the
+    window alone.  Attributes of the result: ``level``, ``cell`` (the side of a cell), ``marks`` (the layout: the mark
+    of every cell, -1 for an empty one), ``tags`` (the tag of every column, or None)."""
+    if level is not None:
+        level = _check_level(level)
+    if overlay not in OVERLAYS:
+        raise ValueError(f"overlay must be one of {OVERLAYS}, got {overlay!r}")
+    if group_by not in (None, "tag"):
+        raise ValueError(f"group_by must be 'tag' or None, got {group_by!r}")
+    alpha = float(alpha)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"alpha must lie in [0, 1], got {alpha!r}")
+    if columns is not None and (isinstance(columns, bool) or not isinstance(columns, (int, np.integer)) or columns < 1):
+        raise ValueError(f"columns must be an integer >= 1, got {columns!r}")
+    xp, roi = _roi(xp)
+    m, c, t, L, _ = roi.shape
+    if c > hotpath.OVERVIEW_MAX_CHANNELS:
+        raise ValueError(f"plot.roishow composes at most {hotpath.OVERVIEW_MAX_CHANNELS} channels, got {c}")
+    cols = np.asarray(default_colors(c) if colors is None else colors, dtype=np.float64)
+    if cols.shape != (c, 3):
+        raise ValueError(f"colors must be one RGB triple per channel: {c} triples, got shape {cols.shape}")
+    if not (np.isfinite(cols).all() and (cols >= 0).all() and (cols <= 1).all()):
+        raise ValueError("colors must lie in [0, 1]")
+    if contrast_limits is not None:
+        limits = np.asarray(contrast_limits, dtype=np.float64)
+        if limits.shape != (c, 2):
+            raise ValueError(f"contrast_limits must be one (lo, hi) pair per channel: {c} pairs, got shape {limits.shape}")
+    tags = names = None
+    if group_by == "tag" and "tag" in xp.coords:
+        tags = np.asarray(_marker_tags(xp)).reshape(-1)
+        names = np.unique(tags) if m else tags[:0]
+    layout = montage_layout(tags, m, columns)
+    if level is None:
+        level = montage_level(layout.shape[0], layout.shape[1], L)
+    lk = -(L // -(1 << level))
+    attrs = {"level": level, "cell": lk, "marks": layout, "tags": names}
+    if m == 0:
+        empty = torch.zeros((t, 0, 0, 3), dtype=torch.uint8, device=roi.device)
+        return DataArray(empty, ("time", "y", "x", "rgb"), name="roishow", attrs=attrs)
+    if contrast_limits is None:
+        limits = percentile_limits(xp, 0.0, 100.0, source="roi")
+    fg = bg = None
+    if overlay in ("outline", "fill"):
+        fg, bg = _mask(xp, "fg", m, t, L, roi.device), _mask(xp, "bg", m, t, L, roi.device)
+    rgb = hotpath.render_roi_montage(roi, layout, level, limits, cols, fg, bg, overlay, alpha)
+    return DataArray(rgb, ("time", "y", "x", "rgb"), name="roishow", attrs=attrs)
+
+
+def _marker_tags(xp):
+    """The ``tag`` coordinate per stacked mark (over ``mark``, or over ``mark_row, mark_col`` row-major)."""
+    v = xp.coords["tag"]
+    if "mark" not in v.dims and "mark_row" in v.dims and "mark_col" in v.dims:
+        v = v.transpose("mark_row", "mark_col")
+    elif v.dims != ("mark",):
+        raise ValueError(f"plot: tag must lie over mark or over (mark_row, mark_col), got {v.dims}")
+    return np.asarray(v.values).reshape(-1)
