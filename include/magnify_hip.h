@@ -704,6 +704,37 @@ int mg_roi_window_order(const int32_t* d_beads, int64_t bead_stride, const int32
 int mg_roi_masked_median(const void* d_roi, int dtype, const uint8_t* d_mask, int64_t mask_stride_m,
                          int64_t mask_stride_t, int m, int n_c, int n_t, int roi_len, double* d_median, void* stream);
 
+/* Every statistic that roi.where(mask).<reduction>(dim=[roi_x, roi_y]) can ask for, from one read of each window
+ * (README.md:21-22; the robust intensities of a masked ROI: an upper percentile of the foreground, the spread of the
+ * background, a saturation check by max).  d_roi (m, C, T, L, L) and the masks as for mg_roi_masked_median.  A pixel
+ * takes part iff its mask byte is non-zero and its value is not NaN; n = the number of such pixels of one (g, c, t).
+ * q: HOST array of n_q fractions in [0, 1], 0 <= n_q <= MG_ROISTATS_MAX_Q, read during the call.
+ *   d_count int32[m][C][T]            n
+ *   d_stats double[m][C][T][4]        {sum, m2, min, max}: m2 = sum (x - mean)^2 with mean = sum / n, every operation
+ *                                     in float64 and none contracted (where all n values are equal the mean is
+ *                                     that value: m2 = 0 exactly); {0, 0, NaN, NaN} for n = 0.  For integer pixels
+ *                                     sum is exact; for float pixels sum and m2 are accumulated in an order fixed by
+ *                                     the launch shape (no floating-point atomics): every call gives the same bits.
+ *   d_order double[m][C][T][n_q][2]   {sorted[lo], sorted[hi]} of the n values: pos = (double)(n - 1) * q,
+ *                                     lo = floor(pos), hi = min(lo + 1, n - 1); NaN for n = 0.  Exact: radix select on
+ *                                     the order-preserving bit pattern.  May be NULL when n_q = 0.
+ * One workgroup per window.  A window whose keys (4 bytes a pixel, 8 for MG_F64) fit MG_ROISTATS_LDS_KEY_BYTES of LDS is
+ * read from global memory once and everything after the first pass runs out of LDS; a larger one is read again for m2
+ * and for every selection (mg_roi_masked_stats_keys_in_lds tells which; the results are the same).
+ * MG_EINVAL, with nothing written: a null pointer where one is needed, an unknown dtype, m < 0, n_c / n_t / roi_len <= 0,
+ * roi_len > MG_ROISTATS_MAX_LEN (pixel indices are int), m * n_c * n_t >= 2^31, a negative stride, n_q outside
+ * [0, MG_ROISTATS_MAX_Q], a q that is NaN or outside [0, 1].  m = 0 returns MG_OK and writes nothing.  One kernel
+ * launch; no allocation, no synchronisation. */
+#define MG_ROISTATS_MAX_Q 16
+#define MG_ROISTATS_LDS_KEY_BYTES 49152
+#define MG_ROISTATS_MAX_LEN 32768
+int mg_roi_masked_stats(const void* d_roi, int dtype, const uint8_t* d_mask, int64_t mask_stride_m,
+                        int64_t mask_stride_t, int m, int n_c, int n_t, int roi_len, const double* q, int n_q,
+                        int32_t* d_count, double* d_stats, double* d_order, void* stream);
+/* 1 if a window of roi_len x roi_len pixels of `dtype` keeps its keys in LDS, 0 if it takes the path that selects from
+ * global memory; MG_EINVAL for an unknown dtype or a roi_len that mg_roi_masked_stats refuses.  Host only. */
+int mg_roi_masked_stats_keys_in_lds(int dtype, int roi_len);
+
 /* ------------------------------------------------------------------------------------
  * A16 / A17 ButtonFinder helpers (find.py:205-402, 632-677)
  * ---------------------------------------------------------------------------------- */

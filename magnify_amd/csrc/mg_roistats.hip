@@ -1,0 +1,332 @@
+// roi.where(mask).{sum, mean, std, var, min, max, count, quantile}(dim=[roi_y, roi_x]) of an already gathered roi
+// (README.md:21-22, identify.py:76-80, filter.py:20-22): one workgroup per (marker, channel-time) reads the window and
+// its mask ONCE from global memory, reduces count / sum / min / max on the way in and keeps the keys of the surviving
+// pixels in LDS; the squared deviations and every order statistic asked for then run out of LDS.
+//
+// Roofline: HBM.  Per window L*L*(sizeof(T) + 1) bytes read, 4 + 32 + 16 n_q bytes written.
+#include "mg_select.h"
+
+namespace {
+
+constexpr int NT = MG_SELECT_THREADS, WV = NT / 64;
+constexpr double QNAN = __builtin_nan("");
+
+struct StatsQ {
+  double q[MG_ROISTATS_MAX_Q];
+};
+
+// Do the keys of a window fit the LDS budget?  (n = roi_len^2 pixels, key_bytes = 4 or 8)
+inline bool keys_fit(int64_t n, int key_bytes) { return n * key_bytes <= MG_ROISTATS_LDS_KEY_BYTES; }
+
+template <typename V, class Op>
+__device__ __forceinline__ V block_fold(V v, Op op) {  // the same value in every thread; called by all (it synchronises)
+  __shared__ V s_part[WV];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = op(v, __shfl_xor(v, off));
+  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
+  __syncthreads();
+  static_assert(WV == 4, "the fold below is written out for four waves");
+  const V r = op(op(s_part[0], s_part[1]), op(s_part[2], s_part[3]));
+  __syncthreads();
+  return r;
+}
+
+// What a thread has seen of its window.  Integer pixels are their own keys and are summed exactly; float pixels are
+// summed in float64, every thread its own pixels in the order it meets them.
+template <typename T>
+struct Seen {
+  typedef typename median_key<T>::type K;
+  typedef std::conditional_t<std::is_integral<T>::value, unsigned long long, double> Acc;
+  int count = 0;
+  Acc sum = 0;
+  K kmin = ~(K)0, kmax = 0;
+  __device__ __forceinline__ void take(K key) {
+    ++count;
+    if constexpr (std::is_integral<T>::value) sum += key; else sum += median_key<T>::value(key);
+    kmin = key < kmin ? key : kmin;
+    kmax = key > kmax ? key : kmax;
+  }
+};
+
+// A chunk as it comes from memory: VW pixels (16 bytes of them, or one) and their mask bytes, byte j in mw[j / 4].
+// Pixels beyond the window have mask byte 0.
+template <typename T, int VW>
+struct RawChunk {
+  T px[VW];
+  uint32_t mw[4];
+};
+template <typename T, int VW>
+__device__ __forceinline__ RawChunk<T, VW> fetch(const T* __restrict__ v, const uint8_t* __restrict__ mask, int n, int c,
+                                                 int end) {
+  RawChunk<T, VW> r = {};
+  if (c >= end) return r;
+  if (VW > 1 && (c + 1) * VW <= n) {
+    const uint4 bits = *reinterpret_cast<const uint4*>(v + (int64_t)c * VW);
+    __builtin_memcpy(r.px, &bits, 16);
+    const uint8_t* mp = mask + (int64_t)c * VW;
+    if constexpr (VW == 16) {
+      const uint4 t = *reinterpret_cast<const uint4*>(mp);
+      r.mw[0] = t.x, r.mw[1] = t.y, r.mw[2] = t.z, r.mw[3] = t.w;
+    } else if constexpr (VW == 8) {
+      const uint2 t = *reinterpret_cast<const uint2*>(mp);
+      r.mw[0] = t.x, r.mw[1] = t.y;
+    } else if constexpr (VW == 4) {
+      r.mw[0] = *reinterpret_cast<const uint32_t*>(mp);
+    } else {
+      r.mw[0] = *reinterpret_cast<const uint16_t*>(mp);
+    }
+  } else {  // VW = 1, or the window's last, partial chunk
+#pragma unroll
+    for (int j = 0; j < VW; ++j) {
+      const int p = c * VW + j;
+      if (p < n) r.px[j] = v[p], r.mw[j >> 2] |= (uint32_t)mask[p] << (8 * (j & 3));
+    }
+  }
+  return r;
+}
+
+// The pass over the window.  The window is cut into chunks of VW consecutive pixels (VW = 16 bytes of pixels where the
+// window starts on 16 bytes and its mask on VW bytes: one 16-byte load per lane and chunk; VW = 1 otherwise), the chunks
+// into WV equal runs, one per wave, which its lanes walk 64 chunks at a time, the loads of IN_FLIGHT such steps issued
+// before the first is worked on.  COMPACT: wave w writes the keys of its surviving pixels to keys[seg .. seg + its
+// count), seg = its first pixel, in pixel order -- no wave waits for another, and a survivor's slot depends on the mask
+// and the pixels alone.  Returns the wave's count of survivors.
+constexpr int IN_FLIGHT = 4;
+template <typename T, int VW, bool COMPACT>
+__device__ __forceinline__ int ingest(const T* __restrict__ v, const uint8_t* __restrict__ mask, int n,
+                                      typename median_key<T>::type* keys, Seen<T>& seen) {
+  typedef typename median_key<T>::type K;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int chunks = (n + VW - 1) / VW, per_wave = (chunks + WV - 1) / WV;
+  const int begin = min(wave * per_wave, chunks), end = min(begin + per_wave, chunks);
+  int written = 0;  // wave-uniform
+  for (int c0 = begin; c0 < end; c0 += 64 * IN_FLIGHT) {  // wave-uniform trip counts: every lane takes part in the scans
+    RawChunk<T, VW> raw[IN_FLIGHT];
+#pragma unroll
+    for (int u = 0; u < IN_FLIGHT; ++u) raw[u] = fetch<T, VW>(v, mask, n, c0 + 64 * u + lane, end);
+#pragma unroll
+    for (int u = 0; u < IN_FLIGHT; ++u) {
+      if (c0 + 64 * u >= end) break;
+      K ks[VW];
+      bool ok[VW];
+      int mine = 0;
+#pragma unroll
+      for (int j = 0; j < VW; ++j) {
+        ok[j] = median_key<T>::key(raw[u].px[j], &ks[j]) && ((raw[u].mw[j >> 2] >> (8 * (j & 3))) & 0xFFu) != 0u;
+        if (ok[j]) {
+          seen.take(ks[j]);
+          ++mine;
+        }
+      }
+      const int incl = mg_wave_scan_incl_i32(mine);
+      if (COMPACT) {
+        int at = begin * VW + written + incl - mine;  // < the wave's last pixel: no more survivors than pixels
+#pragma unroll
+        for (int j = 0; j < VW; ++j)
+          if (ok[j]) keys[at++] = ks[j];
+      }
+      written += __builtin_amdgcn_readlane(incl, 63);
+    }
+  }
+  return written;
+}
+
+// Where survivor i (0 <= i < count) of the window lies in `keys`: the waves' runs one after the other.  (Scalars and
+// conditional adds, not arrays: a table indexed by the run would go to scratch.)
+struct Runs {
+  int first1, first2, first3;  // index of the first survivor of waves 1, 2, 3
+  int shift0, step1, step2, step3;  // slot - index inside the run of wave 0; what every later run adds to it
+  __device__ __forceinline__ int slot(int i) const {
+    return i + shift0 + (i >= first1 ? step1 : 0) + (i >= first2 ? step2 : 0) + (i >= first3 ? step3 : 0);
+  }
+};
+
+// select_kth (mg_select.h) over the compacted keys in LDS.  hist[256] is all zero on entry and on return.
+template <typename K, int LV>
+__device__ __forceinline__ K select_kth_lds(const K* keys, const Runs& runs, int count, int k, uint32_t* hist, int* s_pick) {
+  const int lane = threadIdx.x & 63;
+  K prefix = 0;
+  int rank = k;
+  for (int level = 0; level < LV; ++level) {
+    const int shift = 8 * (LV - 1 - level);
+    for (int i = threadIdx.x; i < count; i += NT) {
+      const K key = keys[runs.slot(i)];
+      if (level == 0 || (key >> (shift + 8)) == prefix) atomicAdd(&hist[(uint32_t)(key >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    if (threadIdx.x < 64) {  // wave 0: four bins a lane, a scan of the lanes' totals, then the bin inside one lane
+      uint32_t h[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) h[j] = hist[4 * lane + j], hist[4 * lane + j] = 0u;
+      const int total = (int)(h[0] + h[1] + h[2] + h[3]);
+      const int incl = mg_wave_scan_incl_i32(total);
+      const unsigned long long reached = __ballot(incl > rank);
+      const int owner = reached ? __ffsll((long long)reached) - 1 : 63;  // (rank < count: some lane reaches it)
+      if (lane == owner) {
+        int acc = incl - total, b = 0;
+#pragma unroll
+        for (; b < 3; ++b) {
+          if (acc + (int)h[b] > rank) break;
+          acc += (int)h[b];
+        }
+        s_pick[0] = 4 * lane + b;
+        s_pick[1] = rank - acc;
+      }
+    }
+    __syncthreads();
+    prefix = (prefix << 8) | (K)s_pick[0];
+    rank = s_pick[1];
+  }
+  return prefix;  // (the next call writes s_pick only behind its first barrier: every thread has read it by then)
+}
+
+// One workgroup per (marker, channel-time) window.  IN_LDS: the keys of the window fit `keys` (dynamic LDS, n keys);
+// otherwise nothing is kept, the deviations and the selections read the window again from global memory.
+template <typename T, bool IN_LDS>
+__global__ __launch_bounds__(NT) void k_masked_stats(const T* __restrict__ d_roi, const uint8_t* __restrict__ d_mask,
+                                                     int64_t mask_stride_m, int64_t mask_stride_t, int n_t, int n_ct,
+                                                     int n, StatsQ qs, int n_q, int32_t* __restrict__ d_count,
+                                                     double* __restrict__ d_stats, double* __restrict__ d_order) {
+  typedef typename median_key<T>::type K;
+  extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
+  __shared__ uint32_t hist[256];
+  __shared__ int s_pick[2], s_run[WV];
+  K* keys = reinterpret_cast<K*>(s_dyn);
+  const int64_t window = blockIdx.x;
+  const int g = (int)(window / n_ct), ct = (int)(window % n_ct);
+  const T* v = d_roi + window * n;
+  const uint8_t* mask = d_mask + (int64_t)g * mask_stride_m + (int64_t)(ct % n_t) * mask_stride_t;
+  constexpr int VW = 16 / (int)sizeof(T);
+  const bool wide = (reinterpret_cast<uintptr_t>(v) & 15) == 0 && (reinterpret_cast<uintptr_t>(mask) & (VW - 1)) == 0;
+
+  Seen<T> seen;
+  const int run = wide ? ingest<T, VW, IN_LDS>(v, mask, n, keys, seen) : ingest<T, 1, IN_LDS>(v, mask, n, keys, seen);
+  if (IN_LDS) {
+    for (int i = threadIdx.x; i < 256; i += NT) hist[i] = 0u;
+    if ((threadIdx.x & 63) == 0) s_run[threadIdx.x >> 6] = run;
+  }
+  // (block_fold synchronises: s_run, hist and the keys are in place after the first of these)
+  const int count = block_fold(seen.count, [](int a, int b) { return a + b; });
+  const auto sum = block_fold(seen.sum, [](auto a, auto b) { return a + b; });
+  const K kmin = block_fold(seen.kmin, [](K a, K b) { return a < b ? a : b; });
+  const K kmax = block_fold(seen.kmax, [](K a, K b) { return a > b ? a : b; });
+
+  double* stats = d_stats + window * 4;
+  double* order = d_order + window * n_q * 2;  // (not touched when n_q = 0)
+  if (count == 0) {  // block-uniform
+    if (threadIdx.x == 0) {
+      d_count[window] = 0;
+      stats[0] = 0.0, stats[1] = 0.0, stats[2] = QNAN, stats[3] = QNAN;
+    }
+    for (int i = threadIdx.x; i < 2 * n_q; i += NT) order[i] = QNAN;
+    return;
+  }
+
+  Runs runs = {};
+  if (IN_LDS) {
+    // run w starts at pixel min(w * per_wave, chunks) * chunk (ingest) and holds s_run[w] survivors
+    const int chunk = wide ? VW : 1, chunks = (n + chunk - 1) / chunk, per_wave = (chunks + WV - 1) / WV;
+    const int p1 = min(per_wave, chunks) * chunk, p2 = min(2 * per_wave, chunks) * chunk;
+    const int p3 = min(3 * per_wave, chunks) * chunk;
+    runs.first1 = s_run[0], runs.first2 = runs.first1 + s_run[1], runs.first3 = runs.first2 + s_run[2];
+    runs.shift0 = 0;
+    runs.step1 = p1 - runs.first1;
+    runs.step2 = (p2 - runs.first2) - (p1 - runs.first1);
+    runs.step3 = (p3 - runs.first3) - (p2 - runs.first2);
+  }
+
+  // m2 = sum (x - mean)^2, each thread its own survivors in index order, then the fold's fixed tree
+  // (where every survivor has the same value that value is the mean, whatever the rounded sum of n of them gives: m2
+  // of a constant window is exactly 0 -- NaN if the constant is an infinity, as with any infinity under the mask)
+  const double total = (double)sum, mean = kmin == kmax ? median_key<T>::value(kmin) : total / (double)count;
+  double dev = 0.0;
+  if (IN_LDS) {
+    for (int i = threadIdx.x; i < count; i += NT) {
+      const double d = median_key<T>::value(keys[runs.slot(i)]) - mean;
+      dev += d * d;
+    }
+  } else {
+    for (int p = threadIdx.x; p < n; p += NT) {
+      K key;
+      if (!mask[p] || !median_key<T>::key(v[p], &key)) continue;
+      const double d = median_key<T>::value(key) - mean;
+      dev += d * d;
+    }
+  }
+  const double m2 = block_fold(dev, [](double a, double b) { return a + b; });
+  if (threadIdx.x == 0) {
+    d_count[window] = count;
+    stats[0] = total, stats[1] = m2, stats[2] = median_key<T>::value(kmin), stats[3] = median_key<T>::value(kmax);
+  }
+
+  // sorted[lo], sorted[hi] of every q: pos = (count - 1) q, lo = floor(pos), hi = min(lo + 1, count - 1)
+  int have_rank = -1;  // the last selection, kept: hi of one q is often lo of the next, or lo itself
+  K have_key = 0;
+  for (int j = 0; j < n_q; ++j) {
+    const double pos = (double)(count - 1) * qs.q[j];
+    const int lo = (int)floor(pos), hi = min(lo + 1, count - 1);
+    K pair[2];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const int rank = e ? hi : lo;
+      if (rank != have_rank) {  // block-uniform
+        if (IN_LDS)
+          have_key = select_kth_lds<K, median_key<T>::LEVELS>(keys, runs, count, rank, hist, s_pick);
+        else
+          have_key = select_kth<T>(v, mask, n, rank, hist);
+        have_rank = rank;
+      }
+      pair[e] = have_key;
+    }
+    if (threadIdx.x == 0) {
+      order[2 * j] = median_key<T>::value(pair[0]);
+      order[2 * j + 1] = median_key<T>::value(pair[1]);
+    }
+  }
+}
+
+template <typename T>
+int launch_stats(const void* d_roi, const uint8_t* d_mask, int64_t sm, int64_t st, int m, int n_c, int n_t, int len,
+                 const StatsQ& qs, int n_q, int32_t* d_count, double* d_stats, double* d_order, hipStream_t s) {
+  typedef typename median_key<T>::type K;
+  const int n = len * len, n_ct = n_c * n_t;
+  const dim3 grid((unsigned)((int64_t)m * n_ct));
+  if (keys_fit(n, sizeof(K)))
+    hipLaunchKernelGGL((k_masked_stats<T, true>), grid, dim3(NT), (size_t)n * sizeof(K), s, (const T*)d_roi, d_mask, sm, st,
+                       n_t, n_ct, n, qs, n_q, d_count, d_stats, d_order);
+  else
+    hipLaunchKernelGGL((k_masked_stats<T, false>), grid, dim3(NT), 0, s, (const T*)d_roi, d_mask, sm, st, n_t, n_ct, n, qs,
+                       n_q, d_count, d_stats, d_order);
+  MG_CHECK_LAUNCH();
+  return MG_OK;
+}
+
+}  // namespace
+
+extern "C" int mg_roi_masked_stats_keys_in_lds(int dtype, int roi_len) {
+  if (roi_len <= 0 || roi_len > MG_ROISTATS_MAX_LEN) return MG_EINVAL;
+  return mg_dispatch_pixel(dtype, [&](auto t) {
+    return (int)keys_fit((int64_t)roi_len * roi_len, sizeof(typename median_key<decltype(t)>::type));
+  });
+}
+
+extern "C" int mg_roi_masked_stats(const void* d_roi, int dtype, const uint8_t* d_mask, int64_t mask_stride_m,
+                                   int64_t mask_stride_t, int m, int n_c, int n_t, int roi_len, const double* q, int n_q,
+                                   int32_t* d_count, double* d_stats, double* d_order, void* stream) {
+  if (!d_roi || !d_mask || !d_count || !d_stats || m < 0 || n_c <= 0 || n_t <= 0 || roi_len <= 0) return MG_EINVAL;
+  if (n_q < 0 || n_q > MG_ROISTATS_MAX_Q || (n_q > 0 && (!q || !d_order))) return MG_EINVAL;
+  if (mask_stride_m < 0 || mask_stride_t < 0 || roi_len > MG_ROISTATS_MAX_LEN) return MG_EINVAL;
+  if ((int64_t)n_c * n_t > INT32_MAX || (int64_t)m * n_c * n_t > INT32_MAX) return MG_EINVAL;  // one workgroup a window
+  StatsQ qs = {};
+  for (int j = 0; j < n_q; ++j) {
+    if (!(q[j] >= 0.0 && q[j] <= 1.0)) return MG_EINVAL;  // (NaN fails both)
+    qs.q[j] = q[j];
+  }
+  if (dtype != MG_U8 && dtype != MG_U16 && dtype != MG_F32 && dtype != MG_F64) return MG_EINVAL;
+  if (m == 0) return MG_OK;
+  hipStream_t s = mg_stream(stream);
+  return mg_dispatch_pixel(dtype, [&](auto t) {
+    return launch_stats<decltype(t)>(d_roi, d_mask, mask_stride_m, mask_stride_t, m, n_c, n_t, roi_len, qs, n_q, d_count,
+                                     d_stats, d_order, s);
+  });
+}

@@ -1525,6 +1525,20 @@ def marker_table(out: dict, assay_offset: int, n_channels: int) -> torch.Tensor:
     return tab
 
 
+def _window_masks(what: str, mask: torch.Tensor, m: int, t: int, L: int):
+    """(mask, marker stride, time stride) as the masked window kernels read it: uint8 bytes, (M, L, L) or (M, T, L, L);
+    made contiguous only where the strides require it (a broadcast view with time stride 0 is read in place)."""
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    if mask.dim() == 3:
+        return mask.contiguous(), L * L, 0
+    if mask.shape[1] not in (1, t):
+        raise ValueError(f"{what}: {mask.shape[1]} mask timepoints for {t} roi timepoints")
+    if mask.stride(3) != 1 or mask.stride(2) != L or (m > 1 and mask.stride(0) < L * L):
+        mask = mask.contiguous()
+    return mask, (mask.stride(0) if m > 1 else L * L), (mask.stride(1) if mask.shape[1] == t and t > 1 else 0)
+
+
 def masked_median(roi: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
     """nanmedian of roi (M, C, T, L, L) -- uint8, uint16, float32 or float64 -- under mask (M, L, L) (one mask for all
     timepoints) or (M, T, L, L) (a mask per timepoint; a broadcast view with time stride 0 is read in place)
@@ -1532,23 +1546,49 @@ def masked_median(roi: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
     require_gpu()
     m, c, t, L, _ = roi.shape
     roi = roi.contiguous()
-    if mask.dtype == torch.bool:
-        mask = mask.view(torch.uint8)
-    if mask.dim() == 3:
-        mask = mask.contiguous()
-        sm, st = L * L, 0
-    else:
-        if mask.shape[1] not in (1, t):
-            raise ValueError(f"masked_median: {mask.shape[1]} mask timepoints for {t} roi timepoints")
-        if mask.stride(3) != 1 or mask.stride(2) != L or (m > 1 and mask.stride(0) < L * L):
-            mask = mask.contiguous()
-        sm, st = (mask.stride(0) if m > 1 else L * L), (mask.stride(1) if mask.shape[1] == t and t > 1 else 0)
+    mask, sm, st = _window_masks("masked_median", mask, m, t, L)
     out = torch.empty((m, c, t), dtype=torch.float64, device=roi.device)
     if m == 0:
         return out
     _call("mg_roi_masked_median", roi.data_ptr(), nat.dtype_code(roi.dtype), mask.data_ptr(), sm, st, m, c, t, L,
           out.data_ptr(), _stream())
     return out
+
+
+ROISTATS_MAX_Q, ROISTATS_LDS_KEY_BYTES = 16, 49152  # MG_ROISTATS_MAX_Q, MG_ROISTATS_LDS_KEY_BYTES
+
+
+def masked_stats_keys_in_lds(dtype, roi_len: int) -> bool:
+    """Does mg_roi_masked_stats keep the keys of a roi_len x roi_len window of ``dtype`` in LDS (4 bytes a pixel, 8 for
+    float64, within ROISTATS_LDS_KEY_BYTES), or select from global memory?"""
+    code = nat.dtype_code(dtype if isinstance(dtype, torch.dtype) else np.dtype(dtype))
+    rc = nat.lib().mg_roi_masked_stats_keys_in_lds(code, int(roi_len))
+    nat.check(min(rc, 0), "mg_roi_masked_stats_keys_in_lds")
+    return bool(rc)
+
+
+def masked_stats(roi: torch.Tensor, mask: torch.Tensor, q=()):
+    """Every statistic of roi (M, C, T, L, L) -- uint8, uint16, float32 or float64 -- under mask (the forms of
+    ``masked_median``) from one read of each window (mg_roi_masked_stats); a pixel takes part iff its mask byte is
+    non-zero and it is not NaN.  -> count (M, C, T) int32, stats (M, C, T, 4) float64 = {sum, m2, min, max} with
+    m2 = sum (x - mean)^2, {0, 0, NaN, NaN} where nothing takes part, and order (M, C, T, len(q), 2) float64 =
+    {sorted[lo], sorted[hi]} with lo = floor((n - 1) q), hi = min(lo + 1, n - 1): what a linear quantile interpolates
+    between.  ``q``: up to ROISTATS_MAX_Q fractions in [0, 1] (ValueError otherwise)."""
+    require_gpu()
+    m, c, t, L, _ = roi.shape
+    code = nat.dtype_code(roi.dtype)
+    roi = roi.contiguous()
+    mask, sm, st = _window_masks("masked_stats", mask, m, t, L)
+    qs = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)).reshape(-1))
+    count = torch.empty((m, c, t), dtype=torch.int32, device=roi.device)
+    stats = torch.empty((m, c, t, 4), dtype=torch.float64, device=roi.device)
+    order = torch.empty((m, c, t, len(qs), 2), dtype=torch.float64, device=roi.device)
+    if m == 0:
+        return count, stats, order
+    _call("mg_roi_masked_stats", roi.data_ptr(), code, mask.data_ptr(), sm, st, m, c, t, L,
+          qs.ctypes.data if len(qs) else None, len(qs), count.data_ptr(), stats.data_ptr(),
+          order.data_ptr() if len(qs) else None, _stream())
+    return count, stats, order
 
 
 # --------------------------------------------------------------------------------------

@@ -98,3 +98,105 @@ def fg_mean_minus_bg_median(xp, time=None):
     if time is not None:
         mean = mean[:, :, time:time + 1]
     return DataArray(mean - masked_median(xp, "bg", time=time).data, ("mark", "channel", "time"))
+
+
+# ---- every statistic of a masked ROI from one read of each window (mg_roi_masked_stats) --------------------------------
+_MCT = ("mark", "channel", "time")
+
+
+def _roi_and_mask(xp, mask, time):
+    roi = xp.data_vars["roi"].transpose("mark", "channel", "time", "roi_y", "roi_x").data
+    if not isinstance(roi, torch.Tensor):
+        roi = np.ascontiguousarray(roi)
+        if roi.dtype.byteorder not in ("=", "|"):
+            roi = roi.astype(roi.dtype.newbyteorder("="))
+        roi = torch.from_numpy(roi)
+    hotpath.nat.dtype_code(roi.dtype)  # TypeError for anything but uint8 / uint16 / float32 / float64
+    if isinstance(mask, str):
+        m = _masks(xp, mask)
+    else:  # a DataArray on (mark[, time], roi_y, roi_x)
+        m = mask.transpose(*[d for d in ("mark", "time", "roi_y", "roi_x") if d in mask.dims]).data
+        if not isinstance(m, torch.Tensor):
+            m = torch.from_numpy(np.ascontiguousarray(m))
+        if m.dtype not in (torch.bool, torch.uint8):
+            m = m != 0
+        m = m.cuda()
+    if time is not None:
+        roi = roi[:, :, time:time + 1] if time != -1 else roi[:, :, -1:]
+        if m.dim() == 4 and m.shape[1] != 1:
+            m = m[:, time:time + 1] if time != -1 else m[:, -1:]
+    return roi.cuda(), m
+
+
+def masked_stats(xp, mask="fg", q=(), time=None):
+    """(count, stats, order) of roi under ``mask`` -- a coordinate name, or a DataArray on (mark[, time], roi_y, roi_x)
+    -- as DataArrays on the device: count (mark, channel, time) int32, stats (mark, channel, time, stat) =
+    {sum, m2, min, max} and order (mark, channel, time, quantile, bound) = the two order statistics every fraction of
+    ``q`` falls between (``hotpath.masked_stats``).  A pixel takes part iff the mask is set and it is not NaN.
+    ``time=k``: of timepoint ``k`` only, selected before the reduction as ``masked_median`` does."""
+    count, stats, order = hotpath.masked_stats(*_roi_and_mask(xp, mask, time), q)
+    return (DataArray(count, _MCT), DataArray(stats, _MCT + ("stat",)), DataArray(order, _MCT + ("quantile", "bound")))
+
+
+def interpolate_quantiles(count, order, q):
+    """numpy's ``method="linear"`` between the order statistics of ``hotpath.masked_stats``, operation for operation
+    in float64: pos = (n - 1) q, g = pos - floor(pos), d = b - a; b - d (1 - g) where g >= 0.5, else a + d g.
+    count (...), order (..., n_q, 2), q (n_q,) -> (..., n_q); torch tensors or NumPy arrays alike."""
+    xp_ = torch if isinstance(order, torch.Tensor) else np
+    if xp_ is torch:
+        qv = torch.as_tensor(np.asarray(q, dtype=np.float64).reshape(-1), device=order.device)
+        n = count.to(torch.float64)[..., None]
+    else:
+        qv = np.asarray(q, dtype=np.float64).reshape(-1)
+        n = np.asarray(count).astype(np.float64)[..., None]
+    pos = (n - 1.0) * qv
+    g = pos - xp_.floor(pos)
+    a, b = order[..., 0], order[..., 1]
+    d = b - a
+    return xp_.where(g >= 0.5, b - d * (1.0 - g), a + d * g)
+
+
+def variance_from_m2(count, m2, ddof=0):
+    """m2 / (n - ddof), NaN where n - ddof <= 0 (torch tensors)."""
+    dof = count.to(torch.float64) - float(ddof)
+    return torch.where(dof > 0, m2 / dof, torch.full_like(m2, float("nan")))
+
+
+def masked_count(xp, mask="fg", time=None):
+    """roi.where(mask).count(dim=[roi_y, roi_x]) -> (mark, channel, time) int64."""
+    return DataArray(masked_stats(xp, mask, (), time)[0].data.to(torch.int64), _MCT)
+
+
+def masked_min(xp, mask="fg", time=None):
+    """roi.where(mask).min(dim=[roi_y, roi_x]) -> (mark, channel, time) float64, NaN for an empty mask."""
+    return DataArray(masked_stats(xp, mask, (), time)[1].data[..., 2], _MCT)
+
+
+def masked_max(xp, mask="fg", time=None):
+    """roi.where(mask).max(dim=[roi_y, roi_x]) -> (mark, channel, time) float64, NaN for an empty mask."""
+    return DataArray(masked_stats(xp, mask, (), time)[1].data[..., 3], _MCT)
+
+
+def masked_var(xp, mask="fg", ddof=0, time=None):
+    """roi.where(mask).var(dim=[roi_y, roi_x], ddof=ddof): m2 / (n - ddof), NaN where n - ddof <= 0."""
+    count, stats, _ = masked_stats(xp, mask, (), time)
+    return DataArray(variance_from_m2(count.data, stats.data[..., 1], ddof), _MCT)
+
+
+def masked_std(xp, mask="fg", ddof=0, time=None):
+    """roi.where(mask).std(dim=[roi_y, roi_x], ddof=ddof): the square root of ``masked_var``."""
+    return DataArray(torch.sqrt(masked_var(xp, mask, ddof, time).data), _MCT)
+
+
+def masked_quantile(xp, q, mask="fg", time=None):
+    """roi.where(mask).quantile(q, dim=[roi_y, roi_x]) -> (mark, channel, time) for a scalar ``q``, (quantile, mark,
+    channel, time) for a sequence, as xarray has it; NaN for an empty mask.  The order statistics are exact and the
+    interpolation between them is numpy's ``method="linear"`` operation for operation, so the result equals
+    ``np.nanquantile`` bit for bit.  ``masked_quantile(xp, 0.5)`` therefore follows ``nanquantile`` while
+    ``masked_median`` follows ``nanmedian`` (the mean of the two middle values): for float64 pixels the two can
+    differ in the last bit."""
+    count, _, order = masked_stats(xp, mask, np.atleast_1d(q), time)
+    val = interpolate_quantiles(count.data, order.data, np.atleast_1d(q))
+    if np.ndim(q) == 0:
+        return DataArray(val[..., 0], _MCT)
+    return DataArray(val.permute(3, 0, 1, 2), ("quantile",) + _MCT, {"quantile": np.asarray(q, dtype=np.float64)})

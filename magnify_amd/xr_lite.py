@@ -40,6 +40,72 @@ def _take(data, idx, axis):
     return data.index_select(axis, index)
 
 
+_ROI_YX = ("roi_y", "roi_x")
+_ROI_LEAD = ("mark", "channel", "time")
+
+
+def _where_on_host(arr, cond, dims):
+    """``arr`` as float64 with NaN outside ``cond``, broadcast by dimension name (a NumPy array)."""
+    return np.where(_align(cond, dims).astype(bool), _align(arr, dims).astype(np.float64), np.nan)
+
+
+class MaskedRoi:
+    """``roi.where(mask)`` of a device-resident roi, not yet computed: a lazy operand of ``DataArray`` (float64, the
+    shape and dims of the roi).  Reduced over exactly (roi_y, roi_x) -- or over everything -- it is handed to the
+    masked-statistics kernel (``hotpath.masked_stats``: one read of each window, no float64 copy); anything else
+    ``materialize()``s it into the host array ``where`` has always returned."""
+
+    def __init__(self, arr, cond):
+        self.arr = DataArray(arr.raw, arr.dims)
+        self.cond = DataArray(cond.raw, cond.dims)
+        self.shape, self.dtype = self.arr.shape, np.dtype(np.float64)
+
+    @staticmethod
+    def accepts(arr, cond):
+        data = arr.raw
+        if not (_is_tensor(data) and data.is_cuda and str(data.dtype) in
+                ("torch.uint8", "torch.uint16", "torch.float32", "torch.float64")):
+            return False
+        dims, cdims = set(arr.dims), set(cond.dims)
+        if not (set(_ROI_YX) <= cdims <= dims and dims <= set(_ROI_YX + _ROI_LEAD) and "channel" not in cdims):
+            return False
+        if len(dims) != len(arr.dims) or arr.sizes["roi_y"] != arr.sizes["roi_x"]:
+            return False
+        return all(cond.sizes[d] == arr.sizes[d] for d in cdims)
+
+    def materialize(self):
+        return _where_on_host(self.arr, self.cond, list(self.arr.dims))
+
+    def operands(self):
+        """(roi (M, C, T, L, L), mask (M, T or 1, L, L)): views of the two tensors, missing dimensions of length 1."""
+        def canonical(a, names):
+            t = a.data
+            if not _is_tensor(t):
+                t = torch.from_numpy(np.ascontiguousarray(t))
+            t = t.permute(*[a.dims.index(d) for d in names if d in a.dims])
+            for i, d in enumerate(names):
+                if d not in a.dims:
+                    t = t.unsqueeze(i)
+            return t
+
+        roi = canonical(self.arr, _ROI_LEAD + _ROI_YX)
+        mask = canonical(self.cond, ("mark", "time") + _ROI_YX)
+        if mask.dtype not in (torch.bool, torch.uint8):
+            mask = mask != 0
+        mask = mask.to(roi.device)
+        return roi, mask.expand(roi.shape[0], -1, -1, -1)
+
+    def lead_dims(self):
+        return tuple(d for d in self.arr.dims if d not in _ROI_YX)
+
+    def per_window(self, t):
+        """A result (M, C, T, ...) of the kernels in the dims ``lead_dims()`` (+ whatever follows)."""
+        have = [d for d in _ROI_LEAD if d in self.arr.dims]
+        t = t.reshape(tuple(self.arr.sizes[d] for d in have) + tuple(t.shape[3:]))
+        extra = list(range(len(have), t.dim()))
+        return t.permute(*[have.index(d) for d in self.lead_dims()], *extra)
+
+
 class DataArray:
     def __init__(self, data=None, dims=(), coords=None, name=None, attrs=None):
         if isinstance(dims, str):
@@ -312,31 +378,103 @@ class DataArray:
         return self._replace(self.values.astype(dtype), self.dims, dict(self.coords))
 
     def where(self, cond):
-        """NaN outside ``cond`` (float64), broadcasting by dimension name."""
+        """NaN outside ``cond`` (float64), broadcasting by dimension name.  A device-resident roi under a mask on
+        (mark, time, roi_y, roi_x) or fewer stays on the device as a pending ``MaskedRoi``: ``sum`` / ``mean`` / ``median``
+        / ``min`` / ``max`` / ``count`` / ``std`` / ``var`` / ``quantile`` over (roi_y, roi_x) are computed there."""
         if isinstance(cond, str):
             cond = self.coords[cond]
         dims = list(self.dims) + [d for d in cond.dims if d not in self.dims]
-        a = _align(self, dims).astype(np.float64)
-        c = _align(cond, dims).astype(bool)
         coords = dict(cond.coords)
         coords.update(self.coords)
-        return DataArray(np.where(c, a, np.nan), dims, {k: v for k, v in coords.items() if set(v.dims) <= set(dims)},
-                         self.name)
+        data = MaskedRoi(self, cond) if MaskedRoi.accepts(self, cond) else _where_on_host(self, cond, dims)
+        return DataArray(data, dims, {k: v for k, v in coords.items() if set(v.dims) <= set(dims)}, self.name)
 
-    def _reduce(self, fn, dim=None, **kw):
+    def _masked(self, what, dim, q=None, ddof=0):
+        """The reduction ``what`` of a pending ``MaskedRoi`` on the device, or None where it is not one of those the
+        kernels compute (the caller then materialises and reduces on the host, as ever)."""
+        lazy = self._data
+        if not isinstance(lazy, MaskedRoi):
+            return None
+        names = None if dim is None else ([dim] if isinstance(dim, str) else list(dim))
+        if names is not None and sorted(names) != ["roi_x", "roi_y"]:
+            return None
+        if names is None and (what not in ("sum", "mean", "min", "max", "count") or not self.size):
+            return None
+        from . import hotpath, reduce
+
+        roi, mask = lazy.operands()
+        if what == "median":
+            return self._replace(lazy.per_window(hotpath.masked_median(roi, mask)), lazy.lead_dims())
+        qs = np.atleast_1d(np.asarray(q, dtype=np.float64)) if what == "quantile" else ()
+        count, stats, order = hotpath.masked_stats(roi, mask, qs)
+        if names is None:  # over everything: the per-window records combined on the device
+            n = count.sum()
+            any_ = n > 0
+            nan = torch.full((), float("nan"), dtype=torch.float64, device=stats.device)
+            inf = torch.full((), float("inf"), dtype=torch.float64, device=stats.device)
+            out = {"count": lambda: n,
+                   "sum": lambda: stats[..., 0].sum(),
+                   "mean": lambda: stats[..., 0].sum() / n.to(torch.float64),
+                   "min": lambda: torch.where(any_, torch.where(count > 0, stats[..., 2], inf).min(), nan),
+                   "max": lambda: torch.where(any_, torch.where(count > 0, stats[..., 3], -inf).max(), nan)}[what]()
+            return self._replace(out, ())
+        if what == "quantile":
+            val = lazy.per_window(reduce.interpolate_quantiles(count, order, qs))
+            if np.ndim(q) == 0:
+                return self._replace(val[..., 0], lazy.lead_dims())
+            out = self._replace(val.permute(val.dim() - 1, *range(val.dim() - 1)), ("quantile",) + lazy.lead_dims())
+            out.coords["quantile"] = DataArray(qs, ("quantile",))
+            return out
+        out = {"count": lambda: count.to(torch.int64),
+               "sum": lambda: stats[..., 0],
+               "mean": lambda: stats[..., 0] / count.to(torch.float64),
+               "min": lambda: stats[..., 2],
+               "max": lambda: stats[..., 3],
+               "var": lambda: reduce.variance_from_m2(count, stats[..., 1], ddof),
+               "std": lambda: torch.sqrt(reduce.variance_from_m2(count, stats[..., 1], ddof))}[what]()
+        return self._replace(lazy.per_window(out), lazy.lead_dims())
+
+    def _reduce(self, fn, dim=None, lead=(), **kw):
+        """``fn`` over the axes of ``dim`` (all of them: None); ``lead`` names the axes ``fn`` puts in front."""
         if dim is None:
             axes, dims = None, ()
         else:
             names = [dim] if isinstance(dim, str) else list(dim)
             axes = tuple(self.dims.index(d) for d in names)
             dims = tuple(d for d in self.dims if d not in names)
-        return self._replace(fn(self.values, axis=axes, **kw), dims)
+        return self._replace(fn(self.values, axis=axes, **kw), tuple(lead) + dims)
 
-    def sum(self, dim=None): return self._reduce(np.nansum if self.dtype.kind == "f" else np.sum, dim)
-    def mean(self, dim=None): return self._reduce(np.nanmean, dim)
-    def median(self, dim=None): return self._reduce(np.nanmedian, dim)
-    def max(self, dim=None): return self._reduce(np.nanmax if self.dtype.kind == "f" else np.max, dim)
-    def min(self, dim=None): return self._reduce(np.nanmin if self.dtype.kind == "f" else np.min, dim)
+    def _reduce_or_masked(self, what, fn, dim, **kw):
+        out = self._masked(what, dim, **kw)
+        return out if out is not None else self._reduce(fn, dim, **kw)
+
+    def sum(self, dim=None): return self._reduce_or_masked("sum", np.nansum if self.dtype.kind == "f" else np.sum, dim)
+    def mean(self, dim=None): return self._reduce_or_masked("mean", np.nanmean, dim)
+    def median(self, dim=None): return self._reduce_or_masked("median", np.nanmedian, dim)
+    def max(self, dim=None): return self._reduce_or_masked("max", np.nanmax if self.dtype.kind == "f" else np.max, dim)
+    def min(self, dim=None): return self._reduce_or_masked("min", np.nanmin if self.dtype.kind == "f" else np.min, dim)
+    def std(self, dim=None, ddof=0): return self._reduce_or_masked("std", np.nanstd, dim, ddof=ddof)
+    def var(self, dim=None, ddof=0): return self._reduce_or_masked("var", np.nanvar, dim, ddof=ddof)
+
+    def count(self, dim=None):
+        """The number of non-NaN values (``xarray.DataArray.count``)."""
+        def valid(v, axis):
+            return np.sum(~np.isnan(v) if v.dtype.kind in "fc" else np.ones(v.shape, dtype=bool), axis=axis)
+
+        return self._reduce_or_masked("count", valid, dim)
+
+    def quantile(self, q, dim=None):
+        """``np.nanquantile`` (linear) over ``dim``; a sequence ``q`` adds a leading ``quantile`` dimension, as xarray."""
+        out = self._masked("quantile", dim, q=q)
+        if out is not None:
+            return out
+        if np.ndim(q) == 0:
+            return self._reduce(lambda v, axis: np.nanquantile(v, q, axis=axis), dim)
+        qs = np.asarray(q, dtype=np.float64)
+        out = self._reduce(lambda v, axis: np.nanquantile(v, qs, axis=axis), dim, lead=("quantile",))
+        out.coords["quantile"] = DataArray(qs, ("quantile",))
+        return out
+
     def any(self, dim=None): return self._reduce(np.any, dim)
     def all(self, dim=None): return self._reduce(np.all, dim)
 
