@@ -306,6 +306,9 @@ __global__ __launch_bounds__(NT) void k_layer_count(const uint32_t* __restrict__
 // the 6.1 ms candidates kernel.)
 constexpr int MAX_RANGES = 64;
 constexpr int DEDUP_TX = 2;
+struct Keys4 {  // four keys stored at once; aligned like one key
+  uint32_t k[4];
+};
 
 // TX = adjacent tiles of one tile row handled by a workgroup: the scanned cell ranges of neighbours
 // overlap by 2 * (max_r + 2) pixels, so wider groups read every key fewer times.
@@ -324,7 +327,15 @@ __global__ __launch_bounds__(NT) void k_tile_dedup(const uint32_t* __restrict__ 
   __shared__ int s_pre[MAX_RANGES + 1];
   __shared__ int s_cnt[TX * 32 + 1];  // circles per (tile, layer), then their exclusive prefix (nr <= 32)
   __shared__ int s_base;
-  const int plane = blockIdx.z, tr = blockIdx.y, tc0 = blockIdx.x * TX;
+  // The grid is (tile pairs of a row, tile rows, planes), but workgroups that start one after the other take
+  // DIFFERENT planes (the plane is the fastest index of the dispatch order x, y, z), the tile groups of a plane still
+  // in their order.  Every group ends its counting with one returning atomicAdd on d_num_circles[plane]; those on one
+  // address are served one at a time at the memory side, 10 ns each -- launched plane by plane, the 137 280 groups of
+  // the bench waited 1.4 ms for them, however little else they did.
+  // (tile groups < 2^15 by mg_key_layout, planes < 2^16: the linear index fits an int)
+  const int lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
+  const int plane = lin % (int)gridDim.z, group = lin / (int)gridDim.z;
+  const int tr = group / (int)gridDim.x, tc0 = (group - tr * (int)gridDim.x) * TX;
   const int ntx = min(TX, ntc - tc0);  // tiles of this group that exist
   const int tile0 = tr * ntc + tc0;
   const int words = nr * LAYER_WORDS;  // per tile
@@ -386,27 +397,41 @@ __global__ __launch_bounds__(NT) void k_tile_dedup(const uint32_t* __restrict__ 
   __syncthreads();
   // Ordered emission straight from LDS.  The bit index inside a tile IS the low 17 bits of the key
   // (layer | row | col), so walking the tile's words in order yields its keys in ascending order.
-  // Every thread owns a run of consecutive words: count its bits, one block-wide exclusive scan of the counts
-  // (its entries at the layer boundaries are the per-(tile, radius) starts), reserve the group's slice of the
-  // plane's list with one atomicAdd (d_num_circles is the cursor), then every thread stores the keys of its run.
+  // Every thread owns a run of `per` consecutive words and reads it ONCE for everything the counts decide: the
+  // run's bit count (`mine`), the part of it in front of the first layer start inside the run (`head`), and a
+  // mask of the run's non-empty words.  per <= 32 < LAYER_WORDS, so the mask is one register and a run holds at
+  // most one layer start (a tile starts on a layer start): after one block-wide exclusive scan of the counts,
+  // ex + head IS that layer's entry of s_cnt -- the per-(tile, radius) starts need no second walk.  The group's
+  // slice of the plane's list is reserved with one atomicAdd (d_num_circles is the cursor).
+  // Emission then is ONE flat loop over the keys the thread may store: a step yields one key, and first fetches
+  // the next non-empty word (ctz of the mask, one LDS read) when the current one is used up; four keys go out per
+  // store.  With ~0.3 keys per word three words in four are empty; a wave runs max-over-lanes(keys of the run)
+  // steps instead of visiting all `per` words with max-over-lanes(popcount) rounds in each.  Keys at or beyond
+  // circle_cap are not visited at all: the cursor has already advanced by the whole group, k_clamp_counts clamps it.
   // (A wave per sparse layer -- ~40 keys in 4096 bits -- spent most of its instructions on empty rows.)
   // Slices of different groups land in arrival order; everything downstream that needs the canonical order
   // compares the keys themselves, never list positions.
+  static_assert(TX * 32 * LAYER_WORDS <= 32 * NT, "a thread's run of words must fit the 32-bit mask of non-empty words");
   const int n_li = ntx * nr;
   const int n_words = n_li * LAYER_WORDS;
   const int per = (n_words + NT - 1) / NT;
   const int w0 = min((int)threadIdx.x * per, n_words), w1 = min(w0 + per, n_words);
-  int mine = 0;
-  for (int wd = w0; wd < w1; ++wd) mine += __popc(lbits[wd]);
+  const int wb = (w0 + LAYER_WORDS - 1) & ~(LAYER_WORDS - 1);  // first layer start at or behind w0: in the run if < w1
+  const int n_run = w1 - w0, j_start = wb - w0;
+  const uint32_t* run = lbits + w0;
+  int mine = 0, head = 0;
+  uint32_t full = 0u;  // bit j: word w0 + j has a key
+#pragma clang loop vectorize(disable)
+#pragma unroll 4
+  for (int j = 0; j < n_run; ++j) {
+    const uint32_t v = run[j];
+    head = j == j_start ? mine : head;  // the count in front of the layer start
+    mine += __popc(v);
+    full |= min(v, 1u) << j;
+  }
   int n_unique;
   const int ex = mg_block_exscan(mine, &n_unique);
-  {
-    int run = ex;  // exclusive prefix at the thread's first word
-    for (int wd = w0; wd < w1; ++wd) {
-      if ((wd & (LAYER_WORDS - 1)) == 0) s_cnt[wd / LAYER_WORDS] = run;  // first word of a layer
-      run += __popc(lbits[wd]);
-    }
-  }
+  if (wb < w1) s_cnt[wb / LAYER_WORDS] = ex + head;
   if (threadIdx.x == 0) {
     s_cnt[n_li] = n_unique;
     s_base = n_unique ? atomicAdd(&d_num_circles[plane], n_unique) : 0;
@@ -426,22 +451,36 @@ __global__ __launch_bounds__(NT) void k_tile_dedup(const uint32_t* __restrict__ 
     }
   }
   uint32_t* out = d_ukeys + (int64_t)plane * circle_cap;
-  int64_t pos = base + ex;
-  for (int wd = w0; wd < w1; ++wd) {
-    uint32_t bits = lbits[wd];
-    if (!bits) continue;
-    int t = 0, rem = wd;  // tile of the group; rem * 32 + bit = the key's low 17 bits  (TX - 1 compares, not a division)
+  const int64_t first = min(base + ex, circle_cap);             // the thread's keys go to [first, first + room)
+  const int room = (int)min((int64_t)mine, circle_cap - first);  // keys of the run in front of circle_cap
+  uint32_t* mykeys = out + first;
+  // key of bit b of word wd of the group = (wd << 5) + b + tile0 << 17 + t * next_tile for its tile t: the tile index
+  // goes up by one, the word index inside the tile down by `words`  (TX - 1 compares, not a division)
+  const uint32_t key0 = mg_key_from_low17(tile0, 0u), next_tile = mg_key_from_low17(1, 0u) - ((uint32_t)words << 5);
+  uint32_t bits = 0u, hi = 0u;
+  auto next_key = [&]() -> uint32_t {  // called at most room <= mine times: a non-empty word is left, so neither
+    if (!bits) {                       // `full` nor the word fetched is 0
+      const int wd = w0 + __builtin_ctz(full);
+      full &= full - 1;
+      bits = lbits[wd];
+      hi = key0 + ((uint32_t)wd << 5);
 #pragma unroll
-    for (int k = 1; k < TX; ++k)
-      if (rem >= words) rem -= words, ++t;
-    const uint32_t hi = mg_key_from_low17(tile0 + t, (uint32_t)rem << 5);
-    while (bits) {
-      const int b = __ffs(bits) - 1;
-      bits &= bits - 1;
-      if (pos < circle_cap) out[pos] = hi | (uint32_t)b;
-      ++pos;
+      for (int t = 1; t < TX; ++t) hi += wd >= t * words ? next_tile : 0u;
     }
+    const uint32_t key = hi | (uint32_t)__builtin_ctz(bits);
+    bits &= bits - 1;
+    return key;
+  };
+  // Four keys per store: the lanes of a wave write to 64 different places of the list (each its own run's keys), so
+  // what this costs is the number of store requests, not the bytes -- measured, DESIGN §21.  (Global accesses need
+  // no more than the 4-byte alignment the list has.)
+  int k = 0;
+  for (; k + 4 <= room; k += 4) {
+    Keys4 q;
+    q.k[0] = next_key(), q.k[1] = next_key(), q.k[2] = next_key(), q.k[3] = next_key();
+    *reinterpret_cast<Keys4*>(mykeys + k) = q;
   }
+  for (; k < room; ++k) mykeys[k] = next_key();
 }
 
 __global__ __launch_bounds__(1024) void k_layer_scan(int32_t* __restrict__ d_layer_offsets, int n_layers,
