@@ -700,7 +700,12 @@ int mg_roi_window_order(const int32_t* d_beads, int64_t bead_stride, const int32
  * nothing is left.  The mask of marker g at timepoint t is the L x L bytes at d_mask + g * mask_stride_m +
  * t * mask_stride_t (elements; mask_stride_t = 0: one mask for all timepoints, as find_beads replicates its geometry,
  * find.py:585-586; chips searched at several timesteps have a mask per timepoint, find.py:119-140).
- * d_median double[m][C][T].  Exact: radix select on the order-preserving bit pattern of the values. */
+ * d_median double[m][C][T].  Exact: radix select on the order-preserving bit pattern of the values.
+ * Served by the kernel of mg_roi_masked_stats (below) in its median mode: one read of a window whose keys fit the LDS
+ * budget, the two middle ranks selected directly (one where the count is odd), one double written per window.  Its
+ * limits are that entry point's -- MG_EINVAL, with nothing written: a null pointer, an unknown dtype, m < 0,
+ * n_c / n_t / roi_len <= 0, roi_len > MG_ROISTATS_MAX_LEN, m * n_c * n_t >= 2^31, a negative stride (n_c * n_t itself
+ * is no longer limited to 65535).  m = 0 returns MG_OK and writes nothing.  One kernel launch. */
 int mg_roi_masked_median(const void* d_roi, int dtype, const uint8_t* d_mask, int64_t mask_stride_m,
                          int64_t mask_stride_t, int m, int n_c, int n_t, int roi_len, double* d_median, void* stream);
 

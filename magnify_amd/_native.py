@@ -15,10 +15,6 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "_lib", "libmagnify_hip.so")
 
-MG_U8, MG_U16, MG_F32, MG_F64 = 0, 1, 2, 3
-MG_NO_EDGE = 100.0
-MG_SCORE_SKIPPED = -2.0
-
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "magnify_hip.h")
 
 
@@ -40,22 +36,28 @@ def _ctype(decl: str, what: str):
 
 
 def _parse_header():
-    """(name -> argtypes, name -> restype) of every `int|int64_t mg_*(...);` declared in the header."""
+    """(name -> argtypes, name -> restype) of every `int|int64_t mg_*(...);` declared in the header, and name -> value
+    of every `#define MG_NAME <integer or float literal>` (in parentheses or not, with or without an f suffix)."""
     if not os.path.exists(HEADER_PATH):
         raise NativeLibraryMissing(f"{HEADER_PATH} not found: the ctypes binding is read from it.  "
                                    "magnify_amd has no fallback table.")
     with open(HEADER_PATH) as f:
         text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", f.read(), flags=re.S)
+    defines = {}
+    for name, number, is_float in re.findall(r"^[ \t]*#define[ \t]+(MG_\w+)[ \t]+\(?(-?\d+(\.\d*)?)f?\)?[ \t]*$", text, flags=re.M):
+        defines[name] = float(number) if is_float else int(number)
     argtypes, restypes = {}, {}
     for ret, name, args in re.findall(r"\b(\w+)\s+(mg_\w+)\s*\(([^)]*)\)\s*;", text):
         args = [] if args.strip() in ("", "void") else args.split(",")
         argtypes[name] = [_ctype(a, name) for a in args]
         restypes[name] = _ctype(ret, name)
-    return argtypes, restypes
+    return argtypes, restypes, defines
 
 
-# name -> argtypes / restype: the prototypes of include/magnify_hip.h, read from it
-PROTOTYPES, RESTYPES = _parse_header()
+# name -> argtypes / restype / value: the prototypes and the constants of include/magnify_hip.h, read from it
+PROTOTYPES, RESTYPES, DEFINES = _parse_header()
+MG_U8, MG_U16, MG_F32, MG_F64 = (DEFINES[k] for k in ("MG_U8", "MG_U16", "MG_F32", "MG_F64"))
+MG_NO_EDGE, MG_SCORE_SKIPPED = DEFINES["MG_NO_EDGE"], DEFINES["MG_SCORE_SKIPPED"]
 
 _lib = None
 

@@ -121,6 +121,22 @@ __device__ __forceinline__ double mg_load_f64(const void* p, int dtype, int64_t 
   }
 }
 
+// i = (a * nb + b) * nc + c of a grid-stride loop, taken apart; row = a * nb + b.  `small` (uniform): the loop's total
+// fits 31 bits, so the divisions are 32-bit ones.
+struct MgIndex3 {
+  int64_t row;
+  int a, b, c;
+};
+__device__ __forceinline__ MgIndex3 mg_split3(int64_t i, bool small, int nb, int nc) {
+  if (small) {
+    const uint32_t u = (uint32_t)i, r = u / (uint32_t)nc, a = r / (uint32_t)nb;
+    return {(int64_t)r, (int)a, (int)(r - a * (uint32_t)nb), (int)(u - r * (uint32_t)nc)};
+  }
+  const int64_t r = i / nc;
+  const int a = (int)(r / nb);
+  return {r, a, (int)(r - (int64_t)a * nb), (int)(i - r * nc)};
+}
+
 // NaN-propagating max / min, as np.max / np.min.
 __device__ __forceinline__ double mg_nanmax(double a, double b) { return (a != a) ? a : (b != b) ? b : (a > b ? a : b); }
 __device__ __forceinline__ double mg_nanmin(double a, double b) { return (a != a) ? a : (b != b) ? b : (a < b ? a : b); }
@@ -301,6 +317,9 @@ __device__ __forceinline__ int mg_block_exscan(int v, int* total) {
 // arctan2(dy, dx) evaluated in float64 and rounded once (utils.py:118-119, 170).
 struct __attribute__((packed)) MgUnaligned32 {
   uint32_t v;
+};
+struct __attribute__((packed)) MgUnaligned64 {
+  uint64_t v;
 };
 __device__ __forceinline__ float mg_edge_angle(const uint8_t* __restrict__ pb, int h, int w, int y, int x) {
   if (y >= 1 && y < h - 1 && x >= 1 && x < w - 2) {

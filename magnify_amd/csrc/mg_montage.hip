@@ -6,19 +6,13 @@
 // names the marker shown there (-1: an empty cell, written as 0), at block (Y % lk, X % lk) of its window.  Per
 // channel the block's in-window pixels are summed -- uint32 for u8 / u16 (64^2 * 65535 < 2^32, exact), float64 for
 // float pixels, rows from the top, each from the left -- then mean, (mean - lo) / (hi - lo), clamp, acc += u * colour,
-// min(acc, 1), all float64, one operation at a time: steps 1-4 of mg_render_overview on a window.  A row of a block
+// min(acc, 1): mg_composite_add (mg_composite.h), what mg_render_overview does, on a window.  A row of a block
 // starts anywhere (a u16 window row of L = 100 is 200 bytes): elements up to the next 16-byte boundary, whole vectors,
 // elements again -- left to right on every path.  Then the masks: a block is on where any mask byte in it is set;
 // "outline" keeps the on-blocks with an off 4-neighbour in the cell.  The three bytes are written once.  No LDS.
-#include "mg_common.h"
+#include "mg_composite.h"
 
 namespace {
-
-constexpr int MT_NONE = 0, MT_OUTLINE = 1, MT_FILL = 2;
-
-struct MontageChannels {
-  double lo[MG_OVERVIEW_MAX_CHANNELS], hi[MG_OVERVIEW_MAX_CHANNELS], rgb[MG_OVERVIEW_MAX_CHANNELS][3];
-};
 
 struct MontageMask {  // mask of marker g at timepoint t: L x L bytes at p + g * stride_m + t * stride_t
   const uint8_t* p;
@@ -45,10 +39,6 @@ __device__ __forceinline__ Acc row_sum(const T* __restrict__ q, int nc, Acc sum)
   return sum;
 }
 
-struct __attribute__((packed)) MtUnaligned64 {
-  uint64_t v;
-};
-
 // any byte set in block (by, bx) of the L x L mask at m; a block outside the cell is off.  A row of the block starts
 // anywhere: eight bytes, four bytes, then single bytes per load (unaligned loads; the order does not matter to an OR).
 __device__ __forceinline__ bool block_on(const uint8_t* __restrict__ m, int L, int lk, int s, int by, int bx) {
@@ -58,7 +48,7 @@ __device__ __forceinline__ bool block_on(const uint8_t* __restrict__ m, int L, i
     const uint8_t* q = m + y * L + x0;
     uint64_t any = 0;
     int k = 0;
-    for (; k + 8 <= nc; k += 8) any |= reinterpret_cast<const MtUnaligned64*>(q + k)->v;
+    for (; k + 8 <= nc; k += 8) any |= reinterpret_cast<const MgUnaligned64*>(q + k)->v;
     if (k + 4 <= nc) any |= reinterpret_cast<const MgUnaligned32*>(q + k)->v, k += 4;
     for (; k < nc; ++k) any |= q[k];
     if (any) return true;
@@ -70,21 +60,15 @@ template <typename T>
 __global__ __launch_bounds__(256) void k_roi_montage(const T* __restrict__ roi, int64_t stride_m, int64_t stride_c,
                                                      int64_t stride_t, int n_marks, int n_c, int L, int level,
                                                      int lk, const int32_t* __restrict__ layout, int cols, int hp, int wp,
-                                                     int64_t total, MontageChannels ch, MontageMask bg, MontageMask fg,
+                                                     int64_t total, MgChannels ch, MontageMask bg, MontageMask fg,
                                                      int overlay, double alpha, uint8_t* __restrict__ out) {
-  using Acc = std::conditional_t<std::is_integral<T>::value, uint32_t, double>;
+  using Acc = mg_block_acc_t<T>;
   const int s = 1 << level;
   const bool small = total <= 0x7FFFFFFFLL;  // (uniform) 32-bit index arithmetic
   const int64_t stride = (int64_t)gridDim.x * 256;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
-    int X, Y, t;  // i = (t * hp + Y) * wp + X
-    if (small) {
-      const uint32_t u = (uint32_t)i, r = u / (uint32_t)wp, tt = r / (uint32_t)hp;
-      X = (int)(u - r * (uint32_t)wp), Y = (int)(r - tt * (uint32_t)hp), t = (int)tt;
-    } else {
-      const int64_t r = i / wp;
-      X = (int)(i - r * wp), t = (int)(r / hp), Y = (int)(r - (int64_t)t * hp);
-    }
+    const MgIndex3 at = mg_split3(i, small, hp, wp);  // i = (t * hp + Y) * wp + X
+    const int t = at.a, Y = at.b, X = at.c;
     const int cr = Y / lk, cc = X / lk, by = Y - cr * lk, bx = X - cc * lk;
     const int g = layout[cr * cols + cc];
     uint8_t* o = out + i * 3;
@@ -98,35 +82,23 @@ __global__ __launch_bounds__(256) void k_roi_montage(const T* __restrict__ roi, 
       const T* p = roi + (int64_t)g * stride_m + (int64_t)k * stride_c + (int64_t)t * stride_t + y0 * L + x0;
       Acc sum = (Acc)0;
       for (int r = 0; r < nr; ++r) sum = row_sum<T, Acc>(p + r * L, nc, sum);
-      double mean = (double)sum;
-      if (n != 1) mean = mean / (double)n;  // (x / 1 is x)
-      const double lo = ch.lo[k], range = ch.hi[k] - lo;
-      double u = (mean - lo) / range;
-      if (!(ch.hi[k] > lo) || !(u >= 0.0)) u = 0.0;  // hi <= lo, NaN, u < 0
-      if (u > 1.0) u = 1.0;
-      acc[0] = fmin(acc[0] + u * ch.rgb[k][0], 1.0);
-      acc[1] = fmin(acc[1] + u * ch.rgb[k][1], 1.0);
-      acc[2] = fmin(acc[2] + u * ch.rgb[k][2], 1.0);
+      mg_composite_add(mg_channel(ch, k), sum, n, acc);
     }
-    if (overlay != MT_NONE) {
+    if (overlay != MG_OVERLAY_NONE) {
 #pragma unroll
       for (int which = 0; which < 2; ++which) {  // bg in red, then fg in green on top
         const MontageMask& mk = which ? fg : bg;
         if (!mk.p) continue;
         const uint8_t* m = mk.p + (int64_t)g * mk.stride_m + (int64_t)t * mk.stride_t;
         bool on = block_on(m, L, lk, s, by, bx);
-        if (on && overlay == MT_OUTLINE)
+        if (on && overlay == MG_OVERLAY_OUTLINE)
           on = !(block_on(m, L, lk, s, by - 1, bx) && block_on(m, L, lk, s, by + 1, bx) &&
                  block_on(m, L, lk, s, by, bx - 1) && block_on(m, L, lk, s, by, bx + 1));
-        if (on) {
-          const double a = overlay == MT_FILL ? alpha : 1.0, keep = 1.0 - a;
-#pragma unroll
-          for (int e = 0; e < 3; ++e) acc[e] = keep * acc[e] + (a * (e == which ? 255.0 : 0.0)) / 255.0;
-        }
+        if (on) mg_overlay_blend(overlay == MG_OVERLAY_FILL ? alpha : 1.0, which ? 0.0 : 255.0, which ? 255.0 : 0.0, 0.0, acc);
       }
     }
 #pragma unroll
-    for (int e = 0; e < 3; ++e) o[e] = (uint8_t)floor(255.0 * acc[e] + 0.5);
+    for (int e = 0; e < 3; ++e) o[e] = mg_composite_byte(acc[e]);
   }
 }
 
@@ -140,17 +112,10 @@ extern "C" int mg_render_roi_montage(const void* d_roi, int dtype, int64_t strid
   if (!limits || !colors || n_marks < 0 || n_c < 1 || n_c > MG_OVERVIEW_MAX_CHANNELS || n_t < 1 || roi_len < 1 ||
       roi_len > 32767 || level < 0 || level > MG_OVERVIEW_MAX_LEVEL || rows < 0 || cols < 0 || stride_m < 0 || stride_c < 0 ||
       stride_t < 0 || bg_stride_m < 0 || bg_stride_t < 0 || fg_stride_m < 0 || fg_stride_t < 0 ||
-      !(overlay == MT_NONE || overlay == MT_OUTLINE || overlay == MT_FILL) || !(alpha >= 0.0 && alpha <= 1.0))
+      !mg_overlay_ok(overlay, alpha))
     return MG_EINVAL;
-  MontageChannels ch;
-  for (int k = 0; k < MG_OVERVIEW_MAX_CHANNELS; ++k) {
-    const bool used = k < n_c;
-    ch.lo[k] = used ? limits[2 * k] : 0.0, ch.hi[k] = used ? limits[2 * k + 1] : 0.0;
-    for (int e = 0; e < 3; ++e) {
-      ch.rgb[k][e] = used ? colors[3 * k + e] : 0.0;
-      if (!(ch.rgb[k][e] >= 0.0 && ch.rgb[k][e] <= 1.0)) return MG_EINVAL;
-    }
-  }
+  MgChannels ch;
+  if (mg_fill_channels(limits, colors, n_c, &ch) != MG_OK) return MG_EINVAL;
   const int s = 1 << level, lk = (roi_len + s - 1) / s;
   const int64_t hp = (int64_t)rows * lk, wp = (int64_t)cols * lk;
   if (hp > 0x7FFFFFFFLL || wp > 0x7FFFFFFFLL) return MG_EINVAL;

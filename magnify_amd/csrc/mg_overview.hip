@@ -17,11 +17,9 @@
 // from the top, each from the left, on every path.  The channels of an output pixel are accumulated in the same
 // thread -- mean, (mean - lo) / (hi - lo), clamp, acc += u * colour, min(acc, 1), all float64, one operation at a time
 // -- then the overlay is applied from the label map and the three bytes are written once.  No LDS, no atomics.
-#include "mg_common.h"
+#include "mg_composite.h"
 
 namespace {
-
-constexpr int OV_NONE = 0, OV_OUTLINE = 1, OV_FILL = 2;
 
 // ---- label map ------------------------------------------------------------------------------------------------------
 
@@ -67,10 +65,6 @@ __global__ __launch_bounds__(256) void k_image_labels(const uint8_t* __restrict_
 }
 
 // ---- composite ------------------------------------------------------------------------------------------------------
-
-struct OverviewChannels {  // by value: what every thread needs of every channel
-  double lo[MG_OVERVIEW_MAX_CHANNELS], hi[MG_OVERVIEW_MAX_CHANNELS], rgb[MG_OVERVIEW_MAX_CHANNELS][3];
-};
 
 template <typename T, int S>
 struct RunShape {
@@ -162,23 +156,18 @@ __device__ __forceinline__ void run_labels(const int32_t* __restrict__ p, int n,
 template <typename T, int S>
 __global__ __launch_bounds__(256) void k_overview(const T* __restrict__ image, int64_t chan_stride, int64_t time_stride,
                                                   int n_c, int n_t, int h, int w, int hk, int wk, int cpr, int64_t total,
-                                                  OverviewChannels ch, const int32_t* __restrict__ labels,
+                                                  MgChannels ch, const int32_t* __restrict__ labels,
                                                   const uint8_t* __restrict__ table, int n_marks, int overlay, double alpha,
                                                   uint8_t* __restrict__ out) {
   using Sh = RunShape<T, S>;
-  using Acc = std::conditional_t<std::is_integral<T>::value, uint32_t, double>;
+  using Acc = mg_block_acc_t<T>;
   constexpr int OC = Sh::OC;
   const bool small = total <= 0x7FFFFFFFLL;  // (uniform) 32-bit index arithmetic
   const int64_t stride = (int64_t)gridDim.x * 256;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
-    int64_t ri;
-    int c, Y, t;
-    if (small) {
-      const uint32_t u = (uint32_t)i, r = u / (uint32_t)cpr, tt = r / (uint32_t)hk;
-      c = (int)(u - r * (uint32_t)cpr), Y = (int)(r - tt * (uint32_t)hk), ri = r, t = (int)tt;
-    } else {
-      ri = i / cpr, c = (int)(i - ri * cpr), t = (int)(ri / hk), Y = (int)(ri - (int64_t)t * hk);
-    }
+    const MgIndex3 at = mg_split3(i, small, hk, cpr);  // i = (t * hk + Y) * cpr + run of the row
+    const int64_t ri = at.row;
+    const int t = at.a, Y = at.b, c = at.c;
     const int j0 = c * OC, nj = min(OC, wk - j0);
     const int nrows = min(S, h - Y * S), cols_left = w - j0 * S;
     double acc[OC][3];
@@ -190,23 +179,12 @@ __global__ __launch_bounds__(256) void k_overview(const T* __restrict__ image, i
 #pragma unroll
       for (int j = 0; j < OC; ++j) sum[j] = (Acc)0;
       block_sums<T, S, Acc>(p, w, nrows, nj, cols_left, sum);
-      const double lo = ch.lo[k], range = ch.hi[k] - lo, cr = ch.rgb[k][0], cg = ch.rgb[k][1], cb = ch.rgb[k][2];
-      const bool flat = !(ch.hi[k] > lo);
+      const MgChannel c = mg_channel(ch, k);
 #pragma unroll
       for (int j = 0; j < OC; ++j)
-        if (j < nj) {
-          const int n = nrows * min(S, cols_left - j * S);
-          double mean = (double)sum[j];
-          if (n != 1) mean = mean / (double)n;  // (x / 1 is x)
-          double u = (mean - lo) / range;
-          if (flat || !(u >= 0.0)) u = 0.0;  // hi <= lo, NaN, u < 0
-          if (u > 1.0) u = 1.0;
-          acc[j][0] = fmin(acc[j][0] + u * cr, 1.0);
-          acc[j][1] = fmin(acc[j][1] + u * cg, 1.0);
-          acc[j][2] = fmin(acc[j][2] + u * cb, 1.0);
-        }
+        if (j < nj) mg_composite_add(c, sum[j], nrows * min(S, cols_left - j * S), acc[j]);
     }
-    if (overlay != OV_NONE) {
+    if (overlay != MG_OVERLAY_NONE) {
       const int32_t* lrow = labels + ri * wk + j0;  // the run's labels; its neighbours only where it holds one
       int lab[OC];
       run_labels<OC>(lrow, nj, lab);
@@ -215,7 +193,7 @@ __global__ __launch_bounds__(256) void k_overview(const T* __restrict__ image, i
       for (int j = 0; j < OC; ++j) any |= lab[j] > 0 && lab[j] <= n_marks;
       if (any) {
         int up[OC], down[OC], lf = 0, rt = 0;
-        if (overlay == OV_OUTLINE) {  // (0 outside the picture)
+        if (overlay == MG_OVERLAY_OUTLINE) {  // (0 outside the picture)
           run_labels<OC>(lrow - wk, Y > 0 ? nj : 0, up);
           run_labels<OC>(lrow + wk, Y + 1 < hk ? nj : 0, down);
           lf = j0 > 0 ? lrow[-1] : 0, rt = j0 + nj < wk ? lrow[nj] : 0;
@@ -224,15 +202,13 @@ __global__ __launch_bounds__(256) void k_overview(const T* __restrict__ image, i
         for (int j = 0; j < OC; ++j)
           if (j < nj && lab[j] > 0 && lab[j] <= n_marks) {
             bool on = true;
-            if (overlay == OV_OUTLINE) {  // an edge of its region: a 4-neighbour with another label
+            if (overlay == MG_OVERLAY_OUTLINE) {  // an edge of its region: a 4-neighbour with another label
               const int left = j > 0 ? lab[j > 0 ? j - 1 : 0] : lf, right = j + 1 < nj ? lab[j + 1 < OC ? j + 1 : 0] : rt;
               on = up[j] != lab[j] || down[j] != lab[j] || left != lab[j] || right != lab[j];
             }
             if (on) {
-              const double a = overlay == OV_FILL ? alpha : 1.0, keep = 1.0 - a;
               const uint8_t* col = table + ((int64_t)(lab[j] - 1) * n_t + t) * 3;
-#pragma unroll
-              for (int e = 0; e < 3; ++e) acc[j][e] = keep * acc[j][e] + (a * (double)col[e]) / 255.0;
+              mg_overlay_blend(overlay == MG_OVERLAY_FILL ? alpha : 1.0, (double)col[0], (double)col[1], (double)col[2], acc[j]);
             }
           }
       }
@@ -242,7 +218,7 @@ __global__ __launch_bounds__(256) void k_overview(const T* __restrict__ image, i
 #pragma unroll
     for (int j = 0; j < OC; ++j)
 #pragma unroll
-      for (int e = 0; e < 3; ++e) by[3 * j + e] = (uint8_t)floor(255.0 * acc[j][e] + 0.5);
+      for (int e = 0; e < 3; ++e) by[3 * j + e] = mg_composite_byte(acc[j][e]);
     if (OC % 4 == 0 && nj == OC && (reinterpret_cast<uintptr_t>(o) & 3) == 0) {  // whole words, as wide as they come
       uint32_t wd[OC % 4 == 0 ? OC * 3 / 4 : 1];
 #pragma unroll
@@ -266,7 +242,7 @@ __global__ __launch_bounds__(256) void k_overview(const T* __restrict__ image, i
 
 template <typename T, int S>
 int launch_overview(const void* d_image, int64_t chan_stride, int64_t time_stride, int n_c, int n_t, int h, int w,
-                    const OverviewChannels& ch, const int32_t* d_labels, const uint8_t* d_table, int n_marks, int overlay,
+                    const MgChannels& ch, const int32_t* d_labels, const uint8_t* d_table, int n_marks, int overlay,
                     double alpha, uint8_t* d_out, hipStream_t s) {
   const int hk = (h + S - 1) / S, wk = (w + S - 1) / S, oc = RunShape<T, S>::OC;
   const int cpr = (wk + oc - 1) / oc;
@@ -303,18 +279,11 @@ extern "C" int mg_render_overview(const void* d_image, int dtype, int64_t chan_s
                                   uint8_t* d_out, void* stream) {
   if (!d_image || !d_out || !limits || !colors || n_c < 1 || n_c > MG_OVERVIEW_MAX_CHANNELS || n_t < 1 || h < 1 || w < 1 ||
       level < 0 || level > MG_OVERVIEW_MAX_LEVEL || chan_stride < 0 || time_stride < 0 ||
-      !(overlay == OV_NONE || overlay == OV_OUTLINE || overlay == OV_FILL) || !(alpha >= 0.0 && alpha <= 1.0))
+      !mg_overlay_ok(overlay, alpha))
     return MG_EINVAL;
-  if (overlay != OV_NONE && (!d_labels || !d_table || n_marks < 1)) return MG_EINVAL;
-  OverviewChannels ch;
-  for (int k = 0; k < MG_OVERVIEW_MAX_CHANNELS; ++k) {
-    const bool used = k < n_c;
-    ch.lo[k] = used ? limits[2 * k] : 0.0, ch.hi[k] = used ? limits[2 * k + 1] : 0.0;
-    for (int e = 0; e < 3; ++e) {
-      ch.rgb[k][e] = used ? colors[3 * k + e] : 0.0;
-      if (!(ch.rgb[k][e] >= 0.0 && ch.rgb[k][e] <= 1.0)) return MG_EINVAL;
-    }
-  }
+  if (overlay != MG_OVERLAY_NONE && (!d_labels || !d_table || n_marks < 1)) return MG_EINVAL;
+  MgChannels ch;
+  if (mg_fill_channels(limits, colors, n_c, &ch) != MG_OK) return MG_EINVAL;
   hipStream_t s = mg_stream(stream);
   return mg_dispatch_pixel(dtype, [&](auto t) {
     using T = decltype(t);

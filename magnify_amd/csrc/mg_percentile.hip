@@ -1,8 +1,8 @@
 // plot.percentile_limits ("roishow and percentile contrast limits"): exact order statistics of a resident
 // stack by radix selection on an order-preserving integer key, coarse to fine.  The key of a value: the value itself
 // for u8 (8 bits) and u16 (16 bits); for float32 -- and float64 rounded to float32 first, which is monotone -- the 32
-// bits with the sign flipped for positive and all bits flipped for negative values, -0 counted as +0.  NaN has no key
-// and is not counted.
+// key of median_key<float> (mg_select.h: the sign flipped for positive, all bits flipped for negative values), -0
+// counted as +0.  NaN has no key and is not counted.
 //
 // k_key_hist is one read-once pass: every value whose key bits above `prefix_shift` equal one of up to
 // MG_PERCENTILE_MAX_PREFIXES selected prefixes (the first pass has none: every value takes part) is counted in the
@@ -22,7 +22,7 @@
 // Work: a unit is `unit_len` contiguous elements (a plane, a window) at d + i0 * stride0 + i1 * stride1; a chunk is
 // up to 256 * R vectors of 16 bytes of one unit, a workgroup strides over the chunks.  16-byte loads where the vector
 // lies whole in the unit and its address is aligned, element loads otherwise.
-#include "mg_common.h"
+#include "mg_select.h"
 
 namespace {
 
@@ -42,9 +42,7 @@ __device__ __forceinline__ bool pc_key(T x, uint32_t& key) {
     float f = (float)x;  // (float64: round to nearest even, the order statistic commutes with it)
     if (f != f) return false;
     if (f == 0.0f) f = 0.0f;  // -0 is +0
-    const uint32_t b = __float_as_uint(f);
-    key = b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-    return true;
+    return median_key<float>::key(f, &key);  // (true: f is no NaN)
   }
 }
 

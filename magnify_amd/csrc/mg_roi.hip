@@ -7,7 +7,6 @@
 
 #include "mg_common.h"
 #include "mg_flatcorr.h"
-#include "mg_select.h"
 
 namespace {
 
@@ -547,51 +546,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(5, 8))) void
   }
 }
 
-// ---- masked median: byte-wise radix select in LDS -------------------------------------------------
-// (median_key<T>, the order-preserving key of a pixel, and select_kth: mg_select.h, shared with mg_roistats.hip)
-static_assert(NT == MG_SELECT_THREADS, "select_kth strides by the workgroup size");
-
-// one workgroup per (marker, channel-time): mask of marker g at time t = d_mask + g * mask_stride_m + t * mask_stride_t
-template <typename T>
-__global__ __launch_bounds__(NT) void k_masked_median(const T* __restrict__ d_roi, const uint8_t* __restrict__ d_mask,
-                                                      int64_t mask_stride_m, int64_t mask_stride_t, int n_t, int n_ct,
-                                                      int n, double* __restrict__ d_median) {
-  __shared__ uint32_t hist[256];
-  __shared__ int s_count;
-  const int g = blockIdx.x, ct = blockIdx.y;
-  const T* v = d_roi + ((int64_t)g * n_ct + ct) * n;
-  const uint8_t* mask = d_mask + (int64_t)g * mask_stride_m + (int64_t)(ct % n_t) * mask_stride_t;
-  int c = 0;
-  for (int p = threadIdx.x; p < n; p += NT) {
-    typename median_key<T>::type key;
-    c += mask[p] != 0 && median_key<T>::key(v[p], &key);
-  }
-  int total;
-  mg_block_exscan(c, &total);
-  if (threadIdx.x == 0) s_count = total;
-  __syncthreads();
-  const int cnt = s_count;
-  double* out = d_median + (int64_t)g * n_ct + ct;
-  if (cnt == 0) {
-    if (threadIdx.x == 0) *out = __longlong_as_double(0x7FF8000000000000ll);
-    return;
-  }
-  const auto lo = select_kth<T>(v, mask, n, (cnt - 1) / 2, hist);
-  auto hi = lo;
-  if ((cnt & 1) == 0) hi = select_kth<T>(v, mask, n, cnt / 2, hist);
-  // numpy's nanmedian: the mean of the two middle values (here in float64: exact for every type but float64 itself)
-  if (threadIdx.x == 0) *out = (median_key<T>::value(lo) + median_key<T>::value(hi)) / 2.0;
-}
-
-template <typename T>
-int launch_median(const void* d_roi, const uint8_t* d_mask, int64_t sm, int64_t st, int m, int n_c, int n_t, int len,
-                  double* d_median, hipStream_t s) {
-  hipLaunchKernelGGL((k_masked_median<T>), dim3(m, n_c * n_t), dim3(NT), 0, s, (const T*)d_roi, d_mask, sm, st, n_t,
-                     n_c * n_t, len * len, d_median);
-  MG_CHECK_LAUNCH();
-  return MG_OK;
-}
-
 // ---- host side of the ROI pass ---------------------------------------------------------------------------------------
 // What one call of the pass is given: the entry points fill it, roi_dispatch chooses the kernel.
 struct RoiCall {
@@ -872,16 +826,4 @@ extern "C" int mg_roi_segment_reduce_raw(const void* d_image, const void* d_raw,
                               .d_fg = d_fg, .d_bg = d_bg, .d_sums = d_sums, .d_counts = d_counts,
                               .stream = mg_stream(stream)},
                       &rw);
-}
-
-extern "C" int mg_roi_masked_median(const void* d_roi, int dtype, const uint8_t* d_mask, int64_t mask_stride_m,
-                                    int64_t mask_stride_t, int m, int n_c, int n_t, int roi_len, double* d_median,
-                                    void* stream) {
-  if (!d_roi || !d_mask || !d_median || m < 0 || n_c <= 0 || n_t <= 0 || roi_len <= 0) return MG_EINVAL;
-  if (mask_stride_m < 0 || mask_stride_t < 0 || (int64_t)n_c * n_t > 65535) return MG_EINVAL;
-  if (m == 0) return MG_OK;
-  hipStream_t s = mg_stream(stream);
-  return mg_dispatch_pixel(dtype, [&](auto t) {
-    return launch_median<decltype(t)>(d_roi, d_mask, mask_stride_m, mask_stride_t, m, n_c, n_t, roi_len, d_median, s);
-  });
 }

@@ -1,7 +1,8 @@
 // roi.where(mask).{sum, mean, std, var, min, max, count, quantile}(dim=[roi_y, roi_x]) of an already gathered roi
 // (README.md:21-22, identify.py:76-80, filter.py:20-22): one workgroup per (marker, channel-time) reads the window and
 // its mask ONCE from global memory, reduces count / sum / min / max on the way in and keeps the keys of the surviving
-// pixels in LDS; the squared deviations and every order statistic asked for then run out of LDS.
+// pixels in LDS; the squared deviations and every order statistic asked for then run out of LDS.  The masked median
+// (mg_roi_masked_median: numpy's nanmedian) is the same kernel in its median mode: the middle ranks, nothing else.
 //
 // Roofline: HBM.  Per window L*L*(sizeof(T) + 1) bytes read, 4 + 32 + 16 n_q bytes written.
 #include "mg_select.h"
@@ -141,48 +142,12 @@ struct Runs {
   }
 };
 
-// select_kth (mg_select.h) over the compacted keys in LDS.  hist[256] is all zero on entry and on return.
-template <typename K, int LV>
-__device__ __forceinline__ K select_kth_lds(const K* keys, const Runs& runs, int count, int k, uint32_t* hist, int* s_pick) {
-  const int lane = threadIdx.x & 63;
-  K prefix = 0;
-  int rank = k;
-  for (int level = 0; level < LV; ++level) {
-    const int shift = 8 * (LV - 1 - level);
-    for (int i = threadIdx.x; i < count; i += NT) {
-      const K key = keys[runs.slot(i)];
-      if (level == 0 || (key >> (shift + 8)) == prefix) atomicAdd(&hist[(uint32_t)(key >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    if (threadIdx.x < 64) {  // wave 0: four bins a lane, a scan of the lanes' totals, then the bin inside one lane
-      uint32_t h[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) h[j] = hist[4 * lane + j], hist[4 * lane + j] = 0u;
-      const int total = (int)(h[0] + h[1] + h[2] + h[3]);
-      const int incl = mg_wave_scan_incl_i32(total);
-      const unsigned long long reached = __ballot(incl > rank);
-      const int owner = reached ? __ffsll((long long)reached) - 1 : 63;  // (rank < count: some lane reaches it)
-      if (lane == owner) {
-        int acc = incl - total, b = 0;
-#pragma unroll
-        for (; b < 3; ++b) {
-          if (acc + (int)h[b] > rank) break;
-          acc += (int)h[b];
-        }
-        s_pick[0] = 4 * lane + b;
-        s_pick[1] = rank - acc;
-      }
-    }
-    __syncthreads();
-    prefix = (prefix << 8) | (K)s_pick[0];
-    rank = s_pick[1];
-  }
-  return prefix;  // (the next call writes s_pick only behind its first barrier: every thread has read it by then)
-}
-
 // One workgroup per (marker, channel-time) window.  IN_LDS: the keys of the window fit `keys` (dynamic LDS, n keys);
 // otherwise nothing is kept, the deviations and the selections read the window again from global memory.
-template <typename T, bool IN_LDS>
+// MEDIAN (mg_roi_masked_median): d_order is one double per window, numpy's nanmedian -- the mean of the two middle
+// values in float64 (exact for every type but float64 itself), NaN where nothing takes part; no deviations, nothing
+// else is written.
+template <typename T, bool IN_LDS, bool MEDIAN = false>
 __global__ __launch_bounds__(NT) void k_masked_stats(const T* __restrict__ d_roi, const uint8_t* __restrict__ d_mask,
                                                      int64_t mask_stride_m, int64_t mask_stride_t, int n_t, int n_ct,
                                                      int n, StatsQ qs, int n_q, int32_t* __restrict__ d_count,
@@ -201,19 +166,25 @@ __global__ __launch_bounds__(NT) void k_masked_stats(const T* __restrict__ d_roi
 
   Seen<T> seen;
   const int run = wide ? ingest<T, VW, IN_LDS>(v, mask, n, keys, seen) : ingest<T, 1, IN_LDS>(v, mask, n, keys, seen);
-  if (IN_LDS) {
-    for (int i = threadIdx.x; i < 256; i += NT) hist[i] = 0u;
-    if ((threadIdx.x & 63) == 0) s_run[threadIdx.x >> 6] = run;
-  }
+  for (int i = threadIdx.x; i < 256; i += NT) hist[i] = 0u;  // (as select_kth wants it)
+  if (IN_LDS && (threadIdx.x & 63) == 0) s_run[threadIdx.x >> 6] = run;
   // (block_fold synchronises: s_run, hist and the keys are in place after the first of these)
   const int count = block_fold(seen.count, [](int a, int b) { return a + b; });
-  const auto sum = block_fold(seen.sum, [](auto a, auto b) { return a + b; });
-  const K kmin = block_fold(seen.kmin, [](K a, K b) { return a < b ? a : b; });
-  const K kmax = block_fold(seen.kmax, [](K a, K b) { return a > b ? a : b; });
+  typename Seen<T>::Acc sum = 0;
+  K kmin = 0, kmax = 0;
+  if (!MEDIAN) {
+    sum = block_fold(seen.sum, [](auto a, auto b) { return a + b; });
+    kmin = block_fold(seen.kmin, [](K a, K b) { return a < b ? a : b; });
+    kmax = block_fold(seen.kmax, [](K a, K b) { return a > b ? a : b; });
+  }
 
   double* stats = d_stats + window * 4;
-  double* order = d_order + window * n_q * 2;  // (not touched when n_q = 0)
+  double* order = d_order + window * (MEDIAN ? 1 : n_q * 2);  // (not touched when n_q = 0)
   if (count == 0) {  // block-uniform
+    if (MEDIAN) {
+      if (threadIdx.x == 0) order[0] = QNAN;
+      return;
+    }
     if (threadIdx.x == 0) {
       d_count[window] = 0;
       stats[0] = 0.0, stats[1] = 0.0, stats[2] = QNAN, stats[3] = QNAN;
@@ -233,6 +204,20 @@ __global__ __launch_bounds__(NT) void k_masked_stats(const T* __restrict__ d_roi
     runs.step1 = p1 - runs.first1;
     runs.step2 = (p2 - runs.first2) - (p1 - runs.first1);
     runs.step3 = (p3 - runs.first3) - (p2 - runs.first2);
+  }
+  // sorted[rank]: over the survivors' keys in LDS, or over the window's pixels in global memory
+  auto select = [&](int rank) -> K {
+    if (IN_LDS)
+      return select_kth<K, median_key<T>::LEVELS>(
+          count, [&](int i, K* key) { *key = keys[runs.slot(i)]; return true; }, rank, hist, s_pick);
+    return select_kth<K, median_key<T>::LEVELS>(
+        n, [&](int p, K* key) { return mask[p] && median_key<T>::key(v[p], key); }, rank, hist, s_pick);
+  };
+  if (MEDIAN) {
+    const K lo = select((count - 1) / 2);
+    const K hi = (count & 1) ? lo : select(count / 2);  // block-uniform
+    if (threadIdx.x == 0) order[0] = (median_key<T>::value(lo) + median_key<T>::value(hi)) / 2.0;
+    return;
   }
 
   // m2 = sum (x - mean)^2, each thread its own survivors in index order, then the fold's fixed tree
@@ -270,10 +255,7 @@ __global__ __launch_bounds__(NT) void k_masked_stats(const T* __restrict__ d_roi
     for (int e = 0; e < 2; ++e) {
       const int rank = e ? hi : lo;
       if (rank != have_rank) {  // block-uniform
-        if (IN_LDS)
-          have_key = select_kth_lds<K, median_key<T>::LEVELS>(keys, runs, count, rank, hist, s_pick);
-        else
-          have_key = select_kth<T>(v, mask, n, rank, hist);
+        have_key = select(rank);
         have_rank = rank;
       }
       pair[e] = have_key;
@@ -285,20 +267,27 @@ __global__ __launch_bounds__(NT) void k_masked_stats(const T* __restrict__ d_roi
   }
 }
 
-template <typename T>
+// MEDIAN: d_order is the (m, n_c, n_t) medians, and d_count, d_stats, qs are not looked at.
+template <typename T, bool MEDIAN>
 int launch_stats(const void* d_roi, const uint8_t* d_mask, int64_t sm, int64_t st, int m, int n_c, int n_t, int len,
                  const StatsQ& qs, int n_q, int32_t* d_count, double* d_stats, double* d_order, hipStream_t s) {
   typedef typename median_key<T>::type K;
   const int n = len * len, n_ct = n_c * n_t;
   const dim3 grid((unsigned)((int64_t)m * n_ct));
   if (keys_fit(n, sizeof(K)))
-    hipLaunchKernelGGL((k_masked_stats<T, true>), grid, dim3(NT), (size_t)n * sizeof(K), s, (const T*)d_roi, d_mask, sm, st,
-                       n_t, n_ct, n, qs, n_q, d_count, d_stats, d_order);
+    hipLaunchKernelGGL((k_masked_stats<T, true, MEDIAN>), grid, dim3(NT), (size_t)n * sizeof(K), s, (const T*)d_roi, d_mask,
+                       sm, st, n_t, n_ct, n, qs, n_q, d_count, d_stats, d_order);
   else
-    hipLaunchKernelGGL((k_masked_stats<T, false>), grid, dim3(NT), 0, s, (const T*)d_roi, d_mask, sm, st, n_t, n_ct, n, qs,
-                       n_q, d_count, d_stats, d_order);
+    hipLaunchKernelGGL((k_masked_stats<T, false, MEDIAN>), grid, dim3(NT), 0, s, (const T*)d_roi, d_mask, sm, st, n_t, n_ct,
+                       n, qs, n_q, d_count, d_stats, d_order);
   MG_CHECK_LAUNCH();
   return MG_OK;
+}
+
+// What both entry points refuse: one workgroup a window, pixel indices are int.
+bool windows_ok(const void* d_roi, const uint8_t* d_mask, int64_t sm, int64_t st, int m, int n_c, int n_t, int len) {
+  return d_roi && d_mask && m >= 0 && n_c > 0 && n_t > 0 && len > 0 && len <= MG_ROISTATS_MAX_LEN && sm >= 0 && st >= 0 &&
+         (int64_t)n_c * n_t <= INT32_MAX && (int64_t)m * n_c * n_t <= INT32_MAX;
 }
 
 }  // namespace
@@ -313,10 +302,8 @@ extern "C" int mg_roi_masked_stats_keys_in_lds(int dtype, int roi_len) {
 extern "C" int mg_roi_masked_stats(const void* d_roi, int dtype, const uint8_t* d_mask, int64_t mask_stride_m,
                                    int64_t mask_stride_t, int m, int n_c, int n_t, int roi_len, const double* q, int n_q,
                                    int32_t* d_count, double* d_stats, double* d_order, void* stream) {
-  if (!d_roi || !d_mask || !d_count || !d_stats || m < 0 || n_c <= 0 || n_t <= 0 || roi_len <= 0) return MG_EINVAL;
+  if (!windows_ok(d_roi, d_mask, mask_stride_m, mask_stride_t, m, n_c, n_t, roi_len) || !d_count || !d_stats) return MG_EINVAL;
   if (n_q < 0 || n_q > MG_ROISTATS_MAX_Q || (n_q > 0 && (!q || !d_order))) return MG_EINVAL;
-  if (mask_stride_m < 0 || mask_stride_t < 0 || roi_len > MG_ROISTATS_MAX_LEN) return MG_EINVAL;
-  if ((int64_t)n_c * n_t > INT32_MAX || (int64_t)m * n_c * n_t > INT32_MAX) return MG_EINVAL;  // one workgroup a window
   StatsQ qs = {};
   for (int j = 0; j < n_q; ++j) {
     if (!(q[j] >= 0.0 && q[j] <= 1.0)) return MG_EINVAL;  // (NaN fails both)
@@ -326,7 +313,20 @@ extern "C" int mg_roi_masked_stats(const void* d_roi, int dtype, const uint8_t* 
   if (m == 0) return MG_OK;
   hipStream_t s = mg_stream(stream);
   return mg_dispatch_pixel(dtype, [&](auto t) {
-    return launch_stats<decltype(t)>(d_roi, d_mask, mask_stride_m, mask_stride_t, m, n_c, n_t, roi_len, qs, n_q, d_count,
-                                     d_stats, d_order, s);
+    return launch_stats<decltype(t), false>(d_roi, d_mask, mask_stride_m, mask_stride_t, m, n_c, n_t, roi_len, qs, n_q,
+                                            d_count, d_stats, d_order, s);
+  });
+}
+
+extern "C" int mg_roi_masked_median(const void* d_roi, int dtype, const uint8_t* d_mask, int64_t mask_stride_m,
+                                    int64_t mask_stride_t, int m, int n_c, int n_t, int roi_len, double* d_median,
+                                    void* stream) {
+  if (!windows_ok(d_roi, d_mask, mask_stride_m, mask_stride_t, m, n_c, n_t, roi_len) || !d_median) return MG_EINVAL;
+  if (dtype != MG_U8 && dtype != MG_U16 && dtype != MG_F32 && dtype != MG_F64) return MG_EINVAL;
+  if (m == 0) return MG_OK;
+  hipStream_t s = mg_stream(stream);
+  return mg_dispatch_pixel(dtype, [&](auto t) {
+    return launch_stats<decltype(t), true>(d_roi, d_mask, mask_stride_m, mask_stride_t, m, n_c, n_t, roi_len, StatsQ{}, 0,
+                                           nullptr, nullptr, d_median, s);
   });
 }

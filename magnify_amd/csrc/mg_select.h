@@ -1,5 +1,5 @@
-// Exact order statistics of masked windows, shared by mg_roi.hip (k_masked_median) and mg_roistats.hip
-// (k_masked_stats): the order-preserving key of a pixel and the byte-wise radix select over a window in global memory.
+// Exact order statistics: the order-preserving key of a pixel (k_masked_stats in mg_roistats.hip, pc_key in
+// mg_percentile.hip) and the byte-wise radix select over the keys of a window, wherever they lie.
 #pragma once
 #include "mg_common.h"
 
@@ -44,40 +44,47 @@ template <> struct median_key<double> {
   }
 };
 
-// the k-th smallest (0-based) key among the unmasked, non-NaN values: one 256-bin histogram per key byte, most
-// significant first, only the values that share the prefix found so far take part
-template <typename T>
-__device__ typename median_key<T>::type select_kth(const T* __restrict__ v, const uint8_t* __restrict__ mask, int n,
-                                                   int k, uint32_t* hist) {
-  typedef typename median_key<T>::type K;
-  constexpr int LV = median_key<T>::LEVELS;
-  constexpr int NT = MG_SELECT_THREADS;
-  __shared__ int s_bin, s_rank;
+// The k-th smallest (0-based) of the keys of `count` items: one 256-bin histogram per key byte, most significant first,
+// only the keys that share the prefix found so far take part.  key_at(i, &key) gives the key of item i, false where it
+// has none (masked out, NaN); k < the number of items that have one.  The bin that holds the rank is picked by wave 0:
+// four bins a lane, a scan of the lanes' totals, then the bin inside one lane.  hist[256] is all zero on entry and on
+// return; s_pick[2] is written only behind the first barrier of a call, when every thread has read the last call's.
+// Called by all MG_SELECT_THREADS threads (it synchronises).
+template <typename K, int LV, class KeyAt>
+__device__ __forceinline__ K select_kth(int count, KeyAt key_at, int k, uint32_t* hist, int* s_pick) {
+  const int lane = threadIdx.x & 63;
   K prefix = 0;
   int rank = k;
   for (int level = 0; level < LV; ++level) {
     const int shift = 8 * (LV - 1 - level);
-    for (int i = threadIdx.x; i < 256; i += NT) hist[i] = 0;
-    __syncthreads();
-    for (int p = threadIdx.x; p < n; p += NT) {
+    for (int i = threadIdx.x; i < count; i += MG_SELECT_THREADS) {
       K key;
-      if (!mask[p] || !median_key<T>::key(v[p], &key)) continue;
+      if (!key_at(i, &key)) continue;
       if (level == 0 || (key >> (shift + 8)) == prefix) atomicAdd(&hist[(uint32_t)(key >> shift) & 255u], 1u);
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
-      int acc = 0, b = 0;
-      for (; b < 255; ++b) {
-        if (acc + (int)hist[b] > rank) break;
-        acc += hist[b];
+    if (threadIdx.x < 64) {
+      uint32_t h[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) h[j] = hist[4 * lane + j], hist[4 * lane + j] = 0u;
+      const int total = (int)(h[0] + h[1] + h[2] + h[3]);
+      const int incl = mg_wave_scan_incl_i32(total);
+      const unsigned long long reached = __ballot(incl > rank);
+      const int owner = reached ? __ffsll((long long)reached) - 1 : 63;  // (rank < the keys counted: some lane reaches it)
+      if (lane == owner) {
+        int acc = incl - total, b = 0;
+#pragma unroll
+        for (; b < 3; ++b) {
+          if (acc + (int)h[b] > rank) break;
+          acc += (int)h[b];
+        }
+        s_pick[0] = 4 * lane + b;
+        s_pick[1] = rank - acc;
       }
-      s_bin = b;
-      s_rank = rank - acc;
     }
     __syncthreads();
-    prefix = (prefix << 8) | (K)s_bin;
-    rank = s_rank;
-    __syncthreads();
+    prefix = (prefix << 8) | (K)s_pick[0];
+    rank = s_pick[1];
   }
   return prefix;
 }

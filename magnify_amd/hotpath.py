@@ -1525,18 +1525,24 @@ def marker_table(out: dict, assay_offset: int, n_channels: int) -> torch.Tensor:
     return tab
 
 
-def _window_masks(what: str, mask: torch.Tensor, m: int, t: int, L: int):
-    """(mask, marker stride, time stride) as the masked window kernels read it: uint8 bytes, (M, L, L) or (M, T, L, L);
-    made contiguous only where the strides require it (a broadcast view with time stride 0 is read in place)."""
+def _mask_view(what: str, mask: torch.Tensor, m: int, t: int, L: int):
+    """(uint8 tensor, marker stride, time stride) of a mask of m markers as the window kernels read it.  ``mask``: bool /
+    uint8 (M, L, L) -- one mask for all timepoints -- or (M, T', L, L) with T' = t, or T' = 1 or a view expanded along
+    time (stride 0): one mask, read in place for every timepoint.  Copied only where the strides require it: rows that
+    are not contiguous, windows that overlap.  A stride that only ever multiplies index 0 (M <= 1, T' <= 1) is handed
+    over as 0.  ValueError for any other T'."""
     if mask.dtype == torch.bool:
         mask = mask.view(torch.uint8)
     if mask.dim() == 3:
-        return mask.contiguous(), L * L, 0
-    if mask.shape[1] not in (1, t):
-        raise ValueError(f"{what}: {mask.shape[1]} mask timepoints for {t} roi timepoints")
-    if mask.stride(3) != 1 or mask.stride(2) != L or (m > 1 and mask.stride(0) < L * L):
+        mask = mask[:, None]
+    n_t = mask.shape[1]
+    if n_t not in (1, t):
+        raise ValueError(f"{what}: {n_t} mask timepoints for {t} roi timepoints")
+    assert mask.element_size() == 1 and mask.shape[0] == m and tuple(mask.shape[2:]) == (L, L), f"{what}: {mask.shape}"
+    if (L > 1 and (mask.stride(3) != 1 or mask.stride(2) != L)) or (m > 1 and mask.stride(0) < L * L) or \
+            (n_t > 1 and 0 < mask.stride(1) < L * L):
         mask = mask.contiguous()
-    return mask, (mask.stride(0) if m > 1 else L * L), (mask.stride(1) if mask.shape[1] == t and t > 1 else 0)
+    return mask, (mask.stride(0) if m > 1 else 0), (mask.stride(1) if n_t > 1 else 0)
 
 
 def masked_median(roi: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
@@ -1546,7 +1552,7 @@ def masked_median(roi: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
     require_gpu()
     m, c, t, L, _ = roi.shape
     roi = roi.contiguous()
-    mask, sm, st = _window_masks("masked_median", mask, m, t, L)
+    mask, sm, st = _mask_view("masked_median", mask, m, t, L)
     out = torch.empty((m, c, t), dtype=torch.float64, device=roi.device)
     if m == 0:
         return out
@@ -1555,7 +1561,7 @@ def masked_median(roi: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
     return out
 
 
-ROISTATS_MAX_Q, ROISTATS_LDS_KEY_BYTES = 16, 49152  # MG_ROISTATS_MAX_Q, MG_ROISTATS_LDS_KEY_BYTES
+ROISTATS_MAX_Q, ROISTATS_LDS_KEY_BYTES = nat.DEFINES["MG_ROISTATS_MAX_Q"], nat.DEFINES["MG_ROISTATS_LDS_KEY_BYTES"]
 
 
 def masked_stats_keys_in_lds(dtype, roi_len: int) -> bool:
@@ -1578,7 +1584,7 @@ def masked_stats(roi: torch.Tensor, mask: torch.Tensor, q=()):
     m, c, t, L, _ = roi.shape
     code = nat.dtype_code(roi.dtype)
     roi = roi.contiguous()
-    mask, sm, st = _window_masks("masked_stats", mask, m, t, L)
+    mask, sm, st = _mask_view("masked_stats", mask, m, t, L)
     qs = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)).reshape(-1))
     count = torch.empty((m, c, t), dtype=torch.int32, device=roi.device)
     stats = torch.empty((m, c, t, 4), dtype=torch.float64, device=roi.device)
@@ -1595,7 +1601,7 @@ def masked_stats(roi: torch.Tensor, mask: torch.Tensor, q=()):
 # plot.overview: the label map of the fg masks in image coordinates and the composite picture
 # --------------------------------------------------------------------------------------
 
-OVERVIEW_MAX_LEVEL, OVERVIEW_MAX_CHANNELS = 6, 16  # MG_OVERVIEW_MAX_LEVEL, MG_OVERVIEW_MAX_CHANNELS
+OVERVIEW_MAX_LEVEL, OVERVIEW_MAX_CHANNELS = nat.DEFINES["MG_OVERVIEW_MAX_LEVEL"], nat.DEFINES["MG_OVERVIEW_MAX_CHANNELS"]
 OVERLAYS = {None: 0, "none": 0, "outline": 1, "fill": 2}
 
 
@@ -1609,14 +1615,11 @@ def image_labels(fg: torch.Tensor, origin: torch.Tensor, level: int, h: int, w: 
     labels = torch.zeros((t, -(h // -s), -(w // -s)), dtype=torch.int32, device=fg.device if fg.is_cuda else "cuda")
     if m == 0:
         return labels
-    if fg.dtype == torch.bool:
-        fg = fg.view(torch.uint8)
-    if fg.stride(3) != 1 or fg.stride(2) != L or (m > 1 and fg.stride(0) < L * L) or (t > 1 and 0 < fg.stride(1) < L * L):
-        fg = fg.contiguous()
+    fg, sm, st = _mask_view("image_labels", fg, m, t, L)
     origin = torch.as_tensor(origin).to(device=labels.device, dtype=torch.int32).contiguous()
     assert tuple(origin.shape) == (m, t, 2) and fg.is_cuda
-    _call("mg_roi_image_labels", fg.data_ptr(), fg.stride(0) if m > 1 else 0, fg.stride(1) if t > 1 else 0,
-          origin.data_ptr(), m, t, L, int(level), int(h), int(w), labels.data_ptr(), _stream())
+    _call("mg_roi_image_labels", fg.data_ptr(), sm, st, origin.data_ptr(), m, t, L, int(level), int(h), int(w),
+          labels.data_ptr(), _stream())
     return labels
 
 
@@ -1654,7 +1657,7 @@ def render_overview(image: torch.Tensor, level: int, limits, colors, labels: tor
 # plot.percentile_limits / plot.roishow: exact order statistics of a resident stack, the montage of the ROI windows
 # --------------------------------------------------------------------------------------
 
-PERCENTILE_MAX_PREFIXES = 4  # MG_PERCENTILE_MAX_PREFIXES
+PERCENTILE_MAX_PREFIXES = nat.DEFINES["MG_PERCENTILE_MAX_PREFIXES"]
 # (shift, bits) of every read pass over the key, coarse to fine (bits <= MG_PERCENTILE_MAX_BITS)
 _KEY_PASSES = {"uint8": ((0, 8),), "uint16": ((5, 11), (0, 5)), "float32": ((21, 11), (10, 11), (0, 10)),
                "float64": ((21, 11), (10, 11), (0, 10))}
@@ -1769,18 +1772,9 @@ def render_roi_montage(roi: torch.Tensor, layout, level: int, limits, colors, fg
         roi = roi.contiguous()
     mode = OVERLAYS[overlay]
 
-    def mask(a):
-        if a is None or not mode:
-            return None, 0, 0
-        if a.dtype == torch.bool:
-            a = a.view(torch.uint8)
-        assert tuple(a.shape) == (m, t, L, L) and a.dtype == torch.uint8 and a.is_cuda
-        if (L > 1 and (a.stride(3) != 1 or a.stride(2) != L)) or (m > 1 and a.stride(0) < L * L) or \
-                (t > 1 and 0 < a.stride(1) < L * L):
-            a = a.contiguous()
-        return a, a.stride(0) if m > 1 else 0, a.stride(1) if t > 1 else 0
-
-    (bg, bg_m, bg_t), (fg, fg_m, fg_t) = mask(bg), mask(fg)
+    (bg, bg_m, bg_t), (fg, fg_m, fg_t) = ((None, 0, 0) if a is None or not mode else
+                                          _mask_view("render_roi_montage", a, m, t, L) for a in (bg, fg))
+    assert all(a is None or a.is_cuda for a in (bg, fg))
     d_layout = torch.from_numpy(layout).to(roi.device)
     _call("mg_render_roi_montage", roi.data_ptr(), nat.dtype_code(roi.dtype), roi.stride(0) if m > 1 else 0,
           roi.stride(1) if c > 1 else 0, roi.stride(2) if t > 1 else 0, m, c, t, L, int(level), d_layout.data_ptr(), rows,

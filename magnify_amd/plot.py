@@ -103,24 +103,34 @@ def _has_rois(xp):
     return "roi" in xp and all(k in xp for k in ("fg", "x", "y"))
 
 
+def _mask(xp, name, m, n_t, L, device):
+    """Coordinate ``name`` as a (M, T, L, L) bool / uint8 device view (stride 0 along a time of size 1).  ``m`` / ``L``
+    None: whatever the coordinate has."""
+    a = _marker_var(xp, name, ("roi_y", "roi_x"))
+    if not isinstance(a, torch.Tensor):
+        a = torch.from_numpy(np.ascontiguousarray(np.asarray(a), dtype=np.bool_))
+    if not a.is_cuda:
+        hotpath.require_gpu()
+        a = a.to(device)
+    if a.dtype not in (torch.bool, torch.uint8):
+        a = a != 0
+    if m is None:
+        m, L = a.shape[0], a.shape[-1]
+        if a.shape[2] != L:
+            raise ValueError(f"plot: {name} windows must be square, got {tuple(a.shape[2:])}")
+        if a.shape[1] not in (1, n_t):
+            raise ValueError(f"plot: {a.shape[1]} {name} timepoints for {n_t} image timepoints")
+    elif tuple(a.shape[2:]) != (L, L) or a.shape[0] != m or a.shape[1] not in (1, n_t):
+        raise ValueError(f"plot: {name} of shape {tuple(a.shape)} does not match {m} marks, {n_t} timepoints, L = {L}")
+    return a.expand(m, n_t, L, L)
+
+
 def _markers(xp, n_t, h, w):
     """(fg (M, T, L, L) device view, origin (M, T, 2) int32 on the host, valid (M, T) bool) of a dataset with ROIs."""
-    fg = _marker_var(xp, "fg", ("roi_y", "roi_x"))
-    if not isinstance(fg, torch.Tensor):
-        fg = torch.from_numpy(np.ascontiguousarray(np.asarray(fg), dtype=np.bool_))
-    if not fg.is_cuda:
-        hotpath.require_gpu()
-        fg = fg.cuda()
-    if fg.dtype not in (torch.bool, torch.uint8):
-        fg = fg != 0
+    fg = _mask(xp, "fg", None, n_t, None, "cuda")
     m, L = fg.shape[0], fg.shape[-1]
-    if fg.shape[2] != L:
-        raise ValueError(f"plot: fg windows must be square, got {tuple(fg.shape[2:])}")
-    if fg.shape[1] not in (1, n_t):
-        raise ValueError(f"plot: {fg.shape[1]} fg timepoints for {n_t} image timepoints")
     if L > h or L > w:
         raise ValueError(f"plot: roi windows of length {L} do not fit a {h} x {w} image")
-    fg = fg.expand(m, n_t, L, L)  # (stride 0 along a time of size 1)
 
     def per_time(name, dtype):
         a = _marker_var(xp, name, ())
@@ -163,13 +173,38 @@ def roi_to_image_labels(xp, level=0):
     return DataArray(labels, ("time", "y", "x"), name="fg_labels")
 
 
+def _picture_args(what, xp, level, overlay, alpha, colors, contrast_limits):
+    """What ``overview`` and ``roishow`` (``what``) check alike, the arguments that need no data first -> (dataset, its
+    (C, T, H, W) image or (M, C, T, L, L) roi on the device, level or None, alpha, colors (C, 3) float64,
+    contrast_limits (C, 2) float64 or None)."""
+    if level is not None:
+        level = _check_level(level)
+    if overlay not in OVERLAYS:
+        raise ValueError(f"overlay must be one of {OVERLAYS}, got {overlay!r}")
+    alpha = float(alpha)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"alpha must lie in [0, 1], got {alpha!r}")
+    xp, data = _image(xp) if what == "overview" else _roi(xp)
+    c = data.shape[0 if what == "overview" else 1]
+    if c > hotpath.OVERVIEW_MAX_CHANNELS:
+        raise ValueError(f"plot.{what} composes at most {hotpath.OVERVIEW_MAX_CHANNELS} channels, got {c}")
+    cols = np.asarray(default_colors(c) if colors is None else colors, dtype=np.float64)
+    if cols.shape != (c, 3):
+        raise ValueError(f"colors must be one RGB triple per channel: {c} triples, got shape {cols.shape}")
+    if not (np.isfinite(cols).all() and (cols >= 0).all() and (cols <= 1).all()):
+        raise ValueError("colors must lie in [0, 1]")
+    if contrast_limits is not None:
+        contrast_limits = np.asarray(contrast_limits, dtype=np.float64)
+        if contrast_limits.shape != (c, 2):
+            raise ValueError("contrast_limits must be one (lo, hi) pair per channel: "
+                             f"{c} pairs, got shape {contrast_limits.shape}")
+    return xp, data, level, alpha, cols, contrast_limits
+
+
 def _limits(xp, image, contrast_limits):
     c, t, h, w = image.shape
     if contrast_limits is not None:
-        lim = np.asarray(contrast_limits, dtype=np.float64)
-        if lim.shape != (c, 2):
-            raise ValueError(f"contrast_limits must be one (lo, hi) pair per channel: {c} pairs, got shape {lim.shape}")
-        return lim
+        return contrast_limits
     cached = xp._cache.get("image_minmax")
     if cached is not None and cached[0] == image.data_ptr() and cached[1] is not None and cached[1].numel() == c * t * 2:
         mm = cached[1]
@@ -194,26 +229,13 @@ def overview(xp, level=None, contrast_limits=None, colors=None, overlay="outline
     blends the marker's colour with weight ``alpha``, ``"outline"`` paints the rim of every mask, ``"none"`` / None
     leaves the image alone.  ``color_by="mark"``: a colour per marker (``MARK_COLORS[i % 8]``); ``"valid"``: green
     where ``valid[i, t]``, red elsewhere."""
-    if level is not None:
-        level = _check_level(level)
-    if overlay not in OVERLAYS:
-        raise ValueError(f"overlay must be one of {OVERLAYS}, got {overlay!r}")
     if color_by not in COLOR_BY:
         raise ValueError(f"color_by must be one of {COLOR_BY}, got {color_by!r}")
-    alpha = float(alpha)
-    if not 0.0 <= alpha <= 1.0:
-        raise ValueError(f"alpha must lie in [0, 1], got {alpha!r}")
-    xp, image = _image(xp)
+    xp, image, level, alpha, cols, contrast_limits = _picture_args("overview", xp, level, overlay, alpha, colors,
+                                                                   contrast_limits)
     c, t, h, w = image.shape
-    if c > hotpath.OVERVIEW_MAX_CHANNELS:
-        raise ValueError(f"plot.overview composes at most {hotpath.OVERVIEW_MAX_CHANNELS} channels, got {c}")
     if level is None:
         level = default_level(h, w)
-    cols = np.asarray(default_colors(c) if colors is None else colors, dtype=np.float64)
-    if cols.shape != (c, 3):
-        raise ValueError(f"colors must be one RGB triple per channel: {c} triples, got shape {cols.shape}")
-    if not (np.isfinite(cols).all() and (cols >= 0).all() and (cols <= 1).all()):
-        raise ValueError("colors must lie in [0, 1]")
     limits = _limits(xp, image, contrast_limits)
     labels = table = None
     if overlay in ("outline", "fill") and _has_rois(xp):
@@ -341,22 +363,6 @@ def montage_level(rows, cols, L):
     return MAX_LEVEL
 
 
-def _mask(xp, name, m, n_t, L, device):
-    """Coordinate ``name`` as a (M, T, L, L) device view (stride 0 along a time of size 1), or None without it."""
-    if name not in xp:
-        return None
-    a = _marker_var(xp, name, ("roi_y", "roi_x"))
-    if not isinstance(a, torch.Tensor):
-        a = torch.from_numpy(np.ascontiguousarray(np.asarray(a), dtype=np.bool_))
-    if not a.is_cuda:
-        a = a.to(device)
-    if a.dtype not in (torch.bool, torch.uint8):
-        a = a != 0
-    if tuple(a.shape[2:]) != (L, L) or a.shape[0] != m or a.shape[1] not in (1, n_t):
-        raise ValueError(f"plot: {name} of shape {tuple(a.shape)} does not match {m} marks, {n_t} timepoints, L = {L}")
-    return a.expand(m, n_t, L, L)
-
-
 def roishow(xp, level=None, contrast_limits=None, colors=None, overlay="fill", alpha=0.7, group_by="tag", columns=None):
     """Every marker's ROI window side by side, uint8 ``(time, y, x, rgb)`` on the device: the picture the reference's
     ``roishow`` (plot/image.py:14-49) hands to a viewer.
@@ -369,30 +375,12 @@ def roishow(xp, level=None, contrast_limits=None, colors=None, overlay="fill", a
     masks: ``overlay="fill"`` blends with weight ``alpha``, ``"outline"`` paints the rim, ``"none"`` / None leaves the
     window alone.  Attributes of the result: ``level``, ``cell`` (the side of a cell), ``marks`` (the layout: the mark
     of every cell, -1 for an empty one), ``tags`` (the tag of every column, or None)."""
-    if level is not None:
-        level = _check_level(level)
-    if overlay not in OVERLAYS:
-        raise ValueError(f"overlay must be one of {OVERLAYS}, got {overlay!r}")
     if group_by not in (None, "tag"):
         raise ValueError(f"group_by must be 'tag' or None, got {group_by!r}")
-    alpha = float(alpha)
-    if not 0.0 <= alpha <= 1.0:
-        raise ValueError(f"alpha must lie in [0, 1], got {alpha!r}")
     if columns is not None and (isinstance(columns, bool) or not isinstance(columns, (int, np.integer)) or columns < 1):
         raise ValueError(f"columns must be an integer >= 1, got {columns!r}")
-    xp, roi = _roi(xp)
+    xp, roi, level, alpha, cols, limits = _picture_args("roishow", xp, level, overlay, alpha, colors, contrast_limits)
     m, c, t, L, _ = roi.shape
-    if c > hotpath.OVERVIEW_MAX_CHANNELS:
-        raise ValueError(f"plot.roishow composes at most {hotpath.OVERVIEW_MAX_CHANNELS} channels, got {c}")
-    cols = np.asarray(default_colors(c) if colors is None else colors, dtype=np.float64)
-    if cols.shape != (c, 3):
-        raise ValueError(f"colors must be one RGB triple per channel: {c} triples, got shape {cols.shape}")
-    if not (np.isfinite(cols).all() and (cols >= 0).all() and (cols <= 1).all()):
-        raise ValueError("colors must lie in [0, 1]")
-    if contrast_limits is not None:
-        limits = np.asarray(contrast_limits, dtype=np.float64)
-        if limits.shape != (c, 2):
-            raise ValueError(f"contrast_limits must be one (lo, hi) pair per channel: {c} pairs, got shape {limits.shape}")
     tags = names = None
     if group_by == "tag" and "tag" in xp.coords:
         tags = np.asarray(_marker_tags(xp)).reshape(-1)
@@ -405,11 +393,11 @@ def roishow(xp, level=None, contrast_limits=None, colors=None, overlay="fill", a
     if m == 0:
         empty = torch.zeros((t, 0, 0, 3), dtype=torch.uint8, device=roi.device)
         return DataArray(empty, ("time", "y", "x", "rgb"), name="roishow", attrs=attrs)
-    if contrast_limits is None:
+    if limits is None:
         limits = percentile_limits(xp, 0.0, 100.0, source="roi")
     fg = bg = None
     if overlay in ("outline", "fill"):
-        fg, bg = _mask(xp, "fg", m, t, L, roi.device), _mask(xp, "bg", m, t, L, roi.device)
+        fg, bg = (_mask(xp, name, m, t, L, roi.device) if name in xp else None for name in ("fg", "bg"))
     rgb = hotpath.render_roi_montage(roi, layout, level, limits, cols, fg, bg, overlay, alpha)
     return DataArray(rgb, ("time", "y", "x", "rgb"), name="roishow", attrs=attrs)
 

@@ -78,18 +78,7 @@ def masked_median(xp, mask="bg", time=None):
     chip searched at several timesteps, find.py:119-140).  ``time=k``: of timepoint ``k`` only, selected BEFORE the
     reduction as ``assay.isel(time=0)`` does in filter.py:20-22, 69-75 and identify.py:76 -- the other timepoints are
     neither read nor reduced; the result keeps a time axis of length 1."""
-    roi = xp.data_vars["roi"].transpose("mark", "channel", "time", "roi_y", "roi_x").data
-    if not isinstance(roi, torch.Tensor):
-        roi = np.ascontiguousarray(roi)
-        if roi.dtype.byteorder not in ("=", "|"):
-            roi = roi.astype(roi.dtype.newbyteorder("="))
-        roi = torch.from_numpy(roi)
-    hotpath.nat.dtype_code(roi.dtype)  # TypeError for anything but uint8 / uint16 / float32 / float64
-    m = _masks(xp, mask)
-    if time is not None:
-        roi = roi[:, :, time:time + 1] if time != -1 else roi[:, :, -1:]
-        m = m[:, time:time + 1] if m.shape[1] != 1 else m
-    return DataArray(hotpath.masked_median(roi.cuda(), m.cuda()), ("mark", "channel", "time"))
+    return DataArray(hotpath.masked_median(*_roi_and_mask(xp, mask, time)), _MCT)
 
 
 def fg_mean_minus_bg_median(xp, time=None):

@@ -172,6 +172,7 @@ def test_host_side_matches_the_restatement():
 def test_public_names_and_binding():
     import magnify_amd as mg
     from magnify_amd import _native as nat
+    from magnify_amd import hotpath
 
     assert "plot" in mg.__all__ and mg.plot.overview and mg.plot.roi_to_image_labels and mg.plot.write_png
     a = nat.PROTOTYPES["mg_roi_image_labels"]
@@ -180,6 +181,10 @@ def test_public_names_and_binding():
     assert len(b) == 18 and b[2] is ctypes.c_int64 and b[3] is ctypes.c_int64 and b[15] is ctypes.c_double
     for name in ("mg_roi_image_labels", "mg_render_overview"):
         assert nat.RESTYPES[name] is ctypes.c_int and hasattr(nat.lib(), name)
+    # (read from the header: its values)
+    assert (hotpath.OVERVIEW_MAX_LEVEL, hotpath.OVERVIEW_MAX_CHANNELS, hotpath.PERCENTILE_MAX_PREFIXES) == (6, 16, 4)
+    assert mg.plot.MAX_LEVEL == 6 and (nat.MG_U8, nat.MG_U16, nat.MG_F32, nat.MG_F64) == (0, 1, 2, 3)
+    assert (nat.MG_NO_EDGE, nat.MG_SCORE_SKIPPED) == (100.0, -2.0)
 
 
 def test_argument_errors_need_no_gpu():

@@ -120,6 +120,62 @@ def test_both_sides_of_the_lds_budget(hp, dtype, L, in_lds):
     check(hp, roi, ref.mask_set(M, T, L, rng), Q7, what=f"{np.dtype(dtype).name} L={L}")
 
 
+@pytest.mark.parametrize("dtype,L,in_lds", [(np.uint8, 16, True), (np.uint16, 110, True), (np.uint16, 111, False),
+                                            (np.float32, 110, True), (np.float32, 111, False), (np.float64, 78, True),
+                                            (np.float64, 79, False)])
+def test_median_on_both_sides_of_the_lds_budget(hp, dtype, L, in_lds):
+    """``hotpath.masked_median`` is the median mode of the statistics kernel: numpy's nanmedian exactly, with the keys
+    in LDS and selecting from global memory, through the 16-byte loads (uint8, L = 16: every window aligned) and the
+    one-pixel path (the other sizes: window bases off 16 bytes), for an even and an odd count on either side.  Per
+    marker: a random mask (timepoint 0 trimmed to an even, timepoint 1 to an odd count), an empty one (NaN), one
+    pixel, all set; a mask per timepoint, then one mask for both as a stride-0 view.  Floats: NaN pixels under the mask;
+    +-0 and +-inf in one window."""
+    assert hp.masked_stats_keys_in_lds(dtype, L) == in_lds
+    m, c, t = 4, 1, 2
+    rng = np.random.default_rng(L + np.dtype(dtype).itemsize)
+    is_float = np.dtype(dtype).kind == "f"
+    if is_float:
+        roi = rng.normal(0, 50, size=(m, c, t, L, L)).astype(dtype)
+        roi[rng.random(roi.shape) < 0.02] = np.nan
+        roi[3, 0, 0, 0, :4] = [-0.0, 0.0, np.inf, -np.inf]
+    else:
+        roi = rng.integers(0, np.iinfo(dtype).max + 1, size=(m, c, t, L, L)).astype(dtype)
+    mask = np.zeros((m, t, L, L), dtype=bool)
+    mask[0] = rng.random((t, L, L)) < 0.4
+    mask[2, :, L // 2, L // 3] = True
+    mask[3] = True
+    for i in range(t):  # the random mask: an even count of values at timepoint 0, an odd one at timepoint 1
+        live = np.argwhere(mask[0, i] & ~np.isnan(roi[0, 0, i].astype(np.float64)))
+        assert len(live) > 2
+        if len(live) % 2 != i:
+            mask[0, i][tuple(live[0])] = False
+
+    def oracle(masks):
+        want, n = np.full((m, c, t), np.nan), np.zeros((m, c, t), dtype=np.int64)
+        for g, k, i in np.ndindex(m, c, t):
+            values = roi[g, k, i].astype(np.float64)
+            under = np.sort(values[masks[g, i] & ~np.isnan(values)])
+            n[g, k, i] = under.size
+            if under.size and dtype == np.float64:  # the mean of the two middle values in float64, as rp.roi_reduce has it
+                want[g, k, i] = (under[(under.size - 1) // 2] + under[under.size // 2]) / 2.0
+            elif under.size:
+                want[g, k, i] = np.nanmedian(np.where(masks[g, i], values, np.nan))
+        return want, n
+
+    d_roi = dev(roi)
+    one = np.broadcast_to(mask[:, 1:], mask.shape)
+    d_one = dev(mask[:, 1:].view(np.uint8)).expand(m, t, L, L)
+    assert d_one.stride(1) == 0
+    for what, host, device in (("a mask per timepoint", mask, dev(mask.view(np.uint8))), ("stride-0 time view", one, d_one)):
+        want, n = oracle(host)
+        got = hp.masked_median(d_roi, device).cpu().numpy()
+        print(f"{np.dtype(dtype).name} L={L} {what}: counts {n.reshape(-1).tolist()}")
+        np.testing.assert_array_equal(got, want, err_msg=what)
+        assert np.isnan(got[1]).all() and not np.isnan(got[[0, 2, 3]]).any()
+    n = oracle(mask)[1]
+    assert {int(v) % 2 for v in n[n > 1]} == {0, 1} and (n == 1).any() and (n == 0).any()
+
+
 def test_mask_layouts(hp):
     """(M, L, L); (M, T, L, L); a stride-0 time view; bool and uint8 (any non-zero byte is set); a marker stride larger
     than L * L, read in place."""

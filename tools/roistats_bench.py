@@ -3,13 +3,15 @@ inputs resident, every figure the median of ``--calls`` timed calls after ``--wa
 events per call), at the scale of tools/track_bench.py: ``--marks`` markers x 1 channel x ``--time`` timepoints of
 ``--roi`` x ``--roi`` pixels under one disk mask per marker (radii 8 .. 25), uint16 and float32:
 
-  * ``stats_q0`` / ``stats_q1`` / ``stats_q7``: the new kernel with q = (), (0.5,) and the seven-value list;
-  * ``median``: mg_roi_masked_median on the same roi and mask -- the existing kernel, as the yardstick; the new kernel
-    with q = (0.5,) should not be slower than the yardstick's slowest timed call (``ms_max``);
+  * ``stats_q0`` / ``stats_q1`` / ``stats_q7``: the kernel with q = (), (0.5,) and the seven-value list;
+  * ``median``: mg_roi_masked_median on the same roi and mask -- the same kernel in its median mode (one double per
+    window, no deviations; it was a kernel of its own, one read of the window per radix level, until DESIGN.md
+    section 22); it should not be slower than q = (0.5,);
   * ``read_ceiling``: one streaming read of the same number of bytes by the library's own 16-byte-per-lane probe.
 
-``bytes`` = what the new kernel has to read: every pixel and every mask byte of every window once; the rates are those
-bytes over the median time.  The results of both kernels are compared before anything is timed.  Prints one JSON line.
+``bytes`` = what the kernel has to read: every pixel and every mask byte of every window once; the rates are those
+bytes over the median time.  The results of both entry points are compared before anything is timed.  ``--roi 111``
+puts the windows beyond the LDS budget: the path that selects from global memory.  Prints one JSON line.
 
     python tools/roistats_bench.py [--marks 2000] [--time 64] [--roi 100] [--calls 20] [--warmup 5]
 """
@@ -24,7 +26,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT]
 
-from magnify_amd import _native as nat, hotpath  # noqa: E402
+from magnify_amd import _native as nat, hotpath, reduce  # noqa: E402
 
 Q7 = (0, 0.01, 0.25, 0.5, 0.75, 0.998, 1)
 
@@ -75,7 +77,7 @@ def main():
         count, _, order = hotpath.masked_stats(roi, mask, (0.5,))
         median = hotpath.masked_median(roi, mask)
         case = {"bytes": n_bytes, "in_lds": hotpath.masked_stats_keys_in_lds(roi.dtype, L),
-                "median_agrees": bool(torch.equal((order[..., 0, 0] + order[..., 0, 1]) / 2.0, median))}
+                "median_agrees": bool(torch.equal(reduce.interpolate_quantiles(count, order, (0.5,))[..., 0], median))}
         for key, q in (("stats_q0", ()), ("stats_q1", (0.5,)), ("stats_q7", Q7)):
             t = timed(lambda: hotpath.masked_stats(roi, mask, q), args.calls, args.warmup)
             case[key] = dict(t, bytes_per_s=n_bytes / (t["ms"] * 1e-3))
