@@ -740,6 +740,49 @@ int mg_roi_masked_stats(const void* d_roi, int dtype, const uint8_t* d_mask, int
  * global memory; MG_EINVAL for an unknown dtype or a roi_len that mg_roi_masked_stats refuses.  Host only. */
 int mg_roi_masked_stats_keys_in_lds(int dtype, int roi_len);
 
+/* Data-driven fg / bg masks of an already gathered roi (segment_rois).  NOT in the reference, whose masks are drawn
+ * shapes -- the fitted circle (find.py:561-586), disk and annulus (find.py:383-400); this is the threshold / dilation /
+ * erosion family that BASELINE.json's north star names for the fg/bg masks.  tests/segment_ref.py restates the contract
+ * in NumPy + scipy.ndimage and the kernel equals it bit for bit.
+ * d_roi points at the first window of ONE channel, element type `dtype`; window (g, t), roi_len x roi_len contiguous
+ * pixels, is at d_roi + g * stride_m + t * stride_t (elements).  The drawn masks fg0 / bg0 and the optional `allowed`
+ * (d_allowed may be NULL) are roi_len x roi_len bytes at their pointer + g * stride_m + t * stride_t of their own (a
+ * time stride of 0: one mask for all timepoints); a byte is set iff it is non-zero.  S = the 3x3 all-ones structuring
+ * element, outside the window is off.  Per window:
+ *   1. lo, hi = min, max of the non-NaN pixels as float64.  The window is UNSEGMENTED where hi - lo is not finite or
+ *      not > 0, or there is no such pixel.
+ *   2. b(v) = floor((255.0 * (v - lo)) / (hi - lo)) in float64, one operation at a time (to_uint8's order, utils.py:24-26),
+ *      at most 255.  A NaN pixel has no bin and is off.
+ *   3. use_otsu: h = the histogram of b, N = sum h, Stot = sum i h[i]; for k = 0 .. 254 with w0 = sum_{i<=k} h > 0 and
+ *      w1 = N - w0 > 0: d = Stot w0 - N sum_{i<=k} i h[i] (exact, int64), value = (d * d) / (double)(w0 w1); k* = the
+ *      smallest k of the largest value; on = b > k*; reported threshold lo + ((k* + 1) * (hi - lo)) / 255.0.
+ *      Otherwise on = v > threshold and that number is reported.
+ *   4. opened = open_radius erosions of `on` by S, then open_radius dilations; opened &= allowed where given.
+ *   5. fg = opened & fg0, then max_grow times fg = dilate(fg, S) & opened.
+ *   6. Where the window is unsegmented or sum(fg) < max(min_area, 1): fg0 and bg0 are written out (as 0 / 1),
+ *      segmented = 0, threshold = NaN if unsegmented and the threshold found otherwise.
+ *   7. Else bg = bg0 & ~(bg_guard dilations of on | fg), segmented = 1.
+ * d_fg, d_bg uint8 [m][n_t][roi_len][roi_len] (0 / 1, every byte written once), d_threshold double[m][n_t], d_counts
+ * int32[m][n_t][2] = {sum fg, sum bg} of what was written, d_segmented uint8[m][n_t].
+ * One workgroup per window: bins as bytes and every mask as a bit plane in LDS (at most 40 KB), integer histogram and
+ * prefix sums, a total order in the arg-max -- the same bits on every call.  MG_EINVAL, with nothing launched: a null
+ * pointer where one is needed, an unknown dtype, m < 0, n_t <= 0, roi_len outside 1 .. MG_SEGMENT_MAX_LEN,
+ * m * n_t >= 2^31, a negative stride, open_radius / max_grow / bg_guard outside 0 .. MG_SEGMENT_MAX_OPEN / _GROW /
+ * _GUARD, min_area < 0, a NaN threshold with use_otsu = 0.  m = 0 returns MG_OK and writes nothing.  One kernel launch;
+ * no scratch buffer, no allocation, no synchronisation. */
+#define MG_SEGMENT_MAX_LEN 128
+#define MG_SEGMENT_MAX_OPEN 8
+#define MG_SEGMENT_MAX_GROW 32
+#define MG_SEGMENT_MAX_GUARD 16
+int mg_roi_threshold_masks(const void* d_roi, int dtype, int64_t stride_m, int64_t stride_t,
+                           const uint8_t* d_fg0, int64_t fg_stride_m, int64_t fg_stride_t,
+                           const uint8_t* d_bg0, int64_t bg_stride_m, int64_t bg_stride_t,
+                           const uint8_t* d_allowed, int64_t al_stride_m, int64_t al_stride_t,
+                           int m, int n_t, int roi_len, int use_otsu, double threshold,
+                           int open_radius, int max_grow, int bg_guard, int min_area,
+                           uint8_t* d_fg, uint8_t* d_bg, double* d_threshold, int32_t* d_counts, uint8_t* d_segmented,
+                           void* stream);
+
 /* ------------------------------------------------------------------------------------
  * A16 / A17 ButtonFinder helpers (find.py:205-402, 632-677)
  * ---------------------------------------------------------------------------------- */

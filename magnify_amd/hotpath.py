@@ -1597,6 +1597,42 @@ def masked_stats(roi: torch.Tensor, mask: torch.Tensor, q=()):
     return count, stats, order
 
 
+def threshold_masks(roi_channel: torch.Tensor, fg0: torch.Tensor, bg0: torch.Tensor, allowed: torch.Tensor | None = None, *,
+                    method="otsu", open_radius=1, max_grow=4, bg_guard=2, min_area=1):
+    """Data-driven masks of roi_channel (M, T, L, L) -- ONE channel of a gathered roi, uint8 / uint16 / float32 / float64;
+    a view such as ``roi[:, c]`` is read in place -- from the drawn masks fg0 / bg0 and the optional ``allowed`` (the
+    forms of ``masked_median``), by mg_roi_threshold_masks (include/magnify_hip.h states the contract,
+    tests/segment_ref.py restates it).  -> fg, bg uint8 (M, T, L, L), threshold float64 (M, T), counts int32 (M, T, 2) =
+    {sum fg, sum bg}, segmented uint8 (M, T).  ValueError for a setting ``segment.check_segment`` refuses."""
+    from .segment import check_segment
+
+    require_gpu()
+    m, t, L, _ = roi_channel.shape
+    use_otsu, number = check_segment(method, open_radius, max_grow, bg_guard, min_area, L)
+    code = nat.dtype_code(roi_channel.dtype)
+    if (L > 1 and (roi_channel.stride(3) != 1 or roi_channel.stride(2) != L)) or (m > 1 and roi_channel.stride(0) < L * L) \
+            or (t > 1 and roi_channel.stride(1) < L * L):
+        roi_channel = roi_channel.contiguous()
+    dev = roi_channel.device
+    fg = torch.empty((m, t, L, L), dtype=torch.uint8, device=dev)
+    bg = torch.empty((m, t, L, L), dtype=torch.uint8, device=dev)
+    threshold = torch.empty((m, t), dtype=torch.float64, device=dev)
+    counts = torch.empty((m, t, 2), dtype=torch.int32, device=dev)
+    segmented = torch.empty((m, t), dtype=torch.uint8, device=dev)
+    if m == 0:
+        return fg, bg, threshold, counts, segmented
+    fg0, fsm, fst = _mask_view("threshold_masks fg0", fg0, m, t, L)
+    bg0, bsm, bst = _mask_view("threshold_masks bg0", bg0, m, t, L)
+    asm = ast = 0
+    if allowed is not None:
+        allowed, asm, ast = _mask_view("threshold_masks allowed", allowed, m, t, L)
+    _call("mg_roi_threshold_masks", roi_channel.data_ptr(), code, roi_channel.stride(0) if m > 1 else 0,
+          roi_channel.stride(1) if t > 1 else 0, fg0.data_ptr(), fsm, fst, bg0.data_ptr(), bsm, bst, _ptr(allowed), asm, ast,
+          m, t, L, int(use_otsu), float(number), int(open_radius), int(max_grow), int(bg_guard), int(min_area),
+          fg.data_ptr(), bg.data_ptr(), threshold.data_ptr(), counts.data_ptr(), segmented.data_ptr(), _stream())
+    return fg, bg, threshold, counts, segmented
+
+
 # --------------------------------------------------------------------------------------
 # plot.overview: the label map of the fg masks in image coordinates and the composite picture
 # --------------------------------------------------------------------------------------

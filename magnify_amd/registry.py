@@ -81,13 +81,26 @@ def component(name):
 from .pipeline import Pipeline  # noqa: E402  (Pipeline looks the registries up lazily)
 
 
+def _add_segment(pipe, segment, channel, open_radius, max_grow, bg_guard, roi_length):
+    """``segment=`` of the marker pipelines ("otsu" or a threshold; not in the reference): ``segment_rois`` directly
+    after the finder, its settings checked now, not at the first assay.  None adds nothing."""
+    if segment is None:
+        return
+    from .segment import check_segment
+
+    check_segment(segment, open_radius, max_grow, bg_guard, roi_length=roi_length)
+    pipe.add_pipe("segment_rois", method=segment, channel=channel, open_radius=open_radius, max_grow=max_grow,
+                  bg_guard=bg_guard)
+
+
 def microfluidic_chip(data, shape=(8, 8), pinlist=None, blank=None, overlap=102, rotation=0, row_dist=375 / 1.61,
                       col_dist=400 / 1.61, chip_type=None, min_button_diameter=8, max_button_diameter=30,
                       chamber_diameter=60, top_chamber=None, left_chamber=None, low_edge_quantile=0.1,
                       high_edge_quantile=0.9, num_iter=5000000, min_roundness=0.2, cluster_penalty=50, roi_length=None,
                       progress_bar=False, search_timestep=0, search_channel=None, roi_only=False, drop_tiles=True,
                       interactive=False, blend=None,
-                      register=None, max_shift=8, register_channel=None):
+                      register=None, max_shift=8, register_channel=None,
+                      segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2):
     """registry.py:32-110 (``blend``: ``stitch``'s overlap blending; ``register``, ``max_shift``, ``register_channel``:
     its tile registration -- neither is in the reference)."""
     kw = dict(locals())
@@ -101,7 +114,8 @@ def microfluidic_chip_pipe(shape=(8, 8), pinlist=None, blank=None, overlap=102, 
                            high_edge_quantile=0.9, num_iter=5000000, min_roundness=0.2, cluster_penalty=50,
                            roi_length=None, progress_bar=False, search_timestep=0, search_channel=None,
                            roi_only=False, drop_tiles=True, interactive=False, blend=None,
-                           register=None, max_shift=8, register_channel=None):
+                           register=None, max_shift=8, register_channel=None,
+                           segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2):
     """registry.py:196-271."""
     if chip_type is not None:
         if chip_type == "minichip":
@@ -124,6 +138,7 @@ def microfluidic_chip_pipe(shape=(8, 8), pinlist=None, blank=None, overlap=102, 
                   high_edge_quantile=high_edge_quantile, num_iter=num_iter, min_roundness=min_roundness,
                   cluster_penalty=cluster_penalty, roi_length=roi_length, progress_bar=progress_bar,
                   search_timestep=search_timestep, search_channel=search_channel, interactive=interactive)
+    _add_segment(pipe, segment, segment_channel, segment_open, segment_grow, segment_guard, roi_length)
     pipe.add_pipe("drop", roi_only=roi_only, drop_tiles=drop_tiles)
     pipe.add_pipe("restore_format")
     return pipe
@@ -134,7 +149,8 @@ def mrbles(data, spectra, codes, flatfield=1.0, darkfield=0.0, overlap=102, min_
            search_channel=None, reference="eu", roi_only=False, drop_tiles=True, interactive=False, blend=None,
            register=None, max_shift=8, register_channel=None,
            track=None, max_drift=8, track_min_score=0.5, track_channel=None, track_patch=None,
-           stage_drift=None):
+           stage_drift=None,
+           segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2):
     """registry.py:274-399."""
     kw = dict(locals())
     kw.pop("data")
@@ -146,7 +162,8 @@ def mrbles_pipe(spectra, codes, flatfield=1.0, darkfield=0.0, overlap=102, min_b
                 search_channel=None, reference="eu", roi_only=False, drop_tiles=True, interactive=False, blend=None,
                 register=None, max_shift=8, register_channel=None,
                 track=None, max_drift=8, track_min_score=0.5, track_channel=None, track_patch=None,
-                stage_drift=None):
+                stage_drift=None,
+                segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2):
     """registry.py:402-451."""
     pipe = Pipeline("read")
     pipe.add_pipe("standardize_format")
@@ -158,6 +175,7 @@ def mrbles_pipe(spectra, codes, flatfield=1.0, darkfield=0.0, overlap=102, min_b
                   min_roundness=min_roundness, roi_length=roi_length, search_channel=search_channel,
                   interactive=interactive, track=track, max_drift=max_drift, track_min_score=track_min_score,
                   track_channel=track_channel, track_patch=track_patch, stage_drift=stage_drift)
+    _add_segment(pipe, segment, segment_channel, segment_open, segment_grow, segment_guard, roi_length)
     pipe.add_pipe("identify_mrbles", spectra=spectra, codes=codes, reference=reference)
     pipe.add_pipe("drop", roi_only=roi_only, drop_tiles=drop_tiles)
     pipe.add_pipe("restore_format")
@@ -169,7 +187,8 @@ def beads(data, flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=10,
           search_channel=None, roi_only=False, drop_tiles=True, interactive=False, blend=None,
           register=None, max_shift=8, register_channel=None,
           track=None, max_drift=8, track_min_score=0.5, track_channel=None, track_patch=None,
-          stage_drift=None):
+          stage_drift=None,
+          segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2):
     """registry.py:454-565."""
     kw = dict(locals())
     kw.pop("data")
@@ -181,7 +200,8 @@ def beads_pipe(flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=5, m
                search_channel=None, roi_only=False, drop_tiles=True, interactive=False, blend=None,
                register=None, max_shift=8, register_channel=None,
                track=None, max_drift=8, track_min_score=0.5, track_channel=None, track_patch=None,
-               stage_drift=None):
+               stage_drift=None,
+               segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2):
     """registry.py:568-612 (note the 5/25 defaults here versus 10/50 in ``beads``)."""
     pipe = Pipeline("read")
     pipe.add_pipe("standardize_format")
@@ -193,6 +213,7 @@ def beads_pipe(flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=5, m
                   min_roundness=min_roundness, roi_length=roi_length, search_channel=search_channel,
                   interactive=interactive, track=track, max_drift=max_drift, track_min_score=track_min_score,
                   track_channel=track_channel, track_patch=track_patch, stage_drift=stage_drift)
+    _add_segment(pipe, segment, segment_channel, segment_open, segment_grow, segment_guard, roi_length)
     pipe.add_pipe("drop", roi_only=roi_only, drop_tiles=drop_tiles)
     pipe.add_pipe("restore_format")
     return pipe

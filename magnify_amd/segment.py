@@ -1,0 +1,132 @@
+"""Data-driven fg / bg masks: ``segment_rois`` (not in the reference, whose masks are drawn shapes -- the fitted circle of
+a bead, find.py:561-586, the disk and annulus of a chip marker, find.py:383-400; DESIGN.md, "segment_rois: masks from
+the pixels").
+
+Per (marker, timepoint) the window of ONE channel decides: a threshold (Otsu on the window's 256 ``to_uint8`` bins, or a
+number), a 3x3 opening, the drawn foreground's part of the opened mask grown inside it by at most ``max_grow`` pixels,
+and the drawn background without a guard band around everything bright.  A window where nothing is left (a blank
+chamber, a flat window) keeps its drawn masks.  All of it is one kernel (``hotpath.threshold_masks``:
+mg_roi_threshold_masks); ``tests/segment_ref.py`` restates the contract in NumPy + scipy.ndimage.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _native as nat
+from . import registry
+
+MAX_LEN = nat.DEFINES["MG_SEGMENT_MAX_LEN"]
+MAX_OPEN, MAX_GROW, MAX_GUARD = (nat.DEFINES[k] for k in ("MG_SEGMENT_MAX_OPEN", "MG_SEGMENT_MAX_GROW",
+                                                           "MG_SEGMENT_MAX_GUARD"))
+
+
+def _int_in(name, value, lo, hi):
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)):
+        raise ValueError(f"{name} must be an integer, got {value!r}")
+    if value < lo or (hi is not None and value > hi):
+        raise ValueError(f"{name} must be in [{lo}, {hi}], got {value}" if hi is not None else
+                         f"{name} must be at least {lo}, got {value}")
+    return int(value)
+
+
+def check_segment(method="otsu", open_radius=1, max_grow=4, bg_guard=2, min_area=1, roi_length=None):
+    """The settings of ``segment_rois`` as the pipelines take them: ``method`` "otsu" or a (non-NaN) number;
+    ``0 <= open_radius <= 8``, ``0 <= max_grow <= 32``, ``0 <= bg_guard <= 16``, ``min_area >= 0``, all integers; with
+    ``roi_length`` also ``1 <= roi_length <= 128``.  ValueError otherwise.  Returns (use_otsu, threshold)."""
+    if isinstance(method, str):
+        if method != "otsu":
+            raise ValueError(f'segment method must be "otsu" or a number, got {method!r}')
+        use_otsu, threshold = True, 0.0
+    else:
+        if isinstance(method, (bool, np.bool_)) or not isinstance(method, (int, float, np.integer, np.floating)):
+            raise ValueError(f'segment method must be "otsu" or a number, got {method!r}')
+        use_otsu, threshold = False, float(method)
+        if threshold != threshold:
+            raise ValueError("segment threshold must not be NaN")
+    _int_in("open_radius", open_radius, 0, MAX_OPEN)
+    _int_in("max_grow", max_grow, 0, MAX_GROW)
+    _int_in("bg_guard", bg_guard, 0, MAX_GUARD)
+    _int_in("min_area", min_area, 0, None)
+    if roi_length is not None:
+        _int_in("roi_length", roi_length, 1, None)
+        if roi_length > MAX_LEN:
+            raise ValueError(f"segment_rois holds a window's masks in LDS: roi_length must not exceed {MAX_LEN}, "
+                             f"got {roi_length}")
+    return use_otsu, threshold
+
+
+def channel_index(assay, channel):
+    """Index of ``channel`` -- a name of the ``channel`` coordinate, or an index; None: the first channel.  An unknown
+    name raises ValueError, as the filters' channel lookup does."""
+    if channel is None:
+        return 0
+    names = np.asarray(assay.coords["channel"].values).tolist() if "channel" in assay.coords else None
+    if names is not None and channel in names:
+        return names.index(channel)
+    if isinstance(channel, (int, np.integer)) and not isinstance(channel, (bool, np.bool_)):
+        if not 0 <= channel < assay.sizes["channel"]:
+            raise ValueError(f"channel index {channel} outside [0, {assay.sizes['channel']})")
+        return int(channel)
+    if names is None:
+        raise ValueError(f"{channel!r} is no channel index and the dataset has no channel names")
+    return names.index(channel)
+
+
+def _device_tensor(arr, dims):
+    import torch
+
+    data = arr.transpose(*[d for d in dims if d in arr.dims]).data
+    if not isinstance(data, torch.Tensor):
+        data = np.ascontiguousarray(data)
+        if data.dtype.byteorder not in ("=", "|"):
+            data = data.astype(data.dtype.newbyteorder("="))
+        data = torch.from_numpy(data)
+    data = data.cuda()
+    if "time" in dims and "time" not in arr.dims:  # one mask for all timepoints
+        data = data[:, None].expand(data.shape[0], -1, *data.shape[1:])
+    return data
+
+
+@registry.component("segment_rois")
+def segment_rois(assay, method="otsu", channel=None, open_radius=1, max_grow=4, bg_guard=2, min_area=1):
+    """Replace ``fg`` / ``bg`` of every (marker, timepoint) by masks derived from the window's pixels in ``channel``
+    (module docstring); adds ``segmented`` (bool) and ``seg_threshold`` (float64) on (mark, time).  Beads (no ``tag``
+    coordinate): only pixels of the bead's own drawn fg or bg can become its foreground, so a neighbour's disk and
+    contested pixels never do.  ``roi``, ``x``, ``y`` and ``valid`` are untouched."""
+    import torch
+
+    from . import hotpath
+    from .xr_lite import DataArray
+
+    mask_dims, roi_dims = ("mark", "time", "roi_y", "roi_x"), ("mark", "channel", "time", "roi_y", "roi_x")
+    roi_var = assay.data_vars["roi"]
+    L, m, n_t = roi_var.sizes["roi_y"], roi_var.sizes["mark"], roi_var.sizes["time"]
+    check_segment(method, open_radius, max_grow, bg_guard, min_area, L)
+    ch = channel_index(assay, channel)
+    if m == 0:
+        return assay.assign_coords(segmented=(("mark", "time"), np.zeros((0, n_t), dtype=bool)),
+                                   seg_threshold=(("mark", "time"), np.zeros((0, n_t), dtype=np.float64)))
+    hotpath.require_gpu()
+    roi = _device_tensor(roi_var, roi_dims)
+    old_fg, old_bg = assay.coords["fg"], assay.coords["bg"]
+    fg0, bg0 = (t if t.dtype in (torch.bool, torch.uint8) else t != 0
+                for t in (_device_tensor(old_fg, mask_dims), _device_tensor(old_bg, mask_dims)))
+    allowed = None
+    if "tag" not in assay.coords:
+        if all(t.shape[1] == 1 or t.stride(1) == 0 for t in (fg0, bg0)):  # one drawn mask for all timepoints: one union
+            allowed = fg0[:, :1].view(torch.uint8) | bg0[:, :1].view(torch.uint8)
+        else:
+            allowed = fg0.view(torch.uint8) | bg0.view(torch.uint8)
+    fg, bg, threshold, counts, segmented = hotpath.threshold_masks(
+        roi[:, ch], fg0, bg0, allowed, method=method, open_radius=open_radius, max_grow=max_grow, bg_guard=bg_guard,
+        min_area=min_area)
+    out = assay.assign_coords(
+        fg=DataArray(fg.view(torch.bool), mask_dims, None, "fg", dict(old_fg.attrs)),
+        bg=DataArray(bg.view(torch.bool), mask_dims, None, "bg", dict(old_bg.attrs)),
+        segmented=(("mark", "time"), segmented.view(torch.bool)),
+        seg_threshold=(("mark", "time"), threshold),
+    )
+    # the finder's fused reductions answered for the drawn masks: counts come from the kernel, sums are recomputed on demand
+    out._cache["roi_counts"] = counts  # (mark, time, {fg, bg}) int32, the layout of the tracked path
+    out._cache.pop("roi_sums", None)
+    return out
