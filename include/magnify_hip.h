@@ -802,10 +802,13 @@ int mg_button_masks(const int32_t* d_centers, const int32_t* d_radii, int m, int
                     const int32_t* d_cv_halfwidths, int hw_stride, int max_table_r, uint8_t* d_fg, uint8_t* d_bg,
                     void* stream);
 
-/* Masked sums with explicit masks: roi (m, n_ct, L, L), fg / bg (m, L, L) uint8 ->
- * d_sums double[m][n_ct][2] = {fg sum, bg sum}, d_counts int32[m][2] (optional). */
-int mg_masked_sums(const void* d_roi, int dtype, const uint8_t* d_fg, const uint8_t* d_bg, int m, int n_ct,
-                   int roi_len, double* d_sums, int32_t* d_counts, void* stream);
+/* Masked sums with explicit masks: roi (m, n_c, n_t, L, L); fg / bg uint8, the L x L bytes of marker g at timepoint t
+ * at d_xx + g * xx_stride_m + t * xx_stride_t (strides >= 0 in bytes; a time stride of 0: one mask for all timepoints),
+ * as mg_roi_masked_stats reads its mask -> d_sums double[m][n_c][n_t][2] = {fg sum, bg sum}; d_counts (optional)
+ * int32[m][n_tm][2] = {fg count, bg count} of timepoints 0 .. n_tm - 1, n_tm = 1 or n_t.  n_c * n_t <= 65535. */
+int mg_masked_sums(const void* d_roi, int dtype, const uint8_t* d_fg, int64_t fg_stride_m, int64_t fg_stride_t,
+                   const uint8_t* d_bg, int64_t bg_stride_m, int64_t bg_stride_t, int m, int n_c, int n_t, int roi_len,
+                   double* d_sums, int32_t* d_counts, int n_tm, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Measurement aid ("confirm with a measured streaming-copy ceiling on the box")

@@ -85,16 +85,19 @@ __global__ __launch_bounds__(NT) void k_button_masks(const int32_t* __restrict__
   }
 }
 
+// Window (g, ct) of the (m, n_c, n_t) windows under the masks of its timepoint ct % n_t.  The workgroups of channel 0
+// write the counts of their timepoint: d_counts is (m, n_tm, 2) with n_tm = n_t, or n_tm = 1 -- the counts of timepoint 0
+// only (ct < n_tm picks exactly those workgroups).
 template <typename T, typename ACC>
-__global__ __launch_bounds__(NT) void k_masked_sums(const T* __restrict__ d_roi, const uint8_t* __restrict__ d_fg,
-                                                    const uint8_t* __restrict__ d_bg, int n_ct, int n,
-                                                    double* __restrict__ d_sums, int32_t* __restrict__ d_counts) {
+__global__ __launch_bounds__(NT) void k_masked_sums(const T* __restrict__ d_roi, MgMaskView d_fg, MgMaskView d_bg, int n_t,
+                                                    int n_ct, int n, double* __restrict__ d_sums,
+                                                    int32_t* __restrict__ d_counts, int n_tm) {
   __shared__ ACC s_f[NT / 64], s_b[NT / 64];
   __shared__ int c_f[NT / 64], c_b[NT / 64];
   const int g = blockIdx.x, ct = blockIdx.y;
   const T* v = d_roi + ((int64_t)g * n_ct + ct) * n;
-  const uint8_t* fg = d_fg + (int64_t)g * n;
-  const uint8_t* bg = d_bg + (int64_t)g * n;
+  const uint8_t* fg = d_fg.at(g, ct % n_t);
+  const uint8_t* bg = d_bg.at(g, ct % n_t);
   ACC sf = 0, sb = 0;
   int cf = 0, cb = 0;
   for (int p = threadIdx.x; p < n; p += NT) {
@@ -116,9 +119,10 @@ __global__ __launch_bounds__(NT) void k_masked_sums(const T* __restrict__ d_roi,
     double* o = d_sums + ((int64_t)g * n_ct + ct) * 2;
     o[0] = (double)(s_f[0] + s_f[1] + s_f[2] + s_f[3]);
     o[1] = (double)(s_b[0] + s_b[1] + s_b[2] + s_b[3]);
-    if (ct == 0 && d_counts) {
-      d_counts[2 * (int64_t)g] = c_f[0] + c_f[1] + c_f[2] + c_f[3];
-      d_counts[2 * (int64_t)g + 1] = c_b[0] + c_b[1] + c_b[2] + c_b[3];
+    if (ct < n_tm && d_counts) {
+      int32_t* c = d_counts + 2 * ((int64_t)g * n_tm + ct);
+      c[0] = c_f[0] + c_f[1] + c_f[2] + c_f[3];
+      c[1] = c_b[0] + c_b[1] + c_b[2] + c_b[3];
     }
   }
 }
@@ -150,17 +154,22 @@ extern "C" int mg_button_masks(const int32_t* d_centers, const int32_t* d_radii,
   return MG_OK;
 }
 
-extern "C" int mg_masked_sums(const void* d_roi, int dtype, const uint8_t* d_fg, const uint8_t* d_bg, int m, int n_ct,
-                              int roi_len, double* d_sums, int32_t* d_counts, void* stream) {
-  if (!d_roi || !d_fg || !d_bg || !d_sums || m < 0 || n_ct <= 0 || n_ct > 65535 || roi_len <= 0) return MG_EINVAL;
+extern "C" int mg_masked_sums(const void* d_roi, int dtype, const uint8_t* d_fg, int64_t fg_stride_m, int64_t fg_stride_t,
+                              const uint8_t* d_bg, int64_t bg_stride_m, int64_t bg_stride_t, int m, int n_c, int n_t,
+                              int roi_len, double* d_sums, int32_t* d_counts, int n_tm, void* stream) {
+  const MgMaskView fg = {d_fg, fg_stride_m, fg_stride_t}, bg = {d_bg, bg_stride_m, bg_stride_t};
+  if (!d_roi || !mg_mask_view_ok(fg) || !mg_mask_view_ok(bg) || !d_sums || m < 0 || n_c <= 0 || n_t <= 0 ||
+      (int64_t)n_c * n_t > 65535 || roi_len <= 0 || (n_tm != 1 && n_tm != n_t))
+    return MG_EINVAL;
   if (m == 0) return MG_OK;
+  const int n_ct = n_c * n_t;
   const dim3 g(m, n_ct);
   hipStream_t s = mg_stream(stream);
   const int n = roi_len * roi_len;
   return mg_dispatch_pixel(dtype, [&](auto t) {
     using T = decltype(t);
-    hipLaunchKernelGGL((k_masked_sums<T, mg_acc_t<T>>), g, dim3(NT), 0, s, (const T*)d_roi, d_fg, d_bg, n_ct, n, d_sums,
-                       d_counts);
+    hipLaunchKernelGGL((k_masked_sums<T, mg_acc_t<T>>), g, dim3(NT), 0, s, (const T*)d_roi, fg, bg, n_t, n_ct, n, d_sums,
+                       d_counts, n_tm);
     MG_CHECK_LAUNCH();
     return MG_OK;
   });

@@ -93,6 +93,15 @@ static inline int mg_dispatch_pixel(int dtype, F&& f) {
 template <class T>
 using mg_acc_t = std::conditional_t<std::is_integral<T>::value, long long, double>;
 
+// A byte mask of gathered windows as every window kernel reads it: the L x L bytes of marker g at timepoint t start at
+// p + g * stride_m + t * stride_t (a stride of 0: one mask for all markers / timepoints).
+struct MgMaskView {
+  const uint8_t* p;
+  int64_t stride_m, stride_t;
+  __device__ __forceinline__ const uint8_t* at(int64_t g, int64_t t) const { return p + g * stride_m + t * stride_t; }
+};
+static inline bool mg_mask_view_ok(const MgMaskView& v) { return v.p && v.stride_m >= 0 && v.stride_t >= 0; }
+
 // Stitch crop (stitch.py:22-39): every tile keeps rows / columns [clip, clip + hy / hx) -- half the overlap goes on
 // each side, the odd pixel on the far one -- and the n_tr x n_tc kept parts are laid side by side.
 struct MgStitchGeom {
@@ -279,6 +288,24 @@ __device__ __forceinline__ double mg_wave_sum_f64(double v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
   return v;
+}
+
+// op folded over the 256 threads of a workgroup: xor-shuffles in the wave, then the four waves' partials as
+// op(op(s0, s1), op(s2, s3)).  The same value in every thread; called by all (it synchronises, before and after the
+// read of the partials).  The sums of mg_track, mg_register, mg_buttons, mg_roi and mg_flatfield are not callers: they
+// add their four partials left to right, and another tree would change a float sum in the last bit.
+constexpr int MG_FOLD_WAVES = 4;
+template <typename V, class Op>
+__device__ __forceinline__ V mg_block_fold(V v, Op op) {
+  __shared__ V s_part[MG_FOLD_WAVES];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = op(v, __shfl_xor(v, off));
+  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
+  __syncthreads();
+  static_assert(MG_FOLD_WAVES == 4, "the fold below is written out for four waves");
+  const V r = op(op(s_part[0], s_part[1]), op(s_part[2], s_part[3]));
+  __syncthreads();
+  return r;
 }
 
 // Exclusive prefix sum over the threads of a block (blockDim.x <= 1024, multiple of 64).

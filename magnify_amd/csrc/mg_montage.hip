@@ -14,11 +14,6 @@
 
 namespace {
 
-struct MontageMask {  // mask of marker g at timepoint t: L x L bytes at p + g * stride_m + t * stride_t
-  const uint8_t* p;
-  int64_t stride_m, stride_t;
-};
-
 template <typename T, typename Acc>
 __device__ __forceinline__ Acc row_sum(const T* __restrict__ q, int nc, Acc sum) {
   constexpr int N = 16 / (int)sizeof(T);
@@ -60,7 +55,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void k_roi_montage(const T* __restrict__ roi, int64_t stride_m, int64_t stride_c,
                                                      int64_t stride_t, int n_marks, int n_c, int L, int level,
                                                      int lk, const int32_t* __restrict__ layout, int cols, int hp, int wp,
-                                                     int64_t total, MgChannels ch, MontageMask bg, MontageMask fg,
+                                                     int64_t total, MgChannels ch, MgMaskView bg, MgMaskView fg,
                                                      int overlay, double alpha, uint8_t* __restrict__ out) {
   using Acc = mg_block_acc_t<T>;
   const int s = 1 << level;
@@ -87,9 +82,10 @@ __global__ __launch_bounds__(256) void k_roi_montage(const T* __restrict__ roi, 
     if (overlay != MG_OVERLAY_NONE) {
 #pragma unroll
       for (int which = 0; which < 2; ++which) {  // bg in red, then fg in green on top
-        const MontageMask& mk = which ? fg : bg;
+        // (a copy, not a reference: at() through a reference schedules the whole kernel another way; no pointer: no mask)
+        const MgMaskView mk = which ? fg : bg;
         if (!mk.p) continue;
-        const uint8_t* m = mk.p + (int64_t)g * mk.stride_m + (int64_t)t * mk.stride_t;
+        const uint8_t* m = mk.at(g, t);
         bool on = block_on(m, L, lk, s, by, bx);
         if (on && overlay == MG_OVERLAY_OUTLINE)
           on = !(block_on(m, L, lk, s, by - 1, bx) && block_on(m, L, lk, s, by + 1, bx) &&
@@ -122,7 +118,7 @@ extern "C" int mg_render_roi_montage(const void* d_roi, int dtype, int64_t strid
   const int64_t total = (int64_t)n_t * hp * wp;
   if (total == 0) return MG_OK;  // no cells: an empty picture
   if (!d_roi || !d_layout || !d_out || n_marks < 1) return MG_EINVAL;
-  const MontageMask bg = {d_bg, bg_stride_m, bg_stride_t}, fg = {d_fg, fg_stride_m, fg_stride_t};
+  const MgMaskView bg = {d_bg, bg_stride_m, bg_stride_t}, fg = {d_fg, fg_stride_m, fg_stride_t};
   const int blocks = (int)std::min<int64_t>((total + 255) / 256, 1 << 16);
   hipStream_t st = mg_stream(stream);
   return mg_dispatch_pixel(dtype, [&](auto t) {

@@ -23,9 +23,8 @@ namespace {
 
 // ---- label map ------------------------------------------------------------------------------------------------------
 
-__global__ __launch_bounds__(256) void k_image_labels(const uint8_t* __restrict__ fg, int64_t stride_m, int64_t stride_t,
-                                                      const int32_t* __restrict__ origin, int n_t, int L, int qpr,
-                                                      int level, int h, int w, int hk, int wk, int64_t total,
+__global__ __launch_bounds__(256) void k_image_labels(MgMaskView fg, const int32_t* __restrict__ origin, int n_t, int L,
+                                                      int qpr, int level, int h, int w, int hk, int wk, int64_t total,
                                                       int32_t* __restrict__ labels) {
   const bool small = total <= 0x7FFFFFFFLL;  // (uniform) 32-bit index arithmetic
   const int64_t stride = (int64_t)gridDim.x * 256;
@@ -39,7 +38,7 @@ __global__ __launch_bounds__(256) void k_image_labels(const uint8_t* __restrict_
       const int64_t row = i / qpr;
       rx0 = (int)(i - row * qpr) * 4, mt = row / L, ry = (int)(row - mt * L), g = mt / n_t, t = (int)(mt - g * n_t);
     }
-    const uint8_t* q = fg + g * stride_m + (int64_t)t * stride_t + (int64_t)ry * L;
+    const uint8_t* q = fg.at(g, t) + (int64_t)ry * L;
     const int y = origin[2 * mt] + ry, left = origin[2 * mt + 1];
     if (y < 0 || y >= h) continue;
     int32_t* out = labels + ((int64_t)t * hk + (y >> level)) * wk;
@@ -259,16 +258,17 @@ int launch_overview(const void* d_image, int64_t chan_stride, int64_t time_strid
 extern "C" int mg_roi_image_labels(const uint8_t* d_fg, int64_t mask_stride_m, int64_t mask_stride_t,
                                    const int32_t* d_origin, int m, int n_t, int roi_len, int level, int h, int w,
                                    int32_t* d_labels, void* stream) {
+  const MgMaskView fg = {d_fg, mask_stride_m, mask_stride_t};
   if (m < 0 || n_t < 1 || roi_len < 1 || level < 0 || level > MG_OVERVIEW_MAX_LEVEL || h < 1 || w < 1 || !d_labels ||
-      mask_stride_m < 0 || mask_stride_t < 0)
+      fg.stride_m < 0 || fg.stride_t < 0)
     return MG_EINVAL;
-  if (m == 0) return MG_OK;
-  if (!d_fg || !d_origin) return MG_EINVAL;
+  if (m == 0) return MG_OK;  // (no markers: the mask need not exist)
+  if (!mg_mask_view_ok(fg) || !d_origin) return MG_EINVAL;
   const int s = 1 << level, hk = (h + s - 1) / s, wk = (w + s - 1) / s, qpr = (roi_len + 3) / 4;
   const int64_t total = (int64_t)m * n_t * roi_len * qpr;
   const int blocks = (int)std::min<int64_t>((total + 255) / 256, 8192);
-  hipLaunchKernelGGL(k_image_labels, dim3(blocks), dim3(256), 0, mg_stream(stream), d_fg, mask_stride_m, mask_stride_t,
-                     d_origin, n_t, roi_len, qpr, level, h, w, hk, wk, total, d_labels);
+  hipLaunchKernelGGL(k_image_labels, dim3(blocks), dim3(256), 0, mg_stream(stream), fg, d_origin, n_t, roi_len, qpr,
+                     level, h, w, hk, wk, total, d_labels);
   MG_CHECK_LAUNCH();
   return MG_OK;
 }

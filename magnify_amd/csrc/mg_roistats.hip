@@ -10,6 +10,7 @@
 namespace {
 
 constexpr int NT = MG_SELECT_THREADS, WV = NT / 64;
+static_assert(WV == MG_FOLD_WAVES, "mg_block_fold folds four waves");
 constexpr double QNAN = __builtin_nan("");
 
 struct StatsQ {
@@ -18,19 +19,6 @@ struct StatsQ {
 
 // Do the keys of a window fit the LDS budget?  (n = roi_len^2 pixels, key_bytes = 4 or 8)
 inline bool keys_fit(int64_t n, int key_bytes) { return n * key_bytes <= MG_ROISTATS_LDS_KEY_BYTES; }
-
-template <typename V, class Op>
-__device__ __forceinline__ V block_fold(V v, Op op) {  // the same value in every thread; called by all (it synchronises)
-  __shared__ V s_part[WV];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = op(v, __shfl_xor(v, off));
-  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
-  __syncthreads();
-  static_assert(WV == 4, "the fold below is written out for four waves");
-  const V r = op(op(s_part[0], s_part[1]), op(s_part[2], s_part[3]));
-  __syncthreads();
-  return r;
-}
 
 // What a thread has seen of its window.  Integer pixels are their own keys and are summed exactly; float pixels are
 // summed in float64, every thread its own pixels in the order it meets them.
@@ -160,6 +148,9 @@ __global__ __launch_bounds__(NT) void k_masked_stats(const T* __restrict__ d_roi
   const int64_t window = blockIdx.x;
   const int g = (int)(window / n_ct), ct = (int)(window % n_ct);
   const T* v = d_roi + window * n;
+  // (the mask stays three scalar arguments and this line: as an MgMaskView argument its fields are fetched one by one
+  // and three median instances take more scalar registers; through at() the prologue is scheduled another way, and
+  // the uint16 statistics measured 0.7 % slower)
   const uint8_t* mask = d_mask + (int64_t)g * mask_stride_m + (int64_t)(ct % n_t) * mask_stride_t;
   constexpr int VW = 16 / (int)sizeof(T);
   const bool wide = (reinterpret_cast<uintptr_t>(v) & 15) == 0 && (reinterpret_cast<uintptr_t>(mask) & (VW - 1)) == 0;
@@ -168,14 +159,14 @@ __global__ __launch_bounds__(NT) void k_masked_stats(const T* __restrict__ d_roi
   const int run = wide ? ingest<T, VW, IN_LDS>(v, mask, n, keys, seen) : ingest<T, 1, IN_LDS>(v, mask, n, keys, seen);
   for (int i = threadIdx.x; i < 256; i += NT) hist[i] = 0u;  // (as select_kth wants it)
   if (IN_LDS && (threadIdx.x & 63) == 0) s_run[threadIdx.x >> 6] = run;
-  // (block_fold synchronises: s_run, hist and the keys are in place after the first of these)
-  const int count = block_fold(seen.count, [](int a, int b) { return a + b; });
+  // (mg_block_fold synchronises: s_run, hist and the keys are in place after the first of these)
+  const int count = mg_block_fold(seen.count, [](int a, int b) { return a + b; });
   typename Seen<T>::Acc sum = 0;
   K kmin = 0, kmax = 0;
   if (!MEDIAN) {
-    sum = block_fold(seen.sum, [](auto a, auto b) { return a + b; });
-    kmin = block_fold(seen.kmin, [](K a, K b) { return a < b ? a : b; });
-    kmax = block_fold(seen.kmax, [](K a, K b) { return a > b ? a : b; });
+    sum = mg_block_fold(seen.sum, [](auto a, auto b) { return a + b; });
+    kmin = mg_block_fold(seen.kmin, [](K a, K b) { return a < b ? a : b; });
+    kmax = mg_block_fold(seen.kmax, [](K a, K b) { return a > b ? a : b; });
   }
 
   double* stats = d_stats + window * 4;
@@ -238,7 +229,7 @@ __global__ __launch_bounds__(NT) void k_masked_stats(const T* __restrict__ d_roi
       dev += d * d;
     }
   }
-  const double m2 = block_fold(dev, [](double a, double b) { return a + b; });
+  const double m2 = mg_block_fold(dev, [](double a, double b) { return a + b; });
   if (threadIdx.x == 0) {
     d_count[window] = count;
     stats[0] = total, stats[1] = m2, stats[2] = median_key<T>::value(kmin), stats[3] = median_key<T>::value(kmax);
@@ -267,26 +258,28 @@ __global__ __launch_bounds__(NT) void k_masked_stats(const T* __restrict__ d_roi
   }
 }
 
-// MEDIAN: d_order is the (m, n_c, n_t) medians, and d_count, d_stats, qs are not looked at.
+// MEDIAN: d_order is the (m, n_c, n_t) medians, and d_count, d_stats, qs are not looked at.  Runs inside
+// mg_dispatch_pixel, which has refused every other dtype code by now: no markers is MG_OK for a valid dtype only.
 template <typename T, bool MEDIAN>
-int launch_stats(const void* d_roi, const uint8_t* d_mask, int64_t sm, int64_t st, int m, int n_c, int n_t, int len,
-                 const StatsQ& qs, int n_q, int32_t* d_count, double* d_stats, double* d_order, hipStream_t s) {
+int launch_stats(const void* d_roi, const MgMaskView& mask, int m, int n_c, int n_t, int len, const StatsQ& qs, int n_q,
+                 int32_t* d_count, double* d_stats, double* d_order, hipStream_t s) {
   typedef typename median_key<T>::type K;
+  if (m == 0) return MG_OK;
   const int n = len * len, n_ct = n_c * n_t;
   const dim3 grid((unsigned)((int64_t)m * n_ct));
   if (keys_fit(n, sizeof(K)))
-    hipLaunchKernelGGL((k_masked_stats<T, true, MEDIAN>), grid, dim3(NT), (size_t)n * sizeof(K), s, (const T*)d_roi, d_mask,
-                       sm, st, n_t, n_ct, n, qs, n_q, d_count, d_stats, d_order);
+    hipLaunchKernelGGL((k_masked_stats<T, true, MEDIAN>), grid, dim3(NT), (size_t)n * sizeof(K), s, (const T*)d_roi, mask.p,
+                       mask.stride_m, mask.stride_t, n_t, n_ct, n, qs, n_q, d_count, d_stats, d_order);
   else
-    hipLaunchKernelGGL((k_masked_stats<T, false, MEDIAN>), grid, dim3(NT), 0, s, (const T*)d_roi, d_mask, sm, st, n_t, n_ct,
-                       n, qs, n_q, d_count, d_stats, d_order);
+    hipLaunchKernelGGL((k_masked_stats<T, false, MEDIAN>), grid, dim3(NT), 0, s, (const T*)d_roi, mask.p, mask.stride_m,
+                       mask.stride_t, n_t, n_ct, n, qs, n_q, d_count, d_stats, d_order);
   MG_CHECK_LAUNCH();
   return MG_OK;
 }
 
 // What both entry points refuse: one workgroup a window, pixel indices are int.
-bool windows_ok(const void* d_roi, const uint8_t* d_mask, int64_t sm, int64_t st, int m, int n_c, int n_t, int len) {
-  return d_roi && d_mask && m >= 0 && n_c > 0 && n_t > 0 && len > 0 && len <= MG_ROISTATS_MAX_LEN && sm >= 0 && st >= 0 &&
+bool windows_ok(const void* d_roi, const MgMaskView& mask, int m, int n_c, int n_t, int len) {
+  return d_roi && mg_mask_view_ok(mask) && m >= 0 && n_c > 0 && n_t > 0 && len > 0 && len <= MG_ROISTATS_MAX_LEN &&
          (int64_t)n_c * n_t <= INT32_MAX && (int64_t)m * n_c * n_t <= INT32_MAX;
 }
 
@@ -302,31 +295,27 @@ extern "C" int mg_roi_masked_stats_keys_in_lds(int dtype, int roi_len) {
 extern "C" int mg_roi_masked_stats(const void* d_roi, int dtype, const uint8_t* d_mask, int64_t mask_stride_m,
                                    int64_t mask_stride_t, int m, int n_c, int n_t, int roi_len, const double* q, int n_q,
                                    int32_t* d_count, double* d_stats, double* d_order, void* stream) {
-  if (!windows_ok(d_roi, d_mask, mask_stride_m, mask_stride_t, m, n_c, n_t, roi_len) || !d_count || !d_stats) return MG_EINVAL;
+  const MgMaskView mask = {d_mask, mask_stride_m, mask_stride_t};
+  if (!windows_ok(d_roi, mask, m, n_c, n_t, roi_len) || !d_count || !d_stats) return MG_EINVAL;
   if (n_q < 0 || n_q > MG_ROISTATS_MAX_Q || (n_q > 0 && (!q || !d_order))) return MG_EINVAL;
   StatsQ qs = {};
   for (int j = 0; j < n_q; ++j) {
     if (!(q[j] >= 0.0 && q[j] <= 1.0)) return MG_EINVAL;  // (NaN fails both)
     qs.q[j] = q[j];
   }
-  if (dtype != MG_U8 && dtype != MG_U16 && dtype != MG_F32 && dtype != MG_F64) return MG_EINVAL;
-  if (m == 0) return MG_OK;
   hipStream_t s = mg_stream(stream);
   return mg_dispatch_pixel(dtype, [&](auto t) {
-    return launch_stats<decltype(t), false>(d_roi, d_mask, mask_stride_m, mask_stride_t, m, n_c, n_t, roi_len, qs, n_q,
-                                            d_count, d_stats, d_order, s);
+    return launch_stats<decltype(t), false>(d_roi, mask, m, n_c, n_t, roi_len, qs, n_q, d_count, d_stats, d_order, s);
   });
 }
 
 extern "C" int mg_roi_masked_median(const void* d_roi, int dtype, const uint8_t* d_mask, int64_t mask_stride_m,
                                     int64_t mask_stride_t, int m, int n_c, int n_t, int roi_len, double* d_median,
                                     void* stream) {
-  if (!windows_ok(d_roi, d_mask, mask_stride_m, mask_stride_t, m, n_c, n_t, roi_len) || !d_median) return MG_EINVAL;
-  if (dtype != MG_U8 && dtype != MG_U16 && dtype != MG_F32 && dtype != MG_F64) return MG_EINVAL;
-  if (m == 0) return MG_OK;
+  const MgMaskView mask = {d_mask, mask_stride_m, mask_stride_t};
+  if (!windows_ok(d_roi, mask, m, n_c, n_t, roi_len) || !d_median) return MG_EINVAL;
   hipStream_t s = mg_stream(stream);
   return mg_dispatch_pixel(dtype, [&](auto t) {
-    return launch_stats<decltype(t), true>(d_roi, d_mask, mask_stride_m, mask_stride_t, m, n_c, n_t, roi_len, StatsQ{}, 0,
-                                           nullptr, nullptr, d_median, s);
+    return launch_stats<decltype(t), true>(d_roi, mask, m, n_c, n_t, roi_len, StatsQ{}, 0, nullptr, nullptr, d_median, s);
   });
 }

@@ -14,6 +14,7 @@
 namespace {
 
 constexpr int NT = 256, WV = NT / 64;
+static_assert(WV == MG_FOLD_WAVES, "mg_block_fold folds four waves");
 constexpr int HIST_COPIES = 4;  // a power of two
 constexpr double QNAN = __builtin_nan("");
 
@@ -23,8 +24,7 @@ enum Plane { P_ON, P_OPEN, P_FG, P_TMP, P_FG0, P_BG0, P_ALLOWED, P_NOTFIRST, P_N
 struct SegArgs {
   const void* roi;
   int64_t stride_m, stride_t;
-  const uint8_t *fg0, *bg0, *allowed;
-  int64_t fg_sm, fg_st, bg_sm, bg_st, al_sm, al_st;
+  MgMaskView fg0, bg0, allowed;  // allowed.p may be null: no such mask
   int n_t, len;
   int use_otsu;
   double threshold;
@@ -34,19 +34,6 @@ struct SegArgs {
   int32_t* counts;
   uint8_t* segmented;
 };
-
-template <typename V, class Op>
-__device__ __forceinline__ V block_fold(V v, Op op) {  // the same value in every thread; called by all (it synchronises)
-  __shared__ V s_part[WV];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = op(v, __shfl_xor(v, off));
-  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
-  __syncthreads();
-  static_assert(WV == 4, "the fold below is written out for four waves");
-  const V r = op(op(s_part[0], s_part[1]), op(s_part[2], s_part[3]));
-  __syncthreads();
-  return r;
-}
 
 // The drawn masks: src[k][0 .. n) bytes -> plane[k] bits (non-zero = set; bits n .. 64 chunks are clear), k < count, a
 // wave per 64 pixels.  The loads of PACK_CHUNKS chunks of every mask are issued before the first ballot: the pass is a
@@ -120,7 +107,7 @@ __device__ __forceinline__ void morph(uint32_t* x, uint32_t* tmp, const uint32_t
 __device__ __forceinline__ int block_popcount(const uint32_t* plane, int words) {
   int c = 0;
   for (int i = threadIdx.x; i < words; i += NT) c += __popc(plane[i]);
-  return block_fold(c, [](int a, int b) { return a + b; });
+  return mg_block_fold(c, [](int a, int b) { return a + b; });
 }
 
 // bit plane -> 0 / 1 bytes, every byte of out[0 .. n) written once; four pixels a thread where `out` is 4-byte aligned
@@ -155,10 +142,10 @@ __global__ __launch_bounds__(NT) void k_threshold_masks(SegArgs a) {
   const T* v = static_cast<const T*>(a.roi) + g * a.stride_m + t * a.stride_t;
 
   // the drawn masks, once
-  const uint8_t* const fg0 = a.fg0 + g * a.fg_sm + t * a.fg_st;
-  const uint8_t* const bg0 = a.bg0 + g * a.bg_sm + t * a.bg_st;
-  if (a.allowed) {  // block-uniform
-    const uint8_t* const src[3] = {fg0, bg0, a.allowed + g * a.al_sm + t * a.al_st};
+  const uint8_t* const fg0 = a.fg0.at(g, t);
+  const uint8_t* const bg0 = a.bg0.at(g, t);
+  if (a.allowed.p) {  // block-uniform
+    const uint8_t* const src[3] = {fg0, bg0, a.allowed.at(g, t)};
     uint32_t* const dst[3] = {plane(P_FG0), plane(P_BG0), plane(P_ALLOWED)};
     pack_bytes<3>(src, n, chunks, dst);
   } else {
@@ -186,9 +173,9 @@ __global__ __launch_bounds__(NT) void k_threshold_masks(SegArgs a) {
     });
     tlo = (double)flo, thi = (double)fhi;
   }
-  // (block_fold synchronises: the planes above and the cleared histogram are in place after the first)
-  const double lo = block_fold(tlo, [](double x, double y) { return x < y ? x : y; });
-  const double hi = block_fold(thi, [](double x, double y) { return x > y ? x : y; });
+  // (mg_block_fold synchronises: the planes above and the cleared histogram are in place after the first)
+  const double lo = mg_block_fold(tlo, [](double x, double y) { return x < y ? x : y; });
+  const double hi = mg_block_fold(thi, [](double x, double y) { return x > y ? x : y; });
   const double range = hi - lo;
   const bool flat = !(range > 0.0) || !(range < INFINITY);  // no pixels: -inf; an infinity among them: inf or NaN
 
@@ -298,7 +285,7 @@ __global__ __launch_bounds__(NT) void k_threshold_masks(SegArgs a) {
       morph<true>(plane(P_OPEN), plane(P_TMP), plane(P_NOTFIRST), plane(P_NOTLAST), plane(P_VALID), words, q, s);
     for (int i = threadIdx.x; i < words; i += NT) {
       uint32_t o = plane(P_OPEN)[i];
-      if (a.allowed) o &= plane(P_ALLOWED)[i];
+      if (a.allowed.p) o &= plane(P_ALLOWED)[i];
       plane(P_OPEN)[i] = o;
       plane(P_FG)[i] = o & plane(P_FG0)[i];
     }
@@ -341,26 +328,25 @@ extern "C" int mg_roi_threshold_masks(const void* d_roi, int dtype, int64_t stri
                                       int roi_len, int use_otsu, double threshold, int open_radius, int max_grow,
                                       int bg_guard, int min_area, uint8_t* d_fg, uint8_t* d_bg, double* d_threshold,
                                       int32_t* d_counts, uint8_t* d_segmented, void* stream) {
-  if (!d_roi || !d_fg0 || !d_bg0 || !d_fg || !d_bg || !d_threshold || !d_counts || !d_segmented) return MG_EINVAL;
-  if (dtype != MG_U8 && dtype != MG_U16 && dtype != MG_F32 && dtype != MG_F64) return MG_EINVAL;
-  if (m < 0 || n_t <= 0 || roi_len < 1 || roi_len > MG_SEGMENT_MAX_LEN || (int64_t)m * n_t > INT32_MAX) return MG_EINVAL;
-  if (stride_m < 0 || stride_t < 0 || fg_stride_m < 0 || fg_stride_t < 0 || bg_stride_m < 0 || bg_stride_t < 0 ||
-      al_stride_m < 0 || al_stride_t < 0)
+  const MgMaskView fg0 = {d_fg0, fg_stride_m, fg_stride_t}, bg0 = {d_bg0, bg_stride_m, bg_stride_t};
+  const MgMaskView allowed = {d_allowed, al_stride_m, al_stride_t};  // (no pointer: no such mask; its strides still count)
+  if (!d_roi || !mg_mask_view_ok(fg0) || !mg_mask_view_ok(bg0) || !d_fg || !d_bg || !d_threshold || !d_counts || !d_segmented)
     return MG_EINVAL;
+  if (m < 0 || n_t <= 0 || roi_len < 1 || roi_len > MG_SEGMENT_MAX_LEN || (int64_t)m * n_t > INT32_MAX) return MG_EINVAL;
+  if (stride_m < 0 || stride_t < 0 || al_stride_m < 0 || al_stride_t < 0) return MG_EINVAL;
   if (open_radius < 0 || open_radius > MG_SEGMENT_MAX_OPEN || max_grow < 0 || max_grow > MG_SEGMENT_MAX_GROW ||
       bg_guard < 0 || bg_guard > MG_SEGMENT_MAX_GUARD || min_area < 0)
     return MG_EINVAL;
   if (!use_otsu && threshold != threshold) return MG_EINVAL;
-  if (m == 0) return MG_OK;
-  SegArgs a = {d_roi,       stride_m,    stride_t,    d_fg0,       d_bg0,       d_allowed,    fg_stride_m, fg_stride_t,
-               bg_stride_m, bg_stride_t, al_stride_m, al_stride_t, n_t,         roi_len,      use_otsu ? 1 : 0, threshold,
-               open_radius, max_grow,    bg_guard,    min_area,    d_fg,        d_bg,         d_threshold, d_counts,
+  SegArgs a = {d_roi,     stride_m,    stride_t, fg0,      bg0,      allowed, n_t,  roi_len,     use_otsu ? 1 : 0,
+               threshold, open_radius, max_grow, bg_guard, min_area, d_fg,    d_bg, d_threshold, d_counts,
                d_segmented};
   const int n = roi_len * roi_len, words = 2 * ((n + 63) / 64);
   const size_t lds = (size_t)N_PLANES * words * 4 + (size_t)n;
   const dim3 grid((unsigned)((int64_t)m * n_t));
   hipStream_t s = mg_stream(stream);
-  return mg_dispatch_pixel(dtype, [&](auto t) {
+  return mg_dispatch_pixel(dtype, [&](auto t) {  // (any other dtype code: MG_EINVAL, with or without markers)
+    if (m == 0) return (int)MG_OK;
     hipLaunchKernelGGL((k_threshold_masks<decltype(t)>), grid, dim3(NT), lds, s, a);
     MG_CHECK_LAUNCH();
     return (int)MG_OK;

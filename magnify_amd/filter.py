@@ -11,7 +11,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import reduce, registry
-from .utils import to_list
+from ._dataset import channel_indexes
 
 
 def _first_step_medians(assay):
@@ -20,16 +20,6 @@ def _first_step_medians(assay):
     fg = reduce.masked_median(assay, "fg", time=0).data[:, :, 0].cpu().numpy()
     bg = reduce.masked_median(assay, "bg", time=0).data[:, :, 0].cpu().numpy()
     return fg, bg
-
-
-def _channel_indexes(assay, search_channel):
-    names = np.asarray(assay.coords["channel"].values).tolist() if "channel" in assay.coords else None
-    if search_channel is None:
-        return list(range(assay.sizes["channel"]))
-    wanted = to_list(search_channel)
-    if names is None:
-        return [int(c) for c in wanted]
-    return [names.index(c) for c in wanted]
 
 
 def _pairwise_spread(bg: np.ndarray) -> float:
@@ -50,7 +40,7 @@ def filter_expression(assay, search_channel=None, min_contrast=None):
     deviations of the pairwise background differences) in at least one search channel."""
     fg, bg = _first_step_medians(assay)
     keep = np.zeros(assay.sizes["mark"], dtype=bool)
-    for c in _channel_indexes(assay, search_channel):
+    for c in channel_indexes(assay, search_channel):
         bound = 4 * _pairwise_spread(bg[:, c]) if min_contrast is None else min_contrast
         keep |= (fg[:, c] - bg[:, c]) > bound
     var, valid = _valid_array(assay)
@@ -68,7 +58,7 @@ def filter_leaky_buttons(assay, search_channel=None):
     var, valid = _valid_array(assay)
     flat = valid.reshape(len(tag), -1)
     last_row = rows.max()
-    for c in _channel_indexes(assay, search_channel):
+    for c in channel_indexes(assay, search_channel):
         empty = (fg[:, c] - bg[:, c]) < 5 * _pairwise_spread(bg[:, c])
         for i in range(len(tag)):
             if tag[i] == "":
@@ -153,7 +143,7 @@ def filter_nonround(assay, min_roundness=0.75, search_channel=None):
     an independent restatement of its border following (oracle/ref_contours.py, tests/test_cpu_host.py)."""
     import scipy.ndimage
 
-    _channel_indexes(assay, search_channel)  # validates the names like the other filters
+    channel_indexes(assay, search_channel)  # validates the names like the other filters
     fg = assay.coords["fg"] if "fg" in assay.coords else assay.data_vars["fg"]
     masks = fg.transpose("mark", "time", "roi_y", "roi_x").data
     masks = (masks[:, 0].cpu().numpy() if hasattr(masks, "cpu") else np.asarray(masks)[:, 0]).astype(bool)

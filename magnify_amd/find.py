@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import hotpath, preprocess, registry, track as tracking, utils
+from ._dataset import channel_index
 from .stack import dedup_against
 from .xr_lite import DataArray
 
@@ -24,15 +25,6 @@ def _finder(n_planes, h, w, min_r, max_r, num_iter, device):
             _FINDERS.clear()
         _FINDERS[key] = hotpath.CircleFinder(n_planes, h, w, min_r, max_r, num_iter, device=device)
     return _FINDERS[key]
-
-
-def _channel_index(assay, channel):
-    labels = assay.coords["channel"].values.tolist() if "channel" in assay.coords else None
-    if labels is not None and channel in labels:
-        return labels.index(channel)
-    if isinstance(channel, (int, np.integer)) and 0 <= int(channel) < assay.sizes["channel"]:
-        return int(channel)
-    raise KeyError(f"channel {channel!r} not found")
 
 
 def _image_tensor(assay):
@@ -103,7 +95,7 @@ class BeadFinder:
         (tracked_roi_pass).  With ``stage_drift`` every timepoint's search is centred on the offset its anchors vote for
         (track.stage_drift); the shifts are then the total displacements."""
         h, w = image.shape[2:]
-        ch = _channel_index(assay, self.search_channels[0] if self.track_channel is None else self.track_channel)
+        ch = channel_index(assay, self.search_channels[0] if self.track_channel is None else self.track_channel)
         half = self.max_bead_radius + 2 if self.track_patch is None else self.track_patch
         stage = None
         if self.stage_drift is not None:
@@ -130,7 +122,7 @@ class BeadFinder:
         if len(self.search_channels) == 1 and self.track is None:
             # one search channel (nothing to de-duplicate across channels, find.py:490-500): the ROI pass reads the
             # bead table where the suppression left it on the device; the host copy of the table runs beside it
-            ch = _channel_index(assay, self.search_channels[0])
+            ch = channel_index(assay, self.search_channels[0])
             roi_pass = lambda d_tab, d_num, cap: hotpath.roi_gather_reduce(  # noqa: E731  (queued before the counts come back)
                 image[None], None, L, None, disks=True, device_tables=(d_tab, None, self.max_bead_radius),
                 device_counts=(d_num, cap, None))
@@ -141,7 +133,7 @@ class BeadFinder:
             beads = finder.fetch_results(counts, d_out, d_scores, overlap=True)[0][0]
         else:
             for channel in self.search_channels:
-                ch = _channel_index(assay, channel)
+                ch = channel_index(assay, channel)
                 res, _ = finder.find(image[ch, 0:1], _plane_minmax(assay, image, (ch, 0)), self.low_edge_quantile,
                                      self.high_edge_quantile, self.min_roundness, self.min_bead_radius,
                                      [utils.next_seed()])
@@ -436,7 +428,7 @@ class ButtonFinder:
         if not self.search_channels:
             self.search_channels = (assay.coords["channel"].values.tolist() if "channel" in assay.coords
                                     else list(range(n_c)))
-        search_idx = [_channel_index(assay, c) for c in self.search_channels]
+        search_idx = [channel_index(assay, c) for c in self.search_channels]
         tag = assay.coords["tag"].values
         n_rows, n_cols = tag.shape
         m, L = n_rows * n_cols, self.roi_length

@@ -1525,24 +1525,30 @@ def marker_table(out: dict, assay_offset: int, n_channels: int) -> torch.Tensor:
     return tab
 
 
+def _window_view(what: str, x: torch.Tensor, m: int, t: int, L: int):
+    """(tensor, marker stride, time stride), in elements, of L x L windows x (M, L, L) -- one for all timepoints -- or
+    (M, T', L, L) with T' = t, or T' = 1 or a view expanded along time (stride 0): one window, read in place for every
+    timepoint, as the window kernels read them.  Copied only where the strides require it: rows that are not contiguous,
+    windows that overlap.  A stride that only ever multiplies index 0 (M <= 1, T' <= 1) is handed over as 0.  ValueError
+    for any other T'."""
+    if x.dim() == 3:
+        x = x[:, None]
+    n_t = x.shape[1]
+    if n_t not in (1, t):
+        raise ValueError(f"{what}: {n_t} timepoints for {t} roi timepoints")
+    assert x.shape[0] == m and tuple(x.shape[2:]) == (L, L), f"{what}: {x.shape}"
+    if (L > 1 and (x.stride(3) != 1 or x.stride(2) != L)) or (m > 1 and x.stride(0) < L * L) or \
+            (n_t > 1 and 0 < x.stride(1) < L * L):
+        x = x.contiguous()
+    return x, (x.stride(0) if m > 1 else 0), (x.stride(1) if n_t > 1 else 0)
+
+
 def _mask_view(what: str, mask: torch.Tensor, m: int, t: int, L: int):
-    """(uint8 tensor, marker stride, time stride) of a mask of m markers as the window kernels read it.  ``mask``: bool /
-    uint8 (M, L, L) -- one mask for all timepoints -- or (M, T', L, L) with T' = t, or T' = 1 or a view expanded along
-    time (stride 0): one mask, read in place for every timepoint.  Copied only where the strides require it: rows that
-    are not contiguous, windows that overlap.  A stride that only ever multiplies index 0 (M <= 1, T' <= 1) is handed
-    over as 0.  ValueError for any other T'."""
+    """``_window_view`` of a bool / uint8 mask, as uint8."""
     if mask.dtype == torch.bool:
         mask = mask.view(torch.uint8)
-    if mask.dim() == 3:
-        mask = mask[:, None]
-    n_t = mask.shape[1]
-    if n_t not in (1, t):
-        raise ValueError(f"{what}: {n_t} mask timepoints for {t} roi timepoints")
-    assert mask.element_size() == 1 and mask.shape[0] == m and tuple(mask.shape[2:]) == (L, L), f"{what}: {mask.shape}"
-    if (L > 1 and (mask.stride(3) != 1 or mask.stride(2) != L)) or (m > 1 and mask.stride(0) < L * L) or \
-            (n_t > 1 and 0 < mask.stride(1) < L * L):
-        mask = mask.contiguous()
-    return mask, (mask.stride(0) if m > 1 else 0), (mask.stride(1) if n_t > 1 else 0)
+    assert mask.element_size() == 1, f"{what}: {mask.dtype}"
+    return _window_view(what, mask, m, t, L)
 
 
 def masked_median(roi: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
@@ -1610,9 +1616,7 @@ def threshold_masks(roi_channel: torch.Tensor, fg0: torch.Tensor, bg0: torch.Ten
     m, t, L, _ = roi_channel.shape
     use_otsu, number = check_segment(method, open_radius, max_grow, bg_guard, min_area, L)
     code = nat.dtype_code(roi_channel.dtype)
-    if (L > 1 and (roi_channel.stride(3) != 1 or roi_channel.stride(2) != L)) or (m > 1 and roi_channel.stride(0) < L * L) \
-            or (t > 1 and roi_channel.stride(1) < L * L):
-        roi_channel = roi_channel.contiguous()
+    roi_channel, rsm, rst = _window_view("threshold_masks roi_channel", roi_channel, m, t, L)
     dev = roi_channel.device
     fg = torch.empty((m, t, L, L), dtype=torch.uint8, device=dev)
     bg = torch.empty((m, t, L, L), dtype=torch.uint8, device=dev)
@@ -1626,8 +1630,8 @@ def threshold_masks(roi_channel: torch.Tensor, fg0: torch.Tensor, bg0: torch.Ten
     asm = ast = 0
     if allowed is not None:
         allowed, asm, ast = _mask_view("threshold_masks allowed", allowed, m, t, L)
-    _call("mg_roi_threshold_masks", roi_channel.data_ptr(), code, roi_channel.stride(0) if m > 1 else 0,
-          roi_channel.stride(1) if t > 1 else 0, fg0.data_ptr(), fsm, fst, bg0.data_ptr(), bsm, bst, _ptr(allowed), asm, ast,
+    _call("mg_roi_threshold_masks", roi_channel.data_ptr(), code, rsm, rst, fg0.data_ptr(), fsm, fst, bg0.data_ptr(), bsm, bst,
+          _ptr(allowed), asm, ast,
           m, t, L, int(use_otsu), float(number), int(open_radius), int(max_grow), int(bg_guard), int(min_area),
           fg.data_ptr(), bg.data_ptr(), threshold.data_ptr(), counts.data_ptr(), segmented.data_ptr(), _stream())
     return fg, bg, threshold, counts, segmented
@@ -1878,13 +1882,19 @@ def button_masks(centers_rc, radii, roi_len, outer_r, inner_r, device="cuda"):
     return fg, bg
 
 
-def masked_sums(roi: torch.Tensor, fg: torch.Tensor, bg: torch.Tensor):
-    """roi (M, C, T, L, L), fg/bg (M, L, L) uint8 -> sums (M, C, T, 2) float64, counts (M, 2) int32."""
+def masked_sums(roi: torch.Tensor, fg: torch.Tensor, bg: torch.Tensor | None = None):
+    """roi (M, C, T, L, L), fg / bg bool / uint8 in the forms of ``masked_median``, read in place -> sums (M, C, T, 2)
+    float64 = {fg sum, bg sum} and counts int32 = {fg count, bg count}: (M, 2) for masks (M, L, L), (M, T', 2) for masks
+    (M, T', L, L) (mg_masked_sums).  ``bg=None``: one mask, its figures in both columns."""
     require_gpu()
     m, c, t, L, _ = roi.shape
+    bg = fg if bg is None else bg
+    n_tm = max(1 if a.dim() == 3 else a.shape[1] for a in (fg, bg))
+    per_time = fg.dim() == 4 or bg.dim() == 4
     sums = torch.empty((m, c, t, 2), dtype=torch.float64, device=roi.device)
-    counts = torch.empty((m, 2), dtype=torch.int32, device=roi.device)
+    counts = torch.empty((m, n_tm, 2), dtype=torch.int32, device=roi.device)
     if m:
-        _call("mg_masked_sums", roi.contiguous().data_ptr(), nat.dtype_code(roi.dtype), fg.contiguous().data_ptr(),
-              bg.contiguous().data_ptr(), m, c * t, L, sums.data_ptr(), counts.data_ptr(), _stream())
-    return sums, counts
+        (fg, fsm, fst), (bg, bsm, bst) = (_mask_view("masked_sums", a, m, t, L) for a in (fg, bg))
+        _call("mg_masked_sums", roi.contiguous().data_ptr(), nat.dtype_code(roi.dtype), fg.data_ptr(), fsm, fst,
+              bg.data_ptr(), bsm, bst, m, c, t, L, sums.data_ptr(), counts.data_ptr(), n_tm, _stream())
+    return sums, counts if per_time else counts[:, 0]

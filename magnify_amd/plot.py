@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from . import hotpath, preprocess, xr_lite
+from ._dataset import device_tensor
 from .xr_lite import DataArray
 
 MAX_LEVEL = hotpath.OVERVIEW_MAX_LEVEL
@@ -86,8 +87,8 @@ def _image(xp):
 
 
 def _marker_var(xp, name, tail):
-    """Variable ``name`` as (mark, time) + tail, marks stacked as the reference does (plot/image.py:55-56); a missing
-    ``time`` counts as size 1.  Views only: nothing is copied."""
+    """Variable ``name`` as a DataArray on (mark, time) + tail, marks stacked as the reference does
+    (plot/image.py:55-56); a missing ``time`` counts as size 1.  Views only: nothing is copied."""
     v = xp.coords[name] if name in xp.coords else xp.data_vars[name]
     if "mark" not in v.dims and "mark_row" in v.dims and "mark_col" in v.dims:
         v = v.transpose("mark_row", "mark_col", ...)
@@ -96,24 +97,17 @@ def _marker_var(xp, name, tail):
     if extra or "mark" not in v.dims:
         raise ValueError(f"plot: {name} must have the dimensions {('mark', 'time') + tail} or a subset, got {v.dims}")
     v = v.transpose("mark", "time", *tail)
-    return v.data if "time" in v.dims else v.expand_dims("time", 1).data
+    return v if "time" in v.dims else v.expand_dims("time", 1)
 
 
 def _has_rois(xp):
     return "roi" in xp and all(k in xp for k in ("fg", "x", "y"))
 
 
-def _mask(xp, name, m, n_t, L, device):
+def _mask(xp, name, m, n_t, L):
     """Coordinate ``name`` as a (M, T, L, L) bool / uint8 device view (stride 0 along a time of size 1).  ``m`` / ``L``
     None: whatever the coordinate has."""
-    a = _marker_var(xp, name, ("roi_y", "roi_x"))
-    if not isinstance(a, torch.Tensor):
-        a = torch.from_numpy(np.ascontiguousarray(np.asarray(a), dtype=np.bool_))
-    if not a.is_cuda:
-        hotpath.require_gpu()
-        a = a.to(device)
-    if a.dtype not in (torch.bool, torch.uint8):
-        a = a != 0
+    a = device_tensor(_marker_var(xp, name, ("roi_y", "roi_x")), ("mark", "time", "roi_y", "roi_x"), as_mask=True)
     if m is None:
         m, L = a.shape[0], a.shape[-1]
         if a.shape[2] != L:
@@ -127,13 +121,13 @@ def _mask(xp, name, m, n_t, L, device):
 
 def _markers(xp, n_t, h, w):
     """(fg (M, T, L, L) device view, origin (M, T, 2) int32 on the host, valid (M, T) bool) of a dataset with ROIs."""
-    fg = _mask(xp, "fg", None, n_t, None, "cuda")
+    fg = _mask(xp, "fg", None, n_t, None)
     m, L = fg.shape[0], fg.shape[-1]
     if L > h or L > w:
         raise ValueError(f"plot: roi windows of length {L} do not fit a {h} x {w} image")
 
     def per_time(name, dtype):
-        a = _marker_var(xp, name, ())
+        a = _marker_var(xp, name, ()).data
         a = a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
         return np.broadcast_to(a.reshape(m, -1) if m else a.reshape(0, 1), (m, n_t)).astype(dtype)
 
@@ -284,7 +278,7 @@ def _roi(xp):
     if isinstance(xp, DataArray) or "roi" not in xp.data_vars:
         raise AttributeError("Dataset must contain 'roi' data variable.")
     has_channel = "channel" in xp.data_vars["roi"].dims
-    data = _marker_var(xp, "roi", ("channel", "roi_y", "roi_x"))  # (mark, time, [channel,] roi_y, roi_x)
+    data = _marker_var(xp, "roi", ("channel", "roi_y", "roi_x")).data  # (mark, time, [channel,] roi_y, roi_x)
     if not isinstance(data, torch.Tensor) or not data.is_cuda:
         data = preprocess.to_device(data)
     data = data.permute(0, 2, 1, 3, 4) if has_channel else data.unsqueeze(1)
@@ -397,7 +391,7 @@ def roishow(xp, level=None, contrast_limits=None, colors=None, overlay="fill", a
         limits = percentile_limits(xp, 0.0, 100.0, source="roi")
     fg = bg = None
     if overlay in ("outline", "fill"):
-        fg, bg = (_mask(xp, name, m, t, L, roi.device) if name in xp else None for name in ("fg", "bg"))
+        fg, bg = (_mask(xp, name, m, t, L) if name in xp else None for name in ("fg", "bg"))
     rgb = hotpath.render_roi_montage(roi, layout, level, limits, cols, fg, bg, overlay, alpha)
     return DataArray(rgb, ("time", "y", "x", "rgb"), name="roishow", attrs=attrs)
 

@@ -11,39 +11,19 @@ import numpy as np
 import torch
 
 from . import hotpath
+from ._dataset import device_tensor
 from .xr_lite import DataArray
 
 
-def _masks(xp, name):
-    m = xp.coords[name].transpose("mark", "time", "roi_y", "roi_x").data
-    if not isinstance(m, torch.Tensor):
-        m = torch.from_numpy(np.ascontiguousarray(m))
-    return m.cuda()
+_ROI_DIMS, _MASK_DIMS = ("mark", "channel", "time", "roi_y", "roi_x"), ("mark", "time", "roi_y", "roi_x")
 
 
 def _sums_counts(xp, mask):
-    """(sums (M, C, T) float64, counts (M, T) int64) of roi under a mask, by the masked-sum kernel (mg_masked_sums):
-    one call when the mask is the same at every timepoint (beads: geometry replicated over time, find.py:585-586),
-    one per timepoint otherwise (chips searched at several timesteps)."""
-    roi = xp.data_vars["roi"].transpose("mark", "channel", "time", "roi_y", "roi_x").data
-    if not isinstance(roi, torch.Tensor):
-        roi = torch.from_numpy(np.ascontiguousarray(roi))
-    roi = roi.cuda()
-    m = _masks(xp, mask)
-    m = m.view(torch.uint8) if m.dtype == torch.bool else m.to(torch.uint8)
-    n_m, n_c, n_t = roi.shape[:3]
-    if n_t == 1 or m.stride(1) == 0:
-        one = m[:, 0].contiguous()
-        sums, cnt = hotpath.masked_sums(roi.contiguous(), one, one)
-        return sums[..., 0], cnt[:, :1].to(torch.int64).expand(n_m, n_t)
-    sums = torch.empty((n_m, n_c, n_t), dtype=torch.float64, device=roi.device)
-    cnt = torch.empty((n_m, n_t), dtype=torch.int64, device=roi.device)
-    for t in range(n_t):
-        one = m[:, t].contiguous()
-        s_t, c_t = hotpath.masked_sums(roi[:, :, t:t + 1].contiguous(), one, one)
-        sums[:, :, t] = s_t[:, :, 0, 0]
-        cnt[:, t] = c_t[:, 0]
-    return sums, cnt
+    """(sums (M, C, T) float64, counts (M, T) int64) of roi under a mask: one call of the masked-sum kernel
+    (mg_masked_sums), which reads the mask of every timepoint where it lies."""
+    roi = device_tensor(xp.data_vars["roi"], _ROI_DIMS)
+    sums, cnt = hotpath.masked_sums(roi, device_tensor(xp.coords[mask], _MASK_DIMS, as_mask=True))
+    return sums[..., 0], cnt[..., 0].to(torch.int64).expand(roi.shape[0], roi.shape[2])
 
 
 def counts(xp, mask="fg"):
@@ -67,9 +47,11 @@ def masked_sum(xp, mask="fg"):
 
 def masked_mean(xp, mask="fg"):
     """roi.where(mask).mean(dim=[roi_y, roi_x]) (README.md:22): sum / count, NaN for an empty mask."""
-    s = masked_sum(xp, mask).data
-    n = counts(xp, mask).data.to(torch.float64)[:, None]
-    return DataArray(s / n, ("mark", "channel", "time"))
+    if xp._cache.get("roi_sums") is None and xp._cache.get("roi_counts") is None:  # no answer yet: one pass gives both
+        s, n = _sums_counts(xp, mask)
+    else:
+        s, n = masked_sum(xp, mask).data, counts(xp, mask).data
+    return DataArray(s / n.to(torch.float64)[:, None], ("mark", "channel", "time"))
 
 
 def masked_median(xp, mask="bg", time=None):
@@ -94,27 +76,16 @@ _MCT = ("mark", "channel", "time")
 
 
 def _roi_and_mask(xp, mask, time):
-    roi = xp.data_vars["roi"].transpose("mark", "channel", "time", "roi_y", "roi_x").data
-    if not isinstance(roi, torch.Tensor):
-        roi = np.ascontiguousarray(roi)
-        if roi.dtype.byteorder not in ("=", "|"):
-            roi = roi.astype(roi.dtype.newbyteorder("="))
-        roi = torch.from_numpy(roi)
+    """``mask``: a coordinate name, or a DataArray on (mark[, time], roi_y, roi_x)."""
+    roi, m = xp.data_vars["roi"], xp.coords[mask] if isinstance(mask, str) else mask
+    if time is not None:  # selected where the data lies: the other timepoints are neither moved nor read
+        one = slice(time, time + 1) if time != -1 else slice(-1, None)
+        roi = roi.isel(time=one)
+        if m.sizes.get("time", 1) != 1:
+            m = m.isel(time=one)
+    roi = device_tensor(roi, _ROI_DIMS)
     hotpath.nat.dtype_code(roi.dtype)  # TypeError for anything but uint8 / uint16 / float32 / float64
-    if isinstance(mask, str):
-        m = _masks(xp, mask)
-    else:  # a DataArray on (mark[, time], roi_y, roi_x)
-        m = mask.transpose(*[d for d in ("mark", "time", "roi_y", "roi_x") if d in mask.dims]).data
-        if not isinstance(m, torch.Tensor):
-            m = torch.from_numpy(np.ascontiguousarray(m))
-        if m.dtype not in (torch.bool, torch.uint8):
-            m = m != 0
-        m = m.cuda()
-    if time is not None:
-        roi = roi[:, :, time:time + 1] if time != -1 else roi[:, :, -1:]
-        if m.dim() == 4 and m.shape[1] != 1:
-            m = m[:, time:time + 1] if time != -1 else m[:, -1:]
-    return roi.cuda(), m
+    return roi, device_tensor(m, _MASK_DIMS, as_mask=True)
 
 
 def masked_stats(xp, mask="fg", q=(), time=None):

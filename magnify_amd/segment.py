@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import _dataset
 from . import _native as nat
 from . import registry
 
@@ -56,35 +57,9 @@ def check_segment(method="otsu", open_radius=1, max_grow=4, bg_guard=2, min_area
 
 
 def channel_index(assay, channel):
-    """Index of ``channel`` -- a name of the ``channel`` coordinate, or an index; None: the first channel.  An unknown
-    name raises ValueError, as the filters' channel lookup does."""
-    if channel is None:
-        return 0
-    names = np.asarray(assay.coords["channel"].values).tolist() if "channel" in assay.coords else None
-    if names is not None and channel in names:
-        return names.index(channel)
-    if isinstance(channel, (int, np.integer)) and not isinstance(channel, (bool, np.bool_)):
-        if not 0 <= channel < assay.sizes["channel"]:
-            raise ValueError(f"channel index {channel} outside [0, {assay.sizes['channel']})")
-        return int(channel)
-    if names is None:
-        raise ValueError(f"{channel!r} is no channel index and the dataset has no channel names")
-    return names.index(channel)
-
-
-def _device_tensor(arr, dims):
-    import torch
-
-    data = arr.transpose(*[d for d in dims if d in arr.dims]).data
-    if not isinstance(data, torch.Tensor):
-        data = np.ascontiguousarray(data)
-        if data.dtype.byteorder not in ("=", "|"):
-            data = data.astype(data.dtype.newbyteorder("="))
-        data = torch.from_numpy(data)
-    data = data.cuda()
-    if "time" in dims and "time" not in arr.dims:  # one mask for all timepoints
-        data = data[:, None].expand(data.shape[0], -1, *data.shape[1:])
-    return data
+    """Index of ``channel`` -- a name of the ``channel`` coordinate, or an index; None: the first channel
+    (``_dataset.channel_index``; an unknown channel is a ValueError and a KeyError)."""
+    return _dataset.channel_index(assay, channel, default=0)
 
 
 @registry.component("segment_rois")
@@ -107,10 +82,9 @@ def segment_rois(assay, method="otsu", channel=None, open_radius=1, max_grow=4, 
         return assay.assign_coords(segmented=(("mark", "time"), np.zeros((0, n_t), dtype=bool)),
                                    seg_threshold=(("mark", "time"), np.zeros((0, n_t), dtype=np.float64)))
     hotpath.require_gpu()
-    roi = _device_tensor(roi_var, roi_dims)
+    roi = _dataset.device_tensor(roi_var, roi_dims)
     old_fg, old_bg = assay.coords["fg"], assay.coords["bg"]
-    fg0, bg0 = (t if t.dtype in (torch.bool, torch.uint8) else t != 0
-                for t in (_device_tensor(old_fg, mask_dims), _device_tensor(old_bg, mask_dims)))
+    fg0, bg0 = (_dataset.device_tensor(a, mask_dims, as_mask=True) for a in (old_fg, old_bg))
     allowed = None
     if "tag" not in assay.coords:
         if all(t.shape[1] == 1 or t.stride(1) == 0 for t in (fg0, bg0)):  # one drawn mask for all timepoints: one union

@@ -160,6 +160,32 @@ def test_beads_roi_contents_and_reductions(mg):
     np.testing.assert_allclose(xp.roi.where(xp.fg).mean(dim=["roi_x", "roi_y"]).values[:, 0, 0], mean)
 
 
+def test_reductions_of_a_host_dataset_take_one_kernel_call_each(mg, monkeypatch):
+    """A Dataset as a file gives it -- a big-endian roi, int8 0 / 1 masks that differ per timepoint, nothing cached --
+    reduces to what NumPy says, and every reduction is ONE call of the masked-sum kernel, whatever the number of
+    timepoints."""
+    rng = np.random.default_rng(5)
+    roi = rng.integers(0, 65536, (4, 2, 3, 9, 9)).astype(">u2")
+    masks = {"fg": (rng.random((4, 3, 9, 9)) > 0.6).astype(np.int8), "bg": (rng.random((4, 3, 9, 9)) > 0.4).astype(np.int8)}
+    masks["bg"][2, 1] = 0  # an empty mask: mean NaN
+    ds = mg.Dataset({"roi": mg.DataArray(roi, ("mark", "channel", "time", "roi_y", "roi_x"))},
+                    coords={k: (("mark", "time", "roi_y", "roi_x"), v) for k, v in masks.items()})
+    assert not ds._cache
+    calls = []
+    kernel = mg.hotpath.masked_sums
+    monkeypatch.setattr(mg.hotpath, "masked_sums", lambda *a, **k: calls.append(1) or kernel(*a, **k))
+    for name, mask in masks.items():
+        want_sum = (roi.astype(np.int64) * mask[:, None]).sum(axis=(-1, -2))
+        want_n = mask.astype(np.int64).sum(axis=(-1, -2))
+        for reduction, want in (("counts", want_n), ("masked_sum", want_sum.astype(np.float64)),
+                                ("masked_mean", want_sum / np.where(want_n > 0, want_n, np.nan)[:, None])):
+            del calls[:]
+            got = getattr(mg.reduce, reduction)(ds, name).values
+            assert len(calls) == 1, (reduction, name, len(calls))
+            np.testing.assert_array_equal(got, want)
+    assert np.isnan(mg.reduce.masked_mean(ds, "bg").values[2, :, 1]).all()
+
+
 def test_flatfield_in_pipeline_matches_oracle(mg):
     from oracle import ref_pipeline as rp
     from synth import noisy_bead_image, vignette
