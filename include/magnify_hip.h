@@ -923,6 +923,53 @@ int mg_render_roi_montage(const void* d_roi, int dtype, int64_t stride_m, int64_
                           int64_t bg_stride_t, const uint8_t* d_fg, int64_t fg_stride_m, int64_t fg_stride_t, int overlay,
                           double alpha, uint8_t* d_out, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Depth stacks (depth.py, the `project_depth` component; not in the reference, which refuses a Z axis; DESIGN.md
+ * "Depth stacks"; tests/depth_ref.py restates every rule).  The input of all three entries is one contiguous block
+ * (n, z, h, w) of `dtype`: n focal series (every channel x time x tile) of z slices.  The focus measure is the modified
+ * Laplacian ML(y, x) = |2c - l - r| + |2c - u - d| of the pixel c and its left / right / upper / lower neighbours,
+ * a neighbour outside the plane being the edge pixel (np.pad(mode="edge")).  Integer pixels: int32 arithmetic, exact.
+ * Float pixels: float64, every operation rounded on its own, fabs((2 * c - l) - r) + fabs((2 * c - u) - d).
+ * Every entry: MG_EINVAL, with nothing launched, for a null or misaligned pointer, an unknown dtype, n, h or w < 0,
+ * z < 1; MG_OK with nothing launched (and nothing written) when n, h or w is 0.  No allocation, no synchronisation.
+ * ---------------------------------------------------------------------------------- */
+#define MG_DEPTH_MAX 0
+#define MG_DEPTH_MEAN 1
+#define MG_DEPTH_PICK 2
+#define MG_DEPTH_TILE 32  /* mg_depth_fuse: a workgroup's output tile is MG_DEPTH_TILE x MG_DEPTH_TILE pixels */
+#define MG_DEPTH_MAX_K 15
+#define MG_DEPTH_MAX_Z 255
+
+/* d_dst (n, h, w) of `dtype` (a buffer other than d_src) = the fold of every stack over z.
+ *   MG_DEPTH_MAX: m = slice 0; for z = 1, 2, ...: m = s where s > m; for floats a NaN in any slice gives NaN (the first
+ *     one met), and of equal values (-0.0 and 0.0) the first stays.
+ *   MG_DEPTH_MEAN: integer pixels: rint(sum / z) in float64 with the exact integer sum (half to even); float pixels: a
+ *     float64 accumulator that starts at 0.0, slices added in the order z = 0, 1, ..., then / z, then the cast.
+ *   MG_DEPTH_PICK: d_dst[i] = d_src[i, d_pick[i]]; d_pick is int32 (n) on the device (null otherwise).  The CALLER
+ *     checks 0 <= d_pick[i] < z before the call (depth.project does); the kernel clamps what it reads, so that a bad
+ *     index reads a wrong slice and no foreign memory.
+ * One launch; every input byte is read once (PICK: the chosen slices only).  MG_EINVAL also for an unknown method and
+ * a null d_pick with MG_DEPTH_PICK. */
+int mg_depth_project(const void* d_src, void* d_dst, int dtype, int64_t n, int z, int h, int w, int method,
+                     const int32_t* d_pick, void* stream);
+
+/* d_totals (n, z), 8 bytes per entry, 8-byte aligned: the sum of ML over all pixels of slice (i, z) -- uint64 and exact
+ * for MG_U8 / MG_U16, float64 for MG_F32 / MG_F64 (a sum of float64 terms in no defined order: compare by tolerance).
+ * The entry zeroes d_totals itself; one 64-bit atomic per workgroup and slice. */
+int mg_depth_focus_totals(const void* d_src, int dtype, int64_t n, int z, int h, int w, void* d_totals, void* stream);
+
+/* The per-pixel pick of the sharpest slice, z <= MG_DEPTH_MAX_Z, window half-width 1 <= k <= MG_DEPTH_MAX_K.  The
+ * measure of pixel (y, x) in a slice is the sum of ML over the (2k + 1)^2 window centred on it, window positions
+ * outside the plane left out.  Integer pixels: uint32 sums, exact in any order (at most 4 * 65535 * 31^2 < 2^32).  Float
+ * pixels: float64, in this order: per window row a sum that starts at 0.0 and adds the row's 2k + 1 values left to
+ * right, then a sum that starts at 0.0 and adds the 2k + 1 row sums top to bottom (a position left out adds nothing).
+ * The winner is found with best = -inf, winner = 0, and for z = 0, 1, ...: measure > best makes z the winner -- the
+ * first of equal measures wins, an all-equal stack gives 0, a NaN measure never wins.  d_dst (n, h, w) of `dtype` (a
+ * buffer other than d_src) receives the winner's pixel, d_index (n, h, w) uint8, if not null, its z.  One launch;
+ * MG_EINVAL also for z > MG_DEPTH_MAX_Z and k outside 1 .. MG_DEPTH_MAX_K. */
+int mg_depth_fuse(const void* d_src, int dtype, int64_t n, int z, int h, int w, int k, void* d_dst, uint8_t* d_index,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,10 +8,11 @@ attach an alternative labelling ``name`` to dimension ``key``; ``*`` / ``?`` / `
 Files are TIFFs read with this build's own TIFF layer (``magnify_amd.tiff``: classic and BigTIFF, strips or tiles,
 the usual lossless codecs): one 2-D page per file, or a series whose axes the file itself names -- OME-XML
 (``DimensionOrder`` / ``SizeC`` / ``SizeT``, ``Plane DeltaT``), MicroManager's summary (``StartTime``, ``ChNames``) or
-an ImageJ hyperstack -- with the reference's rules (reader.py:194-258): a Z axis is refused, the position axis ``R``
-is ignored (tiles come from the path), X and Y must be there, a dimension named both in the path and in the file is
-an error.  ``read_tiffs`` fills one host array per assay page by page; SURVEY 8f N2's streaming half is
-``iter_time_chunks``: the series chunk by chunk of the time axis into page-locked blocks, one page decoded at a time
+an ImageJ hyperstack -- with the reference's rules (reader.py:194-258): a Z axis is refused (unless the reader is
+made with ``depth=True``: the pages then keep a ``depth`` axis, after ``time``, for ``project_depth`` to fold), the
+position axis ``R`` is ignored (tiles come from the path), X and Y must be there, a dimension named both in the path
+and in the file is an error.  ``read_tiffs`` fills one host array per assay page by page; SURVEY 8f N2's streaming
+half is ``iter_time_chunks``: the series chunk by chunk of the time axis into page-locked blocks, one page decoded at a time
 (the reference maps every page to its own dask block, reader.py:265-292), feeding ``stack.process_stream``.
 """
 from __future__ import annotations
@@ -88,10 +89,11 @@ def extract_paths(pattern, **keys):
 _LETTER_TO_DIM = {"C": "channel", "T": "time", "Z": "depth", "Y": "tile_y", "X": "tile_x", "R": "tile_pos"}  # reader.py:196-203
 
 
-def series_layout(path, need_times=True, need_channels=True):
+def series_layout(path, need_times=True, need_channels=True, depth=False):
     """What the reference learns from the first file of an assay (reader.py:189-258): the dimensions inside the file
     (position axis dropped), the shape of the axes in front of a page, page size and dtype, and -- when the path does
     not give them -- the timepoints (MicroManager ``StartTime`` + OME ``Plane DeltaT``) and channel names (``ChNames``).
+    ``depth``: keep a Z axis as dimension ``depth`` (not in the reference) where the default refuses the file.
     -> dict(dims, inner, page, dtype, times, channels)."""
     from . import tiff
 
@@ -112,10 +114,16 @@ def series_layout(path, need_times=True, need_channels=True):
                 if not all(pl.get("DeltaTUnit") == "ms" for pl in planes):
                     raise ValueError(f"{path}: OME Plane DeltaT in a unit other than ms")
                 times = [start + datetime.timedelta(milliseconds=float(pl.get("DeltaT"))) for pl in planes]
-                stride = inner[dims.index("channel")] if "channel" in dims else 1
-                if len(times) % stride:
-                    raise ValueError(f"{path}: {len(times)} OME planes for {stride} channels")
-                times = times[::stride]
+                if depth and "depth" in dims:
+                    # planes are listed in page order: the first page of every timepoint (pages run in C order)
+                    k = dims.index("time")
+                    step = int(np.prod(inner[k + 1:len(dims) - 2], dtype=np.int64))
+                    times = times[::step][:inner[k]] if step * inner[k] <= len(times) else None
+                else:
+                    stride = inner[dims.index("channel")] if "channel" in dims else 1
+                    if len(times) % stride:
+                        raise ValueError(f"{path}: {len(times)} OME planes for {stride} channels")
+                    times = times[::stride]
             else:
                 times = [start]
         if need_channels and "ChNames" in summary:
@@ -123,7 +131,7 @@ def series_layout(path, need_times=True, need_channels=True):
         if "tile_pos" in dims:  # positions are separate files: the user names tiles in the search path (reader.py:249-254)
             k = dims.index("tile_pos")
             inner, dims = inner[:k] + inner[k + 1:], dims[:k] + dims[k + 1:]
-        if "depth" in dims:
+        if "depth" in dims and not depth:
             raise ValueError("tiff files with a Z dimension are not yet supported.")
         if "tile_y" not in dims or "tile_x" not in dims:
             raise ValueError("tiff files must contain an X and Y dimension.")
@@ -132,9 +140,10 @@ def series_layout(path, need_times=True, need_channels=True):
                 "channels": channels}
 
 
-def read_tiffs(xp_dict, name, meta_dict):
+def read_tiffs(xp_dict, name, meta_dict, depth=False):
     """reader.py:163-324: one Dataset with ``tile`` over the dimensions found in the paths and inside
-    the files, in the standard order (channel, time, tile_row, tile_col, tile_y, tile_x)."""
+    the files, in the standard order (channel, time, tile_row, tile_col, tile_y, tile_x); with ``depth`` a Z axis inside
+    the files is kept as ``depth``, after ``time``."""
     from . import tiff
 
     channel_idx, time_idx, row_idx, col_idx = (sorted(set(i)) for i in zip(*xp_dict.keys()))
@@ -144,7 +153,7 @@ def read_tiffs(xp_dict, name, meta_dict):
             in_path.append(dim)
             outer += (len(values),)
     files = [p for _, p in sorted(xp_dict.items())]
-    lay = series_layout(files[0], need_times="time" not in in_path, need_channels="channel" not in in_path)
+    lay = series_layout(files[0], need_times="time" not in in_path, need_channels="channel" not in in_path, depth=depth)
     in_file, inner, (ty, tx) = lay["dims"], lay["inner"], lay["page"]
     if set(in_file) & set(in_path):
         raise ValueError("Dimensions specified in the path names and inside the tiff file overlap.")
@@ -166,7 +175,7 @@ def read_tiffs(xp_dict, name, meta_dict):
     if times is not None and ("time" not in dims or len(times) == tiles.shape[dims.index("time")]):
         coords["time"] = [int(t.timestamp()) if isinstance(t, datetime.datetime) else t for t in times]  # seconds
     xp = xr_lite.Dataset({"tile": xr_lite.DataArray(tiles, dims)}, coords=coords, attrs={"name": name})
-    order = [d for d in ("channel", "time", "tile_row", "tile_col", "tile_y", "tile_x") if d in xp.tile.dims]
+    order = [d for d in ("channel", "time", "depth", "tile_row", "tile_col", "tile_y", "tile_x") if d in xp.tile.dims]
     xp = xp.transpose(*order)
     for (meta_name, dim), table in meta_dict.items():
         keys = time_idx if dim == "time" else {"channel": channel_idx, "row": row_idx, "col": col_idx}.get(dim, [])
@@ -177,6 +186,11 @@ def read_tiffs(xp_dict, name, meta_dict):
 
 
 class Reader:
+    def __init__(self, depth=False):
+        """``depth``: keep the Z axis of a file as dimension ``depth`` (for ``project_depth``); False refuses such a
+        file, as the reference does."""
+        self.depth = bool(depth)
+
     def __call__(self, data):
         single = isinstance(data, (str, bytes, os.PathLike, xr_lite.DataArray, xr_lite.Dataset)) or \
             type(data).__module__.startswith("xarray")
@@ -192,11 +206,11 @@ class Reader:
             for xp_name in sorted({k[0] for k in path_dict}, key=natural_sort_key):
                 xp_dict = {tuple(-1 if x is None else x for x in k[1:]): v for k, v in path_dict.items()
                            if k[0] == xp_name}
-                yield read_tiffs(xp_dict, name=xp_name, meta_dict=meta_dict)
+                yield read_tiffs(xp_dict, name=xp_name, meta_dict=meta_dict, depth=self.depth)
 
     @registry.readers.register("read")
-    def make():
-        return Reader()
+    def make(depth=False):
+        return Reader(depth=depth)
 
 
 class _BlockPool:

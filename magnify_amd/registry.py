@@ -93,6 +93,19 @@ def _add_segment(pipe, segment, channel, open_radius, max_grow, bg_guard, roi_le
                   bg_guard=bg_guard)
 
 
+def _add_depth(pipe, depth, depth_window):
+    """``depth=`` of the pipelines ("max", "mean", "sharpest" or "focus"; not in the reference, which refuses a Z
+    axis): the reader keeps the files' Z axis as ``depth`` and ``project_depth`` folds it first, before
+    ``standardize_format``; its settings are checked now, not at the first assay.  None changes nothing."""
+    if depth is None:
+        return
+    from .depth import check_depth
+
+    check_depth(depth, depth_window)
+    pipe.reader = readers.get("read")(depth=True)
+    pipe.add_pipe("project_depth", first=True, method=depth, window=depth_window)
+
+
 def microfluidic_chip(data, shape=(8, 8), pinlist=None, blank=None, overlap=102, rotation=0, row_dist=375 / 1.61,
                       col_dist=400 / 1.61, chip_type=None, min_button_diameter=8, max_button_diameter=30,
                       chamber_diameter=60, top_chamber=None, left_chamber=None, low_edge_quantile=0.1,
@@ -100,7 +113,8 @@ def microfluidic_chip(data, shape=(8, 8), pinlist=None, blank=None, overlap=102,
                       progress_bar=False, search_timestep=0, search_channel=None, roi_only=False, drop_tiles=True,
                       interactive=False, blend=None,
                       register=None, max_shift=8, register_channel=None,
-                      segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2):
+                      segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2,
+                      depth=None, depth_window=9):
     """registry.py:32-110 (``blend``: ``stitch``'s overlap blending; ``register``, ``max_shift``, ``register_channel``:
     its tile registration -- neither is in the reference)."""
     kw = dict(locals())
@@ -115,7 +129,8 @@ def microfluidic_chip_pipe(shape=(8, 8), pinlist=None, blank=None, overlap=102, 
                            roi_length=None, progress_bar=False, search_timestep=0, search_channel=None,
                            roi_only=False, drop_tiles=True, interactive=False, blend=None,
                            register=None, max_shift=8, register_channel=None,
-                           segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2):
+                           segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2,
+                           depth=None, depth_window=9):
     """registry.py:196-271."""
     if chip_type is not None:
         if chip_type == "minichip":
@@ -128,6 +143,7 @@ def microfluidic_chip_pipe(shape=(8, 8), pinlist=None, blank=None, overlap=102, 
             raise ValueError(f"Invalid chip type: {chip_type}. Must be one of ['pc', 'ps', 'minichip']")
     pipe = Pipeline("read")
     pipe.add_pipe("standardize_format")
+    _add_depth(pipe, depth, depth_window)
     pipe.add_pipe("identify_buttons", shape=shape, pinlist=pinlist, blank=blank)
     pipe.add_pipe("stitch", overlap=overlap, blend=blend, register=register, max_shift=max_shift,
                   register_channel=register_channel)
@@ -150,7 +166,8 @@ def mrbles(data, spectra, codes, flatfield=1.0, darkfield=0.0, overlap=102, min_
            register=None, max_shift=8, register_channel=None,
            track=None, max_drift=8, track_min_score=0.5, track_channel=None, track_patch=None,
            stage_drift=None,
-           segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2):
+           segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2,
+           depth=None, depth_window=9):
     """registry.py:274-399."""
     kw = dict(locals())
     kw.pop("data")
@@ -163,10 +180,12 @@ def mrbles_pipe(spectra, codes, flatfield=1.0, darkfield=0.0, overlap=102, min_b
                 register=None, max_shift=8, register_channel=None,
                 track=None, max_drift=8, track_min_score=0.5, track_channel=None, track_patch=None,
                 stage_drift=None,
-                segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2):
+                segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2,
+                depth=None, depth_window=9):
     """registry.py:402-451."""
     pipe = Pipeline("read")
     pipe.add_pipe("standardize_format")
+    _add_depth(pipe, depth, depth_window)
     pipe.add_pipe("flatfield_correct", flatfield=flatfield, darkfield=darkfield)
     pipe.add_pipe("stitch", overlap=overlap, blend=blend, register=register, max_shift=max_shift,
                   register_channel=register_channel)
@@ -188,7 +207,8 @@ def beads(data, flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=10,
           register=None, max_shift=8, register_channel=None,
           track=None, max_drift=8, track_min_score=0.5, track_channel=None, track_patch=None,
           stage_drift=None,
-          segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2):
+          segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2,
+          depth=None, depth_window=9):
     """registry.py:454-565."""
     kw = dict(locals())
     kw.pop("data")
@@ -201,10 +221,12 @@ def beads_pipe(flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=5, m
                register=None, max_shift=8, register_channel=None,
                track=None, max_drift=8, track_min_score=0.5, track_channel=None, track_patch=None,
                stage_drift=None,
-               segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2):
+               segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2,
+               depth=None, depth_window=9):
     """registry.py:568-612 (note the 5/25 defaults here versus 10/50 in ``beads``)."""
     pipe = Pipeline("read")
     pipe.add_pipe("standardize_format")
+    _add_depth(pipe, depth, depth_window)
     pipe.add_pipe("flatfield_correct", flatfield=flatfield, darkfield=darkfield)
     pipe.add_pipe("stitch", overlap=overlap, blend=blend, register=register, max_shift=max_shift,
                   register_channel=register_channel)
@@ -220,17 +242,19 @@ def beads_pipe(flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=5, m
 
 
 def image(data, overlap=102, rotation=0, roi_only=False, drop_tiles=True, blend=None,
-          register=None, max_shift=8, register_channel=None):
+          register=None, max_shift=8, register_channel=None, depth=None, depth_window=9):
     """registry.py:615-669."""
     return image_pipe(overlap=overlap, rotation=rotation, roi_only=roi_only, drop_tiles=drop_tiles, blend=blend,
-                      register=register, max_shift=max_shift, register_channel=register_channel)(data=data)
+                      register=register, max_shift=max_shift, register_channel=register_channel, depth=depth,
+                      depth_window=depth_window)(data=data)
 
 
 def image_pipe(overlap=102, rotation=0, roi_only=False, drop_tiles=True, blend=None,
-               register=None, max_shift=8, register_channel=None):
+               register=None, max_shift=8, register_channel=None, depth=None, depth_window=9):
     """registry.py:672-693."""
     pipe = Pipeline("read")
     pipe.add_pipe("standardize_format")
+    _add_depth(pipe, depth, depth_window)
     pipe.add_pipe("stitch", overlap=overlap, blend=blend, register=register, max_shift=max_shift,
                   register_channel=register_channel)
     pipe.add_pipe("rotate", rotation=rotation)
