@@ -970,6 +970,48 @@ int mg_depth_focus_totals(const void* d_src, int dtype, int64_t n, int z, int h,
 int mg_depth_fuse(const void* d_src, int dtype, int64_t n, int z, int h, int w, int k, void* d_dst, uint8_t* d_index,
                   void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Hot pixels (despeckle.py, the `remove_outliers` component; not in the reference; DESIGN.md "Despeckle";
+ * tests/despeckle_ref.py restates every rule).  The input of both entries is one contiguous block (n, h, w) of `dtype`:
+ * n planes.  With the window half-width k (1 .. MG_DESPECKLE_MAX_K), the WINDOW MEDIAN m(y, x) of a plane P is the
+ * middle element (index ((2k + 1)^2 - 1) / 2) of the ascending sort of the (2k + 1)^2 values P[clamp(y + dy, 0, h - 1),
+ * clamp(x + dx, 0, w - 1)], |dy|, |dx| <= k: scipy.ndimage.median_filter(P, 2k + 1, mode="nearest").  It is one of
+ * the window's pixels, exact in every dtype.  Floats sort as numpy.sort sorts them, every NaN after +inf: the median
+ * is NaN only when more than half of the window is; -0.0 and 0.0 are not told apart (either may be returned).
+ * The OUTLIER TEST of a pixel, with d = (double)P[y, x] - (double)m(y, x) and the threshold in pixel units:
+ *   MG_OUTLIER_BRIGHT: d > threshold;  MG_OUTLIER_DARK: -d > threshold;  MG_OUTLIER_BOTH: either;
+ *   MG_OUTLIER_ALL: always true (the plain median filter).
+ * The inequality is strict (at threshold 0 a pixel equal to its median passes no test) and false whenever d is NaN
+ * (a NaN pixel, a NaN median, inf - inf): such a pixel is kept.
+ * Both entries: MG_EINVAL, with nothing launched, for a null or misaligned pointer, an unknown dtype or `which`, n, h
+ * or w < 0, h above 2^30 or w above 2^20, k outside 1 .. MG_DESPECKLE_MAX_K, a negative or NaN threshold where it is used; MG_OK
+ * with nothing launched (and nothing written) when n, h or w is 0.  A workgroup takes one MG_DESPECKLE_TILE x
+ * MG_DESPECKLE_TILE output tile of a plane at a time, the tile and its halo of k in LDS; the plane index is not bounded by a grid
+ * dimension and every offset into the block is 64-bit.  One kernel launch behind the clearing of the counters; no
+ * allocation, no synchronisation.
+ * ---------------------------------------------------------------------------------- */
+#define MG_OUTLIER_BRIGHT 0
+#define MG_OUTLIER_DARK 1
+#define MG_OUTLIER_BOTH 2
+#define MG_OUTLIER_ALL 3
+#define MG_DESPECKLE_MAX_K 2
+#define MG_DESPECKLE_TILE 64  /* a workgroup's output tile is MG_DESPECKLE_TILE x MG_DESPECKLE_TILE pixels */
+
+/* d_dst (n, h, w) of `dtype` (a buffer other than d_src): d_dst[i, y, x] = m(y, x) of plane i where the CONDITION holds,
+ * else d_src[i, y, x] bit for bit.  The condition is the outlier test `which` with `threshold`, or, with a defect map
+ * d_defects (uint8 (h, w), shared by all planes; may be null), d_defects[y, x] != 0 -- `which` (still a known one) and
+ * `threshold` are then ignored, as `threshold` is with MG_OUTLIER_ALL.  d_counts (n) int64, 8-byte aligned, may be
+ * null: the number of pixels of every plane for which the condition held; the entry zeroes it itself, one 64-bit
+ * integer atomic per workgroup and plane (integers: exact in any order). */
+int mg_despeckle_planes(const void* d_src, void* d_dst, int dtype, int64_t n, int h, int w, int k, int which,
+                        double threshold, const uint8_t* d_defects, int64_t* d_counts, void* stream);
+
+/* d_votes (h, w) int32: the number of the n planes in which pixel (y, x) passes the outlier test (BRIGHT, DARK or
+ * BOTH; MG_EINVAL for MG_OUTLIER_ALL).  The entry zeroes d_votes itself; one int32 atomic per pixel that passes, so the
+ * table is exact in any order.  n > 2^31 - 1 is MG_EINVAL (a vote count is int32). */
+int mg_outlier_votes(const void* d_src, int dtype, int64_t n, int h, int w, int k, int which, double threshold,
+                     int32_t* d_votes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -106,6 +106,19 @@ def _add_depth(pipe, depth, depth_window):
     pipe.add_pipe("project_depth", first=True, method=depth, window=depth_window)
 
 
+def _add_despeckle(pipe, despeckle, radius, which, scope):
+    """``despeckle=`` of the pipelines (a threshold in pixel units; not in the reference): ``remove_outliers`` directly
+    after ``standardize_format`` -- on the raw tiles, before the flat-field maxima, the stitch and the finders -- its
+    settings checked now, not at the first assay.  None adds nothing."""
+    if despeckle is None:
+        return
+    from .despeckle import check_despeckle
+
+    check_despeckle(despeckle, radius, which, scope)
+    pipe.add_pipe("remove_outliers", after="standardize_format", threshold=despeckle, radius=radius, which=which,
+                  scope=scope)
+
+
 def microfluidic_chip(data, shape=(8, 8), pinlist=None, blank=None, overlap=102, rotation=0, row_dist=375 / 1.61,
                       col_dist=400 / 1.61, chip_type=None, min_button_diameter=8, max_button_diameter=30,
                       chamber_diameter=60, top_chamber=None, left_chamber=None, low_edge_quantile=0.1,
@@ -114,7 +127,8 @@ def microfluidic_chip(data, shape=(8, 8), pinlist=None, blank=None, overlap=102,
                       interactive=False, blend=None,
                       register=None, max_shift=8, register_channel=None,
                       segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2,
-                      depth=None, depth_window=9):
+                      depth=None, depth_window=9,
+                      despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane"):
     """registry.py:32-110 (``blend``: ``stitch``'s overlap blending; ``register``, ``max_shift``, ``register_channel``:
     its tile registration -- neither is in the reference)."""
     kw = dict(locals())
@@ -130,7 +144,8 @@ def microfluidic_chip_pipe(shape=(8, 8), pinlist=None, blank=None, overlap=102, 
                            roi_only=False, drop_tiles=True, interactive=False, blend=None,
                            register=None, max_shift=8, register_channel=None,
                            segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2,
-                           depth=None, depth_window=9):
+                           depth=None, depth_window=9,
+                           despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane"):
     """registry.py:196-271."""
     if chip_type is not None:
         if chip_type == "minichip":
@@ -144,6 +159,7 @@ def microfluidic_chip_pipe(shape=(8, 8), pinlist=None, blank=None, overlap=102, 
     pipe = Pipeline("read")
     pipe.add_pipe("standardize_format")
     _add_depth(pipe, depth, depth_window)
+    _add_despeckle(pipe, despeckle, despeckle_radius, despeckle_which, despeckle_scope)
     pipe.add_pipe("identify_buttons", shape=shape, pinlist=pinlist, blank=blank)
     pipe.add_pipe("stitch", overlap=overlap, blend=blend, register=register, max_shift=max_shift,
                   register_channel=register_channel)
@@ -167,7 +183,8 @@ def mrbles(data, spectra, codes, flatfield=1.0, darkfield=0.0, overlap=102, min_
            track=None, max_drift=8, track_min_score=0.5, track_channel=None, track_patch=None,
            stage_drift=None,
            segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2,
-           depth=None, depth_window=9):
+           depth=None, depth_window=9,
+           despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane"):
     """registry.py:274-399."""
     kw = dict(locals())
     kw.pop("data")
@@ -181,11 +198,13 @@ def mrbles_pipe(spectra, codes, flatfield=1.0, darkfield=0.0, overlap=102, min_b
                 track=None, max_drift=8, track_min_score=0.5, track_channel=None, track_patch=None,
                 stage_drift=None,
                 segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2,
-                depth=None, depth_window=9):
+                depth=None, depth_window=9,
+                despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane"):
     """registry.py:402-451."""
     pipe = Pipeline("read")
     pipe.add_pipe("standardize_format")
     _add_depth(pipe, depth, depth_window)
+    _add_despeckle(pipe, despeckle, despeckle_radius, despeckle_which, despeckle_scope)
     pipe.add_pipe("flatfield_correct", flatfield=flatfield, darkfield=darkfield)
     pipe.add_pipe("stitch", overlap=overlap, blend=blend, register=register, max_shift=max_shift,
                   register_channel=register_channel)
@@ -208,7 +227,8 @@ def beads(data, flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=10,
           track=None, max_drift=8, track_min_score=0.5, track_channel=None, track_patch=None,
           stage_drift=None,
           segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2,
-          depth=None, depth_window=9):
+          depth=None, depth_window=9,
+          despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane"):
     """registry.py:454-565."""
     kw = dict(locals())
     kw.pop("data")
@@ -222,11 +242,13 @@ def beads_pipe(flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=5, m
                track=None, max_drift=8, track_min_score=0.5, track_channel=None, track_patch=None,
                stage_drift=None,
                segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2,
-               depth=None, depth_window=9):
+               depth=None, depth_window=9,
+               despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane"):
     """registry.py:568-612 (note the 5/25 defaults here versus 10/50 in ``beads``)."""
     pipe = Pipeline("read")
     pipe.add_pipe("standardize_format")
     _add_depth(pipe, depth, depth_window)
+    _add_despeckle(pipe, despeckle, despeckle_radius, despeckle_which, despeckle_scope)
     pipe.add_pipe("flatfield_correct", flatfield=flatfield, darkfield=darkfield)
     pipe.add_pipe("stitch", overlap=overlap, blend=blend, register=register, max_shift=max_shift,
                   register_channel=register_channel)
@@ -242,19 +264,23 @@ def beads_pipe(flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=5, m
 
 
 def image(data, overlap=102, rotation=0, roi_only=False, drop_tiles=True, blend=None,
-          register=None, max_shift=8, register_channel=None, depth=None, depth_window=9):
+          register=None, max_shift=8, register_channel=None, depth=None, depth_window=9,
+          despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane"):
     """registry.py:615-669."""
     return image_pipe(overlap=overlap, rotation=rotation, roi_only=roi_only, drop_tiles=drop_tiles, blend=blend,
                       register=register, max_shift=max_shift, register_channel=register_channel, depth=depth,
-                      depth_window=depth_window)(data=data)
+                      depth_window=depth_window, despeckle=despeckle, despeckle_radius=despeckle_radius,
+                      despeckle_which=despeckle_which, despeckle_scope=despeckle_scope)(data=data)
 
 
 def image_pipe(overlap=102, rotation=0, roi_only=False, drop_tiles=True, blend=None,
-               register=None, max_shift=8, register_channel=None, depth=None, depth_window=9):
+               register=None, max_shift=8, register_channel=None, depth=None, depth_window=9,
+               despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane"):
     """registry.py:672-693."""
     pipe = Pipeline("read")
     pipe.add_pipe("standardize_format")
     _add_depth(pipe, depth, depth_window)
+    _add_despeckle(pipe, despeckle, despeckle_radius, despeckle_which, despeckle_scope)
     pipe.add_pipe("stitch", overlap=overlap, blend=blend, register=register, max_shift=max_shift,
                   register_channel=register_channel)
     pipe.add_pipe("rotate", rotation=rotation)
