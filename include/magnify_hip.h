@@ -376,6 +376,8 @@ int mg_edge_thresholds_window(const uint32_t* d_hist_win, int n_planes, int pass
  * allocates them (the words inside the image are overwritten by every call). */
 int mg_canny_nms(const uint8_t* d_blur, int n_planes, int h, int w, const int32_t* d_thresh, uint32_t* d_weak,
                  uint32_t* d_strong, uint32_t* d_class, int64_t words_per_plane, void* stream);
+/* How mg_canny_nms cuts an (aligned) image of width w: columns per wave strip, rows per wave, rows per workgroup. */
+int mg_canny_nms_strips(int w, int* strip_w, int* wave_rows, int* group_rows);
 
 /* One sweep of 8-connected hysteresis, bit-parallel on the bitmaps: every 256 x 256 tile grows its strong set into
  * its weak set to a fixed point in LDS (halo from global memory) and ORs the new bits into d_strong.  Where that

@@ -6,9 +6,11 @@
 //   K4 hysteresis, bit-parallel in LDS, active tiles only                (bits only)
 //   K5 grid_array from the strong bitmap, K6 gradient angle per edge pixel
 //
-// Stencil kernels stage a 256 x 64 tile (+halo, BORDER_REFLECT_101) through LDS with 16-byte
-// loads; every lane owns 4 adjacent pixels (one dword) of 16 rows.  Integer arithmetic throughout:
-// bit-exact against the oracle.  Roofline: HBM.
+// The tile kernels (k_u8_blur, k_scharr_hist<false>, k_canny_nms) stage a 256 x 64 tile (+halo,
+// BORDER_REFLECT_101) through LDS with 16-byte loads; every lane owns 4 adjacent pixels (one dword) of
+// 16 rows.  The strip walks (k_blur_hist, k_canny_nms_strips: w % 4 == 0) have no tile: a wave walks down
+// 64 rows, a lane loads its dword of a row into registers, neighbours by whole-wave DPP shifts.  Integer
+// arithmetic throughout: bit-exact against the oracle.  Roofline: HBM, vector issue for K3.
 #include <math.h>
 #include <stdlib.h>
 
@@ -219,6 +221,14 @@ __device__ __forceinline__ uint32_t wave_from_left(uint32_t v) {
 }
 __device__ __forceinline__ uint32_t wave_from_right(uint32_t v) {
   return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x130, 0xF, 0xF, false);
+}
+
+// The same shifts where the lane without a neighbour gets its own `fill` instead of 0.
+__device__ __forceinline__ uint32_t wave_from_left(uint32_t v, uint32_t fill) {
+  return (uint32_t)__builtin_amdgcn_update_dpp((int)fill, (int)v, 0x138, 0xF, 0xF, false);
+}
+__device__ __forceinline__ uint32_t wave_from_right(uint32_t v, uint32_t fill) {
+  return (uint32_t)__builtin_amdgcn_update_dpp((int)fill, (int)v, 0x130, 0xF, 0xF, false);
 }
 
 // Scharr gradients of 2 (NP - 1) adjacent pixels from three rows a, b, c given as NP pixel PAIRS, the first pair
@@ -858,6 +868,76 @@ __device__ __forceinline__ uint32_t or_reduce8(uint32_t v) {
 }
 
 // ---- K3: Canny non-maximum suppression + double threshold -> weak / strong bitmaps --------------
+// One image row of decisions, shared by the two kernels below.  A lane holds its four pixels' magnitudes in columns
+// 1 .. 4 of three magnitude rows mg[0 .. 2] = image rows yo - 1, yo, yo + 1 (columns 0 and 5: its neighbours' nearest;
+// zero outside the image) and the row's gradients xy[q] = (dx | dy << 16).  Bit q of a result is pixel q.
+// Every decision is a per-lane boolean = a wave mask in scalar registers: the compares write the masks, the logic
+// runs on the scalar unit, and a plane's bit enters its accumulator as the carry-in of ONE v_addc (v = 2 v + bit).
+// No value selects: all four direction tests are evaluated and the gradient direction picks the result.  (The
+// select-chain version spent two thirds of its instructions on v_cndmask / shift / or.)
+struct NmsBits {
+  uint32_t wb, sb, cb0, cb1, cb2;  // weak, strong, orientation planes c0, c1, c2
+};
+// up[q] = "pixel q of `row` is greater than the pixel above it": what nms_row wants for its first row.
+__device__ __forceinline__ void nms_rising(const int (&above)[6], const int (&row)[6], uint64_t (&up)[4]) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) up[q] = __ballot(row[q + 1] > above[q + 1]);
+}
+// `up` comes in for row yo and goes out for row yo + 1: m >= below is the complement of below > m, which is the
+// next row's m > above; likewise m >= right is the complement of the right pixel's m > left (integers: exact).  The
+// diagonal tests are strict on both sides and do not pair up.  `inside`: the pixels inside the image row.
+__device__ __forceinline__ NmsBits nms_row(const int (&mg)[3][6], const uint32_t (&xy)[4], int low, int high,
+                                           const uint64_t (&inside)[4], uint64_t (&up)[4]) {
+  constexpr int TG22 = 13573;  // tan(22.5 deg) in Q15; tan(67.5 deg) = TG22 + 2 in Q15
+  NmsBits o{0u, 0u, 0u, 0u, 0u};
+  uint64_t gt[5], dn[4];  // column k + 1 > column k of the row; the row below > the row
+#pragma unroll
+  for (int k = 0; k < 5; ++k) gt[k] = __ballot(mg[1][k + 1] > mg[1][k]);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) dn[q] = __ballot(mg[2][q + 1] > mg[1][q + 1]);
+#pragma unroll
+  for (int q = 3; q >= 0; --q) {
+    const int m = mg[1][q + 1];
+    // (|dx|, |dy|) by packed 16-bit arithmetic; x << 16 is the packed word << 16
+    const s2 g = __builtin_bit_cast(s2, xy[q]);
+    const uint32_t au = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(g, (s2)(0) - g));
+    const int x = (int)(au & 0xFFFFu), ay = (int)(au >> 16);
+    const int y = ay << 15, tg22x = __mul24(x, TG22), tg67x = tg22x + (int)(au << 16);
+    const uint64_t horiz = __ballot(y < tg22x);
+    const uint64_t vert = __ballot(y > tg67x) & ~horiz;
+    // diagonal: s = -1 where the signs differ
+    const uint64_t neg = __ballot((int16_t)(xy[q] & 0xFFFFu) < 0) ^ __ballot((int)xy[q] < 0);
+    // > towards the previous pixel; >= towards the next one on the axes, > on the diagonals
+    const uint64_t ok_h = gt[q] & ~gt[q + 1];
+    const uint64_t ok_v = up[q] & ~dn[q];
+    const uint64_t ok_d = __ballot(m > mg[0][q]) & __ballot(m > mg[2][q + 2]);      // signs equal
+    const uint64_t ok_n = __ballot(m > mg[0][q + 2]) & __ballot(m > mg[2][q]);      // signs differ
+    const uint64_t is_max = (horiz & ok_h) | (vert & ok_v) | (~(horiz | vert) & ((neg & ok_n) | (~neg & ok_d)));
+    const uint64_t cand = is_max & __ballot(m > low) & inside[q];
+    o.wb = shl1_or(o.wb, cand);
+    o.sb = shl1_or(o.sb, cand & __ballot(m > high));
+    // class 0: [0, pi/4), 1: [pi/4, pi/2), 2: [pi/2, 3pi/4), 3: [3pi/4, pi)
+    const int dif = x - ay, sum = x + ay;
+    const uint64_t le = __ballot(dif >= 0), ge = __ballot(dif <= 0);
+    o.cb0 = shl1_or(o.cb0, (neg & le) | (~neg & ge));
+    o.cb1 = shl1_or(o.cb1, neg);
+    // halves of a quarter: psi = atan(|dy| / |dx|) against pi/8 (psi < pi/4: tan = sqrt(2) - 1, i.e.
+    // (|dx| + |dy|)^2 > 2 dx^2) or 3 pi/8 (tan = sqrt(2) + 1, i.e. (|dy| - |dx|)^2 > 2 dx^2); phi = psi or
+    // pi - psi (signs differ), which mirrors the halves.  Irrational tangents: never an equality.  Both tests are
+    // made and the quarter picks one on the scalar unit: a per-lane select would bring the masks back into VGPRs.
+    const int xx2 = 2 * __mul24(x, x);
+    const uint64_t lowq = (neg & le) | ~(neg | ge);
+    const uint64_t upper = (lowq & __ballot(__mul24(sum, sum) > xx2)) |
+                           (~lowq & __ballot(__mul24(dif, dif) > xx2));
+    o.cb2 = shl1_or(o.cb2, neg ^ upper);
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) up[q] = dn[q];
+  return o;
+}
+
+// The tile kernel: every width, rows and columns staged through LDS.  mg_canny_nms takes it where the strip walk
+// below does not apply (w % 4 != 0, or a misaligned image).
 __global__ __launch_bounds__(NT) void k_canny_nms(const uint8_t* __restrict__ d_blur, int h, int w,
                                                   const int32_t* __restrict__ d_thresh, int64_t words_per_plane,
                                                   uint32_t* __restrict__ d_weak, uint32_t* __restrict__ d_strong,
@@ -868,7 +948,8 @@ __global__ __launch_bounds__(NT) void k_canny_nms(const uint8_t* __restrict__ d_
   load_tile<uint8_t, 2>(d_blur + (int64_t)plane * h * w, w, h, w, tx0, ty0, make_scale(nullptr, 0), tile);
   __syncthreads();
   const int low = d_thresh[2 * plane], high = d_thresh[2 * plane + 1];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (rows, and the masks carried down them: scalar)
   const int c0 = 4 * lane, gx = tx0 + c0;
   uint32_t* weak = d_weak + plane * words_per_plane;
   uint32_t* strong = d_strong + plane * words_per_plane;
@@ -879,8 +960,10 @@ __global__ __launch_bounds__(NT) void k_canny_nms(const uint8_t* __restrict__ d_
   uint32_t* cls0 = d_class ? d_class + (3 * plane) * words_per_plane : nullptr;
   uint32_t* cls1 = d_class ? d_class + (3 * plane + 1) * words_per_plane : nullptr;
   uint32_t* cls2 = d_class ? d_class + (3 * plane + 2) * words_per_plane : nullptr;
-  constexpr int TG22 = 13573;
   const uint32_t in_row = gx + 4 <= w ? 0xFu : ((1u << max(w - gx, 0)) - 1u);  // the lane's pixels left of the row end
+  uint64_t inside[4], up[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) inside[q] = __ballot(gx + q < w), up[q] = 0;
   // A row is held as four registers of pixel pairs (columns c0-2 .. c0+5), see scharr_pairs.
   struct Pairs4 {
     u2 p[4];
@@ -920,49 +1003,14 @@ __global__ __launch_bounds__(NT) void k_canny_nms(const uint8_t* __restrict__ d_
     }
     ua = ub;
     ub = uc;
+    if (jr == 3) nms_rising(mg[1], mg[2], up);  // the first NMS row against the row above it
     if (jr < 4) continue;
-    // NMS of image row yo = ym - 1 (mag rows 0, 1, 2 = yo - 1, yo, yo + 1; gradients in cd*[0])
+    // NMS of image row yo = ym - 1 (mag rows 0, 1, 2 = yo - 1, yo, yo + 1; gradients in cxy[0])
     const int yo = ym - 1;
     uint32_t wb = 0, sb = 0, cb0 = 0, cb1 = 0, cb2 = 0;
     if (yo < h) {
-      // Every decision is a per-lane boolean = a wave mask in scalar registers: the compares write the masks,
-      // the logic runs on the scalar unit, and a plane's bit enters its accumulator as the carry-in of ONE
-      // v_addc (v = 2 v + bit).  No value selects: all four direction tests are evaluated and the gradient
-      // direction picks the result.  (The select-chain version spent two thirds of its instructions on
-      // v_cndmask / shift / or.)
-#pragma unroll
-      for (int q = 3; q >= 0; --q) {
-        const int m = mg[1][q + 1];
-        const int xs = (int)(int16_t)(cxy[0][q] & 0xFFFFu), ys = (int)cxy[0][q] >> 16;
-        const int x = abs(xs), ay = abs(ys), y = ay << 15;
-        const int tg22x = x * TG22;
-        const int tg67x = tg22x + (x << 16);
-        const uint64_t horiz = __ballot(y < tg22x);
-        const uint64_t vert = __ballot(y > tg67x) & ~horiz;
-        const bool neg_b = (xs ^ ys) < 0;  // diagonal: s = -1 where the signs differ
-        const uint64_t neg = __ballot(neg_b);
-        // > towards the previous pixel; >= towards the next one on the axes, > on the diagonals
-        const uint64_t ok_h = __ballot(m > mg[1][q]) & __ballot(m >= mg[1][q + 2]);
-        const uint64_t ok_v = __ballot(m > mg[0][q + 1]) & __ballot(m >= mg[2][q + 1]);
-        const uint64_t ok_d = __ballot(m > mg[0][q]) & __ballot(m > mg[2][q + 2]);      // signs equal
-        const uint64_t ok_n = __ballot(m > mg[0][q + 2]) & __ballot(m > mg[2][q]);      // signs differ
-        const uint64_t is_max = (horiz & ok_h) | (vert & ok_v) | (~(horiz | vert) & ((neg & ok_n) | (~neg & ok_d)));
-        const uint64_t cand = is_max & __ballot(m > low) & __ballot(gx + q < w);
-        wb = shl1_or(wb, cand);
-        sb = shl1_or(sb, cand & __ballot(m > high));
-        // class 0: [0, pi/4), 1: [pi/4, pi/2), 2: [pi/2, 3pi/4), 3: [3pi/4, pi)
-        const bool le_b = ay <= x, ge_b = ay >= x;
-        const uint64_t le = __ballot(le_b), ge = __ballot(ge_b);
-        cb0 = shl1_or(cb0, (neg & le) | (~neg & ge));
-        cb1 = shl1_or(cb1, neg);
-        // halves of a quarter: psi = atan(|dy| / |dx|) against pi/8 (psi < pi/4: tan = sqrt(2) - 1, i.e.
-        // (|dx| + |dy|)^2 > 2 dx^2) or 3 pi/8 (tan = sqrt(2) + 1, i.e. (|dy| - |dx|)^2 > 2 dx^2); phi = psi or
-        // pi - psi (signs differ), which mirrors the halves.  Irrational tangents: never an equality.
-        const bool lowq = neg_b ? le_b : !ge_b;
-        const int sq = lowq ? x + ay : ay - x;
-        const uint64_t upper = __ballot(sq * sq > 2 * x * x);
-        cb2 = shl1_or(cb2, neg ^ upper);
-      }
+      const NmsBits o = nms_row(mg, cxy[0], low, high, inside, up);
+      wb = o.wb, sb = o.sb, cb0 = o.cb0, cb1 = o.cb1, cb2 = o.cb2;
     }
     // 8 lanes x 4 bits -> one 32-bit word
     wb = or_reduce8(wb << (4 * (lane & 7)));
@@ -993,6 +1041,191 @@ __global__ __launch_bounds__(NT) void k_canny_nms(const uint8_t* __restrict__ d_
       }
     }
   }
+}
+
+// The strip walk (w % 4 == 0): the kernel is bound by vector issue, and the tile kernel spends a third of its
+// instructions on a front end the result does not need -- 20 rows staged and differentiated per 16 emitted, six
+// gradients and magnitudes per lane for four pixels, and an LDS round trip for data that is read once, in order.
+// Here a wave walks down a strip of NR rows as blur_hist_strip does: a lane loads its dword of a row straight into
+// registers (the next NB rows in flight while these are worked on), the neighbours' pixels come by whole-wave DPP
+// shifts, a lane makes the four gradients and magnitudes of its own pixels (the odd-offset pairs are exactly what
+// scharr_pairs wants for them) and takes the two outer magnitudes of a row from its neighbours by DPP.  No tile, no
+// barrier; NR + 4 rows are differentiated per NR emitted.
+// Strips are whole bitmap words: all 64 lanes own pixels (NW = 256 columns = 8 words per row, each stored whole by
+// its eight lanes), so no lane idles or recomputes in the decisions, which are two thirds of the work.  What halo
+// lanes would have supplied -- the pixel and the magnitude just left of lane 0 and just right of lane 63 -- comes
+// from one more dword per lane and row (lanes 0 .. 31 load the word left of the strip, lanes 32 .. 63 the word
+// right of it: two addresses per wave) and one 2-pair scharr_pairs on it, ~20 instructions per row; strips of 248
+// owned columns with two halo lanes would straddle bitmap words (atomics on cleared buffers, against the
+// w % 32 == 0 contract), strips of 224 with eight idle lanes cost 14 % of every instruction.
+// 251 vector instructions per row of 4 px / lane in the loop (the tile kernel: 311 with its staging), 79 VGPRs.
+constexpr int NW = 256;                // columns of a strip = 64 lanes x 4 pixels
+constexpr int NR = 64;                 // rows per wave
+constexpr int NH = (NT / 64) * NR;     // rows per workgroup
+constexpr int NB = 4;                  // rows per batch of loads
+static_assert((NR + 4) % NB == 0 && NB >= 4, "row loop");
+
+// One wave's strip: rows [y0, y0 + NR) x columns [tx0, tx0 + NW).  VEC: every lane's dword and the two edge dwords
+// lie inside the image row (aligned loads); else every byte is read at its reflected column.  The choice is the
+// launch's (k_canny_nms_strips<VEC>), never a lane's: a branch around a load inside the loop would end every load
+// with a wait.
+template <bool VEC>
+__device__ __forceinline__ void nms_strip(const uint8_t* __restrict__ pb, int h, int w, int y0, int tx0, int low, int high,
+                                          uint32_t* __restrict__ weak, uint32_t* __restrict__ strong,
+                                          uint32_t* __restrict__ cls0, uint32_t* __restrict__ cls1,
+                                          uint32_t* __restrict__ cls2) {
+  const int lane = threadIdx.x & 63;
+  const int cx = tx0 + 4 * lane;  // the lane's first column
+  const bool left_half = lane < 32;
+  const int ex = left_half ? tx0 - 4 : tx0 + NW;  // first column of the lane's edge dword
+  uint32_t col[4], ecol[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    col[q] = VEC ? (uint32_t)(cx + q) : (uint32_t)mg_reflect101(cx + q, w);
+    ecol[q] = VEC ? (uint32_t)(ex + q) : (uint32_t)mg_reflect101(ex + q, w);
+  }
+  const int n_out = min(NR, h - y0), n_rows = n_out + 4;  // rows emitted, rows read: y0 - 2 .. y0 + n_out + 1
+  struct Row {
+    uint32_t d, e;  // the lane's four pixels, its edge dword
+  };
+  auto load = [&](int j) {  // blurred row y0 - 2 + j
+    // rows -1 and h reflect to 1 and h - 2 (to 0 where h == 1); rows -2 and h + 1 only feed magnitude rows outside the
+    // image, which are zero whatever they hold: any row inside the image will do (no loop: scalar, branch-free)
+    int ry = y0 - 2 + j;
+    ry = ry < 0 ? -ry : ry;
+    ry = ry >= h ? 2 * h - 2 - ry : ry;
+    ry = min(max(ry, 0), h - 1);
+    const uint8_t* rowp = pb + (int64_t)ry * w;
+    Row r;
+    if (VEC) {
+      r.d = *reinterpret_cast<const uint32_t*>(rowp + col[0]);
+      r.e = *reinterpret_cast<const uint32_t*>(rowp + ecol[0]);
+    } else {
+      r.d = (uint32_t)rowp[col[0]] | ((uint32_t)rowp[col[1]] << 8) | ((uint32_t)rowp[col[2]] << 16) | ((uint32_t)rowp[col[3]] << 24);
+      r.e = (uint32_t)rowp[ecol[0]] | ((uint32_t)rowp[ecol[1]] << 8) | ((uint32_t)rowp[ecol[2]] << 16) | ((uint32_t)rowp[ecol[3]] << 24);
+    }
+    return r;
+  };
+  // The edge column (tx0 - 1 for lanes 0 .. 31, tx0 + NW for lanes 32 .. 63; only lanes 0 and 63 use it) is the FIRST
+  // result of a 2-pair scharr_pairs: pairs (tx0-2, tx0-1) (tx0, tx0+1), or (tx0+NW-1, tx0+NW) (tx0+NW+1, tx0+NW+2).
+  // v_perm selectors over the bytes {d: 0..3, e: 4..7}.
+  const uint32_t sel_a = left_half ? 0x0C070C06u : 0x0C040C03u, sel_b = left_half ? 0x0C010C00u : 0x0C060C05u;
+  const bool in_img = cx < w;                                      // (w % 4 == 0: all four pixels or none)
+  const bool edge_in = left_half ? tx0 > 0 : tx0 + NW < w;         // the edge column lies inside the image
+  uint64_t inside[4], up[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) inside[q] = __ballot(in_img), up[q] = 0;
+  u2 P[3][3];  // the three newest rows as pairs (c-1, c), (c+1, c+2), (c+3, c+4)
+  u2 Q[3][2];  // ... and their edge pairs
+  int mg[3][6];        // magnitudes of columns c-1 .. c+4 of image rows yo - 1, yo, yo + 1; zero outside the image
+  uint32_t cxy[2][4];  // (dx | dy << 16) of the lane's pixels for the two newest magnitude rows
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    P[k][0] = P[k][1] = P[k][2] = Q[k][0] = Q[k][1] = (u2)(0);
+#pragma unroll
+    for (int c = 0; c < 6; ++c) mg[k][c] = 0;
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) cxy[0][q] = cxy[1][q] = 0u;
+  Row cur[NB], nxt[NB];
+#pragma unroll
+  for (int b = 0; b < NB; ++b) cur[b] = load(min(b, n_rows - 1));
+#pragma unroll 1
+  for (int j0 = 0; j0 < n_rows; j0 += NB) {
+    // the rows of the next batch: in flight while this one is worked on (past the strip: the last row again)
+#pragma unroll
+    for (int b = 0; b < NB; ++b) nxt[b] = load(min(j0 + NB + b, n_rows - 1));
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+      const int j = j0 + b;
+      const uint32_t d1 = cur[b].d, e = cur[b].e;
+      const uint32_t d0 = wave_from_left(d1, e), d2 = wave_from_right(d1, e);
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        P[k][0] = P[k + 1][0], P[k][1] = P[k + 1][1], P[k][2] = P[k + 1][2];
+        Q[k][0] = Q[k + 1][0], Q[k][1] = Q[k + 1][1];
+      }
+      P[2][0] = pair_across(d0, d1);
+      P[2][1] = pair_12(d1);
+      P[2][2] = pair_across(d1, d2);
+      Q[2][0] = __builtin_bit_cast(u2, __builtin_amdgcn_perm(e, d1, sel_a));
+      Q[2][1] = __builtin_bit_cast(u2, __builtin_amdgcn_perm(e, d1, sel_b));
+      // gradients and magnitudes of image row ym, the centre of the three newest rows
+      const int ym = y0 - 3 + j;
+      const bool row_in = ym >= 0 && ym < h;
+#pragma unroll
+      for (int c = 0; c < 6; ++c) mg[0][c] = mg[1][c], mg[1][c] = mg[2][c];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) cxy[0][q] = cxy[1][q];
+      uint32_t exy[2];
+      scharr_pairs(P[0], P[1], P[2], cxy[1]);
+      scharr_pairs(Q[0], Q[1], Q[2], exy);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) mg[2][q + 1] = (row_in && in_img) ? grad_sq(cxy[1][q]) : 0;
+      const uint32_t em = (row_in && edge_in) ? (uint32_t)grad_sq(exy[0]) : 0u;
+      mg[2][0] = (int)wave_from_left((uint32_t)mg[2][4], em);
+      mg[2][5] = (int)wave_from_right((uint32_t)mg[2][1], em);
+      if (j == 3) nms_rising(mg[1], mg[2], up);  // the first NMS row against the row above it
+      if (j0 == 0 || j >= n_rows) continue;      // (wave-uniform)
+      // NMS of image row yo = ym - 1 (magnitude rows 0, 1, 2 = yo - 1, yo, yo + 1; gradients in cxy[0])
+      const int yo = y0 - 4 + j;
+      const NmsBits o = nms_row(mg, cxy[0], low, high, inside, up);
+      // 8 lanes x 4 bits -> one 32-bit word
+      const uint32_t keep = in_img ? 0xFu : 0u;
+      const uint32_t wb = or_reduce8(o.wb << (4 * (lane & 7))), sb = or_reduce8(o.sb << (4 * (lane & 7)));
+      uint32_t cb0 = 0, cb1 = 0, cb2 = 0;
+      if (cls0) {
+        cb0 = or_reduce8((o.cb0 & keep) << (4 * (lane & 7)));
+        cb1 = or_reduce8((o.cb1 & keep) << (4 * (lane & 7)));
+        cb2 = or_reduce8((o.cb2 & keep) << (4 * (lane & 7)));
+      }
+      if ((lane & 7) == 0 && in_img) {
+        const int64_t bit0 = (int64_t)yo * w + cx;
+        if ((bit0 & 31) == 0 && cx + 32 <= w) {  // the word belongs to this lane group alone
+          weak[bit0 >> 5] = wb;
+          strong[bit0 >> 5] = sb;
+          if (cls0) {
+            cls0[bit0 >> 5] = cb0;
+            cls1[bit0 >> 5] = cb1;
+            cls2[bit0 >> 5] = cb2;
+          }
+        } else {
+          bits_or(weak, bit0, wb);
+          bits_or(strong, bit0, sb);
+          if (cls0) {
+            bits_or(cls0, bit0, cb0);
+            bits_or(cls1, bit0, cb1);
+            bits_or(cls2, bit0, cb2);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int b = 0; b < NB; ++b) cur[b] = nxt[b];
+  }
+}
+
+// Two launches: the strips whose dwords all lie inside the image row (VEC), and the first and last strips of a row
+// of strips (strip index = blockIdx.x + x_first, + x_jump behind the first).  The byte loads of the border strips
+// want more registers than the aligned loads; kept apart, the interior kernel fits five waves per SIMD.
+template <bool VEC>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(VEC ? 5 : 4)))
+void k_canny_nms_strips(const uint8_t* __restrict__ d_blur, int h, int w, int x_first, int x_jump,
+                        const int32_t* __restrict__ d_thresh, int64_t words_per_plane, uint32_t* __restrict__ d_weak,
+                        uint32_t* __restrict__ d_strong, uint32_t* __restrict__ d_class) {
+  const int plane = blockIdx.z;
+  const int tx0 = ((int)blockIdx.x + x_first + (blockIdx.x ? x_jump : 0)) * NW;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (rows: scalar arithmetic)
+  const int y0 = blockIdx.y * NH + wave * NR;
+  if (y0 >= h) return;  // a strip below the image
+  const int low = d_thresh[2 * plane], high = d_thresh[2 * plane + 1];
+  const uint8_t* pb = d_blur + (int64_t)plane * h * w;
+  uint32_t* weak = d_weak + plane * words_per_plane;
+  uint32_t* strong = d_strong + plane * words_per_plane;
+  uint32_t* cls0 = d_class ? d_class + (3 * plane) * words_per_plane : nullptr;  // (the planes: see k_canny_nms)
+  uint32_t* cls1 = d_class ? d_class + (3 * plane + 1) * words_per_plane : nullptr;
+  uint32_t* cls2 = d_class ? d_class + (3 * plane + 2) * words_per_plane : nullptr;
+  nms_strip<VEC>(pb, h, w, y0, tx0, low, high, weak, strong, cls0, cls1, cls2);
 }
 
 // ---- K4: hysteresis sweep, bit-parallel ---------------------------------------------------------
@@ -1537,13 +1770,19 @@ extern "C" int mg_edge_thresholds_window(const uint32_t* d_hist_win, int n_plane
   return MG_OK;
 }
 
+// The strip walk takes the widths whose rows are whole dwords (of an image that starts on one); the tile kernel the rest.
+static bool nms_strips(const uint8_t* d_blur, int w) { return (w & 3) == 0 && (reinterpret_cast<uintptr_t>(d_blur) & 3) == 0; }
+
 extern "C" int mg_canny_nms(const uint8_t* d_blur, int n_planes, int h, int w, const int32_t* d_thresh,
                             uint32_t* d_weak, uint32_t* d_strong, uint32_t* d_class, int64_t words_per_plane,
                             void* stream) {
   if (!d_blur || !d_thresh || !d_weak || !d_strong || n_planes < 0 || h < 0 || w < 0) return MG_EINVAL;
   if (n_planes == 0 || h == 0 || w == 0) return MG_OK;
   if (!words_ok(words_per_plane, h, w)) return MG_EINVAL;
-  const dim3 g = tile_grid(h, w, n_planes);
+  const bool strips = nms_strips(d_blur, w);
+  // strips 1 .. n_vec have every dword and both edge dwords inside the row: tx0 >= 4 and tx0 + NW + 4 <= w
+  const int n_strips = (w + NW - 1) / NW, n_vec = std::max(0, (w - NW - 4) / NW);
+  const dim3 g = strips ? dim3(n_strips - n_vec, (h + NH - 1) / NH, n_planes) : tile_grid(h, w, n_planes);
   if (!grid_ok(g)) return MG_EINVAL;
   hipStream_t s = mg_stream(stream);
   // w % 32 == 0: every bitmap word inside the image belongs to one lane group, which stores it whole -- nothing to
@@ -1552,9 +1791,27 @@ extern "C" int mg_canny_nms(const uint8_t* d_blur, int n_planes, int h, int w, c
   if ((w & 31) && (mg_zero_async(d_weak, bytes, s) != hipSuccess || mg_zero_async(d_strong, bytes, s) != hipSuccess ||
                    (d_class && mg_zero_async(d_class, 3 * bytes, s) != hipSuccess)))
     return MG_ELAUNCH;
-  hipLaunchKernelGGL(k_canny_nms, g, dim3(NT), 0, s, d_blur, h, w, d_thresh, words_per_plane, d_weak, d_strong,
-                     d_class);
+  if (strips) {
+    if (n_vec > 0) {
+      hipLaunchKernelGGL(k_canny_nms_strips<true>, dim3(n_vec, g.y, g.z), dim3(NT), 0, s, d_blur, h, w, 1, 0, d_thresh,
+                         words_per_plane, d_weak, d_strong, d_class);
+      MG_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(k_canny_nms_strips<false>, g, dim3(NT), 0, s, d_blur, h, w, 0, n_vec, d_thresh, words_per_plane,
+                       d_weak, d_strong, d_class);
+  } else
+    hipLaunchKernelGGL(k_canny_nms, g, dim3(NT), 0, s, d_blur, h, w, d_thresh, words_per_plane, d_weak, d_strong,
+                       d_class);
   MG_CHECK_LAUNCH();
+  return MG_OK;
+}
+
+extern "C" int mg_canny_nms_strips(int w, int* strip_w, int* wave_rows, int* group_rows) {
+  if (!strip_w || !wave_rows || !group_rows || w < 0) return MG_EINVAL;
+  const bool strips = nms_strips(nullptr, w);  // (of an aligned image)
+  *strip_w = strips ? NW : TW;
+  *wave_rows = strips ? NR : RPW;
+  *group_rows = strips ? NH : TH;
   return MG_OK;
 }
 
