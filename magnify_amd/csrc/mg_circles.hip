@@ -553,14 +553,6 @@ __global__ __launch_bounds__(NT) void k_layer_emit(uint32_t* __restrict__ d_bitm
 //     than min_roundness * P edge pixels on its perimeter cannot reach the threshold;
 //   pass B: the reference's float64 sum in perimeter order for the survivors (block-local list),
 //     gradient angles gathered from the precomputed edge-angle map.
-__device__ __forceinline__ uint32_t bits_at(const uint32_t* __restrict__ bits, int64_t bit0, int n) {
-  const int64_t wi = bit0 >> 5;
-  const int sh = (int)(bit0 & 31);
-  uint64_t two = bits[wi];
-  if (sh + n > 32) two |= (uint64_t)bits[wi + 1] << 32;
-  const uint32_t v = (uint32_t)(two >> sh);
-  return n >= 32 ? v : (v & ((1u << n) - 1u));
-}
 
 // Entry of k_score_tiles' perimeter table in LDS: (dr << 16) | (quarter << 14) | (dc & 0x3FFF).
 __device__ __forceinline__ int32_t per_pack(int dr, int quarter, int dc) { return (dr << 16) | (quarter << 14) | (dc & 0x3FFF); }
@@ -631,10 +623,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(96))) void k_sco
     if (y >= 0 && y < h) {
       const int x_lo = max(xs, 0), x_hi = min(min(xs + 32, wx0 + side), w);
       if (x_lo < x_hi) {
-        v = bits_at(bits, (int64_t)y * w + x_lo, x_hi - x_lo) << (x_lo - xs);
+        v = mg_bits_at(bits, (int64_t)y * w + x_lo, x_hi - x_lo) << (x_lo - xs);
         if (d_class && v) {
-          c0 = bits_at(cls0, (int64_t)y * w + x_lo, x_hi - x_lo) << (x_lo - xs);
-          c1 = bits_at(cls1, (int64_t)y * w + x_lo, x_hi - x_lo) << (x_lo - xs);
+          c0 = mg_bits_at(cls0, (int64_t)y * w + x_lo, x_hi - x_lo) << (x_lo - xs);
+          c1 = mg_bits_at(cls1, (int64_t)y * w + x_lo, x_hi - x_lo) << (x_lo - xs);
         }
       }
     }

@@ -120,6 +120,18 @@ __device__ __forceinline__ int mg_reflect101(int p, int n) {
   return p;
 }
 
+// n (1..32) consecutive bits of a linear (y * w + x) bitmap from bit index bit0 on.  The second word is read only when
+// the group reaches into it: for loads that sit behind data-dependent branches anyway (mg_edges.hip has the
+// branch-free form for loads that are meant to be in flight together).
+__device__ __forceinline__ uint32_t mg_bits_at(const uint32_t* __restrict__ bits, int64_t bit0, int n) {
+  const int64_t wi = bit0 >> 5;
+  const int sh = (int)(bit0 & 31);
+  uint64_t two = bits[wi];
+  if (sh + n > 32) two |= (uint64_t)bits[wi + 1] << 32;
+  const uint32_t v = (uint32_t)(two >> sh);
+  return n >= 32 ? v : (v & ((1u << n) - 1u));
+}
+
 // Load element idx of a scalar-or-image operand as float64.
 __device__ __forceinline__ double mg_load_f64(const void* p, int dtype, int64_t idx) {
   switch (dtype) {

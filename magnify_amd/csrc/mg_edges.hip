@@ -12,7 +12,6 @@
 // 64 rows, a lane loads its dword of a row into registers, neighbours by whole-wave DPP shifts.  Integer
 // arithmetic throughout: bit-exact against the oracle.  Roofline: HBM, vector issue for K3.
 #include <math.h>
-#include <stdlib.h>
 
 #include <algorithm>
 
@@ -215,7 +214,8 @@ __device__ __forceinline__ uint32_t zip_hi(s2 x, s2 y) {
 
 // v of lane - 1 / lane + 1 by a whole-wave DPP shift (wave_shr:1 / wave_shl:1; no LDS permute).  The lane without
 // such a neighbour -- lane 0 from the left, lane 63 from the right -- gets 0: k_scharr_hist<true> fills in the image
-// edge or the next tile's word there, blur_hist_strip never uses what those two lanes compute from it (not owners).
+// edge or the next tile's word there, blur_hist_strip never uses what those two lanes compute from it (not owners);
+// nms_strip, whose 64 lanes all own pixels, takes the form with `fill` below and hands in its edge dword.
 __device__ __forceinline__ uint32_t wave_from_left(uint32_t v) {
   return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xF, 0xF, false);
 }
@@ -256,6 +256,13 @@ __device__ __forceinline__ void scharr_pairs(const u2 (&a)[NP], const u2 (&b)[NP
     xy[2 * jp] = zip_lo(dxp, dyp);
     xy[2 * jp + 1] = zip_hi(dxp, dyp);
   }
+}
+// The three pairs (c-1, c), (c+1, c+2), (c+3, c+4) that scharr_pairs<3> wants for a lane's own four pixels c .. c+3,
+// from the lane's dword d1 and the dwords d0, d2 left and right of it.
+__device__ __forceinline__ void odd_pairs(uint32_t d0, uint32_t d1, uint32_t d2, u2 (&p)[3]) {
+  p[0] = pair_across(d0, d1);
+  p[1] = pair_12(d1);
+  p[2] = pair_across(d1, d2);
 }
 // |gradient|^2 = dx^2 + dy^2 of one (dx | dy << 16): one dot2.
 __device__ __forceinline__ int grad_sq(uint32_t xy) {
@@ -362,14 +369,9 @@ __device__ __forceinline__ void hist_add4_pairs(const u2 (&pa)[3], const u2 (&pb
 __device__ __forceinline__ void hist_add4(const Row12& ra, const Row12& rb, const Row12& rc, int gx, int w, int mode,
                                           uint32_t base, int n_bins, uint32_t* hist, uint32_t& zeros) {
   u2 pa[3], pb2[3], pc[3];
-  auto unpack = [](const Row12& r, u2 (&o)[3]) {
-    o[0] = pair_across(r.d0, r.d1);  // c0-1, c0
-    o[1] = pair_12(r.d1);            // c0+1, c0+2
-    o[2] = pair_across(r.d1, r.d2);  // c0+3, c0+4
-  };
-  unpack(ra, pa);
-  unpack(rb, pb2);
-  unpack(rc, pc);
+  odd_pairs(ra.d0, ra.d1, ra.d2, pa);
+  odd_pairs(rb.d0, rb.d1, rb.d2, pb2);
+  odd_pairs(rc.d0, rc.d1, rc.d2, pc);
   hist_add4_pairs(pa, pb2, pc, gx, w, mode, base, n_bins, hist, zeros);
 }
 
@@ -481,6 +483,57 @@ __global__ __launch_bounds__(NT) void k_scharr_hist(const uint8_t* __restrict__ 
   }
 }
 
+// ---- the strip walks' row reader and row loop (blur_hist_strip, nms_strip) -----------------------------------
+template <typename T>
+struct alignas(4 * sizeof(T)) Raw4 {
+  T v[4];
+};
+
+// The four columns of a lane from cx on: as they are (VEC: inside the row; only the first is used) or reflected.
+template <bool VEC>
+__device__ __forceinline__ void strip_cols(int cx, int w, uint32_t (&col)[4]) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) col[q] = VEC ? (uint32_t)(cx + q) : (uint32_t)mg_reflect101(cx + q, w);
+}
+// A lane's four elements of the row at rowp.  VEC: one aligned load; else four loads at the columns of strip_cols.
+// The choice is the workgroup's or the launch's, never a lane's: a branch around a load inside the row loop would
+// end every load with a wait.
+template <typename T, bool VEC>
+__device__ __forceinline__ Raw4<T> load_row4(const T* __restrict__ rowp, const uint32_t (&col)[4]) {
+  Raw4<T> r;
+  if (VEC) {
+    r = *reinterpret_cast<const Raw4<T>*>(rowp + col[0]);
+  } else {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) r.v[q] = rowp[col[q]];
+  }
+  return r;
+}
+
+// step(j0, j, load(j)) for j = 0 .. n_rows - 1 (and on to the end of the last trip; n_rows need not be a multiple of
+// a trip's HALVES * NB rows), with the loads a batch ahead: the NB rows of the next batch are in flight while this one
+// is worked on (past n_rows: the last row again).  j0 is the first row of the trip (j - j0 is a constant in every call
+// of the unrolled body); what a caller rotates through registers returns to its place over a whole trip.
+template <int NB, int HALVES = 1, class Load, class Step>
+__device__ __forceinline__ void walk_rows(int n_rows, Load load, Step step) {
+  decltype(load(0)) cur[NB], nxt[NB];
+#pragma unroll
+  for (int b = 0; b < NB; ++b) cur[b] = load(min(b, n_rows - 1));
+#pragma unroll 1
+  for (int j0 = 0; j0 < n_rows; j0 += HALVES * NB) {
+#pragma unroll
+    for (int half = 0; half < HALVES; ++half) {
+      const int jb = j0 + half * NB;
+#pragma unroll
+      for (int b = 0; b < NB; ++b) nxt[b] = load(min(jb + NB + b, n_rows - 1));
+#pragma unroll
+      for (int b = 0; b < NB; ++b) step(j0, jb + b, cur[b]);
+#pragma unroll
+      for (int b = 0; b < NB; ++b) cur[b] = nxt[b];
+    }
+  }
+}
+
 // ---- K1 + K2 in one pass (integer inputs, w % 4 == 0): the blurred rows feed the histogram from registers ----
 // Both passes are bound by vector issue, not by their bytes, and the histogram pass read the blurred image back
 // (3.3 GB fetched at 64 planes of 4096^2 for 1.07 GB) only to do arithmetic on it.  Here a wave walks down a strip of
@@ -498,14 +551,8 @@ constexpr int FH = (NT / 64) * FR;
 constexpr int FB = 5;             // rows per batch of loads; two batches per trip (the 5-row ring returns to its place)
 static_assert((FR + 6) % (2 * FB) == 0, "row loop");
 
-template <typename T>
-struct alignas(4 * sizeof(T)) Raw4 {
-  T v[4];
-};
-
-// One wave's strip.  VEC: every lane's four columns lie inside the image row (one aligned load per lane and row);
-// else (the first / last strips of a row of strips) every lane reads its four reflected columns one by one.  The
-// choice is the workgroup's, not the lane's: a branch around a load inside the loop would end every load with a wait.
+// One wave's strip.  VEC (see load_row4): every lane's four columns lie inside the image row; else (the first / last
+// strips of a row of strips) they are reflected.
 template <typename T, bool VEC>
 __device__ __forceinline__ void blur_hist_strip(const T* __restrict__ pin, int64_t row_stride, int h, int w, int y0, int cx,
                                                 bool owner, const U8Scale& sc, uint8_t* __restrict__ pout, uint32_t* hist,
@@ -513,21 +560,12 @@ __device__ __forceinline__ void blur_hist_strip(const T* __restrict__ pin, int64
   constexpr int n_bins = FINE + COARSE;
   const int y_end = min(y0 + FR, h);
   uint32_t col[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) col[q] = VEC ? (uint32_t)(cx + q) : (uint32_t)mg_reflect101(cx + q, w);
+  strip_cols<VEC>(cx, w, col);
   auto load = [&](int j) {  // input row y0 - 3 + j
     int ry = y0 - 3 + j;
     if (ry < 0) ry = -ry;
     if (ry >= h) ry = mg_reflect101(ry, h);
-    const T* rowp = pin + (int64_t)ry * row_stride;
-    Raw4<T> r;
-    if (VEC) {
-      r = *reinterpret_cast<const Raw4<T>*>(rowp + col[0]);
-    } else {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) r.v[q] = rowp[col[q]];
-    }
-    return r;
+    return load_row4<T, VEC>(pin + (int64_t)ry * row_stride, col);
   };
   u2 H[5][2];   // row-pass sums of the five newest input rows, pixels (0, 1) and (2, 3)
   u2 P[3][3];   // the three newest blurred rows as pairs (c-1, c), (c+1, c+2), (c+3, c+4)
@@ -535,56 +573,41 @@ __device__ __forceinline__ void blur_hist_strip(const T* __restrict__ pin, int64
   for (int k = 0; k < 5; ++k) H[k][0] = H[k][1] = (u2)(0);
 #pragma unroll
   for (int k = 0; k < 3; ++k) P[k][0] = P[k][1] = P[k][2] = (u2)(0);
-  Raw4<T> cur[FB], nxt[FB];
+  walk_rows<FB, 2>(FR + 6, load, [&](int, int j, const Raw4<T>& row) {
+    // (to_u8's float64 multiply-add is not what this loop waits for: an exact float32 quotient with one integer
+    // correction, seven single-rate instructions per pixel, ran 2 % slower)
+    const uint32_t d1 = (uint32_t)to_u8<T>(row.v[0], sc) | ((uint32_t)to_u8<T>(row.v[1], sc) << 8) |
+                        ((uint32_t)to_u8<T>(row.v[2], sc) << 16) | ((uint32_t)to_u8<T>(row.v[3], sc) << 24);
+    const uint32_t d0 = wave_from_left(d1), d2 = wave_from_right(d1);
+    // pixel pairs at even and odd offsets: (-2, -1) (0, 1) (2, 3) (4, 5) and (-1, 0) (1, 2) (3, 4)
+    const u2 em = pair_23(d0), e0 = pair_01(d1), e2 = pair_23(d1), e4 = pair_01(d2);
+    u2 o[3];
+    odd_pairs(d0, d1, d2, o);
 #pragma unroll
-  for (int b = 0; b < FB; ++b) cur[b] = load(b);
-#pragma unroll 1
-  for (int j0 = 0; j0 < FR + 6; j0 += 2 * FB) {
+    for (int k = 0; k < 4; ++k) H[k][0] = H[k + 1][0], H[k][1] = H[k + 1][1];
+    H[4][0] = (em + e2) + (o[0] + o[1]) * (unsigned short)4 + e0 * (unsigned short)6;
+    H[4][1] = (e0 + e4) + (o[1] + o[2]) * (unsigned short)4 + e2 * (unsigned short)6;
+    // blurred row br (centre of the five newest input rows); meaningful from j = 4 on
+    const int br = y0 - 1 + (j - 4);
+    u2 B[2];
 #pragma unroll
-    for (int half = 0; half < 2; ++half) {
-      const int jb = j0 + half * FB;
-      // the rows of the next batch: in flight while this one is worked on (past the strip: the last row again)
+    for (int k = 0; k < 2; ++k)
+      B[k] = ((H[0][k] + H[4][k]) + (H[1][k] + H[3][k]) * (unsigned short)4 + H[2][k] * (unsigned short)6 +
+              (unsigned short)128) >> (unsigned short)8;
+    const uint32_t b01 = __builtin_bit_cast(uint32_t, B[0]), b23 = __builtin_bit_cast(uint32_t, B[1]);
+    if (br >= y0 && br < y_end && owner)
+      *reinterpret_cast<uint32_t*>(pout + (int64_t)br * w + cx) = pack_bytes(b01, b23);
+    // the blurred row's odd_pairs, from pairs instead of dwords: (-1, 0) with the left lane's (2, 3), (3, 4) with the
+    // right lane's (0, 1)
+    const uint32_t l23 = wave_from_left(b23), r01 = wave_from_right(b01);
 #pragma unroll
-      for (int b = 0; b < FB; ++b) nxt[b] = load(min(jb + FB + b, FR + 5));
-#pragma unroll
-      for (int b = 0; b < FB; ++b) {
-        const int j = jb + b;
-        // (to_u8's float64 multiply-add is not what this loop waits for: an exact float32 quotient with one integer
-        // correction, seven single-rate instructions per pixel, ran 2 % slower)
-        const uint32_t d1 = (uint32_t)to_u8<T>(cur[b].v[0], sc) | ((uint32_t)to_u8<T>(cur[b].v[1], sc) << 8) |
-                            ((uint32_t)to_u8<T>(cur[b].v[2], sc) << 16) | ((uint32_t)to_u8<T>(cur[b].v[3], sc) << 24);
-        const uint32_t d0 = wave_from_left(d1), d2 = wave_from_right(d1);
-        // pixel pairs at even and odd offsets: (-2, -1) (0, 1) (2, 3) (4, 5) and (-1, 0) (1, 2) (3, 4)
-        const u2 em = pair_23(d0), e0 = pair_01(d1), e2 = pair_23(d1), e4 = pair_01(d2);
-        const u2 om = pair_across(d0, d1), o1 = pair_12(d1), o3 = pair_across(d1, d2);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) H[k][0] = H[k + 1][0], H[k][1] = H[k + 1][1];
-        H[4][0] = (em + e2) + (om + o1) * (unsigned short)4 + e0 * (unsigned short)6;
-        H[4][1] = (e0 + e4) + (o1 + o3) * (unsigned short)4 + e2 * (unsigned short)6;
-        // blurred row br (centre of the five newest input rows); meaningful from j = 4 on
-        const int br = y0 - 1 + (j - 4);
-        u2 B[2];
-#pragma unroll
-        for (int k = 0; k < 2; ++k)
-          B[k] = ((H[0][k] + H[4][k]) + (H[1][k] + H[3][k]) * (unsigned short)4 + H[2][k] * (unsigned short)6 +
-                  (unsigned short)128) >> (unsigned short)8;
-        const uint32_t b01 = __builtin_bit_cast(uint32_t, B[0]), b23 = __builtin_bit_cast(uint32_t, B[1]);
-        if (br >= y0 && br < y_end && owner)
-          *reinterpret_cast<uint32_t*>(pout + (int64_t)br * w + cx) = pack_bytes(b01, b23);
-        // pairs at odd offsets of the blurred row: (-1, 0) with the left lane's (2, 3), (3, 4) with the right lane's (0, 1)
-        const uint32_t l23 = wave_from_left(b23), r01 = wave_from_right(b01);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) P[0][k] = P[1][k], P[1][k] = P[2][k];
-        P[2][0] = __builtin_bit_cast(u2, __builtin_amdgcn_alignbit(b01, l23, 16));
-        P[2][1] = __builtin_bit_cast(u2, __builtin_amdgcn_alignbit(b23, b01, 16));
-        P[2][2] = __builtin_bit_cast(u2, __builtin_amdgcn_alignbit(r01, b23, 16));
-        const int sr = br - 1;  // the Scharr row: centre of the three newest blurred rows
-        if (sr >= y0 && sr < y_end && owner) hist_add4_pairs(P[0], P[1], P[2], cx, w, 0, 0u, n_bins, hist, zeros);
-      }
-#pragma unroll
-      for (int b = 0; b < FB; ++b) cur[b] = nxt[b];
-    }
-  }
+    for (int k = 0; k < 3; ++k) P[0][k] = P[1][k], P[1][k] = P[2][k];
+    P[2][0] = __builtin_bit_cast(u2, __builtin_amdgcn_alignbit(b01, l23, 16));
+    P[2][1] = __builtin_bit_cast(u2, __builtin_amdgcn_alignbit(b23, b01, 16));
+    P[2][2] = __builtin_bit_cast(u2, __builtin_amdgcn_alignbit(r01, b23, 16));
+    const int sr = br - 1;  // the Scharr row: centre of the three newest blurred rows
+    if (sr >= y0 && sr < y_end && owner) hist_add4_pairs(P[0], P[1], P[2], cx, w, 0, 0u, n_bins, hist, zeros);
+  });
 }
 
 template <typename T>
@@ -815,18 +838,10 @@ __global__ __launch_bounds__(NT) void k_window_resolve(const uint32_t* __restric
 
 // ---- bit helpers on the linear (y * w + x) bitmaps --------------------------------------------
 // n (1..32) consecutive bits starting at linear bit index bit0, in two forms:
-//   bits_at     reads the second word only when the group reaches into it.  For row_word (hysteresis, w % 32 != 0)
-//               and k_cell_fill, whose loads are behind data-dependent branches anyway.
+//   mg_bits_at  (mg_common.h) reads the second word only when the group reaches into it.  For row_word (hysteresis,
+//               w % 32 != 0) and k_cell_fill, whose loads are behind data-dependent branches anyway.
 //   bits_at_nb  reads it always (the bitmaps carry a spare word): no branch.  For k_cell_count and k_cell_fill_rows,
 //               whose loads are meant to be in flight together -- a load behind a lane-level branch ends with a wait.
-__device__ __forceinline__ uint32_t bits_at(const uint32_t* __restrict__ bits, int64_t bit0, int n) {
-  const int64_t wi = bit0 >> 5;
-  const int sh = (int)(bit0 & 31);
-  uint64_t two = bits[wi];
-  if (sh + n > 32) two |= (uint64_t)bits[wi + 1] << 32;
-  const uint32_t v = (uint32_t)(two >> sh);
-  return n >= 32 ? v : (v & ((1u << n) - 1u));
-}
 __device__ __forceinline__ uint32_t bits_at_nb(const uint32_t* __restrict__ bits, int64_t bit0, int n) {
   const int64_t wi = bit0 >> 5;
   const int sh = (int)(bit0 & 31);
@@ -847,7 +862,7 @@ __device__ __forceinline__ uint32_t row_word(const uint32_t* __restrict__ bits, 
   if (y < 0 || y >= h) return 0u;
   const int lo = max(x0, 0), hi = min(x0 + 32, w);
   if (lo >= hi) return 0u;
-  return bits_at(bits, (int64_t)y * w + lo, hi - lo) << (lo - x0);
+  return mg_bits_at(bits, (int64_t)y * w + lo, hi - lo) << (lo - x0);
 }
 
 // v = 2 v + (this lane's bit of a wave mask): the mask is the carry-in of one add-with-carry.
@@ -936,6 +951,61 @@ __device__ __forceinline__ NmsBits nms_row(const int (&mg)[3][6], const uint32_t
   return o;
 }
 
+// The five bitmaps of a plane.  Orientation bin of the gradient, phi = atan2(dy, dx) mod pi in eighths of pi (exact,
+// from the integer gradient): bit planes c0, c1 (quarter index 2 c1 + c0) and c2 (upper half of the quarter),
+// bin = 4 c1 + 2 c0 + c2.  The scoring prefilter bounds every perimeter term by the distance between the point's
+// radial direction and the pixel's bin.
+struct NmsPlanes {
+  uint32_t *weak, *strong, *cls0, *cls1, *cls2;  // cls0 .. 2: null where the caller wants no orientation planes
+};
+__device__ __forceinline__ NmsPlanes nms_planes(uint32_t* __restrict__ d_weak, uint32_t* __restrict__ d_strong,
+                                                uint32_t* __restrict__ d_class, int plane, int64_t words_per_plane) {
+  NmsPlanes p{d_weak + plane * words_per_plane, d_strong + plane * words_per_plane, nullptr, nullptr, nullptr};
+  if (d_class) {
+    p.cls0 = d_class + (3 * plane) * words_per_plane;
+    p.cls1 = d_class + (3 * plane + 1) * words_per_plane;
+    p.cls2 = d_class + (3 * plane + 2) * words_per_plane;
+  }
+  return p;
+}
+// A row's decisions into the bitmaps: 8 lanes x 4 bits -> one 32-bit word whose bit 0 is linear bit bit0 (the first
+// pixel of the group's first lane, which writes it: `writes` = that lane has a pixel of an image row to write).
+// class_mask: the lane's pixels inside the row (nms_row masks weak and strong itself, not the orientation bits).
+// A word that begins on a word boundary and ends inside the row (fits_word) belongs to this lane group alone and is
+// stored whole; any other is ORed in, into buffers that mg_canny_nms cleared.  With w % 32 == 0 every word is of the
+// first kind: the contract under which mg_canny_nms clears nothing.
+__device__ __forceinline__ void nms_emit_row(const NmsBits& o, const NmsPlanes& p, int lane, uint32_t class_mask,
+                                             bool writes, int64_t bit0, bool fits_word) {
+  const int sh = 4 * (lane & 7);
+  const uint32_t wb = or_reduce8(o.wb << sh);
+  const uint32_t sb = or_reduce8(o.sb << sh);
+  uint32_t cb0 = 0, cb1 = 0, cb2 = 0;
+  if (p.cls0) {
+    cb0 = or_reduce8((o.cb0 & class_mask) << sh);
+    cb1 = or_reduce8((o.cb1 & class_mask) << sh);
+    cb2 = or_reduce8((o.cb2 & class_mask) << sh);
+  }
+  if ((lane & 7) != 0 || !writes) return;
+  const int64_t wi = bit0 >> 5;
+  if ((bit0 & 31) == 0 && fits_word) {
+    p.weak[wi] = wb;
+    p.strong[wi] = sb;
+    if (p.cls0) {
+      p.cls0[wi] = cb0;
+      p.cls1[wi] = cb1;
+      p.cls2[wi] = cb2;
+    }
+  } else {
+    bits_or(p.weak, bit0, wb);
+    bits_or(p.strong, bit0, sb);
+    if (p.cls0) {
+      bits_or(p.cls0, bit0, cb0);
+      bits_or(p.cls1, bit0, cb1);
+      bits_or(p.cls2, bit0, cb2);
+    }
+  }
+}
+
 // The tile kernel: every width, rows and columns staged through LDS.  mg_canny_nms takes it where the strip walk
 // below does not apply (w % 4 != 0, or a misaligned image).
 __global__ __launch_bounds__(NT) void k_canny_nms(const uint8_t* __restrict__ d_blur, int h, int w,
@@ -951,15 +1021,7 @@ __global__ __launch_bounds__(NT) void k_canny_nms(const uint8_t* __restrict__ d_
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (rows, and the masks carried down them: scalar)
   const int c0 = 4 * lane, gx = tx0 + c0;
-  uint32_t* weak = d_weak + plane * words_per_plane;
-  uint32_t* strong = d_strong + plane * words_per_plane;
-  // Orientation bin of the gradient, phi = atan2(dy, dx) mod pi in eighths of pi (exact, from the
-  // integer gradient): bit planes c0, c1 (quarter index 2 c1 + c0) and c2 (upper half of the quarter),
-  // bin = 4 c1 + 2 c0 + c2.  The scoring prefilter bounds every perimeter term by the distance between
-  // the point's radial direction and the pixel's bin.
-  uint32_t* cls0 = d_class ? d_class + (3 * plane) * words_per_plane : nullptr;
-  uint32_t* cls1 = d_class ? d_class + (3 * plane + 1) * words_per_plane : nullptr;
-  uint32_t* cls2 = d_class ? d_class + (3 * plane + 2) * words_per_plane : nullptr;
+  const NmsPlanes planes = nms_planes(d_weak, d_strong, d_class, plane, words_per_plane);
   const uint32_t in_row = gx + 4 <= w ? 0xFu : ((1u << max(w - gx, 0)) - 1u);  // the lane's pixels left of the row end
   uint64_t inside[4], up[4];
 #pragma unroll
@@ -1007,39 +1069,9 @@ __global__ __launch_bounds__(NT) void k_canny_nms(const uint8_t* __restrict__ d_
     if (jr < 4) continue;
     // NMS of image row yo = ym - 1 (mag rows 0, 1, 2 = yo - 1, yo, yo + 1; gradients in cxy[0])
     const int yo = ym - 1;
-    uint32_t wb = 0, sb = 0, cb0 = 0, cb1 = 0, cb2 = 0;
-    if (yo < h) {
-      const NmsBits o = nms_row(mg, cxy[0], low, high, inside, up);
-      wb = o.wb, sb = o.sb, cb0 = o.cb0, cb1 = o.cb1, cb2 = o.cb2;
-    }
-    // 8 lanes x 4 bits -> one 32-bit word
-    wb = or_reduce8(wb << (4 * (lane & 7)));
-    sb = or_reduce8(sb << (4 * (lane & 7)));
-    if (d_class) {
-      cb0 = or_reduce8((cb0 & in_row) << (4 * (lane & 7)));
-      cb1 = or_reduce8((cb1 & in_row) << (4 * (lane & 7)));
-      cb2 = or_reduce8((cb2 & in_row) << (4 * (lane & 7)));
-    }
-    if ((lane & 7) == 0 && yo < h && gx < w) {
-      const int64_t bit0 = (int64_t)yo * w + gx;
-      if ((bit0 & 31) == 0 && gx + 32 <= w) {  // the word belongs to this lane group alone
-        weak[bit0 >> 5] = wb;
-        strong[bit0 >> 5] = sb;
-        if (d_class) {
-          cls0[bit0 >> 5] = cb0;
-          cls1[bit0 >> 5] = cb1;
-          cls2[bit0 >> 5] = cb2;
-        }
-      } else {
-        bits_or(weak, bit0, wb);
-        bits_or(strong, bit0, sb);
-        if (d_class) {
-          bits_or(cls0, bit0, cb0);
-          bits_or(cls1, bit0, cb1);
-          bits_or(cls2, bit0, cb2);
-        }
-      }
-    }
+    NmsBits o{0u, 0u, 0u, 0u, 0u};
+    if (yo < h) o = nms_row(mg, cxy[0], low, high, inside, up);
+    nms_emit_row(o, planes, lane, in_row, yo < h && gx < w, (int64_t)yo * w + gx, gx + 32 <= w);
   }
 }
 
@@ -1058,32 +1090,26 @@ __global__ __launch_bounds__(NT) void k_canny_nms(const uint8_t* __restrict__ d_
 // right of it: two addresses per wave) and one 2-pair scharr_pairs on it, ~20 instructions per row; strips of 248
 // owned columns with two halo lanes would straddle bitmap words (atomics on cleared buffers, against the
 // w % 32 == 0 contract), strips of 224 with eight idle lanes cost 14 % of every instruction.
-// 251 vector instructions per row of 4 px / lane in the loop (the tile kernel: 311 with its staging), 79 VGPRs.
+// 251 vector instructions per row of 4 px / lane in the loop (the tile kernel: 311 with its staging), 75 VGPRs.
 constexpr int NW = 256;                // columns of a strip = 64 lanes x 4 pixels
 constexpr int NR = 64;                 // rows per wave
 constexpr int NH = (NT / 64) * NR;     // rows per workgroup
 constexpr int NB = 4;                  // rows per batch of loads
 static_assert((NR + 4) % NB == 0 && NB >= 4, "row loop");
 
-// One wave's strip: rows [y0, y0 + NR) x columns [tx0, tx0 + NW).  VEC: every lane's dword and the two edge dwords
-// lie inside the image row (aligned loads); else every byte is read at its reflected column.  The choice is the
-// launch's (k_canny_nms_strips<VEC>), never a lane's: a branch around a load inside the loop would end every load
-// with a wait.
+// One wave's strip: rows [y0, y0 + NR) x columns [tx0, tx0 + NW).  VEC (see load_row4): every lane's dword and the two
+// edge dwords lie inside the image row; else every byte is read at its reflected column.  The choice is the launch's
+// (k_canny_nms_strips<VEC>).
 template <bool VEC>
 __device__ __forceinline__ void nms_strip(const uint8_t* __restrict__ pb, int h, int w, int y0, int tx0, int low, int high,
-                                          uint32_t* __restrict__ weak, uint32_t* __restrict__ strong,
-                                          uint32_t* __restrict__ cls0, uint32_t* __restrict__ cls1,
-                                          uint32_t* __restrict__ cls2) {
+                                          const NmsPlanes& planes) {
   const int lane = threadIdx.x & 63;
   const int cx = tx0 + 4 * lane;  // the lane's first column
   const bool left_half = lane < 32;
   const int ex = left_half ? tx0 - 4 : tx0 + NW;  // first column of the lane's edge dword
   uint32_t col[4], ecol[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    col[q] = VEC ? (uint32_t)(cx + q) : (uint32_t)mg_reflect101(cx + q, w);
-    ecol[q] = VEC ? (uint32_t)(ex + q) : (uint32_t)mg_reflect101(ex + q, w);
-  }
+  strip_cols<VEC>(cx, w, col);
+  strip_cols<VEC>(ex, w, ecol);
   const int n_out = min(NR, h - y0), n_rows = n_out + 4;  // rows emitted, rows read: y0 - 2 .. y0 + n_out + 1
   struct Row {
     uint32_t d, e;  // the lane's four pixels, its edge dword
@@ -1096,15 +1122,8 @@ __device__ __forceinline__ void nms_strip(const uint8_t* __restrict__ pb, int h,
     ry = ry >= h ? 2 * h - 2 - ry : ry;
     ry = min(max(ry, 0), h - 1);
     const uint8_t* rowp = pb + (int64_t)ry * w;
-    Row r;
-    if (VEC) {
-      r.d = *reinterpret_cast<const uint32_t*>(rowp + col[0]);
-      r.e = *reinterpret_cast<const uint32_t*>(rowp + ecol[0]);
-    } else {
-      r.d = (uint32_t)rowp[col[0]] | ((uint32_t)rowp[col[1]] << 8) | ((uint32_t)rowp[col[2]] << 16) | ((uint32_t)rowp[col[3]] << 24);
-      r.e = (uint32_t)rowp[ecol[0]] | ((uint32_t)rowp[ecol[1]] << 8) | ((uint32_t)rowp[ecol[2]] << 16) | ((uint32_t)rowp[ecol[3]] << 24);
-    }
-    return r;
+    return Row{__builtin_bit_cast(uint32_t, load_row4<uint8_t, VEC>(rowp, col)),
+               __builtin_bit_cast(uint32_t, load_row4<uint8_t, VEC>(rowp, ecol))};
   };
   // The edge column (tx0 - 1 for lanes 0 .. 31, tx0 + NW for lanes 32 .. 63; only lanes 0 and 63 use it) is the FIRST
   // result of a 2-pair scharr_pairs: pairs (tx0-2, tx0-1) (tx0, tx0+1), or (tx0+NW-1, tx0+NW) (tx0+NW+1, tx0+NW+2).
@@ -1115,7 +1134,7 @@ __device__ __forceinline__ void nms_strip(const uint8_t* __restrict__ pb, int h,
   uint64_t inside[4], up[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) inside[q] = __ballot(in_img), up[q] = 0;
-  u2 P[3][3];  // the three newest rows as pairs (c-1, c), (c+1, c+2), (c+3, c+4)
+  u2 P[3][3];  // the three newest rows as odd_pairs
   u2 Q[3][2];  // ... and their edge pairs
   int mg[3][6];        // magnitudes of columns c-1 .. c+4 of image rows yo - 1, yo, yo + 1; zero outside the image
   uint32_t cxy[2][4];  // (dx | dy << 16) of the lane's pixels for the two newest magnitude rows
@@ -1127,82 +1146,39 @@ __device__ __forceinline__ void nms_strip(const uint8_t* __restrict__ pb, int h,
   }
 #pragma unroll
   for (int q = 0; q < 4; ++q) cxy[0][q] = cxy[1][q] = 0u;
-  Row cur[NB], nxt[NB];
+  walk_rows<NB>(n_rows, load, [&](int j0, int j, const Row& row) {
+    const uint32_t d1 = row.d, e = row.e;
+    const uint32_t d0 = wave_from_left(d1, e), d2 = wave_from_right(d1, e);
 #pragma unroll
-  for (int b = 0; b < NB; ++b) cur[b] = load(min(b, n_rows - 1));
-#pragma unroll 1
-  for (int j0 = 0; j0 < n_rows; j0 += NB) {
-    // the rows of the next batch: in flight while this one is worked on (past the strip: the last row again)
-#pragma unroll
-    for (int b = 0; b < NB; ++b) nxt[b] = load(min(j0 + NB + b, n_rows - 1));
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      const int j = j0 + b;
-      const uint32_t d1 = cur[b].d, e = cur[b].e;
-      const uint32_t d0 = wave_from_left(d1, e), d2 = wave_from_right(d1, e);
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        P[k][0] = P[k + 1][0], P[k][1] = P[k + 1][1], P[k][2] = P[k + 1][2];
-        Q[k][0] = Q[k + 1][0], Q[k][1] = Q[k + 1][1];
-      }
-      P[2][0] = pair_across(d0, d1);
-      P[2][1] = pair_12(d1);
-      P[2][2] = pair_across(d1, d2);
-      Q[2][0] = __builtin_bit_cast(u2, __builtin_amdgcn_perm(e, d1, sel_a));
-      Q[2][1] = __builtin_bit_cast(u2, __builtin_amdgcn_perm(e, d1, sel_b));
-      // gradients and magnitudes of image row ym, the centre of the three newest rows
-      const int ym = y0 - 3 + j;
-      const bool row_in = ym >= 0 && ym < h;
-#pragma unroll
-      for (int c = 0; c < 6; ++c) mg[0][c] = mg[1][c], mg[1][c] = mg[2][c];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) cxy[0][q] = cxy[1][q];
-      uint32_t exy[2];
-      scharr_pairs(P[0], P[1], P[2], cxy[1]);
-      scharr_pairs(Q[0], Q[1], Q[2], exy);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) mg[2][q + 1] = (row_in && in_img) ? grad_sq(cxy[1][q]) : 0;
-      const uint32_t em = (row_in && edge_in) ? (uint32_t)grad_sq(exy[0]) : 0u;
-      mg[2][0] = (int)wave_from_left((uint32_t)mg[2][4], em);
-      mg[2][5] = (int)wave_from_right((uint32_t)mg[2][1], em);
-      if (j == 3) nms_rising(mg[1], mg[2], up);  // the first NMS row against the row above it
-      if (j0 == 0 || j >= n_rows) continue;      // (wave-uniform)
-      // NMS of image row yo = ym - 1 (magnitude rows 0, 1, 2 = yo - 1, yo, yo + 1; gradients in cxy[0])
-      const int yo = y0 - 4 + j;
-      const NmsBits o = nms_row(mg, cxy[0], low, high, inside, up);
-      // 8 lanes x 4 bits -> one 32-bit word
-      const uint32_t keep = in_img ? 0xFu : 0u;
-      const uint32_t wb = or_reduce8(o.wb << (4 * (lane & 7))), sb = or_reduce8(o.sb << (4 * (lane & 7)));
-      uint32_t cb0 = 0, cb1 = 0, cb2 = 0;
-      if (cls0) {
-        cb0 = or_reduce8((o.cb0 & keep) << (4 * (lane & 7)));
-        cb1 = or_reduce8((o.cb1 & keep) << (4 * (lane & 7)));
-        cb2 = or_reduce8((o.cb2 & keep) << (4 * (lane & 7)));
-      }
-      if ((lane & 7) == 0 && in_img) {
-        const int64_t bit0 = (int64_t)yo * w + cx;
-        if ((bit0 & 31) == 0 && cx + 32 <= w) {  // the word belongs to this lane group alone
-          weak[bit0 >> 5] = wb;
-          strong[bit0 >> 5] = sb;
-          if (cls0) {
-            cls0[bit0 >> 5] = cb0;
-            cls1[bit0 >> 5] = cb1;
-            cls2[bit0 >> 5] = cb2;
-          }
-        } else {
-          bits_or(weak, bit0, wb);
-          bits_or(strong, bit0, sb);
-          if (cls0) {
-            bits_or(cls0, bit0, cb0);
-            bits_or(cls1, bit0, cb1);
-            bits_or(cls2, bit0, cb2);
-          }
-        }
-      }
+    for (int k = 0; k < 2; ++k) {
+      P[k][0] = P[k + 1][0], P[k][1] = P[k + 1][1], P[k][2] = P[k + 1][2];
+      Q[k][0] = Q[k + 1][0], Q[k][1] = Q[k + 1][1];
     }
+    odd_pairs(d0, d1, d2, P[2]);
+    Q[2][0] = __builtin_bit_cast(u2, __builtin_amdgcn_perm(e, d1, sel_a));
+    Q[2][1] = __builtin_bit_cast(u2, __builtin_amdgcn_perm(e, d1, sel_b));
+    // gradients and magnitudes of image row ym, the centre of the three newest rows
+    const int ym = y0 - 3 + j;
+    const bool row_in = ym >= 0 && ym < h;
 #pragma unroll
-    for (int b = 0; b < NB; ++b) cur[b] = nxt[b];
-  }
+    for (int c = 0; c < 6; ++c) mg[0][c] = mg[1][c], mg[1][c] = mg[2][c];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) cxy[0][q] = cxy[1][q];
+    uint32_t exy[2];
+    scharr_pairs(P[0], P[1], P[2], cxy[1]);
+    scharr_pairs(Q[0], Q[1], Q[2], exy);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) mg[2][q + 1] = (row_in && in_img) ? grad_sq(cxy[1][q]) : 0;
+    const uint32_t em = (row_in && edge_in) ? (uint32_t)grad_sq(exy[0]) : 0u;
+    mg[2][0] = (int)wave_from_left((uint32_t)mg[2][4], em);
+    mg[2][5] = (int)wave_from_right((uint32_t)mg[2][1], em);
+    if (j == 3) nms_rising(mg[1], mg[2], up);  // the first NMS row against the row above it
+    if (j0 == 0 || j >= n_rows) return;        // (wave-uniform)
+    // NMS of image row yo = ym - 1 (magnitude rows 0, 1, 2 = yo - 1, yo, yo + 1; gradients in cxy[0])
+    const int yo = y0 - 4 + j;
+    const NmsBits o = nms_row(mg, cxy[0], low, high, inside, up);
+    nms_emit_row(o, planes, lane, in_img ? 0xFu : 0u, in_img, (int64_t)yo * w + cx, cx + 32 <= w);
+  });
 }
 
 // Two launches: the strips whose dwords all lie inside the image row (VEC), and the first and last strips of a row
@@ -1220,12 +1196,7 @@ void k_canny_nms_strips(const uint8_t* __restrict__ d_blur, int h, int w, int x_
   if (y0 >= h) return;  // a strip below the image
   const int low = d_thresh[2 * plane], high = d_thresh[2 * plane + 1];
   const uint8_t* pb = d_blur + (int64_t)plane * h * w;
-  uint32_t* weak = d_weak + plane * words_per_plane;
-  uint32_t* strong = d_strong + plane * words_per_plane;
-  uint32_t* cls0 = d_class ? d_class + (3 * plane) * words_per_plane : nullptr;  // (the planes: see k_canny_nms)
-  uint32_t* cls1 = d_class ? d_class + (3 * plane + 1) * words_per_plane : nullptr;
-  uint32_t* cls2 = d_class ? d_class + (3 * plane + 2) * words_per_plane : nullptr;
-  nms_strip<VEC>(pb, h, w, y0, tx0, low, high, weak, strong, cls0, cls1, cls2);
+  nms_strip<VEC>(pb, h, w, y0, tx0, low, high, nms_planes(d_weak, d_strong, d_class, plane, words_per_plane));
 }
 
 // ---- K4: hysteresis sweep, bit-parallel ---------------------------------------------------------
@@ -1525,7 +1496,7 @@ __global__ __launch_bounds__(NT) void k_cell_fill(const uint32_t* __restrict__ d
   int64_t pos = d_starts[(int64_t)plane * n_cells + cell];
   for (int r = 0; r < ch; ++r)
     for (int c0 = 0; c0 < cw; c0 += 32) {
-      uint32_t v = bits_at(bits, (int64_t)(y0 + r) * w + x0 + c0, min(32, cw - c0));
+      uint32_t v = mg_bits_at(bits, (int64_t)(y0 + r) * w + x0 + c0, min(32, cw - c0));
       while (v) {
         const int b = __ffs(v) - 1;
         v &= v - 1;
@@ -1724,8 +1695,7 @@ extern "C" int mg_to_uint8_blur_hist(const void* d_src, int dtype, int n_planes,
   if (!d_minmax && dtype != MG_U8) return MG_EINVAL;
   if (n_planes == 0 || h == 0 || w == 0) return MG_OK;
   if (d_scratch && scratch_words < mg_blur_hist_scratch_words(n_planes, h, w)) return MG_EINVAL;
-  static const bool off = getenv("MG_NO_BLUR_HIST") != nullptr;
-  if (off || !d_scratch || !blur_hist_fused(d_src, dtype, plane_stride, h, w, row_stride, d_blur, d_u8)) {
+  if (!d_scratch || !blur_hist_fused(d_src, dtype, plane_stride, h, w, row_stride, d_blur, d_u8)) {
     const int rc = mg_to_uint8_blur(d_src, dtype, n_planes, plane_stride, h, w, row_stride, d_minmax, d_blur, d_u8, stream);
     if (rc != MG_OK) return rc;
     return mg_scharr_hist(d_blur, n_planes, h, w, 0, nullptr, d_hist, d_scratch, scratch_words, stream);
@@ -1785,8 +1755,8 @@ extern "C" int mg_canny_nms(const uint8_t* d_blur, int n_planes, int h, int w, c
   const dim3 g = strips ? dim3(n_strips - n_vec, (h + NH - 1) / NH, n_planes) : tile_grid(h, w, n_planes);
   if (!grid_ok(g)) return MG_EINVAL;
   hipStream_t s = mg_stream(stream);
-  // w % 32 == 0: every bitmap word inside the image belongs to one lane group, which stores it whole -- nothing to
-  // clear (the spare words behind the image are never written: the caller zeroes the buffers once, when it makes them)
+  // w % 32 != 0: words shared between lane groups are ORed in (nms_emit_row), so the buffers are cleared first (the
+  // spare words behind the image are never written: the caller zeroes the buffers once, when it makes them)
   const size_t bytes = (size_t)n_planes * words_per_plane * 4;
   if ((w & 31) && (mg_zero_async(d_weak, bytes, s) != hipSuccess || mg_zero_async(d_strong, bytes, s) != hipSuccess ||
                    (d_class && mg_zero_async(d_class, 3 * bytes, s) != hipSuccess)))

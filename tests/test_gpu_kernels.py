@@ -205,6 +205,61 @@ def test_blur_and_histogram_in_one_pass(hp, dtype, shape):
     np.testing.assert_array_equal(u8[0].cpu().numpy(), rn.to_uint8(planes[0]))
 
 
+@pytest.mark.parametrize("shape", [
+    (2, 256),    # one interior tile group of the register-direct kernel, the least height it takes
+    (17, 260),   # a wave's 16 rows plus one; an interior tile column beside a 4-pixel border column
+    (65, 512),   # two interior tile columns, a second tile row
+    (193, 264),  # a second tile group (3 tiles of 64 rows each)
+    (70, 258),   # w % 4 != 0: every tile through the staged kernel
+])
+def test_scharr_histogram_against_numpy(hp, shape):
+    """mg_scharr_hist on a given blurred plane against NumPy: m = dx^2 + dy^2 of the oracle's Scharr, binned as the
+    header says.  Mode 0: m < 8192 exactly, the rest by m >> 13, 12288 bins that sum to h * w (with scratch, and without:
+    the staged kernel alone).  Mode 1: bin m - base of the plane's window; a plane with base 0xFFFFFFFF is left as it
+    was handed in.  The one-pass and the two-pass histograms are otherwise only compared with each other."""
+    from magnify_amd import _native as nat
+
+    h, w = shape
+    rng = np.random.default_rng(h * 1000 + w)
+    yy, xx = np.mgrid[0:h, 0:w]
+    planes = np.stack([rng.integers(0, 256, shape).astype(np.uint8),                       # full-range noise
+                       (100 + 3 * (((yy // 8) + (xx // 8)) & 1)).astype(np.uint8),          # 8 x 8 blocks: equal m, zeros
+                       rng.integers(0, 256, shape).astype(np.uint8)])
+    p = len(planes)
+    mags = []
+    for k in range(p):
+        dx, dy = rcv.scharr(planes[k])
+        mags.append(dx.astype(np.int64) ** 2 + dy.astype(np.int64) ** 2)
+    lib, s = nat.lib(), torch.cuda.current_stream().cuda_stream
+    blur = dev(planes)
+    words = max(int(lib.mg_scharr_hist_scratch_words(p, h, w, mode)) for mode in (0, 1))
+    scratch = torch.empty((max(words, 1),), dtype=torch.int32, device="cuda")
+    # mode 0
+    want0 = np.stack([np.bincount(np.where(m < 8192, m, 8192 + (m >> 13)).ravel(), minlength=12288) for m in mags])
+    assert want0.shape == (p, 12288) and want0.sum(axis=1).tolist() == [h * w] * p
+    for with_scratch in (True, False):
+        hist = torch.zeros((p, 12288), dtype=torch.int32, device="cuda")
+        nat.check(lib.mg_scharr_hist(blur.data_ptr(), p, h, w, 0, 0, hist.data_ptr(),
+                                     scratch.data_ptr() if with_scratch else 0, words if with_scratch else 0, s), "hist")
+        np.testing.assert_array_equal(hist.cpu().numpy().view(np.uint32), want0, err_msg=f"scratch={with_scratch}")
+    # mode 1: plane 0 a window above the fine range (where its median magnitude lies), plane 1 the window at 0 (m == base
+    # is the flat background), plane 2 takes no part
+    base0 = int(np.median(mags[0])) >> 13 << 13
+    assert base0 >= 8192 and base0 % 8192 == 0
+    base = np.array([base0, 0, 0xFFFFFFFF], dtype=np.uint32)
+    handed_in = rng.integers(1, 1000, (p, 8192)).astype(np.int32)
+    handed_in[:2] = 0
+    want1 = handed_in.astype(np.int64)
+    for k in range(2):
+        m = mags[k][(mags[k] >= int(base[k])) & (mags[k] < int(base[k]) + 8192)]
+        want1[k] = np.bincount(m - int(base[k]), minlength=8192)
+    assert want1[0].sum() > 0 and want1[1, 0] > 0
+    hist, d_base = dev(handed_in), dev(base.view(np.int32))
+    nat.check(lib.mg_scharr_hist(blur.data_ptr(), p, h, w, 1, d_base.data_ptr(), hist.data_ptr(),
+                                 scratch.data_ptr(), words, s), "hist window")
+    np.testing.assert_array_equal(hist.cpu().numpy().view(np.uint32), want1)
+
+
 def test_to_uint8_golden_and_constant(hp, golden):
     g = golden("to_uint8")
     for key in ("a16", "a16n", "af32", "af64", "const"):

@@ -1,5 +1,5 @@
 """to_uint8 + blur + histogram of 64 planes of 4096^2 uint16 on their own: the one-pass kernel (mg_to_uint8_blur_hist)
-against the two passes behind the same entry point (MG_NO_BLUR_HIST=1 in another process).  HIP events, best of 7.
+against the two passes (mg_to_uint8_blur + mg_scharr_hist), one JSON line each.  HIP events, best of 7.
 python tools/blur_hist_bench.py [--planes 64] [--size 4096]"""
 import argparse
 import json
@@ -29,22 +29,29 @@ def main():
     scratch = torch.empty((words,), dtype=torch.int32, device="cuda")
     blur = torch.zeros((P, S, S), dtype=torch.uint8, device="cuda")
     hist = torch.zeros((P, 12288), dtype=torch.int32, device="cuda")
+    src = (d.data_ptr(), nat.dtype_code(d.dtype), P, d.stride(0), S, S, d.stride(1), mm.data_ptr(), blur.data_ptr(), 0)
 
-    def run():
-        nat.check(lib.mg_to_uint8_blur_hist(d.data_ptr(), nat.dtype_code(d.dtype), P, d.stride(0), S, S, d.stride(1), mm.data_ptr(),
-                                            blur.data_ptr(), 0, hist.data_ptr(), scratch.data_ptr(), words, s), "blur_hist")
-    ts = []
-    for _ in range(args.reps):
-        hist.zero_()
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        run()
-        b.record()
-        b.synchronize()
-        ts.append(a.elapsed_time(b))
-    print(json.dumps({"one_pass": os.environ.get("MG_NO_BLUR_HIST") is None, "ms_best": round(min(ts), 4),
-                      "ms_median": round(sorted(ts)[len(ts) // 2], 4), "hist_sum_ok": bool((hist.sum(dim=1) == S * S).all()),
-                      "checksum": int(blur.view(torch.int8).to(torch.int64).sum().item()) ^ int(hist.to(torch.int64).mul(torch.arange(12288, device="cuda")).sum().item())}))
+    def one_pass():
+        nat.check(lib.mg_to_uint8_blur_hist(*src, hist.data_ptr(), scratch.data_ptr(), words, s), "blur_hist")
+
+    def two_passes():
+        nat.check(lib.mg_to_uint8_blur(*src, s), "blur")
+        nat.check(lib.mg_scharr_hist(blur.data_ptr(), P, S, S, 0, 0, hist.data_ptr(), scratch.data_ptr(), words, s), "hist")
+
+    for run in (one_pass, two_passes):
+        blur.zero_()
+        ts = []
+        for _ in range(args.reps):
+            hist.zero_()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            run()
+            b.record()
+            b.synchronize()
+            ts.append(a.elapsed_time(b))
+        print(json.dumps({"one_pass": run is one_pass, "ms_best": round(min(ts), 4),
+                          "ms_median": round(sorted(ts)[len(ts) // 2], 4), "hist_sum_ok": bool((hist.sum(dim=1) == S * S).all()),
+                          "checksum": int(blur.view(torch.int8).to(torch.int64).sum().item()) ^ int(hist.to(torch.int64).mul(torch.arange(12288, device="cuda")).sum().item())}))
 
 
 if __name__ == "__main__":
