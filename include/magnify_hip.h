@@ -595,7 +595,9 @@ int mg_nms_cleanup(const int32_t* d_circles, int64_t circle_cap, const float* d_
  * buckets of 32 x 64, or a centre lies at row or col < -(min_dist + 1) (the reference's claim index would be negative
  * and wrap); every plane when min_dist > mg_nms_sparse_max_dist().  d_skip of the three calls above = this d_done:
  * they leave the planes alone that are decided (the cleanup only zeroes their circles' state bytes).  Needs no claim
- * grid and does not look at d_state before writing it. */
+ * grid and does not look at d_state before writing it.  A refused plane's state bytes are not written, alive circles'
+ * included (so is a plane whose d_max_rc understates a centre); tests/test_gpu_nms_paths.py holds the kernel to these
+ * limits, plane by plane. */
 int mg_nms_sparse(const int32_t* d_circles, int64_t circle_cap, const float* d_scores, const int32_t* d_alive,
                   const int32_t* d_num_alive, const int32_t* d_max_rc, int n_planes, int min_dist, const uint32_t* d_dbits,
                   uint8_t* d_state, const uint32_t* d_tie_keys, int32_t* d_done, void* stream);
@@ -604,6 +606,9 @@ int mg_nms_sparse_max_dist(void);
 /* Gather the kept circles in priority order (utils.py:195-199 output order):
  * d_out[n_planes][out_cap][3] int32 (row, col, r), d_out_scores, d_num_out[n_planes].
  * keep_all != 0 skips the state test (min_dist == 0: no suppression, utils.py:197).
+ * Order: score descending, then d_tie_keys ascending, compared as UNSIGNED 32-bit (the unique keys reach bit 31 on large
+ * images), or the index in d_circles when NULL.  At most out_cap rows per plane are written and d_num_out is clamped to
+ * out_cap; which circles drop out then is unspecified.
  * d_scratch: int32[n_planes][3 * out_cap] work space (the kept circles' indices and 64-bit priority keys). */
 int mg_collect_circles(const int32_t* d_circles, int64_t circle_cap, const float* d_scores, const int32_t* d_alive,
                        const int32_t* d_num_alive, const uint8_t* d_state, int keep_all, int n_planes,

@@ -8,8 +8,11 @@ flow of the reference's ``utils.find_circles`` (src/magnify/utils.py:102-222),
 """
 from __future__ import annotations
 
+import contextlib
+import gc
 import math
 import os
+import threading
 from collections import namedtuple
 
 import numpy as np
@@ -93,6 +96,29 @@ _NO_TIMER = TIMER
 
 _SYNC_EVERY_CALL = bool(os.environ.get("MG_SYNC_CALLS"))
 _CAPTURING = False  # inside a stream capture (CircleFinder._capture_chain): no timing events
+_GC_HELD = [0, False, threading.Lock()]  # open captures, whether the collector was on before the first, their lock
+
+
+@contextlib.contextmanager
+def _no_collection():
+    """No cyclic garbage collection, on ANY thread, while a stream capture is open.  The launches of a capture go through
+    ctypes, which lets other host threads run (the sink's writer, a reader): when one of them happened to start a
+    collection there, it destroyed the hipGraphExecs of finders that earlier callers had dropped -- and destroying one
+    while another capture is open aborts the process inside the runtime, without a message (seen once in a whole-suite
+    run: SIGABRT on the writer thread, in the collector, the main thread inside _capture_chain).  The switch is the
+    interpreter's, so captures of several threads share it: the last one out turns the collector back on."""
+    with _GC_HELD[2]:
+        if _GC_HELD[0] == 0:
+            _GC_HELD[1] = gc.isenabled()
+            gc.disable()
+        _GC_HELD[0] += 1
+    try:
+        yield
+    finally:
+        with _GC_HELD[2]:
+            _GC_HELD[0] -= 1
+            if _GC_HELD[0] == 0 and _GC_HELD[1]:
+                gc.enable()
 
 
 def _call(name, *args, stage=None, accept=()):
@@ -1111,7 +1137,7 @@ class CircleFinder:
             # capture_begin / capture_end directly, not torch.cuda.graph: that context manager starts with
             # torch.cuda.empty_cache(), which hands every cached block back to the driver -- 0.4 s when a few tens of
             # gigabytes of grown-out-of output sets sit in the cache, inside whatever region the capture falls into)
-            with torch.cuda.stream(self._cap_stream):
+            with _no_collection(), torch.cuda.stream(self._cap_stream):
                 graph.capture_begin(capture_error_mode="thread_local")
                 try:
                     # (a request with side outputs never gets here: _optimistic_chain launches it eagerly)

@@ -1121,3 +1121,28 @@ def test_save_keeps_the_old_data_until_the_new_is_written(tmp_path, monkeypatch)
     np.testing.assert_array_equal(mg.load(target)["roi"].values, new["roi"].values)
     mg.save(target, old)  # back to one file: the parts go
     assert sorted(p.name for p in tmp_path.iterdir()) == ["res.nc"]
+
+
+def test_no_collection_while_a_capture_is_open():
+    """hotpath._no_collection: the cyclic collector is off inside, for nested / concurrent captures until the last one
+    leaves, and comes back exactly when it was on before; an exception inside does not leave it off."""
+    import gc
+
+    assert gc.isenabled()
+    with hp._no_collection():
+        assert not gc.isenabled()
+        with hp._no_collection():
+            assert not gc.isenabled()
+        assert not gc.isenabled()
+    assert gc.isenabled()
+    with pytest.raises(RuntimeError):
+        with hp._no_collection():
+            raise RuntimeError("capture failed")
+    assert gc.isenabled()
+    gc.disable()
+    try:
+        with hp._no_collection():
+            assert not gc.isenabled()
+        assert not gc.isenabled()  # it was off before: it stays off
+    finally:
+        gc.enable()
