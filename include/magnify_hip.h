@@ -1019,6 +1019,48 @@ int mg_despeckle_planes(const void* d_src, void* d_dst, int dtype, int64_t n, in
 int mg_outlier_votes(const void* d_src, int dtype, int64_t n, int h, int w, int k, int which, double threshold,
                      int32_t* d_votes, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Background (background.py, the `subtract_background` component; not in the reference; DESIGN.md "Background";
+ * tests/background_ref.py restates every rule).  The input is one contiguous block (n, h, w) of `dtype`: n planes P.
+ * With the radius R (1 .. MG_BACKGROUND_MAX_RADIUS) the WINDOW of a pixel is the (2R + 1) x (2R + 1) square centred on
+ * it; window positions outside the plane are left out, and so are NaN pixels; a window with nothing left gives NaN.
+ *   EROSION   E(y, x) = the minimum of F over the window;
+ *   OPENING   B(y, x) = the maximum of E over the window -- the background: what is left of the plane when everything
+ *             narrower than the window is taken away.
+ * F is the FILTERED plane: d_filtered, a block like d_src (mg_despeckle_planes with MG_OUTLIER_ALL makes one), or, where
+ * d_filtered is null, P itself.  On planes without NaN, B is scipy.ndimage.grey_opening(F, size=2R + 1, mode="nearest"),
+ * bit for bit.  Every value of E and B is one of F's: exact in every dtype; -0.0 and 0.0 are not told apart (either
+ * may be returned).
+ *   MG_BACKGROUND_ESTIMATE: d_dst = B.
+ *   MG_BACKGROUND_SUBTRACT: d_dst = P - B where P > B, else 0, computed in `dtype`; NaN where P or B is NaN.  With
+ *     F = P, B <= P everywhere; with a filtered F it is not, and the clamp at 0 is part of the rule.
+ * Minimum and maximum over a square are separable: the opening is min-x, min-y, max-y, max-x, each a 1-D pass over
+ * blocks of 2R + 1 with running extrema from either end (van Herk / Gil-Werman), about three compares per pixel
+ * whatever R.  Three launches -- the two vertical passes are one kernel, which takes up to MG_BACKGROUND_COLS columns
+ * (fewer where the rows it needs, MG_BACKGROUND_ROWS + 4R, would not fit in LDS) and MG_BACKGROUND_ROWS rows at a time;
+ * the horizontal kernels take MG_BACKGROUND_SPAN columns of up to 64 rows at a time.  Four reads and three writes of
+ * a block in all.  The plane index is not bounded by a grid dimension and every offset into the block is 64-bit.
+ * mg_background_planes: MG_EINVAL, with nothing launched, for a null or misaligned pointer (d_filtered may be null),
+ * an unknown dtype or mode, n, h or w < 0, h above 2^30 or w above 2^20, R outside 1 .. MG_BACKGROUND_MAX_RADIUS,
+ * scratch_bytes below mg_background_scratch_bytes of the same sizes, d_dst or d_scratch equal to another buffer; MG_OK
+ * with nothing launched (and nothing written) when n, h or w is 0.  No allocation, no synchronisation.
+ * ---------------------------------------------------------------------------------- */
+#define MG_BACKGROUND_ESTIMATE 0
+#define MG_BACKGROUND_SUBTRACT 1
+#define MG_BACKGROUND_MAX_RADIUS 128
+#define MG_BACKGROUND_ROWS 128  /* the vertical kernel: output rows of a workgroup's step */
+#define MG_BACKGROUND_COLS 64   /* the vertical kernel: columns of a workgroup's step, at most */
+#define MG_BACKGROUND_SPAN 256  /* the horizontal kernels: output columns of a workgroup's step */
+
+/* The bytes of d_scratch that mg_background_planes needs for these sizes (two blocks (n, h, w) of `dtype`; 0 for an
+ * empty block), or -1 where it would refuse them. */
+int64_t mg_background_scratch_bytes(int dtype, int64_t n, int h, int w, int radius);
+
+/* d_dst (n, h, w) of `dtype` = B (MG_BACKGROUND_ESTIMATE) or the clamped P - B (MG_BACKGROUND_SUBTRACT) of every plane
+ * of d_src; d_scratch: scratch_bytes bytes on the device, aligned like the planes, contents undefined afterwards. */
+int mg_background_planes(const void* d_src, const void* d_filtered, void* d_dst, int dtype, int64_t n, int h, int w,
+                         int radius, int mode, void* d_scratch, int64_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -119,6 +119,18 @@ def _add_despeckle(pipe, despeckle, radius, which, scope):
                   scope=scope)
 
 
+def _add_background(pipe, background, smooth, channel, after="stitch"):
+    """``background=`` of the pipelines (the radius of the opening's window; not in the reference):
+    ``subtract_background`` directly after ``after`` -- on the stitched (on the chip: stitched and rotated) image, so
+    that no tile border lies inside a window -- its settings checked now, not at the first assay.  None adds nothing."""
+    if background is None:
+        return
+    from .background import check_background
+
+    check_background(background, smooth, channel)
+    pipe.add_pipe("subtract_background", after=after, radius=background, smooth=smooth, channel=channel)
+
+
 def microfluidic_chip(data, shape=(8, 8), pinlist=None, blank=None, overlap=102, rotation=0, row_dist=375 / 1.61,
                       col_dist=400 / 1.61, chip_type=None, min_button_diameter=8, max_button_diameter=30,
                       chamber_diameter=60, top_chamber=None, left_chamber=None, low_edge_quantile=0.1,
@@ -128,7 +140,8 @@ def microfluidic_chip(data, shape=(8, 8), pinlist=None, blank=None, overlap=102,
                       register=None, max_shift=8, register_channel=None,
                       segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2,
                       depth=None, depth_window=9,
-                      despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane"):
+                      despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane",
+                      background=None, background_smooth=0, background_channel=None):
     """registry.py:32-110 (``blend``: ``stitch``'s overlap blending; ``register``, ``max_shift``, ``register_channel``:
     its tile registration -- neither is in the reference)."""
     kw = dict(locals())
@@ -145,7 +158,8 @@ def microfluidic_chip_pipe(shape=(8, 8), pinlist=None, blank=None, overlap=102, 
                            register=None, max_shift=8, register_channel=None,
                            segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2,
                            depth=None, depth_window=9,
-                           despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane"):
+                           despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane",
+                           background=None, background_smooth=0, background_channel=None):
     """registry.py:196-271."""
     if chip_type is not None:
         if chip_type == "minichip":
@@ -164,6 +178,7 @@ def microfluidic_chip_pipe(shape=(8, 8), pinlist=None, blank=None, overlap=102, 
     pipe.add_pipe("stitch", overlap=overlap, blend=blend, register=register, max_shift=max_shift,
                   register_channel=register_channel)
     pipe.add_pipe("rotate", rotation=rotation)
+    _add_background(pipe, background, background_smooth, background_channel, after="rotate")
     pipe.add_pipe("find_buttons", row_dist=row_dist, col_dist=col_dist, min_button_diameter=min_button_diameter,
                   max_button_diameter=max_button_diameter, chamber_diameter=chamber_diameter, top_chamber=top_chamber,
                   left_chamber=left_chamber, low_edge_quantile=low_edge_quantile,
@@ -184,7 +199,8 @@ def mrbles(data, spectra, codes, flatfield=1.0, darkfield=0.0, overlap=102, min_
            stage_drift=None,
            segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2,
            depth=None, depth_window=9,
-           despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane"):
+           despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane",
+           background=None, background_smooth=0, background_channel=None):
     """registry.py:274-399."""
     kw = dict(locals())
     kw.pop("data")
@@ -199,7 +215,8 @@ def mrbles_pipe(spectra, codes, flatfield=1.0, darkfield=0.0, overlap=102, min_b
                 stage_drift=None,
                 segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2,
                 depth=None, depth_window=9,
-                despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane"):
+                despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane",
+                background=None, background_smooth=0, background_channel=None):
     """registry.py:402-451."""
     pipe = Pipeline("read")
     pipe.add_pipe("standardize_format")
@@ -208,6 +225,7 @@ def mrbles_pipe(spectra, codes, flatfield=1.0, darkfield=0.0, overlap=102, min_b
     pipe.add_pipe("flatfield_correct", flatfield=flatfield, darkfield=darkfield)
     pipe.add_pipe("stitch", overlap=overlap, blend=blend, register=register, max_shift=max_shift,
                   register_channel=register_channel)
+    _add_background(pipe, background, background_smooth, background_channel)
     pipe.add_pipe("find_beads", min_bead_diameter=min_bead_diameter, max_bead_diameter=max_bead_diameter,
                   low_edge_quantile=low_edge_quantile, high_edge_quantile=high_edge_quantile, num_iter=num_iter,
                   min_roundness=min_roundness, roi_length=roi_length, search_channel=search_channel,
@@ -228,7 +246,8 @@ def beads(data, flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=10,
           stage_drift=None,
           segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2,
           depth=None, depth_window=9,
-          despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane"):
+          despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane",
+          background=None, background_smooth=0, background_channel=None):
     """registry.py:454-565."""
     kw = dict(locals())
     kw.pop("data")
@@ -243,7 +262,8 @@ def beads_pipe(flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=5, m
                stage_drift=None,
                segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2,
                depth=None, depth_window=9,
-               despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane"):
+               despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane",
+               background=None, background_smooth=0, background_channel=None):
     """registry.py:568-612 (note the 5/25 defaults here versus 10/50 in ``beads``)."""
     pipe = Pipeline("read")
     pipe.add_pipe("standardize_format")
@@ -252,6 +272,7 @@ def beads_pipe(flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=5, m
     pipe.add_pipe("flatfield_correct", flatfield=flatfield, darkfield=darkfield)
     pipe.add_pipe("stitch", overlap=overlap, blend=blend, register=register, max_shift=max_shift,
                   register_channel=register_channel)
+    _add_background(pipe, background, background_smooth, background_channel)
     pipe.add_pipe("find_beads", min_bead_diameter=min_bead_diameter, max_bead_diameter=max_bead_diameter,
                   low_edge_quantile=low_edge_quantile, high_edge_quantile=high_edge_quantile, num_iter=num_iter,
                   min_roundness=min_roundness, roi_length=roi_length, search_channel=search_channel,
@@ -265,17 +286,20 @@ def beads_pipe(flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=5, m
 
 def image(data, overlap=102, rotation=0, roi_only=False, drop_tiles=True, blend=None,
           register=None, max_shift=8, register_channel=None, depth=None, depth_window=9,
-          despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane"):
+          despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane",
+          background=None, background_smooth=0, background_channel=None):
     """registry.py:615-669."""
     return image_pipe(overlap=overlap, rotation=rotation, roi_only=roi_only, drop_tiles=drop_tiles, blend=blend,
                       register=register, max_shift=max_shift, register_channel=register_channel, depth=depth,
                       depth_window=depth_window, despeckle=despeckle, despeckle_radius=despeckle_radius,
-                      despeckle_which=despeckle_which, despeckle_scope=despeckle_scope)(data=data)
+                      despeckle_which=despeckle_which, despeckle_scope=despeckle_scope, background=background,
+                      background_smooth=background_smooth, background_channel=background_channel)(data=data)
 
 
 def image_pipe(overlap=102, rotation=0, roi_only=False, drop_tiles=True, blend=None,
                register=None, max_shift=8, register_channel=None, depth=None, depth_window=9,
-               despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane"):
+               despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane",
+               background=None, background_smooth=0, background_channel=None):
     """registry.py:672-693."""
     pipe = Pipeline("read")
     pipe.add_pipe("standardize_format")
@@ -283,6 +307,7 @@ def image_pipe(overlap=102, rotation=0, roi_only=False, drop_tiles=True, blend=N
     _add_despeckle(pipe, despeckle, despeckle_radius, despeckle_which, despeckle_scope)
     pipe.add_pipe("stitch", overlap=overlap, blend=blend, register=register, max_shift=max_shift,
                   register_channel=register_channel)
+    _add_background(pipe, background, background_smooth, background_channel)
     pipe.add_pipe("rotate", rotation=rotation)
     pipe.add_pipe("drop", roi_only=roi_only, drop_tiles=drop_tiles)
     pipe.add_pipe("restore_format")
