@@ -938,7 +938,9 @@ int mg_render_roi_montage(const void* d_roi, int dtype, int64_t stride_m, int64_
  * a neighbour outside the plane being the edge pixel (np.pad(mode="edge")).  Integer pixels: int32 arithmetic, exact.
  * Float pixels: float64, every operation rounded on its own, fabs((2 * c - l) - r) + fabs((2 * c - u) - d).
  * Every entry: MG_EINVAL, with nothing launched, for a null or misaligned pointer, an unknown dtype, n, h or w < 0,
- * z < 1; MG_OK with nothing launched (and nothing written) when n, h or w is 0.  No allocation, no synchronisation.
+ * h above 2^30 or w above 2^20 (the limits of all plane filters: csrc/mg_planes.h), z < 1; then MG_OK with nothing
+ * launched (and nothing written) when n, h or w is 0 -- the arguments are judged first, so a misaligned pointer is
+ * refused with an empty block too.  No allocation, no synchronisation.
  * ---------------------------------------------------------------------------------- */
 #define MG_DEPTH_MAX 0
 #define MG_DEPTH_MEAN 1
@@ -991,8 +993,9 @@ int mg_depth_fuse(const void* d_src, int dtype, int64_t n, int z, int h, int w, 
  * The inequality is strict (at threshold 0 a pixel equal to its median passes no test) and false whenever d is NaN
  * (a NaN pixel, a NaN median, inf - inf): such a pixel is kept.
  * Both entries: MG_EINVAL, with nothing launched, for a null or misaligned pointer, an unknown dtype or `which`, n, h
- * or w < 0, h above 2^30 or w above 2^20, k outside 1 .. MG_DESPECKLE_MAX_K, a negative or NaN threshold where it is used; MG_OK
- * with nothing launched (and nothing written) when n, h or w is 0.  A workgroup takes one MG_DESPECKLE_TILE x
+ * or w < 0, h above 2^30 or w above 2^20, k outside 1 .. MG_DESPECKLE_MAX_K, a negative or NaN threshold where it is used;
+ * then MG_OK with nothing launched (and nothing written) when n, h or w is 0 -- the arguments are judged first, so a
+ * misaligned pointer is refused with an empty block too (csrc/mg_planes.h).  A workgroup takes one MG_DESPECKLE_TILE x
  * MG_DESPECKLE_TILE output tile of a plane at a time, the tile and its halo of k in LDS; the plane index is not bounded by a grid
  * dimension and every offset into the block is 64-bit.  One kernel launch behind the clearing of the counters; no
  * allocation, no synchronisation.

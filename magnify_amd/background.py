@@ -17,9 +17,9 @@ import numpy as np
 import torch
 
 from . import _native as nat
-from . import registry, xr_lite
-from .utils import to_list
-from .xr_lite import DataArray
+from . import despeckle, registry
+from ._dataset import channel_indexes, page_view, plane_block
+from .utils import int_in, to_list
 
 MAX_RADIUS = nat.DEFINES["MG_BACKGROUND_MAX_RADIUS"]
 ROWS = nat.DEFINES["MG_BACKGROUND_ROWS"]  # the vertical kernel: output rows / columns (at most) of a workgroup's step
@@ -34,10 +34,8 @@ def check_background(radius, smooth=0, channel=None):
     """The settings of ``subtract_background`` as the pipelines take them: ``radius`` an integer in 1 .. MAX_RADIUS,
     ``smooth`` 0, 1 or 2, ``channel`` None, a name (a string or an integer index) or a list of them.  ValueError
     otherwise."""
-    if isinstance(radius, (bool, np.bool_)) or not isinstance(radius, (int, np.integer)) or not 1 <= radius <= MAX_RADIUS:
-        raise ValueError(f"background radius must be an integer in 1 .. {MAX_RADIUS}, got {radius!r}")
-    if isinstance(smooth, (bool, np.bool_)) or not isinstance(smooth, (int, np.integer)) or smooth not in SMOOTH:
-        raise ValueError(f"background smooth must be one of {SMOOTH}, got {smooth!r}")
+    int_in("background radius", radius, 1, MAX_RADIUS)
+    int_in("background smooth", smooth, SMOOTH[0], SMOOTH[-1])
     if channel is not None:
         names = to_list(channel)
         if not names or any(isinstance(c, (bool, np.bool_)) or not isinstance(c, (str, int, np.integer)) for c in names):
@@ -46,10 +44,9 @@ def check_background(radius, smooth=0, channel=None):
 
 def _run(planes, radius, smooth, what):
     from . import hotpath
-    from .despeckle import _ALL, _block
 
     check_background(radius, smooth)
-    block, lead, n, h, w, code = _block(planes, f"background.{what}")
+    block, _, n, h, w, code, _ = plane_block(planes, f"background.{what}")
     out = torch.empty_like(block)
     if block.numel() == 0:
         return out
@@ -66,7 +63,7 @@ def _run(planes, radius, smooth, what):
         part, filtered, work = src[i:i + m], 0, scratch.data_ptr()
         if smooth:
             filtered, work = work, work + group * plane_bytes
-            hotpath._call("mg_despeckle_planes", part.data_ptr(), filtered, code, m, h, w, smooth, _ALL, 0.0, 0, 0,
+            hotpath._call("mg_despeckle_planes", part.data_ptr(), filtered, code, m, h, w, smooth, despeckle.ALL, 0.0, 0, 0,
                           hotpath._stream())
         hotpath._call("mg_background_planes", part.data_ptr(), filtered, dst[i:i + m].data_ptr(), code, m, h, w, radius,
                       _MODES[what], work, m * per_plane, hotpath._stream())
@@ -92,42 +89,21 @@ def subtract_background(xp, radius, smooth=0, channel=None):
     ``im_y`` / ``im_x`` or ``y`` / ``x``; every other dimension counts planes.  ``channel``: a name or a list of names
     -- only these channels' planes are changed, the others pass through bit for bit (None: every plane).  Every
     dimension, coordinate and attribute is kept; ``attrs["background_radius"]`` is the radius."""
-    from ._dataset import channel_indexes
-    from .preprocess import to_device
-
     check_background(radius, smooth, channel)
-    xp = xr_lite.from_any(xp)
-    is_array = isinstance(xp, DataArray)
-    if not is_array and "image" not in xp.data_vars:
-        raise ValueError("subtract_background: the Dataset has no 'image' variable")
-    image = xp if is_array else xp["image"]  # (with the dataset's coordinates: the channel names)
-    pages = next((p for p in (("im_y", "im_x"), ("y", "x")) if p[0] in image.dims and p[1] in image.dims), None)
-    if pages is None:
-        raise ValueError(f"subtract_background: no page dimensions (im_y, im_x) or (y, x) in {image.dims}")
+    view = page_view(xp, "image", (("im_y", "im_x"), ("y", "x")), "subtract_background", first=("channel",))
     picked = None
     if channel is not None:
-        if "channel" not in image.dims:
+        if "channel" not in view.var.dims:
             raise ValueError(f"subtract_background: channel={channel!r}, but the image has no channel dimension")
-        picked = sorted(set(channel_indexes(image, channel)))  # ChannelError (a ValueError) for an unknown name
-    lead = tuple(d for d in image.dims if d not in pages and d != "channel")
-    if "channel" in image.dims:
-        lead = ("channel",) + lead
-    data = image.transpose(*lead, *pages).data
-    if isinstance(data, np.ndarray):
-        data = np.ascontiguousarray(data)
-    planes = to_device(data)
+        # (the source has the channel names; ChannelError, a ValueError, for an unknown one)
+        picked = sorted(set(channel_indexes(view.source, channel)))
     if picked is None:
-        out = subtract(planes, radius, smooth)
+        out = subtract(view.planes, radius, smooth)
     else:
-        out = planes.clone()
+        out = view.planes.clone()
         for c in picked:
-            out[c] = subtract(planes[c], radius, smooth)
-    extra = {"background_radius": int(radius)}
-    cleaned = DataArray(out, lead + pages, None, image.name, image.attrs).transpose(*image.dims)
-    if is_array:
-        return DataArray(cleaned.raw, image.dims, dict(xp.coords), xp.name, dict(xp.attrs, **extra))
-    res = xp.copy()
-    res.attrs.update(extra)
-    res["image"] = cleaned
-    res._cache.pop("image_minmax", None)  # (the stitch's min / max of the image as it was: the finders take their own)
+            out[c] = subtract(view.planes[c], radius, smooth)
+    res = view.rebuild(out, {"background_radius": int(radius)})
+    if not view.is_array:
+        res._cache.pop("image_minmax", None)  # (the stitch's min / max of the image as it was: the finders take their own)
     return res

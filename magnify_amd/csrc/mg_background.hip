@@ -8,7 +8,7 @@
 #include <algorithm>
 #include <limits>
 
-#include "mg_common.h"
+#include "mg_planes.h"
 
 namespace {
 
@@ -246,10 +246,10 @@ int launch_bg_pass(const T* src, const T* orig, T* dst, int64_t n, int h, int w,
   return MG_OK;
 }
 
-// Bytes of two blocks (n, h, w), or -1 where the sizes are refused.
-static int64_t bg_scratch_bytes(int dtype, int64_t n, int h, int w, int radius) {
-  if (dtype != MG_U8 && dtype != MG_U16 && dtype != MG_F32 && dtype != MG_F64) return -1;
-  if (n < 0 || h < 0 || w < 0 || h > (1 << 30) || w > (1 << 20) || radius < 1 || radius > MG_BACKGROUND_MAX_RADIUS) return -1;
+// Bytes of two blocks (n, h, w), or -1 where the sizes or one of `pixels` (mg_planes_check) are refused.
+static int64_t bg_scratch_bytes(int dtype, int64_t n, int h, int w, int radius, std::initializer_list<const void*> pixels) {
+  if (mg_planes_check(dtype, n, h, w, pixels) == MG_PLANES_REFUSED) return -1;
+  if (radius < 1 || radius > MG_BACKGROUND_MAX_RADIUS) return -1;
   const int64_t per_plane = 2 * (int64_t)h * w * mg_elem_size(dtype);  // at most 2^54
   if (per_plane && n > (INT64_MAX / 2) / per_plane) return -1;
   return n * per_plane;
@@ -258,19 +258,16 @@ static int64_t bg_scratch_bytes(int dtype, int64_t n, int h, int w, int radius) 
 }  // namespace
 
 extern "C" int64_t mg_background_scratch_bytes(int dtype, int64_t n, int h, int w, int radius) {
-  return bg_scratch_bytes(dtype, n, h, w, radius);
+  return bg_scratch_bytes(dtype, n, h, w, radius, {});
 }
 
 extern "C" int mg_background_planes(const void* d_src, const void* d_filtered, void* d_dst, int dtype, int64_t n, int h, int w,
                                     int radius, int mode, void* d_scratch, int64_t scratch_bytes, void* stream) {
-  const int64_t need = bg_scratch_bytes(dtype, n, h, w, radius);
+  const int64_t need = bg_scratch_bytes(dtype, n, h, w, radius, {d_src, d_filtered, d_dst, d_scratch});
   if (need < 0 || (mode != MG_BACKGROUND_ESTIMATE && mode != MG_BACKGROUND_SUBTRACT)) return MG_EINVAL;
   if (!d_src || !d_dst || d_dst == d_src || d_dst == d_filtered || scratch_bytes < need) return MG_EINVAL;
   if (need && (!d_scratch || d_scratch == d_src || d_scratch == d_dst || d_scratch == d_filtered)) return MG_EINVAL;
-  const uintptr_t all = reinterpret_cast<uintptr_t>(d_src) | reinterpret_cast<uintptr_t>(d_filtered) |
-                        reinterpret_cast<uintptr_t>(d_dst) | reinterpret_cast<uintptr_t>(d_scratch);
-  if (all % mg_elem_size(dtype)) return MG_EINVAL;
-  if (n == 0 || h == 0 || w == 0) return MG_OK;
+  if (need == 0) return MG_OK;  // (n, h or w is 0)
   hipStream_t s = mg_stream(stream);
   return mg_dispatch_pixel(dtype, [&](auto t) {
     using T = decltype(t);

@@ -3,9 +3,7 @@
 // (mg_depth_focus_totals), and the per-pixel pick of the sharpest slice (mg_depth_fuse, "extended depth of field").
 // The focus measure is the modified Laplacian ML = |2c - l - r| + |2c - u - d| with edge-clamped neighbours.
 // Oracle: tests/depth_ref.py, the same integer / float64 operations in the same order.
-#include <algorithm>
-
-#include "mg_common.h"
+#include "mg_planes.h"
 
 namespace {
 
@@ -60,8 +58,8 @@ struct DepthFold {
   }
 };
 
-// Grid: x = workgroups that walk the dwords of an output plane, y = workgroups that walk the stacks.  The planes of a
-// stack are contiguous, so a plane is one run of h * w pixels: every lane owns the PX pixels of one ALIGNED dword of
+// Grid: mg_plane_grid, the items of a plane being blocks of 256 lanes (the lanes stride over the plane themselves).  The
+// planes of a stack are contiguous, so a plane is one run of h * w pixels: every lane owns the PX pixels of one ALIGNED dword of
 // the output (a plane of odd size starts anywhere in a dword: lane j of a plane whose first pixel is the s-th of its
 // dword covers pixels PX * j - s .. PX * j - s + PX - 1); the first and last lane of a plane take their pixels one
 // by one, every other lane reads one (unaligned) dword per slice and stores one aligned dword.  METHOD PICK reads
@@ -73,7 +71,7 @@ __global__ __launch_bounds__(256) void k_depth_project(const T* __restrict__ src
   constexpr int PX = DepthPx<T>::N;
   using F = DepthFold<T, METHOD>;
   const int64_t base_px = (int64_t)((reinterpret_cast<uintptr_t>(dst) / sizeof(T)) % PX);
-  for (int64_t stack = blockIdx.y; stack < n_stacks; stack += gridDim.y) {
+  MG_FOR_BLOCK_PLANES(stack, n_stacks) {
     const T* ps = src + stack * z * plane;
     T* pd = dst + stack * plane;
     int z0 = 0, z1 = z;
@@ -126,16 +124,12 @@ __global__ __launch_bounds__(256) void k_depth_project(const T* __restrict__ src
 template <class T, int METHOD>
 int launch_project(const void* d_src, void* d_dst, int64_t n, int z, int h, int w, const int32_t* d_pick, hipStream_t s) {
   constexpr int PX = DepthPx<T>::N;
-  if ((reinterpret_cast<uintptr_t>(d_src) | reinterpret_cast<uintptr_t>(d_dst)) % sizeof(T)) return MG_EINVAL;
   const int64_t plane = (int64_t)h * w;
   // lanes per plane: one more than the plane's dwords when a plane can start inside a dword
   const int64_t lanes = (plane + PX - 1) / PX + (PX > 1 ? 1 : 0);
-  const int64_t blocks = (lanes + 255) / 256;
-  const unsigned gy = (unsigned)std::min<int64_t>(n, 65535);
   // 16 workgroups per CU in all when there is that much work; each walks its share of the plane
-  const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(blocks, std::max<int64_t>(1, 4096 / gy)));
-  hipLaunchKernelGGL((k_depth_project<T, METHOD>), dim3(gx, gy), dim3(256), 0, s, (const T*)d_src, (T*)d_dst, n, z, plane,
-                     d_pick, lanes);
+  hipLaunchKernelGGL((k_depth_project<T, METHOD>), mg_plane_grid((lanes + 255) / 256, n, 4096), dim3(256), 0, s,
+                     (const T*)d_src, (T*)d_dst, n, z, plane, d_pick, lanes);
   MG_CHECK_LAUNCH();
   return MG_OK;
 }
@@ -169,14 +163,14 @@ __global__ __launch_bounds__(256) void k_depth_focus_totals(const T* __restrict_
                                                             int tiles_x, int tiles_y, void* __restrict__ totals) {
   using A = mg_acc_t<T>;
   const int n_tiles = tiles_x * tiles_y;
-  for (int64_t slice = blockIdx.y; slice < n_slices; slice += gridDim.y) {
+  MG_FOR_BLOCK_PLANES(slice, n_slices) {
     const T* p = src + slice * ((int64_t)h * w);
     A acc = 0;
-    for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-      const int tyi = tile / tiles_x, txi = tile - tyi * tiles_x;
-      const int x = txi * 256 + (int)threadIdx.x;
+    MG_FOR_BLOCK_ITEMS(tile, n_tiles) {
+      const MgTile at = mg_tile(tile, tiles_x);
+      const int x = at.x * 256 + (int)threadIdx.x;
       if (x >= w) continue;
-      const int y0 = tyi * FT_ROWS, y1 = min(y0 + FT_ROWS, h);
+      const int y0 = at.y * FT_ROWS, y1 = min(y0 + FT_ROWS, h);
       const int xl = max(x - 1, 0), xr = min(x + 1, w - 1);
       T u = p[(int64_t)max(y0 - 1, 0) * w + x], c = p[(int64_t)y0 * w + x];
       for (int y = y0; y < y1; ++y) {
@@ -200,26 +194,23 @@ __global__ __launch_bounds__(256) void k_depth_focus_totals(const T* __restrict_
 
 template <class T>
 int launch_focus_totals(const void* d_src, int64_t n, int z, int h, int w, void* d_totals, hipStream_t s) {
-  if (reinterpret_cast<uintptr_t>(d_src) % sizeof(T)) return MG_EINVAL;
   const int64_t n_slices = n * z;
   if (mg_zero_async(d_totals, (size_t)n_slices * 8, s) != hipSuccess) return MG_ELAUNCH;
   const int64_t tiles_x = ((int64_t)w + 255) / 256, tiles_y = ((int64_t)h + FT_ROWS - 1) / FT_ROWS;
   if (tiles_x * tiles_y > 0x7FFFFFFF) return MG_EINVAL;
-  const unsigned gy = (unsigned)std::min<int64_t>(n_slices, 65535);
-  // one atomic per workgroup and slice: at most 64 workgroups share a slice
-  const int64_t share = std::max<int64_t>(1, std::min<int64_t>(64, 4096 / gy));
-  const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(tiles_x * tiles_y, share));
   static_assert(MG_FOLD_WAVES * MG_WAVE == 256, "mg_block_fold folds workgroups of 256 threads");
-  hipLaunchKernelGGL((k_depth_focus_totals<T>), dim3(gx, gy), dim3(256), 0, s, (const T*)d_src, n_slices, h, w, (int)tiles_x,
-                     (int)tiles_y, d_totals);
+  // one atomic per workgroup and slice: at most 64 workgroups share a slice
+  hipLaunchKernelGGL((k_depth_focus_totals<T>), mg_plane_grid(tiles_x * tiles_y, n_slices, 4096, 64), dim3(256), 0, s,
+                     (const T*)d_src, n_slices, h, w, (int)tiles_x, (int)tiles_y, d_totals);
   MG_CHECK_LAUNCH();
   return MG_OK;
 }
 
 // ---- mg_depth_fuse ---------------------------------------------------------------------------------------------------
 
-// One workgroup owns an output tile of DF x DF pixels of one stack and loops over z.  LDS, sized by the launch for the
-// window half-width k: region A holds the slice's tile with a halo of k + 1 (PH x PH pixels, edge-clamped), region B
+// One workgroup owns an output tile of DF x DF pixels of one stack and loops over z (mg_plane_grid with no budget: a
+// workgroup per tile).  LDS, sized by the launch for the window half-width k: region A holds the slice's tile with a
+// halo of k + 1 (PH x PH pixels, mg_fill_tile with DF_NLOAD loads of a thread in flight), region B
 // its ML (MH x MH, MH = DF + 2k, zero outside the plane).  The row sums (MH rows x DF columns) then take region A's
 // place -- every thread has its own four pixels in registers by then -- and the column sums of those are the
 // measures.  Lanes run along x in every pass: 32 consecutive words per half wave, no bank conflict.  A thread owns
@@ -233,6 +224,12 @@ static_assert(DF == 32 && DF_PER_THREAD == 4, "a thread's outputs: column t & 31
 __device__ __forceinline__ int depth_div(int i, uint32_t inv) { return (int)(((uint32_t)i * inv) >> 20); }
 static_assert((DF + 2 * MG_DEPTH_MAX_K + 2) * (DF + 2 * MG_DEPTH_MAX_K + 2) <= 4096 && DF + 2 * MG_DEPTH_MAX_K + 2 <= 64,
               "depth_div's range");
+struct DepthSide {  // the side of a padded tile, known at the launch (mg_fill_tile)
+  int n;
+  uint32_t inv;
+  __device__ __forceinline__ int row(int i) const { return depth_div(i, inv); }
+};
+constexpr int DF_NLOAD = 8;  // DESIGN.md, "Plane filters: what they share", has the measurements
 
 template <class T>
 static inline size_t depth_fuse_lds(int k, size_t* region_a) {
@@ -254,22 +251,15 @@ __global__ __launch_bounds__(256) void k_depth_fuse(const T* __restrict__ src, T
   const int ph = DF + 2 * k + 2, mh = DF + 2 * k, win = 2 * k + 1;
   const uint32_t inv_ph = ((1u << 20) + ph - 1) / ph, inv_mh = ((1u << 20) + mh - 1) / mh;
   const int t = threadIdx.x, ox = t & (DF - 1), oy0 = DF_PER_THREAD * (t / DF);
-  const int tyi = blockIdx.x / tiles_x, txi = blockIdx.x - tyi * tiles_x;
-  const int y0 = tyi * DF, x0 = txi * DF;
+  const int y0 = mg_tile(blockIdx.x, tiles_x).y * DF, x0 = mg_tile(blockIdx.x, tiles_x).x * DF;
   const int64_t plane = (int64_t)h * w;
-  for (int64_t stack = blockIdx.y; stack < n_stacks; stack += gridDim.y) {
+  MG_FOR_BLOCK_PLANES(stack, n_stacks) {
     M best[DF_PER_THREAD];
     T best_px[DF_PER_THREAD];
     int best_z[DF_PER_THREAD];
     for (int zi = 0; zi < z; ++zi) {
       const T* p = src + (stack * z + zi) * plane;
-      // the tile and its halo, neighbours outside the plane clamped to the edge pixel
-      for (int i = t; i < ph * ph; i += 256) {
-        const int yy = depth_div(i, inv_ph), xx = i - yy * ph;
-        const int gy = min(max(y0 - k - 1 + yy, 0), h - 1), gx = min(max(x0 - k - 1 + xx, 0), w - 1);
-        s_px[i] = p[(int64_t)gy * w + gx];
-      }
-      __syncthreads();
+      mg_fill_tile<DF_NLOAD>(s_px, p, h, w, y0, x0, k + 1, DepthSide{ph, inv_ph}, false);  // (the loop ends in a barrier)
       for (int i = t; i < mh * mh; i += 256) {
         const int my = depth_div(i, inv_mh), mx = i - my * mh;
         const int gy = y0 - k + my, gx = x0 - k + mx;
@@ -328,7 +318,6 @@ __global__ __launch_bounds__(256) void k_depth_fuse(const T* __restrict__ src, T
 
 template <class T>
 int launch_fuse(const void* d_src, void* d_dst, uint8_t* d_index, int64_t n, int z, int h, int w, int k, hipStream_t s) {
-  if ((reinterpret_cast<uintptr_t>(d_src) | reinterpret_cast<uintptr_t>(d_dst)) % sizeof(T)) return MG_EINVAL;
   const int64_t tiles_x = ((int64_t)w + DF - 1) / DF, tiles_y = ((int64_t)h + DF - 1) / DF;
   if (tiles_x * tiles_y > 0x7FFFFFFF) return MG_EINVAL;
   size_t region_a;
@@ -336,26 +325,21 @@ int launch_fuse(const void* d_src, void* d_dst, uint8_t* d_index, int64_t n, int
   static_assert(sizeof(double) * ((DF + 2 * MG_DEPTH_MAX_K + 2) * (DF + 2 * MG_DEPTH_MAX_K + 2) +
                                   (DF + 2 * MG_DEPTH_MAX_K) * (DF + 2 * MG_DEPTH_MAX_K)) <= 65536,
                 "the largest window of float64 pixels fits the 64 KiB a workgroup may ask for");
-  const unsigned gy = (unsigned)std::min<int64_t>(n, 65535);
-  hipLaunchKernelGGL((k_depth_fuse<T>), dim3((unsigned)(tiles_x * tiles_y), gy), dim3(256), lds, s, (const T*)d_src, (T*)d_dst,
+  hipLaunchKernelGGL((k_depth_fuse<T>), mg_plane_grid(tiles_x * tiles_y, n), dim3(256), lds, s, (const T*)d_src, (T*)d_dst,
                      d_index, n, z, h, w, k, (int)tiles_x, (uint32_t)region_a);
   MG_CHECK_LAUNCH();
   return MG_OK;
-}
-
-bool depth_args_ok(const void* d_src, int dtype, int64_t n, int z, int h, int w) {
-  if (!d_src || n < 0 || z < 1 || h < 0 || w < 0) return false;
-  return dtype == MG_U8 || dtype == MG_U16 || dtype == MG_F32 || dtype == MG_F64;
 }
 
 }  // namespace
 
 extern "C" int mg_depth_project(const void* d_src, void* d_dst, int dtype, int64_t n, int z, int h, int w, int method,
                                 const int32_t* d_pick, void* stream) {
-  if (!depth_args_ok(d_src, dtype, n, z, h, w) || !d_dst || d_src == d_dst) return MG_EINVAL;
+  const MgPlanes block = mg_planes_check(dtype, n, h, w, {d_src, d_dst});
+  if (block == MG_PLANES_REFUSED || z < 1 || !d_src || !d_dst || d_src == d_dst) return MG_EINVAL;
   if (method != MG_DEPTH_MAX && method != MG_DEPTH_MEAN && method != MG_DEPTH_PICK) return MG_EINVAL;
   if (method == MG_DEPTH_PICK && !d_pick) return MG_EINVAL;
-  if (n == 0 || h == 0 || w == 0) return MG_OK;
+  if (block == MG_PLANES_EMPTY) return MG_OK;
   hipStream_t s = mg_stream(stream);
   return mg_dispatch_pixel(dtype, [&](auto t) {
     using T = decltype(t);
@@ -369,8 +353,9 @@ extern "C" int mg_depth_project(const void* d_src, void* d_dst, int dtype, int64
 
 extern "C" int mg_depth_focus_totals(const void* d_src, int dtype, int64_t n, int z, int h, int w, void* d_totals,
                                      void* stream) {
-  if (!depth_args_ok(d_src, dtype, n, z, h, w) || !d_totals || reinterpret_cast<uintptr_t>(d_totals) % 8) return MG_EINVAL;
-  if (n == 0 || h == 0 || w == 0) return MG_OK;
+  const MgPlanes block = mg_planes_check(dtype, n, h, w, {d_src});
+  if (block == MG_PLANES_REFUSED || z < 1 || !d_src || !d_totals || reinterpret_cast<uintptr_t>(d_totals) % 8) return MG_EINVAL;
+  if (block == MG_PLANES_EMPTY) return MG_OK;
   hipStream_t s = mg_stream(stream);
   return mg_dispatch_pixel(dtype, [&](auto t) {
     return launch_focus_totals<decltype(t)>(d_src, n, z, h, w, d_totals, s);
@@ -379,9 +364,10 @@ extern "C" int mg_depth_focus_totals(const void* d_src, int dtype, int64_t n, in
 
 extern "C" int mg_depth_fuse(const void* d_src, int dtype, int64_t n, int z, int h, int w, int k, void* d_dst,
                              uint8_t* d_index, void* stream) {
-  if (!depth_args_ok(d_src, dtype, n, z, h, w) || !d_dst || d_src == d_dst) return MG_EINVAL;
+  const MgPlanes block = mg_planes_check(dtype, n, h, w, {d_src, d_dst});
+  if (block == MG_PLANES_REFUSED || z < 1 || !d_src || !d_dst || d_src == d_dst) return MG_EINVAL;
   if (z > MG_DEPTH_MAX_Z || k < 1 || k > MG_DEPTH_MAX_K) return MG_EINVAL;
-  if (n == 0 || h == 0 || w == 0) return MG_OK;
+  if (block == MG_PLANES_EMPTY) return MG_OK;
   hipStream_t s = mg_stream(stream);
   return mg_dispatch_pixel(dtype, [&](auto t) {
     return launch_fuse<decltype(t)>(d_src, d_dst, d_index, n, z, h, w, k, s);

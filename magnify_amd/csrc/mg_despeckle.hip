@@ -2,10 +2,9 @@
 // of its (2k + 1)^2 window (edge-replicated) and replaced by it where it stands out -- or where a defect map says so
 // (mg_despeckle_planes); the same test counted over the planes of one sensor gives the votes a defect map is made from
 // (mg_outlier_votes).  Oracle: tests/despeckle_ref.py.
-#include <algorithm>
-
 #include "mg_common.h"
 #include "mg_mediannet.h"
+#include "mg_planes.h"
 #include "mg_select.h"
 
 namespace {
@@ -61,14 +60,12 @@ __device__ __forceinline__ bool despeckle_test(const DespeckleWindow<T, WIN>& wi
          (which != MG_OUTLIER_BRIGHT && -d > threshold);
 }
 
-// Grid: x = workgroups that walk the tiles of a plane, y = workgroups that walk the planes.  LDS: the tile with its
-// halo of K, PH x PH pixels of T, coordinates clamped into the plane when it is filled -- the compute loop has no edge
-// cases and never reads another plane.  A thread's loads of the fill are all issued before the first is stored: NLOAD
-// cache lines in flight per wave (one load at a time leaves the kernel waiting on memory latency).  Thread t owns
-// column t % DS and rows DS_ROWS * (t / DS) ..: it walks down with the window's keys in registers, one new window row
-// per pixel.  VOTES: nothing is written but an int32 atomic per pixel that passes; otherwise d_dst gets every pixel and
-// d_counts (if any) one 64-bit atomic per workgroup and plane, after the workgroup's last tile of the plane: the
-// counter of a plane is one address, and an atomic per tile on it took longer than all the rest of the kernel.
+// Grid and walk: mg_plane_grid.  LDS: the tile with its halo of K, PH x PH pixels of T, filled by mg_fill_tile with all
+// of a thread's loads in flight at once.  Thread t owns column t % DS and rows DS_ROWS * (t / DS) ..: it walks down with
+// the window's keys in registers, one new window row per pixel.  VOTES: nothing is written but an int32 atomic per
+// pixel that passes; otherwise d_dst gets every pixel and d_counts (if any) one 64-bit atomic per workgroup and plane,
+// after the workgroup's last tile of the plane: the counter of a plane is one address, and an atomic per tile on it
+// took longer than all the rest of the kernel.
 template <class T, int K, bool VOTES>
 __global__ __launch_bounds__(256) void k_despeckle(const T* __restrict__ src, T* __restrict__ dst, int64_t n, int h, int w,
                                                    int tiles_x, int n_tiles, int which, double threshold,
@@ -79,29 +76,14 @@ __global__ __launch_bounds__(256) void k_despeckle(const T* __restrict__ src, T*
   const int t = threadIdx.x, ox = t % DS, oy0 = DS_ROWS * (t / DS);
   const int64_t plane = (int64_t)h * w;
   bool fresh = true;  // (uniform) nobody has read the tile in LDS yet
-  for (int64_t pi = blockIdx.y; pi < n; pi += gridDim.y) {
+  MG_FOR_BLOCK_PLANES(pi, n) {
     int replaced = 0;
-    for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-      const int tyi = tile / tiles_x, txi = tile - tyi * tiles_x;
-      const int y0 = tyi * DS, x0 = txi * DS;
+    MG_FOR_BLOCK_ITEMS(tile, n_tiles) {
+      const MgTile at = mg_tile(tile, tiles_x);
+      const int y0 = at.y * DS, x0 = at.x * DS;
       const int x = x0 + ox, rows = min(DS_ROWS, h - (y0 + oy0));  // (rows <= 0: the thread has no pixel)
-      // the fill reads relative to the tile's first pixel: 32-bit byte offsets (at most (PH - 1) (w + 1) pixels, w <= 2^20)
-      const int gy0 = max(y0 - K, 0), gx0 = max(x0 - K, 0);
-      const char* first = reinterpret_cast<const char*>(src + pi * plane + (int64_t)gy0 * w + gx0);
-      T staged[NLOAD];
-#pragma unroll
-      for (int j = 0; j < NLOAD; ++j) {  // (the last one may be past the tile: it reads the tile's last pixel again)
-        const int i = min(t + 256 * j, PH * PH - 1), yy = i / PH, xx = i - yy * PH;
-        const int gy = min(max(y0 - K + yy, 0), h - 1), gx = min(max(x0 - K + xx, 0), w - 1);
-        const uint32_t off = ((uint32_t)(gy - gy0) * (uint32_t)w + (uint32_t)(gx - gx0)) * (uint32_t)sizeof(T);
-        staged[j] = *reinterpret_cast<const T*>(first + off);
-      }
-      if (!fresh) __syncthreads();  // every thread is done with the last tile
+      mg_fill_tile<NLOAD>(s_px, src + pi * plane, h, w, y0, x0, K, MgSide<PH>{}, !fresh);
       fresh = false;
-#pragma unroll
-      for (int j = 0; j < NLOAD; ++j)
-        if (t + 256 * j < PH * PH) s_px[t + 256 * j] = staged[j];
-      __syncthreads();
       if (x < w) {
         DespeckleWindow<T, WIN> window;
         const T* col = s_px + oy0 * PH + ox;
@@ -136,7 +118,6 @@ __global__ __launch_bounds__(256) void k_despeckle(const T* __restrict__ src, T*
 template <class T, int K, bool VOTES>
 int launch_despeckle(const void* d_src, void* d_dst, int64_t n, int h, int w, int which, double threshold,
                      const uint8_t* d_defects, int64_t* d_counts, int32_t* d_votes, hipStream_t s) {
-  if ((reinterpret_cast<uintptr_t>(d_src) | reinterpret_cast<uintptr_t>(d_dst)) % sizeof(T)) return MG_EINVAL;
   const int64_t tiles_x = ((int64_t)w + DS - 1) / DS, tiles_y = ((int64_t)h + DS - 1) / DS;
   if (tiles_x * tiles_y > 0x7FFFFFFF) return MG_EINVAL;
   if (VOTES) {
@@ -147,11 +128,9 @@ int launch_despeckle(const void* d_src, void* d_dst, int64_t n, int h, int w, in
   static_assert(sizeof(double) * (DS + 2 * MG_DESPECKLE_MAX_K) * (DS + 2 * MG_DESPECKLE_MAX_K) <= 40 * 1024,
                 "the largest tile (float64, k = 2) leaves room for four workgroups on a CU");
   static_assert(MG_FOLD_WAVES * MG_WAVE == 256, "mg_block_fold folds workgroups of 256 threads");
-  const unsigned gy = (unsigned)std::min<int64_t>(n, 65535);
   // about eight workgroups per CU in all; each walks its share of a plane's tiles and adds to the plane's counter once
-  const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(tiles_x * tiles_y, 2048 / gy));
-  hipLaunchKernelGGL((k_despeckle<T, K, VOTES>), dim3(gx, gy), dim3(256), 0, s, (const T*)d_src, (T*)d_dst, n, h, w,
-                     (int)tiles_x, (int)(tiles_x * tiles_y), which, threshold, d_defects,
+  hipLaunchKernelGGL((k_despeckle<T, K, VOTES>), mg_plane_grid(tiles_x * tiles_y, n, 2048), dim3(256), 0, s, (const T*)d_src,
+                     (T*)d_dst, n, h, w, (int)tiles_x, (int)(tiles_x * tiles_y), which, threshold, d_defects,
                      reinterpret_cast<unsigned long long*>(d_counts), d_votes);
   MG_CHECK_LAUNCH();
   return MG_OK;
@@ -160,11 +139,11 @@ int launch_despeckle(const void* d_src, void* d_dst, int64_t n, int h, int w, in
 template <bool VOTES>
 int despeckle_entry(const void* d_src, void* d_dst, int dtype, int64_t n, int h, int w, int k, int which, double threshold,
                     const uint8_t* d_defects, int64_t* d_counts, int32_t* d_votes, void* stream) {
-  if (!d_src || n < 0 || h < 0 || w < 0 || h > (1 << 30) || w > (1 << 20)) return MG_EINVAL;
-  if (dtype != MG_U8 && dtype != MG_U16 && dtype != MG_F32 && dtype != MG_F64) return MG_EINVAL;
+  const MgPlanes block = mg_planes_check(dtype, n, h, w, {d_src, d_dst});
+  if (block == MG_PLANES_REFUSED || !d_src) return MG_EINVAL;
   if (k < 1 || k > MG_DESPECKLE_MAX_K || which < MG_OUTLIER_BRIGHT || which > MG_OUTLIER_ALL) return MG_EINVAL;
   if (!d_defects && which != MG_OUTLIER_ALL && !(threshold >= 0.0)) return MG_EINVAL;
-  if (n == 0 || h == 0 || w == 0) return MG_OK;
+  if (block == MG_PLANES_EMPTY) return MG_OK;
   hipStream_t s = mg_stream(stream);
   return mg_dispatch_pixel(dtype, [&](auto t) {
     using T = decltype(t);

@@ -14,7 +14,9 @@ import numpy as np
 import torch
 
 from . import _native as nat
-from . import registry, xr_lite
+from . import registry
+from ._dataset import page_view, plane_block
+from .utils import int_in
 from .xr_lite import DataArray, Dataset
 
 TILE = nat.DEFINES["MG_DEPTH_TILE"]  # mg_depth_fuse: output tile of a workgroup (TILE x TILE pixels)
@@ -25,10 +27,8 @@ _PROJECT = {"max": nat.DEFINES["MG_DEPTH_MAX"], "mean": nat.DEFINES["MG_DEPTH_ME
 
 def check_window(window):
     """``window`` of ``fuse``: an odd integer, 3 .. 2 * MAX_K + 1.  Returns the half-width k."""
-    if isinstance(window, (bool, np.bool_)) or not isinstance(window, (int, np.integer)):
-        raise ValueError(f"depth window must be an integer, got {window!r}")
-    if window % 2 == 0 or window < 3 or window > 2 * MAX_K + 1:
-        raise ValueError(f"depth window must be odd and in [3, {2 * MAX_K + 1}], got {window}")
+    if int_in("depth window", window, 3, 2 * MAX_K + 1) % 2 == 0:
+        raise ValueError(f"depth window must be odd, got {window}")
     return int(window) // 2
 
 
@@ -46,25 +46,6 @@ def check_depth(method="max", window=9, z=None):
             raise ValueError(f'depth method "focus" takes at most {MAX_Z} slices, got {z}')
 
 
-def _block(stack, what):
-    """-> (the stack as a contiguous tensor, leading shape, n, z, h, w, dtype code).  Raises before any launch."""
-    from . import hotpath
-
-    if not isinstance(stack, torch.Tensor):
-        raise TypeError(f"{what} takes a device tensor (..., Z, H, W), got {type(stack).__name__}")
-    code = nat.dtype_code(stack.dtype)  # TypeError for an unsupported dtype
-    if stack.dim() < 3:
-        raise ValueError(f"{what} takes a stack (..., Z, H, W), got shape {tuple(stack.shape)}")
-    hotpath.require_gpu()
-    if not stack.is_cuda:
-        raise ValueError(f"{what} takes a device tensor; move it with preprocess.to_device")
-    lead = tuple(stack.shape[:-3])
-    z, h, w = (int(v) for v in stack.shape[-3:])
-    if z < 1:
-        raise ValueError(f"{what}: a depth stack needs at least one slice")
-    return stack.contiguous(), lead, int(np.prod(lead, dtype=np.int64)), z, h, w, code
-
-
 def project(stack, method, pick=None):
     """(..., Z, H, W) -> (..., H, W) of the same dtype.  ``method`` "max": the maximum over z (a NaN in any slice gives
     NaN); "mean": integers rint(exact sum / Z), half to even; floats a float64 sum in slice order, / Z, cast; "pick":
@@ -74,21 +55,21 @@ def project(stack, method, pick=None):
 
     if method not in _PROJECT:
         raise ValueError(f'project method must be "max", "mean" or "pick", got {method!r}')
-    block, lead, n, z, h, w, code = _block(stack, "depth.project")
+    b = plane_block(stack, "depth.project", trailing=3)
     picks = None
     if method == "pick":
         if pick is None:
             raise ValueError('project(..., "pick") needs the slice index of every stack')
         host = (pick.detach().cpu().numpy() if isinstance(pick, torch.Tensor) else np.asarray(pick)).reshape(-1)
-        if host.dtype.kind not in "iu" or host.size != n:
-            raise ValueError(f"pick must hold one integer per stack ({n}), got {host.size} of {host.dtype}")
-        if n and (host.min() < 0 or host.max() >= z):
-            raise ValueError(f"pick index outside [0, {z})")
-        picks = torch.from_numpy(host.astype(np.int32)).to(block.device)
-    out = torch.empty(lead + (h, w), dtype=block.dtype, device=block.device)
+        if host.dtype.kind not in "iu" or host.size != b.n:
+            raise ValueError(f"pick must hold one integer per stack ({b.n}), got {host.size} of {host.dtype}")
+        if b.n and (host.min() < 0 or host.max() >= b.z):
+            raise ValueError(f"pick index outside [0, {b.z})")
+        picks = torch.from_numpy(host.astype(np.int32)).to(b.block.device)
+    out = torch.empty(b.lead + (b.h, b.w), dtype=b.block.dtype, device=b.block.device)
     if out.numel() == 0:
         return out
-    hotpath._call("mg_depth_project", block.data_ptr(), out.data_ptr(), code, n, z, h, w, _PROJECT[method],
+    hotpath._call("mg_depth_project", b.block.data_ptr(), out.data_ptr(), b.code, b.n, b.z, b.h, b.w, _PROJECT[method],
                   hotpath._ptr(picks), hotpath._stream())
     return out
 
@@ -99,12 +80,13 @@ def focus_totals(stack):
     in no defined order)."""
     from . import hotpath
 
-    block, lead, n, z, h, w, code = _block(stack, "depth.focus_totals")
-    integer = code in (nat.MG_U8, nat.MG_U16)
-    totals = torch.empty(lead + (z,), dtype=torch.int64 if integer else torch.float64, device=block.device)
-    if block.numel() == 0:  # no pixel: every total is zero
+    b = plane_block(stack, "depth.focus_totals", trailing=3)
+    integer = b.code in (nat.MG_U8, nat.MG_U16)
+    totals = torch.empty(b.lead + (b.z,), dtype=torch.int64 if integer else torch.float64, device=b.block.device)
+    if b.block.numel() == 0:  # no pixel: every total is zero
         return totals.zero_()
-    hotpath._call("mg_depth_focus_totals", block.data_ptr(), code, n, z, h, w, totals.data_ptr(), hotpath._stream())
+    hotpath._call("mg_depth_focus_totals", b.block.data_ptr(), b.code, b.n, b.z, b.h, b.w, totals.data_ptr(),
+                  hotpath._stream())
     return totals
 
 
@@ -142,14 +124,14 @@ def fuse(stack, window=9, want_index=True):
     from . import hotpath
 
     k = check_window(window)
-    block, lead, n, z, h, w, code = _block(stack, "depth.fuse")
-    if z > MAX_Z:
-        raise ValueError(f"depth.fuse takes at most {MAX_Z} slices, got {z}")
-    out = torch.empty(lead + (h, w), dtype=block.dtype, device=block.device)
-    index = torch.empty(lead + (h, w), dtype=torch.uint8, device=block.device) if want_index else None
+    b = plane_block(stack, "depth.fuse", trailing=3)
+    if b.z > MAX_Z:
+        raise ValueError(f"depth.fuse takes at most {MAX_Z} slices, got {b.z}")
+    out = torch.empty(b.lead + (b.h, b.w), dtype=b.block.dtype, device=b.block.device)
+    index = torch.empty(b.lead + (b.h, b.w), dtype=torch.uint8, device=b.block.device) if want_index else None
     if out.numel() == 0:
         return out, index
-    hotpath._call("mg_depth_fuse", block.data_ptr(), code, n, z, h, w, k, out.data_ptr(), hotpath._ptr(index),
+    hotpath._call("mg_depth_fuse", b.block.data_ptr(), b.code, b.n, b.z, b.h, b.w, k, out.data_ptr(), hotpath._ptr(index),
                   hotpath._stream())
     return out, index
 
@@ -170,37 +152,23 @@ def project_depth(xp, method="max", window=9, dim="depth"):
     ``depth``; the pages are ``tile_y`` / ``tile_x`` or ``y`` / ``x``.  Every other dimension, coordinate and attribute
     is kept; ``attrs["depth_method"]`` records the method and, for "sharpest", ``attrs["depth_chosen"]`` the chosen
     slice of every stack as a nested list over the leading dimensions."""
-    from .preprocess import to_device
-
     check_depth(method, window)
-    xp = xr_lite.from_any(xp)
-    is_array = isinstance(xp, DataArray)
-    if not is_array and "tile" not in xp.data_vars:
-        raise ValueError("project_depth: the Dataset has no 'tile' variable")
-    tile = xp if is_array else xp.data_vars["tile"]
-    name = _depth_dim(tile.dims, dim)
-    pages = next((p for p in (("tile_y", "tile_x"), ("y", "x")) if p[0] in tile.dims and p[1] in tile.dims), None)
-    if pages is None:
-        raise ValueError(f"project_depth: no page dimensions (tile_y, tile_x) or (y, x) in {tile.dims}")
-    lead = tuple(d for d in tile.dims if d != name and d not in pages)
+    view = page_view(xp, "tile", (("tile_y", "tile_x"), ("y", "x")), "project_depth",
+                     fold=lambda dims: _depth_dim(dims, dim))
+    xp, tile, name = view.source, view.var, view.fold
     check_depth(method, window, z=tile.sizes[name])
-    moved = tile.transpose(*lead, name, *pages)
-    data = moved.data
-    if isinstance(data, np.ndarray):
-        data = np.ascontiguousarray(data)
-    stack = to_device(data)
     chosen = None
     if method == "focus":
-        image, _ = fuse(stack, window, want_index=False)
+        image, _ = fuse(view.planes, window, want_index=False)
     elif method == "sharpest":
-        image, chosen = sharpest(stack)
+        image, chosen = sharpest(view.planes)
     else:
-        image = project(stack, method)
-    dims = lead + pages
+        image = project(view.planes, method)
+    dims = view.lead + view.pages
     attrs = dict(xp.attrs, depth_method=method)
     if chosen is not None:
         attrs["depth_chosen"] = chosen.cpu().numpy().tolist()
-    if is_array:
+    if view.is_array:
         coords = {k: v for k, v in xp.coords.items() if name not in v.dims}
         return DataArray(image, dims, coords, xp.name, attrs)
     out = Dataset(attrs=attrs)

@@ -19,15 +19,16 @@ import numpy as np
 import torch
 
 from . import _native as nat
-from . import registry, xr_lite
-from .xr_lite import DataArray
+from . import registry
+from ._dataset import page_view, plane_block
+from .utils import int_in
 
 TILE = nat.DEFINES["MG_DESPECKLE_TILE"]  # the output tile of a workgroup (TILE x TILE pixels)
 MAX_K = nat.DEFINES["MG_DESPECKLE_MAX_K"]
 RADII = tuple(range(1, MAX_K + 1))
 WHICH = {"bright": nat.DEFINES["MG_OUTLIER_BRIGHT"], "dark": nat.DEFINES["MG_OUTLIER_DARK"],
          "both": nat.DEFINES["MG_OUTLIER_BOTH"]}
-_ALL = nat.DEFINES["MG_OUTLIER_ALL"]
+ALL = nat.DEFINES["MG_OUTLIER_ALL"]  # every pixel becomes its window median: ``median``, and background's ``smooth=``
 SCOPES = ("plane", "sensor")
 
 
@@ -39,8 +40,7 @@ def check_despeckle(threshold, radius=1, which="bright", scope="plane", min_frac
         raise ValueError(f"despeckle threshold must be a real number, got {threshold!r}")
     if not math.isfinite(threshold) or threshold < 0:
         raise ValueError(f"despeckle threshold must be finite and >= 0, got {threshold!r}")
-    if isinstance(radius, (bool, np.bool_)) or not isinstance(radius, (int, np.integer)) or radius not in RADII:
-        raise ValueError(f"despeckle radius must be one of {RADII}, got {radius!r}")
+    int_in("despeckle radius", radius, 1, MAX_K)
     if not isinstance(which, str) or which not in WHICH:
         raise ValueError(f"despeckle which must be one of {tuple(WHICH)}, got {which!r}")
     if not isinstance(scope, str) or scope not in SCOPES:
@@ -50,39 +50,22 @@ def check_despeckle(threshold, radius=1, which="bright", scope="plane", min_frac
         raise ValueError(f"despeckle min_fraction must be in (0, 1], got {min_fraction!r}")
 
 
-def _block(planes, what):
-    """-> (the planes as a contiguous tensor, leading shape, n, h, w, dtype code).  Raises before any launch."""
+def _replace(b, radius, which, threshold, defects, want_counts):
     from . import hotpath
 
-    if not isinstance(planes, torch.Tensor):
-        raise TypeError(f"{what} takes a device tensor (..., H, W), got {type(planes).__name__}")
-    code = nat.dtype_code(planes.dtype)  # TypeError for an unsupported dtype
-    if planes.dim() < 2:
-        raise ValueError(f"{what} takes planes (..., H, W), got shape {tuple(planes.shape)}")
-    hotpath.require_gpu()
-    if not planes.is_cuda:
-        raise ValueError(f"{what} takes a device tensor; move it with preprocess.to_device")
-    lead = tuple(planes.shape[:-2])
-    h, w = (int(v) for v in planes.shape[-2:])
-    return planes.contiguous(), lead, int(np.prod(lead, dtype=np.int64)), h, w, code
-
-
-def _replace(block, lead, n, h, w, code, radius, which, threshold, defects, want_counts):
-    from . import hotpath
-
-    out = torch.empty_like(block)
-    counts = torch.empty(lead, dtype=torch.int64, device=block.device) if want_counts else None  # (the entry zeroes it)
-    if block.numel() == 0:
+    out = torch.empty_like(b.block)
+    counts = torch.empty(b.lead, dtype=torch.int64, device=b.block.device) if want_counts else None  # (the entry zeroes it)
+    if b.block.numel() == 0:
         return out, None if counts is None else counts.zero_()
-    hotpath._call("mg_despeckle_planes", block.data_ptr(), out.data_ptr(), code, n, h, w, radius, which, float(threshold),
-                  hotpath._ptr(defects), hotpath._ptr(counts), hotpath._stream())
+    hotpath._call("mg_despeckle_planes", b.block.data_ptr(), out.data_ptr(), b.code, b.n, b.h, b.w, radius, which,
+                  float(threshold), hotpath._ptr(defects), hotpath._ptr(counts), hotpath._stream())
     return out, counts
 
 
 def median(planes, radius=1):
     """(..., H, W) -> the window median of every pixel, window 2 * radius + 1, edges replicated."""
     check_despeckle(0, radius)
-    out, _ = _replace(*_block(planes, "despeckle.median"), radius, _ALL, 0.0, None, False)
+    out, _ = _replace(plane_block(planes, "despeckle.median"), radius, ALL, 0.0, None, False)
     return out
 
 
@@ -93,16 +76,16 @@ def remove_outliers(planes, threshold, radius=1, which="bright", defects=None, w
     for all planes) exactly the mapped pixels are replaced and ``threshold`` / ``which`` play no part.  ``counts``: the
     pixels replaced in every plane."""
     check_despeckle(threshold, radius, which)
-    block, lead, n, h, w, code = _block(planes, "despeckle.remove_outliers")
+    b = plane_block(planes, "despeckle.remove_outliers")
     if defects is not None:
         if not isinstance(defects, torch.Tensor):
             defects = torch.from_numpy(np.ascontiguousarray(defects))
         if defects.dtype not in (torch.bool, torch.uint8):
             raise TypeError(f"a defect map is bool or uint8, got {defects.dtype}")
-        if tuple(defects.shape) != (h, w):
-            raise ValueError(f"the defect map must have the planes' shape {(h, w)}, got {tuple(defects.shape)}")
-        defects = defects.to(device=block.device, dtype=torch.uint8).contiguous()
-    return _replace(block, lead, n, h, w, code, radius, WHICH[which], threshold, defects, want_counts)
+        if tuple(defects.shape) != (b.h, b.w):
+            raise ValueError(f"the defect map must have the planes' shape {(b.h, b.w)}, got {tuple(defects.shape)}")
+        defects = defects.to(device=b.block.device, dtype=torch.uint8).contiguous()
+    return _replace(b, radius, WHICH[which], threshold, defects, want_counts)
 
 
 def outlier_votes(planes, threshold, radius=1, which="bright"):
@@ -110,11 +93,11 @@ def outlier_votes(planes, threshold, radius=1, which="bright"):
     from . import hotpath
 
     check_despeckle(threshold, radius, which)
-    block, _, n, h, w, code = _block(planes, "despeckle.outlier_votes")
-    votes = torch.empty((h, w), dtype=torch.int32, device=block.device)  # (the entry zeroes it)
-    if block.numel() == 0:
+    b = plane_block(planes, "despeckle.outlier_votes")
+    votes = torch.empty((b.h, b.w), dtype=torch.int32, device=b.block.device)  # (the entry zeroes it)
+    if b.block.numel() == 0:
         return votes.zero_()
-    hotpath._call("mg_outlier_votes", block.data_ptr(), code, n, h, w, radius, WHICH[which], float(threshold),
+    hotpath._call("mg_outlier_votes", b.block.data_ptr(), b.code, b.n, b.h, b.w, radius, WHICH[which], float(threshold),
                   votes.data_ptr(), hotpath._stream())
     return votes
 
@@ -136,33 +119,13 @@ def remove_outliers_component(xp, threshold, radius=1, which="bright", scope="pl
     every plane -- a speck in a single plane stays, a fixed defect goes even where a bright marker hides it from the
     per-plane test.  Every dimension, coordinate and attribute is kept; ``attrs["despeckle_replaced"]`` is the number
     of pixels replaced and, for "sensor", ``attrs["despeckle_defects"]`` the number of pixels in the map."""
-    from .preprocess import to_device
-
     check_despeckle(threshold, radius, which, scope, min_fraction)
-    xp = xr_lite.from_any(xp)
-    is_array = isinstance(xp, DataArray)
-    if not is_array and "tile" not in xp.data_vars:
-        raise ValueError("remove_outliers: the Dataset has no 'tile' variable")
-    tile = xp if is_array else xp.data_vars["tile"]
-    pages = next((p for p in (("tile_y", "tile_x"), ("y", "x")) if p[0] in tile.dims and p[1] in tile.dims), None)
-    if pages is None:
-        raise ValueError(f"remove_outliers: no page dimensions (tile_y, tile_x) or (y, x) in {tile.dims}")
-    lead = tuple(d for d in tile.dims if d not in pages)
-    data = tile.transpose(*lead, *pages).data
-    if isinstance(data, np.ndarray):
-        data = np.ascontiguousarray(data)
-    planes = to_device(data)
+    view = page_view(xp, "tile", (("tile_y", "tile_x"), ("y", "x")), "remove_outliers")
     extra = {}
     defects = None
     if scope == "sensor":
-        defects = defect_map(planes, threshold, radius, which, min_fraction)
+        defects = defect_map(view.planes, threshold, radius, which, min_fraction)
         extra["despeckle_defects"] = int(defects.sum().item())
-    out, counts = remove_outliers(planes, threshold, radius, which, defects=defects)
+    out, counts = remove_outliers(view.planes, threshold, radius, which, defects=defects)
     extra["despeckle_replaced"] = int(counts.sum().item())
-    cleaned = DataArray(out, lead + pages, None, tile.name, tile.attrs).transpose(*tile.dims)
-    if is_array:
-        return DataArray(cleaned.raw, tile.dims, dict(xp.coords), xp.name, dict(xp.attrs, **extra))
-    res = xp.copy()
-    res.attrs.update(extra)
-    res["tile"] = cleaned
-    return res
+    return view.rebuild(out, extra)

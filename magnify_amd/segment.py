@@ -15,19 +15,11 @@ import numpy as np
 from . import _dataset
 from . import _native as nat
 from . import registry
+from .utils import int_in
 
 MAX_LEN = nat.DEFINES["MG_SEGMENT_MAX_LEN"]
 MAX_OPEN, MAX_GROW, MAX_GUARD = (nat.DEFINES[k] for k in ("MG_SEGMENT_MAX_OPEN", "MG_SEGMENT_MAX_GROW",
                                                            "MG_SEGMENT_MAX_GUARD"))
-
-
-def _int_in(name, value, lo, hi):
-    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)):
-        raise ValueError(f"{name} must be an integer, got {value!r}")
-    if value < lo or (hi is not None and value > hi):
-        raise ValueError(f"{name} must be in [{lo}, {hi}], got {value}" if hi is not None else
-                         f"{name} must be at least {lo}, got {value}")
-    return int(value)
 
 
 def check_segment(method="otsu", open_radius=1, max_grow=4, bg_guard=2, min_area=1, roi_length=None):
@@ -44,12 +36,12 @@ def check_segment(method="otsu", open_radius=1, max_grow=4, bg_guard=2, min_area
         use_otsu, threshold = False, float(method)
         if threshold != threshold:
             raise ValueError("segment threshold must not be NaN")
-    _int_in("open_radius", open_radius, 0, MAX_OPEN)
-    _int_in("max_grow", max_grow, 0, MAX_GROW)
-    _int_in("bg_guard", bg_guard, 0, MAX_GUARD)
-    _int_in("min_area", min_area, 0, None)
+    int_in("open_radius", open_radius, 0, MAX_OPEN)
+    int_in("max_grow", max_grow, 0, MAX_GROW)
+    int_in("bg_guard", bg_guard, 0, MAX_GUARD)
+    int_in("min_area", min_area, 0, None)
     if roi_length is not None:
-        _int_in("roi_length", roi_length, 1, None)
+        int_in("roi_length", roi_length, 1, None)
         if roi_length > MAX_LEN:
             raise ValueError(f"segment_rois holds a window's masks in LDS: roi_length must not exceed {MAX_LEN}, "
                              f"got {roi_length}")

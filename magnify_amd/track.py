@@ -17,6 +17,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from .utils import int_in
+
 TRACK_MODES = (None, "ncc")
 MAX_DRIFT_LIMIT = 16   # (2 * 16 + 1)^2 displacements per (bead, timepoint)
 MAX_PATCH_SIDE = 95    # 2 * half + 1
@@ -76,11 +78,7 @@ def check_stage_drift(stage_drift, track, max_drift=8, shape=None):
         return None
     if track is None:
         raise ValueError('stage_drift needs track="ncc": the stage offset is where the per-bead search starts')
-    if isinstance(stage_drift, (bool, np.bool_)) or not isinstance(stage_drift, (int, np.integer)):
-        raise ValueError(f"stage_drift must be an integer in [1, {MAX_STAGE_DRIFT}], got {stage_drift!r}")
-    if stage_drift < 1 or stage_drift > MAX_STAGE_DRIFT:
-        raise ValueError(f"stage_drift must be in [1, {MAX_STAGE_DRIFT}], got {stage_drift}")
-    b, mc = stage_bin(int(stage_drift))
+    b, mc = stage_bin(int_in("stage_drift", stage_drift, 1, MAX_STAGE_DRIFT))
     if max_drift < b:
         raise ValueError(f"stage_drift {stage_drift} is searched on planes binned by {b}: max_drift must be at least {b}, "
                          f"got {max_drift}")

@@ -81,6 +81,17 @@ def natural_sort_key(s: str):
     return [int(t) if t.isdigit() else t.lower() for t in re.split("([0-9]+)", s)]
 
 
+def int_in(name, value, lo, hi=None):
+    """``value`` as an int where it is an integer -- ``int`` or ``np.integer``; no bool, no float, not even an integral
+    one -- in [lo, hi] (``hi`` None: no upper bound).  ValueError that names ``name`` and the range otherwise."""
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)):
+        raise ValueError(f"{name} must be an integer, got {value!r}")
+    if value < lo or (hi is not None and value > hi):
+        raise ValueError(f"{name} must be in [{lo}, {hi}], got {value}" if hi is not None else
+                         f"{name} must be at least {lo}, got {value}")
+    return int(value)
+
+
 def to_list(x):
     if x is None:
         return []
