@@ -747,6 +747,38 @@ int mg_roi_masked_stats(const void* d_roi, int dtype, const uint8_t* d_mask, int
  * global memory; MG_EINVAL for an unknown dtype or a roi_len that mg_roi_masked_stats refuses.  Host only. */
 int mg_roi_masked_stats_keys_in_lds(int dtype, int roi_len);
 
+/* Radial intensity profiles of an already gathered roi (profile_rois).  NOT in the reference: its reductions stop at one
+ * number per mask, and the markers are round -- ring against core of a bead, disk or doughnut of a button, the radius at
+ * which a bead falls to the background.  tests/radial_ref.py restates the contract in plain Python.
+ * d_roi (m, C, T, L, L) of `dtype`, the mask as for mg_roi_masked_stats (d_mask may be NULL: every pixel).  d_centre:
+ * {cy, cx} of window (g, t) in window coordinates, int32 at d_centre + g * centre_stride_m + t * centre_stride_t
+ * (elements; a time stride of 0: one centre for all timepoints).  Centres and edges are integers in units of
+ * 1 / MG_PROFILE_SUBPIXEL pixel; edges: HOST array of n_rings + 1, read during the call.  With S = MG_PROFILE_SUBPIXEL,
+ * all in exact integer arithmetic:
+ *   d2(i, j) = (i S - cy)^2 + (j S - cx)^2; pixel (i, j) belongs to ring k iff edges[k]^2 <= d2 < edges[k + 1]^2 (a
+ *   pixel on an edge goes to the outer ring; inside edges[0] or from edges[n_rings] on it belongs to none); it takes
+ *   part iff its mask byte is non-zero (or d_mask is NULL) and its value is not NaN.
+ * Limits, so that 32 unsigned bits hold d2: roi_len <= MG_PROFILE_MAX_LEN, 0 <= edges[0] < edges[1] < ... <= 46340, and
+ * -1024 S <= cy, cx <= 2048 S -- centres are device data and cannot be refused: the kernel clamps them into that range.
+ *   d_count   int32[m][C][T][n_rings]       the pixels that take part
+ *   d_moments double[m][C][T][n_rings][2]   {sum x, sum x^2}; an empty ring: {0, 0}, count 0
+ * Integer pixels: both moments are accumulated exactly in 64-bit integers (integer LDS atomics) and converted once: the
+ * correctly rounded exact values.  Float pixels: float64, nothing contracted, no floating-point atomic anywhere -- runs
+ * of one ring along a row are folded by a segmented scan over the lanes and added to per-wave slots in an order fixed
+ * by the launch shape: every call gives the same bits.  One workgroup per (marker, time); the ring of a pixel is found
+ * once and kept as a byte in LDS for the other channels where L <= 128.
+ * MG_EINVAL, with nothing written: a null pointer where one is needed, an unknown dtype, m < 0, n_c / n_t / roi_len <= 0,
+ * roi_len > MG_PROFILE_MAX_LEN, n_rings outside [1, MG_PROFILE_MAX_RINGS], edges not strictly increasing or out of
+ * range, m * n_c * n_t >= 2^31, a negative stride.  m = 0 returns MG_OK and writes nothing.  One kernel launch; no
+ * allocation, no synchronisation. */
+#define MG_PROFILE_MAX_RINGS 128
+#define MG_PROFILE_SUBPIXEL 16
+#define MG_PROFILE_MAX_LEN 1024
+int mg_roi_radial_profile(const void* d_roi, int dtype, const uint8_t* d_mask, int64_t mask_stride_m,
+                          int64_t mask_stride_t, const int32_t* d_centre, int64_t centre_stride_m,
+                          int64_t centre_stride_t, const int32_t* edges, int n_rings, int m, int n_c, int n_t,
+                          int roi_len, int32_t* d_count, double* d_moments, void* stream);
+
 /* Data-driven fg / bg masks of an already gathered roi (segment_rois).  NOT in the reference, whose masks are drawn
  * shapes -- the fitted circle (find.py:561-586), disk and annulus (find.py:383-400); this is the threshold / dilation /
  * erosion family that BASELINE.json's north star names for the fg/bg masks.  tests/segment_ref.py restates the contract

@@ -37,43 +37,6 @@ struct Seen {
   }
 };
 
-// A chunk as it comes from memory: VW pixels (16 bytes of them, or one) and their mask bytes, byte j in mw[j / 4].
-// Pixels beyond the window have mask byte 0.
-template <typename T, int VW>
-struct RawChunk {
-  T px[VW];
-  uint32_t mw[4];
-};
-template <typename T, int VW>
-__device__ __forceinline__ RawChunk<T, VW> fetch(const T* __restrict__ v, const uint8_t* __restrict__ mask, int n, int c,
-                                                 int end) {
-  RawChunk<T, VW> r = {};
-  if (c >= end) return r;
-  if (VW > 1 && (c + 1) * VW <= n) {
-    const uint4 bits = *reinterpret_cast<const uint4*>(v + (int64_t)c * VW);
-    __builtin_memcpy(r.px, &bits, 16);
-    const uint8_t* mp = mask + (int64_t)c * VW;
-    if constexpr (VW == 16) {
-      const uint4 t = *reinterpret_cast<const uint4*>(mp);
-      r.mw[0] = t.x, r.mw[1] = t.y, r.mw[2] = t.z, r.mw[3] = t.w;
-    } else if constexpr (VW == 8) {
-      const uint2 t = *reinterpret_cast<const uint2*>(mp);
-      r.mw[0] = t.x, r.mw[1] = t.y;
-    } else if constexpr (VW == 4) {
-      r.mw[0] = *reinterpret_cast<const uint32_t*>(mp);
-    } else {
-      r.mw[0] = *reinterpret_cast<const uint16_t*>(mp);
-    }
-  } else {  // VW = 1, or the window's last, partial chunk
-#pragma unroll
-    for (int j = 0; j < VW; ++j) {
-      const int p = c * VW + j;
-      if (p < n) r.px[j] = v[p], r.mw[j >> 2] |= (uint32_t)mask[p] << (8 * (j & 3));
-    }
-  }
-  return r;
-}
-
 // The pass over the window.  The window is cut into chunks of VW consecutive pixels (VW = 16 bytes of pixels where the
 // window starts on 16 bytes and its mask on VW bytes: one 16-byte load per lane and chunk; VW = 1 otherwise), the chunks
 // into WV equal runs, one per wave, which its lanes walk 64 chunks at a time, the loads of IN_FLIGHT such steps issued

@@ -1,5 +1,6 @@
 // Exact order statistics: the order-preserving key of a pixel (k_masked_stats in mg_roistats.hip, pc_key in
-// mg_percentile.hip) and the byte-wise radix select over the keys of a window, wherever they lie.
+// mg_percentile.hip) and the byte-wise radix select over the keys of a window, wherever they lie.  And the chunk loader
+// of the kernels that stream whole ROI windows (k_masked_stats, k_radial_profile in mg_profile.hip).
 #pragma once
 #include "mg_common.h"
 
@@ -43,6 +44,54 @@ template <> struct median_key<double> {
     return __longlong_as_double((long long)((k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k));
   }
 };
+
+// A chunk as it comes from memory: VW pixels (16 bytes of them, or one) and their mask bytes, byte j in mw[j / 4].
+// Pixels beyond the window have mask byte 0.  MASKED = false: there is no mask to read, every pixel of the window has
+// byte 1.
+template <typename T, int VW>
+struct RawChunk {
+  T px[VW];
+  uint32_t mw[4];
+};
+// VW (2, 4, 8 or 16) bytes from p, which is aligned to VW, as one load: byte j in w[j / 4].
+template <int VW>
+__device__ __forceinline__ void load_bytes(const uint8_t* p, uint32_t* w) {
+  if constexpr (VW == 16) {
+    const uint4 t = *reinterpret_cast<const uint4*>(p);
+    w[0] = t.x, w[1] = t.y, w[2] = t.z, w[3] = t.w;
+  } else if constexpr (VW == 8) {
+    const uint2 t = *reinterpret_cast<const uint2*>(p);
+    w[0] = t.x, w[1] = t.y;
+  } else if constexpr (VW == 4) {
+    w[0] = *reinterpret_cast<const uint32_t*>(p);
+  } else {
+    w[0] = *reinterpret_cast<const uint16_t*>(p);
+  }
+}
+template <typename T, int VW, bool MASKED = true>
+__device__ __forceinline__ RawChunk<T, VW> fetch(const T* __restrict__ v, const uint8_t* __restrict__ mask, int n, int c,
+                                                 int end) {
+  RawChunk<T, VW> r = {};
+  if (c >= end) return r;
+  if (VW > 1 && (c + 1) * VW <= n) {
+    const uint4 bits = *reinterpret_cast<const uint4*>(v + (int64_t)c * VW);
+    __builtin_memcpy(r.px, &bits, 16);
+    const uint8_t* mp = mask + (int64_t)c * VW;
+    if constexpr (!MASKED) {
+#pragma unroll
+      for (int j = 0; j < VW; j += 4) r.mw[j >> 2] = VW >= 4 ? 0x01010101u : 0x0101u;
+    } else {
+      load_bytes<VW>(mp, r.mw);
+    }
+  } else {  // VW = 1, or the window's last, partial chunk
+#pragma unroll
+    for (int j = 0; j < VW; ++j) {
+      const int p = c * VW + j;
+      if (p < n) r.px[j] = v[p], r.mw[j >> 2] |= (uint32_t)(MASKED ? mask[p] : (uint8_t)1) << (8 * (j & 3));
+    }
+  }
+  return r;
+}
 
 // The k-th smallest (0-based) of the keys of `count` items: one 256-bin histogram per key byte, most significant first,
 // only the keys that share the prefix found so far take part.  key_at(i, &key) gives the key of item i, false where it

@@ -1629,6 +1629,51 @@ def masked_stats(roi: torch.Tensor, mask: torch.Tensor, q=()):
     return count, stats, order
 
 
+def radial_profile(roi: torch.Tensor, mask, centre_q, edges_q):
+    """Radial profile of roi (M, C, T, L, L) -- uint8, uint16, float32 or float64 -- by mg_roi_radial_profile
+    (include/magnify_hip.h states the contract, tests/radial_ref.py restates it).  ``mask``: None (every pixel) or the
+    forms of ``masked_median``.  ``centre_q``: int32 (M, 2) or (M, T', 2) = {cy, cx} in window coordinates, T' = T, or
+    T' = 1 or a view expanded along time: one centre for all timepoints; ``edges_q``: host integers (R + 1,); both in
+    1/16 pixel (``profile.quantise``).  A pixel belongs to ring k iff edges_q[k]^2 <= d2 < edges_q[k + 1]^2 and takes
+    part iff its mask byte is non-zero and it is not NaN.  -> count (M, C, T, R) int32, moments (M, C, T, R, 2) float64
+    = {sum x, sum x^2}, exact for integer pixels.  Centres outside [-1024, 2048] pixels are clamped by the kernel;
+    ValueError for edges ``profile.check_edges_q`` refuses."""
+    from .profile import MAX_LEN, check_edges_q
+
+    m, c, t, L, _ = roi.shape
+    code = nat.dtype_code(roi.dtype)
+    edges_q = check_edges_q(edges_q)
+    if L > MAX_LEN:
+        raise ValueError(f"radial_profile takes windows up to {MAX_LEN} pixels, got {L}")
+    require_gpu()
+    roi = roi.contiguous()
+    dev = roi.device
+    r = len(edges_q) - 1
+    count = torch.empty((m, c, t, r), dtype=torch.int32, device=dev)
+    moments = torch.empty((m, c, t, r, 2), dtype=torch.float64, device=dev)
+    if not isinstance(centre_q, torch.Tensor):
+        centre_q = torch.from_numpy(np.ascontiguousarray(centre_q, dtype=np.int32))
+    if centre_q.dtype != torch.int32:
+        raise TypeError(f"radial_profile: centres must be int32 (in 1/16 pixel), got {centre_q.dtype}")
+    if centre_q.dim() == 2:
+        centre_q = centre_q[:, None]
+    n_tc = centre_q.shape[1]
+    if centre_q.dim() != 3 or centre_q.shape[0] != m or centre_q.shape[2] != 2 or n_tc not in (1, t):
+        raise ValueError(f"radial_profile: centres {tuple(centre_q.shape)} for {m} markers and {t} timepoints")
+    if m == 0:
+        return count, moments
+    centre_q = centre_q.to(dev)
+    if centre_q.stride(2) != 1 or (m > 1 and centre_q.stride(0) < 2) or (n_tc > 1 and 0 < centre_q.stride(1) < 2):
+        centre_q = centre_q.contiguous()
+    csm, cst = (centre_q.stride(0) if m > 1 else 0), (centre_q.stride(1) if n_tc > 1 else 0)
+    sm = st = 0
+    if mask is not None:
+        mask, sm, st = _mask_view("radial_profile", mask, m, t, L)
+    _call("mg_roi_radial_profile", roi.data_ptr(), code, _ptr(mask), sm, st, centre_q.data_ptr(), csm, cst,
+          edges_q.ctypes.data, r, m, c, t, L, count.data_ptr(), moments.data_ptr(), _stream())
+    return count, moments
+
+
 def threshold_masks(roi_channel: torch.Tensor, fg0: torch.Tensor, bg0: torch.Tensor, allowed: torch.Tensor | None = None, *,
                     method="otsu", open_radius=1, max_grow=4, bg_guard=2, min_area=1):
     """Data-driven masks of roi_channel (M, T, L, L) -- ONE channel of a gathered roi, uint8 / uint16 / float32 / float64;

@@ -160,3 +160,121 @@ def masked_quantile(xp, q, mask="fg", time=None):
     if np.ndim(q) == 0:
         return DataArray(val[..., 0], _MCT)
     return DataArray(val.permute(3, 0, 1, 2), ("quantile",) + _MCT, {"quantile": np.asarray(q, dtype=np.float64)})
+
+
+# ---- radial profiles: R numbers per window instead of one (mg_roi_radial_profile) -----------------------------------------
+_MCTR = _MCT + ("ring",)
+
+
+def _marker_centres(xp, L, time):
+    """(mark, time, 2) float64 {y - top, x - left}: every marker's position inside its own window, the window origin
+    being the one the finder cut -- ``find._window_origin`` of ``find._rounded_centres`` of that timepoint's x, y."""
+    from .find import _rounded_centres, _window_origin
+
+    if "im_y" not in xp.sizes or "im_x" not in xp.sizes:
+        raise ValueError('radial_profile: centre="marker" needs the image sizes im_y / im_x to find the window origins, '
+                         "and this dataset no longer has them (roi_only?): pass centre= (\"window\", or the centres "
+                         "in window coordinates)")
+    x, y = (np.asarray(xp.coords[k].transpose(*[d for d in ("mark", "time") if d in xp.coords[k].dims]).values,
+                       dtype=np.float64) for k in ("x", "y"))
+    if x.ndim == 1:
+        x, y = x[:, None], y[:, None]
+    if time is not None:
+        x, y = (x[:, time:time + 1], y[:, time:time + 1]) if time != -1 else (x[:, -1:], y[:, -1:])
+    if x.size == 0:
+        return np.zeros(x.shape + (2,), dtype=np.float64)
+    rc = _rounded_centres(y, x).reshape(x.shape + (2,))
+    top = _window_origin(rc[..., 0], L, xp.sizes["im_y"])
+    left = _window_origin(rc[..., 1], L, xp.sizes["im_x"])
+    return np.stack([y - top, x - left], axis=-1)
+
+
+def _own_mask(xp):
+    """fg | bg of every marker, on the device, as a DataArray on (mark, time, roi_y, roi_x): the pixels a bead owns
+    (what ``segment_rois`` allows its foreground to grow into).  One drawn mask for all timepoints gives one union."""
+    fg, bg = (device_tensor(xp.coords[k], _MASK_DIMS, as_mask=True) for k in ("fg", "bg"))
+    if all(t.shape[1] == 1 or t.stride(1) == 0 for t in (fg, bg)):
+        fg, bg = fg[:, :1], bg[:, :1]
+    return DataArray((fg.view(torch.uint8) | bg.view(torch.uint8)).view(torch.bool), _MASK_DIMS)
+
+
+def radial_profile(xp, width=1.0, rings=None, edges=None, mask="own", centre="marker", time=None):
+    """(count, moments) of roi in rings about every marker, as DataArrays on the device: count (mark, channel, time,
+    ring) int32 and moments (mark, channel, time, ring, moment) float64 = {sum x, sum x^2} (``hotpath.radial_profile``),
+    with the coordinates ``ring`` (mid radius in pixels), ``ring_inner`` and ``ring_outer``.
+    ``edges``: radii in pixels; otherwise ``0, width, 2 width, ...`` for ``rings`` rings, by default
+    ``ceil(L / (2 width))``.  Edges and centres are quantised on the host as ``np.rint(v * 16)`` in float64 and the
+    coordinates report the quantised values; ring k holds the pixels with edges[k] <= d < edges[k + 1].
+    ``centre``: "marker" -- x - left, y - top of each timepoint's own x, y, the window origin being the finder's;
+    "window" -- L // 2 on both axes; or a DataArray / array on (mark[, time], 2) = {y, x} in window coordinates.
+    ``mask``: "own" -- fg | bg for beads (a dataset without a ``tag`` coordinate), so that a neighbour's disk never
+    enters a bead's profile, every pixel for chips; None -- every pixel; a coordinate name or a DataArray as in
+    ``masked_stats``.  A pixel takes part iff the mask is set and it is not NaN.  ``time=k``: of timepoint ``k`` only,
+    selected before the reduction."""
+    from . import profile
+
+    roi_var = xp.data_vars["roi"]
+    L, m = roi_var.sizes["roi_y"], roi_var.sizes["mark"]
+    if mask is not None and not isinstance(mask, (str, DataArray)):
+        raise ValueError(f'radial_profile: mask must be "own", None, a coordinate name or a DataArray, got {mask!r}')
+    edges_q = profile.check_profile(width, rings, mask if isinstance(mask, str) else None, L, edges)
+    one = None if time is None else (slice(time, time + 1) if time != -1 else slice(-1, None))
+    n_t = roi_var.sizes["time"] if one is None else len(range(roi_var.sizes["time"])[one])
+    # the centres, float64 (mark, 1 or time, 2) in pixels
+    if isinstance(centre, str):
+        if centre == "marker":
+            c = _marker_centres(xp, L, time)
+        elif centre == "window":
+            c = np.full((m, 1, 2), float(L // 2))
+        else:
+            raise ValueError(f'radial_profile: centre must be "marker", "window" or the centres, got {centre!r}')
+    else:
+        if isinstance(centre, DataArray):
+            centre = centre.transpose(*[d for d in ("mark", "time") if d in centre.dims], ...).values
+        c = np.asarray(centre, dtype=np.float64)
+        if c.ndim == 2:
+            c = c[:, None]
+        if c.ndim != 3 or c.shape[0] != m or c.shape[2] != 2 or c.shape[1] not in (1, roi_var.sizes["time"]):
+            raise ValueError(f"radial_profile: centres must be (mark[, time], 2) = {(m, roi_var.sizes['time'], 2)}, "
+                             f"got {c.shape}")
+        if one is not None and c.shape[1] != 1:
+            c = c[:, one]
+    if not np.isfinite(c).all():
+        raise ValueError("radial_profile: a centre is not finite")
+    centre_q = np.clip(profile.quantise(c), -2.0**30, 2.0**30).astype(np.int32)  # (the kernel clamps to its own range)
+    coords = profile.ring_coords(edges_q)
+    r = len(edges_q) - 1
+    if m == 0:
+        n_c = roi_var.sizes["channel"]
+        return (DataArray(np.zeros((0, n_c, n_t, r), dtype=np.int32), _MCTR, coords),
+                DataArray(np.zeros((0, n_c, n_t, r, 2), dtype=np.float64), _MCTR + ("moment",), coords))
+    if isinstance(mask, str) and mask == "own":
+        mask = None if "tag" in xp.coords else _own_mask(xp)
+    if mask is None:
+        roi = roi_var if one is None else roi_var.isel(time=one)
+        roi, mk = device_tensor(roi, _ROI_DIMS), None
+        hotpath.nat.dtype_code(roi.dtype)
+    else:
+        roi, mk = _roi_and_mask(xp, mask, time)
+    count, moments = hotpath.radial_profile(roi, mk, centre_q, edges_q)
+    return DataArray(count, _MCTR, coords), DataArray(moments, _MCTR + ("moment",), coords)
+
+
+def profile_mean(count, moments):
+    """sum / n of a radial profile (torch tensors: count (...), moments (..., 2)), NaN where n = 0."""
+    n = count.to(torch.float64)
+    return torch.where(n > 0, moments[..., 0] / n, torch.full_like(n, float("nan")))
+
+
+def profile_std(count, moments, ddof=0):
+    """sqrt((sum x^2 - (sum x)^2 / n) / (n - ddof)) of a radial profile (torch tensors), NaN where n - ddof <= 0 (and
+    where n = 0).  Raw moments cancel: the difference of two numbers of size n mean^2 carries an absolute error of about
+    2^-53 n mean^2 even where both are exact, so the variance is only good to a relative 2^-53 (mean / std)^2 -- fine
+    for 16-bit pixels (a ring of 600 pixels at 60000 +- 50 keeps 9 digits), useless for a float ring whose spread is
+    below 1e-8 of its level; a result below zero is returned as 0.  ``masked_std`` has the two-pass form."""
+    n = count.to(torch.float64)
+    dof = n - float(ddof)
+    safe = torch.where(n > 0, n, torch.ones_like(n))
+    m2 = torch.clamp(moments[..., 1] - moments[..., 0] * moments[..., 0] / safe, min=0.0)
+    return torch.where((dof > 0) & (n > 0), torch.sqrt(m2 / torch.where(dof > 0, dof, torch.ones_like(dof))),
+                       torch.full_like(n, float("nan")))

@@ -93,6 +93,18 @@ def _add_segment(pipe, segment, channel, open_radius, max_grow, bg_guard, roi_le
                   bg_guard=bg_guard)
 
 
+def _add_profile(pipe, profile, rings, mask, roi_length):
+    """``profile=`` of the marker pipelines (a ring width in pixels; not in the reference): ``profile_rois`` after the
+    finder -- after ``segment_rois`` where that is present, so that the profile sees the final masks -- and before
+    ``drop``, its settings checked now, not at the first assay.  None adds nothing."""
+    if profile is None:
+        return
+    from .profile import check_profile
+
+    check_profile(profile, rings, mask, roi_length)
+    pipe.add_pipe("profile_rois", width=profile, rings=rings, mask=mask)
+
+
 def _add_depth(pipe, depth, depth_window):
     """``depth=`` of the pipelines ("max", "mean", "sharpest" or "focus"; not in the reference, which refuses a Z
     axis): the reader keeps the files' Z axis as ``depth`` and ``project_depth`` folds it first, before
@@ -141,7 +153,8 @@ def microfluidic_chip(data, shape=(8, 8), pinlist=None, blank=None, overlap=102,
                       segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2,
                       depth=None, depth_window=9,
                       despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane",
-                      background=None, background_smooth=0, background_channel=None):
+                      background=None, background_smooth=0, background_channel=None,
+                      profile=None, profile_rings=None, profile_mask="own"):
     """registry.py:32-110 (``blend``: ``stitch``'s overlap blending; ``register``, ``max_shift``, ``register_channel``:
     its tile registration -- neither is in the reference)."""
     kw = dict(locals())
@@ -159,7 +172,8 @@ def microfluidic_chip_pipe(shape=(8, 8), pinlist=None, blank=None, overlap=102, 
                            segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2,
                            depth=None, depth_window=9,
                            despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane",
-                           background=None, background_smooth=0, background_channel=None):
+                           background=None, background_smooth=0, background_channel=None,
+                           profile=None, profile_rings=None, profile_mask="own"):
     """registry.py:196-271."""
     if chip_type is not None:
         if chip_type == "minichip":
@@ -186,6 +200,7 @@ def microfluidic_chip_pipe(shape=(8, 8), pinlist=None, blank=None, overlap=102, 
                   cluster_penalty=cluster_penalty, roi_length=roi_length, progress_bar=progress_bar,
                   search_timestep=search_timestep, search_channel=search_channel, interactive=interactive)
     _add_segment(pipe, segment, segment_channel, segment_open, segment_grow, segment_guard, roi_length)
+    _add_profile(pipe, profile, profile_rings, profile_mask, roi_length)
     pipe.add_pipe("drop", roi_only=roi_only, drop_tiles=drop_tiles)
     pipe.add_pipe("restore_format")
     return pipe
@@ -200,7 +215,8 @@ def mrbles(data, spectra, codes, flatfield=1.0, darkfield=0.0, overlap=102, min_
            segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2,
            depth=None, depth_window=9,
            despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane",
-           background=None, background_smooth=0, background_channel=None):
+           background=None, background_smooth=0, background_channel=None,
+           profile=None, profile_rings=None, profile_mask="own"):
     """registry.py:274-399."""
     kw = dict(locals())
     kw.pop("data")
@@ -216,7 +232,8 @@ def mrbles_pipe(spectra, codes, flatfield=1.0, darkfield=0.0, overlap=102, min_b
                 segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2,
                 depth=None, depth_window=9,
                 despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane",
-                background=None, background_smooth=0, background_channel=None):
+                background=None, background_smooth=0, background_channel=None,
+                profile=None, profile_rings=None, profile_mask="own"):
     """registry.py:402-451."""
     pipe = Pipeline("read")
     pipe.add_pipe("standardize_format")
@@ -232,6 +249,7 @@ def mrbles_pipe(spectra, codes, flatfield=1.0, darkfield=0.0, overlap=102, min_b
                   interactive=interactive, track=track, max_drift=max_drift, track_min_score=track_min_score,
                   track_channel=track_channel, track_patch=track_patch, stage_drift=stage_drift)
     _add_segment(pipe, segment, segment_channel, segment_open, segment_grow, segment_guard, roi_length)
+    _add_profile(pipe, profile, profile_rings, profile_mask, roi_length)
     pipe.add_pipe("identify_mrbles", spectra=spectra, codes=codes, reference=reference)
     pipe.add_pipe("drop", roi_only=roi_only, drop_tiles=drop_tiles)
     pipe.add_pipe("restore_format")
@@ -247,7 +265,8 @@ def beads(data, flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=10,
           segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2,
           depth=None, depth_window=9,
           despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane",
-          background=None, background_smooth=0, background_channel=None):
+          background=None, background_smooth=0, background_channel=None,
+          profile=None, profile_rings=None, profile_mask="own"):
     """registry.py:454-565."""
     kw = dict(locals())
     kw.pop("data")
@@ -263,7 +282,8 @@ def beads_pipe(flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=5, m
                segment=None, segment_channel=None, segment_open=1, segment_grow=4, segment_guard=2,
                depth=None, depth_window=9,
                despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane",
-               background=None, background_smooth=0, background_channel=None):
+               background=None, background_smooth=0, background_channel=None,
+               profile=None, profile_rings=None, profile_mask="own"):
     """registry.py:568-612 (note the 5/25 defaults here versus 10/50 in ``beads``)."""
     pipe = Pipeline("read")
     pipe.add_pipe("standardize_format")
@@ -279,6 +299,7 @@ def beads_pipe(flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=5, m
                   interactive=interactive, track=track, max_drift=max_drift, track_min_score=track_min_score,
                   track_channel=track_channel, track_patch=track_patch, stage_drift=stage_drift)
     _add_segment(pipe, segment, segment_channel, segment_open, segment_grow, segment_guard, roi_length)
+    _add_profile(pipe, profile, profile_rings, profile_mask, roi_length)
     pipe.add_pipe("drop", roi_only=roi_only, drop_tiles=drop_tiles)
     pipe.add_pipe("restore_format")
     return pipe
