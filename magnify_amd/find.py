@@ -11,7 +11,7 @@ import torch
 
 from . import hotpath, preprocess, registry, track as tracking, utils
 from ._dataset import channel_index
-from .stack import dedup_against
+from .stack import detect_range
 from .xr_lite import DataArray
 
 _FINDERS = {}
@@ -115,7 +115,6 @@ class BeadFinder:
         if not self.search_channels:
             self.search_channels = (assay.coords["channel"].values.tolist() if "channel" in assay.coords
                                     else list(range(n_c)))
-        beads = np.empty((0, 3), dtype=np.int32)
         finder = _finder(1, h, w, self.min_bead_radius, self.max_bead_radius, self.num_iter, image.device)
         m, L = None, self.roi_length
         followed = None
@@ -132,13 +131,12 @@ class BeadFinder:
             out = hotpath.finish_roi(finder.follow_result, counts)  # (launched for the full capacity: never None)
             beads = finder.fetch_results(counts, d_out, d_scores, overlap=True)[0][0]
         else:
-            for channel in self.search_channels:
+            def planes(channel, lo, hi):  # time 0 of a search channel (the one assay there is) and its min/max
                 ch = channel_index(assay, channel)
-                res, _ = finder.find(image[ch, 0:1], _plane_minmax(assay, image, (ch, 0)), self.low_edge_quantile,
-                                     self.high_edge_quantile, self.min_roundness, self.min_bead_radius,
-                                     [utils.next_seed()])
-                b = dedup_against(beads, res[0][0], 2 * self.min_bead_radius)  # find.py:490-500
-                beads = np.concatenate([beads, b])
+                return image[ch, 0:1], _plane_minmax(assay, image, (ch, 0))
+
+            (beads,) = detect_range(finder, 0, 1, self.search_channels, planes, lambda a, k: utils.next_seed(),
+                                    (self.low_edge_quantile, self.high_edge_quantile, self.min_roundness, self.min_bead_radius))
             # masks straight from the bead table (what utils.circle_labels + the == i / == -1 tests yield,
             # find.py:561-586) -- no label map is written or read
             if self.track is None:

@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import math
 import os
+from functools import partial
 
 import numpy as np
 import torch
@@ -182,28 +183,17 @@ class StackProcessor:
 
     def detect(self, seed=0):
         """Bead tables per assay: list of (M_a, 3) int32 [row, col, r] (find.py:475-501)."""
-        T, h, w = self.T, self.h, self.w
-        assays = list(range(self.n_assays))
-        beads = [np.empty((0, 3), dtype=np.int32) for _ in assays]
         if self.n_streams > 1:
-            return self._detect_streams(seed, beads)
-        for k, ch in enumerate(self.search_channels):
-            done = 0
-            while done < len(assays):
-                # contiguous window of `batch` assays (the last window overlaps the previous one
-                # instead of being ragged; already finished assays are skipped on output)
-                lo = min(done, len(assays) - self.batch)
-                ids = assays[lo : lo + self.batch]
-                planes = self._image[lo : lo + self.batch, ch]  # strided view, no copy
-                mm = self._minmax[lo : lo + self.batch, ch].contiguous()
-                seeds = [_seed(seed, a, k) for a in ids]
-                res, _ = self.finder.find(planes, mm, self.low_q, self.high_q, self.min_roundness, self.min_r, seeds,
-                                          stable_input=True)  # (a view of this processor's own image block)
-                for j, a in enumerate(ids):
-                    if a >= done:
-                        beads[a] = np.concatenate([beads[a], dedup_against(beads[a], res[j][0], 2 * self.min_r)])
-                done = lo + self.batch
-        return beads
+            return self._detect_streams(seed, [None] * self.n_assays)
+        # (stable_input: the planes are views of this processor's own image block)
+        return detect_range(self.finder, 0, self.n_assays, self.search_channels, self._planes, partial(_seed, seed),
+                            self._find_params(), batch=self.batch, stable_input=True)
+
+    def _planes(self, ch, lo, hi):  # channel ch of assays lo .. hi - 1 for find: a strided view (no copy), contiguous (min, max)
+        return self._image[lo:hi, ch], self._minmax[lo:hi, ch].contiguous()
+
+    def _find_params(self):
+        return self.low_q, self.high_q, self.min_roundness, self.min_r
 
     def _detect_streams(self, seed, beads, stack=None, flatfield=1.0, darkfield=0.0):
         """Detection (and, when ``stack`` is given, the flat-field pass) of every sub-batch on the
@@ -225,6 +215,10 @@ class StackProcessor:
         else:
             tiles = stack.view(T * C, 1, *self.tile_grid) if stack is not None else None
 
+        def record(f):  # one record per (sub-batch, search channel): the device counters stay where they are
+            self.step_stats.append((torch.stack([f.num_circles.sum(), f.num_alive.sum(), f.num_scored.sum()]),
+                                    int(f.n_edges_host.sum()), dict(f.stats)))
+
         def work(k):
             try:
                 stream = self.streams[k]
@@ -236,17 +230,8 @@ class StackProcessor:
                         if tiles is not None:
                             hp.flatfield_stitch(tiles[lo * C : hi * C], self.overlap, flatfield, darkfield, out=self._image[lo:hi],
                                                 minmax_out=self._minmax[lo:hi], n_groups=hi - lo, blend=self.blend)
-                        for j, ch in enumerate(self.search_channels):
-                            planes = self._image[lo:hi, ch]
-                            mm = self._minmax[lo:hi, ch].contiguous()
-                            seeds = [_seed(seed, a, j) for a in range(lo, hi)]
-                            res, _ = self.finders[k].find(planes, mm, self.low_q, self.high_q, self.min_roundness,
-                                                          self.min_r, seeds)
-                            for i, a in enumerate(range(lo, hi)):
-                                beads[a] = np.concatenate([beads[a], dedup_against(beads[a], res[i][0], 2 * self.min_r)])
-                            f = self.finders[k]
-                            self.step_stats.append((torch.stack([f.num_circles.sum(), f.num_alive.sum(), f.num_scored.sum()]),
-                                                    int(f.n_edges_host.sum()), dict(f.stats)))
+                        beads[lo:hi] = detect_range(self.finders[k], lo, hi, self.search_channels, self._planes,
+                                                    partial(_seed, seed), self._find_params(), found=record)
                 main.wait_stream(stream)
             except Exception as exc:  # surfaced on the caller's thread
                 errors.append(exc)
@@ -435,6 +420,29 @@ class StackProcessor:
         self._roi_bound = int(1.1 * int(np.sum(counts))) + 16 * self.n_assays
         out["beads"] = [r[0] for r in self.finder.fetch_results(counts, d_beads, d_scores, overlap=True)]
         return out
+
+
+def detect_range(finder, lo, hi, channels, planes, seeds, params, batch=None, stable_input=False, found=None):
+    """Bead tables [row, col, r] of assays lo .. hi - 1 (find.py:475-501): every search channel in turn, ``batch`` assays
+    (default: all) a ``finder.find``; a circle within 2 min_dist of a bead of an earlier channel is dropped.
+    ``planes(ch, a, b)`` -> planes and (min, max) of channel ``ch`` for assays a .. b - 1; ``seeds(assay, k)`` -> its seed for
+    search channel k; ``params`` = find's (low_q, high_q, min_roundness, min_dist); ``found(finder)`` follows every find."""
+    batch = hi - lo if batch is None else batch
+    beads = [np.empty((0, 3), dtype=np.int32) for _ in range(lo, hi)]
+    for k, ch in enumerate(channels):
+        done = lo
+        while done < hi:
+            # contiguous window of `batch` assays (the last window overlaps the previous one
+            # instead of being ragged; already finished assays are skipped on output)
+            a = min(done, hi - batch)
+            res, _ = finder.find(*planes(ch, a, a + batch), *params, [seeds(i, k) for i in range(a, a + batch)],
+                                 stable_input=stable_input)
+            for i in range(done, a + batch):
+                beads[i - lo] = np.concatenate([beads[i - lo], dedup_against(beads[i - lo], res[i - a][0], 2 * params[3])])
+            if found is not None:
+                found(finder)
+            done = a + batch
+    return beads
 
 
 def stitched_shape(rows, cols, tile_y, tile_x, overlap):

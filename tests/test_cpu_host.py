@@ -984,6 +984,49 @@ def test_process_stream_numbers_a_shard_globally(tmp_path, monkeypatch):
     assert Sink.closed == before + 1
 
 
+def test_detect_range_windows_seeds_and_dedup():
+    """stack.detect_range with a stand-in finder, 5 assays in windows of 2, two search channels: the windows are assays
+    (0, 1), (2, 3), (3, 4) for each channel (the last one overlaps instead of being ragged, and assay 3 keeps what its
+    first window found, once); the seeds are _seed(seed, assay, k); a circle of the second channel within 2 min_r
+    (inclusive) of a bead of the first is dropped, one just outside stays."""
+    from magnify_amd import stack
+
+    min_r, seed = 5, 77
+    asked = []
+
+    def circles(k, a):
+        if k == 0:  # one bead per assay
+            return np.array([[100 + a, 200, 9]], dtype=np.int32)
+        # exactly 2 min_r away along a row and off it (6^2 + 8^2 = 10^2: dropped), a pixel further (kept), far away (kept)
+        return np.array([[100 + a, 210, 8], [106 + a, 208, 8], [100 + a, 211, 8], [300, 40 + a, 7]], dtype=np.int32)
+
+    class Finder:
+        def find(self, planes, minmax, low_q, high_q, min_roundness, min_dist, seeds, stable_input=False):
+            ch, a = divmod(int(planes[0, 0, 0]), 10)  # (the stand-in planes say which they are)
+            k = channels.index(ch)
+            asked.append((k, a, minmax, (low_q, high_q, min_roundness, min_dist), list(seeds), stable_input, planes.shape))
+            return [(circles(k, i), np.ones(len(circles(k, i)), np.float32)) for i in range(a, a + len(seeds))], None
+
+    channels, found = [2, 0], []
+    planes = lambda ch, a, b: (np.full((b - a, 4, 6), 10 * ch + a), (ch, a, b))  # noqa: E731
+    beads = stack.detect_range(Finder(), 0, 5, channels, planes, lambda a, k: stack._seed(seed, a, k),
+                               (0.1, 0.9, 0.3, min_r), batch=2, stable_input=True, found=found.append)
+    windows = [(0, 2), (2, 4), (3, 5)]
+    assert [(x[0], x[1]) for x in asked] == [(k, a) for k in (0, 1) for a, _ in windows]
+    assert [x[2] for x in asked] == [(ch, a, b) for ch in (2, 0) for a, b in windows]  # what ``planes`` was asked for
+    assert all(x[3] == (0.1, 0.9, 0.3, min_r) and x[5] is True and x[6] == (2, 4, 6) for x in asked) and len(found) == 6
+    assert [x[4] for x in asked] == [[stack._seed(seed, i, k) for i in range(a, b)] for k in (0, 1) for a, b in windows]
+    assert len(beads) == 5
+    for a, got in enumerate(beads):  # every assay's circles once, assay 3 included
+        np.testing.assert_array_equal(got, np.concatenate([circles(0, a), circles(1, a)[2:]]))
+    # the stable_input default, and a range that does not start at 0 in one window (what a sub-batch of a stream asks)
+    asked.clear()
+    part = stack.detect_range(Finder(), 3, 5, [2], lambda ch, a, b: (planes(ch, a, b)[0], None), lambda a, k: a,
+                              (0.1, 0.9, 0.3, min_r))
+    assert [(x[1], x[2], x[4], x[5]) for x in asked] == [(3, None, [3, 4], False)]
+    np.testing.assert_array_equal(part[1], circles(0, 4))
+
+
 def test_reader_ring_belongs_to_one_iterator(tmp_path):
     """blocks of iter_time_chunks(ring=...) are owned by ONE live iterator -- two iterators over same-shape
     series never share a block; a block comes back after ``ring`` chunks, not earlier; the pool takes the blocks back
