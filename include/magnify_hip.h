@@ -779,6 +779,66 @@ int mg_roi_radial_profile(const void* d_roi, int dtype, const uint8_t* d_mask, i
                           int64_t centre_stride_t, const int32_t* edges, int n_rings, int m, int n_c, int n_t,
                           int roi_len, int32_t* d_count, double* d_moments, void* stream);
 
+/* Per-pixel linear unmixing of an already gathered roi, reduced per bead (identify_mrbles(unmix="pixel")).  NOT in the
+ * reference, which unmixes one number per bead and channel (identify.py:72-83); this is the published MRBLEs analysis:
+ * unmix every pixel, form the ratio image, take the median of the ratio inside the bead and keep its spread.
+ * tests/unmix_ref.py restates the contract in plain NumPy.
+ * d_roi (m, C, T, L, L) of `dtype`, the mask as for mg_roi_masked_stats (d_mask may be NULL: every pixel).
+ * channels: HOST array of n_k different indices into C, 1 <= n_k <= MG_UNMIX_MAX_CHANNELS; matrix: HOST array
+ * double[n_ln][n_k], 1 <= n_ln <= MG_UNMIX_MAX_LN, every entry finite; q: HOST array of n_q fractions in [0, 1],
+ * 0 <= n_q <= MG_UNMIX_MAX_Q; all three are read during the call.  d_offset: device double[m][C][T], indexed by the
+ * ORIGINAL channel (the output of mg_roi_masked_median as it is), or NULL: zeros.
+ * For pixel p of window (g, t), everything in float64 and nothing contracted:
+ *   x_j = (double)roi[g, channels[j], t, p] - offset[g, channels[j], t]                       j = 0 .. n_k - 1
+ *   v_k = (...((matrix[k][0] * x_0) + matrix[k][1] * x_1) + ...) + matrix[k][n_k-1] * x_{n_k-1}   k = 0 .. n_ln - 1
+ *   r_k = v_k / v_0                                                                           k = 1 .. n_ln - 1
+ * every product rounded, then every sum, left to right in the order of `channels`; the division is IEEE.  The derived
+ * values of a pixel, in this order: v_0 .. v_{n_ln-1}, r_1 .. r_{n_ln-1}; D = 2 n_ln - 1 of them.  A derived value
+ * takes part iff the pixel's mask byte is non-zero (or d_mask is NULL) and the value is not NaN: 0 / 0 drops out,
+ * x / 0 = +-inf stays, as infinities stay in mg_roi_masked_stats.
+ *   d_count int32[m][T][D]            n, the values that take part
+ *   d_sum   double[m][T][D]           their sum in float64, accumulated in an order fixed by the launch shape (no
+ *                                     floating-point atomics): every call gives the same bits; 0 where n = 0
+ *   d_order double[m][T][D][n_q][2]   {sorted[lo], sorted[hi]}: pos = (double)(n - 1) * q, lo = floor(pos),
+ *                                     hi = min(lo + 1, n - 1); NaN for n = 0.  Exact: radix select on the
+ *                                     order-preserving bit pattern (-0.0 sorts below +0.0), the contract of
+ *                                     mg_roi_masked_stats.  May be NULL when n_q = 0.
+ * One workgroup per (marker, time); the mask is read once.  The n_ln volumes of the masked pixels are kept in LDS, 8
+ * bytes each, where n_masked * n_ln * 8 <= MG_UNMIX_LDS_KEY_BYTES (two workgroups of that size fit a compute unit's
+ * 160 KiB), and the ratios are formed from them during the selection passes; a window with more masked pixels computes
+ * its values again from global memory in each pass (mg_roi_unmix_keys_in_lds tells which; the results are the same bits).
+ * MG_EINVAL, with nothing written: a null pointer where one is needed, an unknown dtype, m < 0, C / T / roi_len <= 0,
+ * roi_len > MG_UNMIX_MAX_LEN, n_k / n_ln / n_q out of range, a channel outside [0, C) or repeated, a matrix entry that
+ * is not finite, a q that is NaN or outside [0, 1], m * T * D >= 2^31 (or m * C * T), a negative stride.  m = 0 returns
+ * MG_OK and writes nothing.  One kernel launch; no allocation, no synchronisation. */
+#define MG_UNMIX_MAX_CHANNELS 16
+#define MG_UNMIX_MAX_LN 8
+#define MG_UNMIX_MAX_Q 8
+#define MG_UNMIX_MAX_LEN 1024
+#define MG_UNMIX_LDS_KEY_BYTES 79872
+int mg_roi_unmix_stats(const void* d_roi, int dtype, const uint8_t* d_mask, int64_t mask_stride_m, int64_t mask_stride_t,
+                       int m, int n_c, int n_t, int roi_len, const int* channels, int n_k, const double* matrix, int n_ln,
+                       const double* d_offset, const double* q, int n_q, int32_t* d_count, double* d_sum, double* d_order,
+                       void* stream);
+/* 1 if a window with n_masked pixels under its mask keeps its n_ln volumes in LDS, 0 if it takes the path that computes
+ * them again from global memory; MG_EINVAL for an n_ln that mg_roi_unmix_stats refuses or n_masked < 0.  Host only. */
+int mg_roi_unmix_keys_in_lds(int n_ln, int64_t n_masked);
+
+/* The same arithmetic over whole planes: lanthanide images of a chip or a bead field.  d_src: plane (c, t) of `dtype`,
+ * (h, w) contiguous, at d_src + c * chan_stride + t * time_stride elements; channels and matrix as above; offset: HOST
+ * double[n_k], one finite constant per USED channel, or NULL: zeros.  d_dst float32 (n_out, n_t, h, w), contiguous:
+ * ratios = 0: n_out = n_ln, the planes (float)v_k; ratios = 1: n_out = 2 n_ln - 1, those followed by (float)r_k,
+ * k = 1 .. n_ln - 1.  Computed in float64 exactly as above and cast once; a NaN pixel gives NaN.  A streaming kernel:
+ * every source pixel of a used channel is read once, every output written once, four pixels per load and store where
+ * the planes' addresses allow, pixel by pixel otherwise and for the last h w % 4.
+ * MG_EINVAL, with nothing written: a null pointer where one is needed, a pointer not aligned to its element, an unknown
+ * dtype, n_c / n_t / h / w <= 0 (h above 2^30, w above 2^20), n_k / n_ln out of range, a channel outside [0, n_c) or
+ * repeated, a matrix entry or an offset that is not finite, ratios other than 0 / 1, n_out * n_t >= 2^31, a negative
+ * stride.  One kernel launch; no allocation, no synchronisation. */
+int mg_unmix_planes(const void* d_src, int dtype, int64_t chan_stride, int64_t time_stride, int n_c, int n_t, int h, int w,
+                    const int* channels, int n_k, const double* matrix, int n_ln, const double* offset, int ratios,
+                    float* d_dst, void* stream);
+
 /* Data-driven fg / bg masks of an already gathered roi (segment_rois).  NOT in the reference, whose masks are drawn
  * shapes -- the fitted circle (find.py:561-586), disk and annulus (find.py:383-400); this is the threshold / dilation /
  * erosion family that BASELINE.json's north star names for the fg/bg masks.  tests/segment_ref.py restates the contract

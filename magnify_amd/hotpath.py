@@ -1674,6 +1674,90 @@ def radial_profile(roi: torch.Tensor, mask, centre_q, edges_q):
     return count, moments
 
 
+UNMIX_LDS_KEY_BYTES = nat.DEFINES["MG_UNMIX_LDS_KEY_BYTES"]
+
+
+def unmix_keys_in_lds(n_ln: int, n_masked: int) -> bool:
+    """Does mg_roi_unmix_stats keep the ``n_ln`` volumes of a window with ``n_masked`` pixels under its mask in LDS
+    (8 bytes each, within UNMIX_LDS_KEY_BYTES), or compute them again from global memory in every pass?"""
+    rc = nat.lib().mg_roi_unmix_keys_in_lds(int(n_ln), int(n_masked))
+    nat.check(min(rc, 0), "mg_roi_unmix_keys_in_lds")
+    return bool(rc)
+
+
+def unmix_stats(roi: torch.Tensor, mask, matrix, channels=None, offset=None, q=()):
+    """Per-pixel unmixing of roi (M, C, T, L, L) -- uint8, uint16, float32 or float64 -- reduced per window by
+    mg_roi_unmix_stats (include/magnify_hip.h states the contract, tests/unmix_ref.py restates it).  ``mask``: None
+    (every pixel) or the forms of ``masked_median``; ``matrix``: host float64 (n_ln, n_k); ``channels``: n_k different
+    indices into C (default: all); ``offset``: None or a float64 device tensor (M, C, T) indexed by the ORIGINAL channel
+    (``masked_median``'s output as it is), subtracted from every pixel first; ``q``: up to ``unmix.MAX_Q`` fractions.
+    With D = 2 n_ln - 1 derived values (the volumes, then the ratios to the first) -> count (M, T, D) int32, sum
+    (M, T, D) float64 and order (M, T, D, len(q), 2) float64 = {sorted[lo], sorted[hi]} as ``masked_stats`` has them.
+    ValueError for what ``unmix.check_table`` / ``unmix.check_q`` refuse."""
+    from .unmix import MAX_LEN, check_q, check_table
+
+    m, c, t, L, _ = roi.shape
+    code = nat.dtype_code(roi.dtype)
+    w, ch = check_table(matrix, channels, c)
+    qs = check_q(q)
+    if L > MAX_LEN:
+        raise ValueError(f"unmix_stats takes windows up to {MAX_LEN} pixels, got {L}")
+    require_gpu()
+    roi = roi.contiguous()
+    dev = roi.device
+    d = 2 * w.shape[0] - 1
+    count = torch.empty((m, t, d), dtype=torch.int32, device=dev)
+    total = torch.empty((m, t, d), dtype=torch.float64, device=dev)
+    order = torch.empty((m, t, d, len(qs), 2), dtype=torch.float64, device=dev)
+    if offset is not None:
+        if not isinstance(offset, torch.Tensor) or offset.dtype != torch.float64 or tuple(offset.shape) != (m, c, t):
+            raise ValueError(f"unmix_stats: the offset must be a float64 tensor {(m, c, t)}, got "
+                             f"{getattr(offset, 'dtype', type(offset).__name__)} {tuple(getattr(offset, 'shape', ()))}")
+        offset = offset.to(dev).contiguous()
+    if m == 0:
+        return count, total, order
+    sm = st = 0
+    if mask is not None:
+        mask, sm, st = _mask_view("unmix_stats", mask, m, t, L)
+    _call("mg_roi_unmix_stats", roi.data_ptr(), code, _ptr(mask), sm, st, m, c, t, L, ch.ctypes.data, len(ch),
+          w.ctypes.data, w.shape[0], _ptr(offset), qs.ctypes.data if len(qs) else None, len(qs), count.data_ptr(),
+          total.data_ptr(), order.data_ptr() if len(qs) else None, _stream())
+    return count, total, order
+
+
+def unmix_planes(image: torch.Tensor, matrix, channels=None, offset=None, ratios=False) -> torch.Tensor:
+    """image (C, T, H, W) -- uint8, uint16, float32 or float64, any channel and time strides over contiguous planes --
+    unmixed at every pixel by mg_unmix_planes -> float32 (n_out, T, H, W): the n_ln volumes, followed by the n_ln - 1
+    ratios to the first where ``ratios``.  ``matrix`` and ``channels`` as for ``unmix_stats``; ``offset``: None or one
+    finite constant per used channel, subtracted first."""
+    from .unmix import check_table
+
+    if image.dim() != 4:
+        raise ValueError(f"unmix_planes takes an image (C, T, H, W), got shape {tuple(image.shape)}")
+    c, t, h, w_ = (int(v) for v in image.shape)
+    code = nat.dtype_code(image.dtype)
+    w, ch = check_table(matrix, channels, c)
+    off = None
+    if offset is not None:
+        off = np.ascontiguousarray(np.asarray(offset, dtype=np.float64).reshape(-1))
+        if len(off) != len(ch) or not np.isfinite(off).all():
+            raise ValueError(f"unmix_planes: the offset must be {len(ch)} finite numbers, one per used channel")
+    if min(t, h, w_) < 1:
+        raise ValueError(f"unmix_planes: an empty image {tuple(image.shape)}")
+    require_gpu()
+    if not image.is_cuda:
+        raise ValueError("unmix_planes takes a device tensor; move it with preprocess.to_device")
+    if (w_ > 1 and image.stride(3) != 1) or (h > 1 and image.stride(2) != w_) or \
+            (c > 1 and image.stride(0) < 0) or (t > 1 and image.stride(1) < 0):
+        image = image.contiguous()
+    n_out = 2 * w.shape[0] - 1 if ratios else w.shape[0]
+    out = torch.empty((n_out, t, h, w_), dtype=torch.float32, device=image.device)
+    _call("mg_unmix_planes", image.data_ptr(), code, image.stride(0) if c > 1 else 0, image.stride(1) if t > 1 else 0,
+          c, t, h, w_, ch.ctypes.data, len(ch), w.ctypes.data, w.shape[0], off.ctypes.data if off is not None else None,
+          int(bool(ratios)), out.data_ptr(), _stream())
+    return out
+
+
 def threshold_masks(roi_channel: torch.Tensor, fg0: torch.Tensor, bg0: torch.Tensor, allowed: torch.Tensor | None = None, *,
                     method="otsu", open_radius=1, max_grow=4, bg_guard=2, min_area=1):
     """Data-driven masks of roi_channel (M, T, L, L) -- ONE channel of a gathered roi, uint8 / uint16 / float32 / float64;

@@ -33,7 +33,7 @@ def identify_buttons(assay, shape=None, pinlist=None, blank=None):
 
 
 @registry.component("identify_mrbles")
-def identify_mrbles(assay, spectra, codes, reference="eu", decode=True):
+def identify_mrbles(assay, spectra, codes, reference="eu", decode=True, unmix=None):
     """Front half of the reference's identify_mrbles (identify.py:50-90): per-bead
     intensities ``fg mean - bg median`` at time 0 (the fused device reductions of
     ``magnify_amd.reduce``), lanthanide volumes by least squares against the reference spectra
@@ -44,11 +44,22 @@ def identify_mrbles(assay, spectra, codes, reference="eu", decode=True):
     ``decode`` (default, as the reference always does) adds the reference's code assignment (identify.py:88-234: outlier trimming, affine
     fit of the code levels, Gaussian-mixture assignment -- ``assign_codes``) as the ``tag`` coordinate over
     ``mark`` ("outlier" for beads the mixture gives to its uniform component); host-side NumPy / SciPy on the
-    (mark, lanthanide) table, like the reference."""
+    (mark, lanthanide) table, like the reference.
+
+    ``unmix`` (not in the reference): None -- the path above, nothing else is computed or launched.  "pixel" -- the
+    published MRBLEs analysis: with the same channels and spectra, ``W = unmix.unmixing_matrix(spectra)``, every
+    foreground pixel of time 0 minus its bead's bg median is unmixed on the device (``reduce.unmixed_stats``); ``ln_vol``
+    is the fg median of the per-pixel volume, ``ln_ratio`` the fg median of the per-pixel ratio to the reference
+    lanthanide (column 0: ``ln_vol[:, 0] / ln_vol[:, 0]``, as the reference's expression gives), and two more
+    variables say how far a bead's pixels disagree: ``ln_ratio_spread`` (mark, ln), half the interquartile range of
+    the ratio (0 in column 0 where that column is defined), and ``ln_pixels`` (mark,) int32, the pixels that took
+    part.  ``decode`` then assigns the codes from this ``ln_ratio``, unchanged."""
     import pandas as pd
 
     from . import reduce
+    from .unmix import check_unmix, unmixing_matrix
 
+    check_unmix(unmix)
     table = pd.read_csv(spectra)
     hits = table.index[table["name"] == reference]
     if len(hits) == 0:
@@ -63,20 +74,45 @@ def identify_mrbles(assay, spectra, codes, reference="eu", decode=True):
     names = [str(c) for c in np.asarray(assay.coords["channel"].values).tolist()]
     use = [i for i, c in enumerate(names) if c in table.columns]
     sp = table[[names[i] for i in use]].to_numpy(dtype=np.float64)  # (lanthanide, channel)
-    inten = reduce.fg_mean_minus_bg_median(assay, time=0).data  # `assay.roi.isel(time=0)` first (identify.py:76)
-    inten = inten[:, use, 0].cpu().numpy()  # (mark, channel) at time 0
-    volumes = np.linalg.lstsq(sp.T, inten.T, rcond=None)[0].T
-    with np.errstate(invalid="ignore", divide="ignore"):
-        ratios = volumes / volumes[:, 0:1]
+    spread = pixels = None
+    if unmix is None:
+        inten = reduce.fg_mean_minus_bg_median(assay, time=0).data  # `assay.roi.isel(time=0)` first (identify.py:76)
+        inten = inten[:, use, 0].cpu().numpy()  # (mark, channel) at time 0
+        volumes = np.linalg.lstsq(sp.T, inten.T, rcond=None)[0].T
+        with np.errstate(invalid="ignore", divide="ignore"):
+            ratios = volumes / volumes[:, 0:1]
+    else:
+        volumes, ratios, spread, pixels = _pixel_ratios(assay, unmixing_matrix(sp), use)
     assay = assay.assign_coords(ln=("ln", lanthanides))
     assay["ln_vol"] = (("mark", "ln"), volumes)
     assay["ln_ratio"] = (("mark", "ln"), ratios)
+    if spread is not None:
+        assay["ln_ratio_spread"] = (("mark", "ln"), spread)
+        assay["ln_pixels"] = (("mark",), pixels)
     if decode:
         code_ratios = code_table[lanthanides[1:]].to_numpy(dtype=np.float64)
         names = np.append(code_table["name"].to_numpy(), "outlier")
         tags, _, _ = assign_codes(ratios, code_ratios)
         assay = assay.assign_coords(tag=("mark", names[tags].astype(str)))
     return assay
+
+
+UNMIX_Q = (0.25, 0.5, 0.75)
+
+
+def _pixel_ratios(assay, w, use):
+    """``unmix="pixel"``: (ln_vol, ln_ratio, ln_ratio_spread (mark, ln) float64, ln_pixels (mark,) int32) from the
+    quartiles of the per-pixel volumes and ratios of the foreground at time 0 (``reduce.unmixed_stats``)."""
+    from . import reduce
+
+    count, _, order = reduce.unmixed_stats(assay, w, channels=use, offset="bg_median", mask="fg", q=UNMIX_Q, time=0)
+    quart = reduce.interpolate_quantiles(count.data, order.data, UNMIX_Q)[:, 0].cpu().numpy()  # (mark, derived, 3)
+    n_ln = w.shape[0]
+    volumes = quart[:, :n_ln, 1]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ratios = np.concatenate([volumes[:, :1] / volumes[:, :1], quart[:, n_ln:, 1]], axis=1)
+        spread = np.concatenate([ratios[:, :1] - ratios[:, :1], (quart[:, n_ln:, 2] - quart[:, n_ln:, 0]) / 2.0], axis=1)
+    return volumes, ratios, spread, count.data[:, 0, 0].cpu().numpy().astype(np.int32)
 
 
 def _fit_levels(points, levels, counts, n_grid=100):

@@ -278,3 +278,51 @@ def profile_std(count, moments, ddof=0):
     m2 = torch.clamp(moments[..., 1] - moments[..., 0] * moments[..., 0] / safe, min=0.0)
     return torch.where((dof > 0) & (n > 0), torch.sqrt(m2 / torch.where(dof > 0, dof, torch.ones_like(dof))),
                        torch.full_like(n, float("nan")))
+
+
+# ---- per-pixel unmixing: the channels combined at every pixel, then reduced per bead (mg_roi_unmix_stats) ------------------
+_MTD = ("mark", "time", "derived")
+
+
+def unmixed_stats(xp, matrix, channels=None, offset="bg_median", mask="fg", q=(0.5,), time=None):
+    """(count, sum, order) of the per-pixel lanthanide volumes ``v = matrix @ (roi - offset)`` and ratios ``v_k / v_0``
+    under ``mask``, as DataArrays on the device: count (mark, time, derived) int32, sum (mark, time, derived) float64
+    and order (mark, time, derived, quantile, bound) = the two order statistics every fraction of ``q`` falls between
+    (``hotpath.unmix_stats``; ``interpolate_quantiles`` turns them into quantiles).  ``derived``: the n_ln volumes, then
+    the n_ln - 1 ratios to the first.  ``matrix`` (lanthanide, channel) over ``channels`` -- names of the channel
+    coordinate or indices, default all.  ``offset``: "bg_median" -- ``masked_median(xp, "bg", time=time)``, handed over
+    without leaving the device; None; or a DataArray on (mark, channel, time).  ``mask``: a coordinate name, a DataArray
+    as in ``masked_stats``, or None: every pixel.  ``time=k``: of timepoint ``k`` only, selected before anything is
+    read, as ``masked_median`` does."""
+    from . import unmix
+
+    roi_var = xp.data_vars["roi"]
+    names = np.asarray(xp.coords["channel"].values).tolist() if "channel" in xp.coords else \
+        list(range(roi_var.sizes["channel"]))
+    idx = unmix.channel_indices(names, channels)
+    w, ch = unmix.check_table(matrix, idx, roi_var.sizes["channel"])
+    qs = unmix.check_q(q)
+    if isinstance(offset, str) and offset != "bg_median":
+        raise ValueError(f'unmixed_stats: offset must be "bg_median", None or a DataArray, got {offset!r}')
+    if offset is not None and not isinstance(offset, (str, DataArray)):
+        raise ValueError(f'unmixed_stats: offset must be "bg_median", None or a DataArray, got {type(offset).__name__}')
+    if mask is not None and not isinstance(mask, (str, DataArray)):
+        raise ValueError(f"unmixed_stats: mask must be None, a coordinate name or a DataArray, got {mask!r}")
+    if mask is None:
+        roi = roi_var if time is None else roi_var.isel(time=slice(time, time + 1) if time != -1 else slice(-1, None))
+        roi, mk = device_tensor(roi, _ROI_DIMS), None
+        hotpath.nat.dtype_code(roi.dtype)
+    else:
+        roi, mk = _roi_and_mask(xp, mask, time)
+    if isinstance(offset, str):
+        off = masked_median(xp, "bg", time=time).data
+    elif offset is not None:
+        off = offset
+        if time is not None and off.sizes.get("time", 1) != 1:
+            off = off.isel(time=slice(time, time + 1) if time != -1 else slice(-1, None))
+        off = device_tensor(off, _MCT).to(torch.float64)
+    else:
+        off = None
+    count, total, order = hotpath.unmix_stats(roi, mk, w, ch, off, qs)
+    coords = {"quantile": qs}
+    return (DataArray(count, _MTD), DataArray(total, _MTD), DataArray(order, _MTD + ("quantile", "bound"), coords))

@@ -216,8 +216,8 @@ def mrbles(data, spectra, codes, flatfield=1.0, darkfield=0.0, overlap=102, min_
            depth=None, depth_window=9,
            despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane",
            background=None, background_smooth=0, background_channel=None,
-           profile=None, profile_rings=None, profile_mask="own"):
-    """registry.py:274-399."""
+           profile=None, profile_rings=None, profile_mask="own", unmix=None):
+    """registry.py:274-399 (``unmix``: ``identify_mrbles``' per-pixel unmixing; not in the reference)."""
     kw = dict(locals())
     kw.pop("data")
     return mrbles_pipe(**kw)(data=data)
@@ -233,8 +233,11 @@ def mrbles_pipe(spectra, codes, flatfield=1.0, darkfield=0.0, overlap=102, min_b
                 depth=None, depth_window=9,
                 despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane",
                 background=None, background_smooth=0, background_channel=None,
-                profile=None, profile_rings=None, profile_mask="own"):
+                profile=None, profile_rings=None, profile_mask="own", unmix=None):
     """registry.py:402-451."""
+    from .unmix import check_unmix
+
+    check_unmix(unmix)  # now, not at the first assay
     pipe = Pipeline("read")
     pipe.add_pipe("standardize_format")
     _add_depth(pipe, depth, depth_window)
@@ -250,7 +253,7 @@ def mrbles_pipe(spectra, codes, flatfield=1.0, darkfield=0.0, overlap=102, min_b
                   track_channel=track_channel, track_patch=track_patch, stage_drift=stage_drift)
     _add_segment(pipe, segment, segment_channel, segment_open, segment_grow, segment_guard, roi_length)
     _add_profile(pipe, profile, profile_rings, profile_mask, roi_length)
-    pipe.add_pipe("identify_mrbles", spectra=spectra, codes=codes, reference=reference)
+    pipe.add_pipe("identify_mrbles", spectra=spectra, codes=codes, reference=reference, unmix=unmix)
     pipe.add_pipe("drop", roi_only=roi_only, drop_tiles=drop_tiles)
     pipe.add_pipe("restore_format")
     return pipe
