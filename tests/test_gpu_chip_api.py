@@ -208,6 +208,16 @@ def test_button_finder_stages_match_oracle(mg):
     np.testing.assert_allclose(x, x_o, atol=1e-9)
     np.testing.assert_allclose(y, y_o, atol=1e-9)
     assert radius[1, 2] == 16 and (radius[tag != ""] <= 12).all()
+    # the masks as ``__call__`` makes them from the refined positions: the oracle's fg and bg
+    from magnify_amd import hotpath as hp
+    from magnify_amd.find import _rounded_centres, _window_origin
+
+    centres = _rounded_centres(y, x)
+    rel = np.stack([centres[:, 0] - _window_origin(centres[:, 0], 72, img.shape[0]),
+                    centres[:, 1] - _window_origin(centres[:, 1], 72, img.shape[1])], axis=1)
+    fg, bg = hp.button_masks(rel, radius.reshape(-1), 72, bf.chamber_radius, bf.max_button_radius)
+    np.testing.assert_array_equal(fg.cpu().numpy().astype(bool).reshape(fg_o.shape), fg_o)
+    np.testing.assert_array_equal(bg.cpu().numpy().astype(bool).reshape(bg_o.shape), bg_o)
 
 
 def test_marker_filters(mg):

@@ -211,7 +211,7 @@ def test_full_size_chip_stages_match_c_oracle(mg, monkeypatch):
     np.testing.assert_allclose(gx, ox, rtol=0, atol=1e-9)
     np.testing.assert_allclose(gy, oy, rtol=0, atol=1e-9)
     x, y, radius = bf.refine(d_img[None], gx, gy, tag, [0], 777)
-    _, fg_o, _, x_o, y_o = rp.find_rois(img[None], ox, oy, tag, [0], 4, 15, 30, 72, 0.1, 5_000_000, 0.2, seed=777)
+    _, fg_o, bg_o, x_o, y_o = rp.find_rois(img[None], ox, oy, tag, [0], 4, 15, 30, 72, 0.1, 5_000_000, 0.2, seed=777)
     np.testing.assert_allclose(x, x_o, atol=1e-9)
     np.testing.assert_allclose(y, y_o, atol=1e-9)
     found = tag != ""
@@ -222,6 +222,16 @@ def test_full_size_chip_stages_match_c_oracle(mg, monkeypatch):
     np.testing.assert_array_equal(fg_o.sum(axis=(-1, -2)), np.vectorize(area.get)(radius))
     assert (np.abs(x[found] - pitch * (np.arange(n)[None, :] + 1).repeat(n, 0)[found]) <= 2).all()
     assert radius[3, 4] == 15 and (radius[found] >= 8).all() and (radius[found] <= 12).all()
+    # the masks as ``__call__`` makes them from the refined positions: the oracle's bg (and fg, pixel by pixel)
+    from magnify_amd import hotpath as hp
+    from magnify_amd.find import _rounded_centres, _window_origin
+
+    centres = _rounded_centres(y, x)
+    rel = np.stack([centres[:, 0] - _window_origin(centres[:, 0], 72, 7376),
+                    centres[:, 1] - _window_origin(centres[:, 1], 72, 7376)], axis=1)
+    fg, bg = hp.button_masks(rel, radius.reshape(-1), 72, bf.chamber_radius, bf.max_button_radius)
+    np.testing.assert_array_equal(bg.cpu().numpy().astype(bool).reshape(bg_o.shape), bg_o)
+    np.testing.assert_array_equal(fg.cpu().numpy().astype(bool).reshape(fg_o.shape), fg_o)
 
 
 def test_public_api_c2_matches_c_oracle(mg):
