@@ -1156,6 +1156,35 @@ int64_t mg_background_scratch_bytes(int dtype, int64_t n, int h, int w, int radi
 int mg_background_planes(const void* d_src, const void* d_filtered, void* d_dst, int dtype, int64_t n, int h, int w,
                          int radius, int mode, void* d_scratch, int64_t scratch_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Skew (skew.py, `rotate(rotation="auto")`; not in the reference; tests/skew_ref.py restates every
+ * rule): the projection profiles of one plane along every angle of a table, in integers only -- the same bits in any
+ * order.  d_plane: (h, w) of `dtype`, row y at d_plane + y * row_stride elements.  With D = min(h, w) and
+ * nb = D + 2, d_sums (uint64) and d_counts (uint32) are contiguous (n_angles, 2, nb), ZEROED BY THE CALLER; axis 0 is
+ * the row profile, axis 1 the column profile.
+ *   QUANTISED PIXEL q.  MG_U8 / MG_U16: q = p.  MG_F32 / MG_F64: a NaN pixel is left out of sums and counts; otherwise
+ *     t = (p - lo) * scale in float64 (two roundings, no fused multiply-add), q = 0 where t < 0, 65535 where t > 65535,
+ *     else floor(t) (a NaN t, which only an infinite pixel can give, counts as 0).  lo and scale are not read for
+ *     integer pixels, but are checked.
+ *   GEOMETRY.  dy = 2 y - (h - 1), dx = 2 x - (w - 1); a pixel takes part iff dy^2 + dx^2 <= (D - 1)^2 (the inscribed
+ *     disk: the length of a projection line does not depend on the angle).  d_cs[a] = (C, S) =
+ *     (rint(32768 cos), rint(32768 sin)) of angle a, built by the caller;
+ *     kr = ((dy C - dx S) >> 16) + nb / 2,  kc = ((dx C + dy S) >> 16) + nb / 2   (int64 products, arithmetic shift);
+ *     sums[a, 0, kr] += q, counts[a, 0, kr] += 1, sums[a, 1, kc] += q, counts[a, 1, kc] += 1.
+ *     With such a table both indices lie in [0, nb); an index that a table of other numbers puts outside is dropped.
+ * A workgroup takes one MG_SKEW_TILE x MG_SKEW_TILE tile at a time, reads it once, and walks the whole table over it:
+ * the plane is read from memory once per call.  A tile's partial sums are 32-bit (MG_SKEW_TILE^2 * 65535 < 2^32), held
+ * in LDS, and reach d_sums / d_counts as 64- / 32-bit integer atomics, non-empty bins only.
+ * MG_EINVAL, with nothing launched: a null or misaligned pointer, an unknown dtype, h or w outside 8 .. MG_SKEW_MAX_SIDE,
+ * row_stride < w, n_angles outside 1 .. MG_SKEW_MAX_ANGLES, a non-finite lo or scale.  One kernel launch; no
+ * allocation, no synchronisation.
+ * ---------------------------------------------------------------------------------- */
+#define MG_SKEW_TILE 64
+#define MG_SKEW_MAX_ANGLES 64
+#define MG_SKEW_MAX_SIDE 32768
+int mg_skew_profiles(const void* d_plane, int dtype, int h, int w, int64_t row_stride, double lo, double scale,
+                     const int32_t* d_cs, int n_angles, uint64_t* d_sums, uint32_t* d_counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

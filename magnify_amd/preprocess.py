@@ -82,11 +82,22 @@ def rename_labels(xp, **coords):
 
 
 @registry.component("rotate")
-def rotate(xp, rotation=0):
+def rotate(xp, rotation=0, rotation_feature=16, rotation_max=10.0, rotation_channel=None, rotation_min_confidence=2.0,
+           rotation_time=0):
     """Rotate every plane of the stitched ``image`` by ``rotation`` degrees about its centre, keeping its size: the
     disabled body of the reference's stub (preprocess.py:54-59, ``ndinterp.rotate(..., reshape=False)``) with bilinear
     interpolation, ``scipy.ndimage.rotate(plane, rotation, axes=(-1, -2), reshape=False, order=1)`` per plane
-    (deliberate differences).  A whole number of turns returns the dataset untouched."""
+    (deliberate differences).  A whole number of turns returns the dataset untouched.
+
+    ``rotation="auto"`` (not in the reference): the angle is ``skew.estimate_rotation`` of the plane
+    (``rotation_channel`` -- a name or an index, None: the first -- at ``rotation_time``), with ``rotation_feature`` the
+    width in pixels of what the grid is made of and ``rotation_max`` the largest tilt looked for.
+    ``attrs["rotation"]`` is the angle every plane was rotated by and ``attrs["rotation_confidence"]`` the estimate's
+    confidence; below ``rotation_min_confidence`` the image stays as it is, ``attrs["rotation"]`` is 0.0 and a warning
+    says so.  The other ``rotation_*`` settings are not read with a numeric ``rotation``."""
+    if isinstance(rotation, str):
+        return _rotate_auto(xp, rotation, rotation_feature, rotation_max, rotation_channel, rotation_min_confidence,
+                            rotation_time)
     rotation = float(rotation)
     if not math.isfinite(rotation):
         raise ValueError(f"rotation must be a finite number of degrees, got {rotation!r}")
@@ -101,6 +112,23 @@ def rotate(xp, rotation=0):
     image, minmax = hotpath.rotate_image(data, rotation)
     xp["image"] = DataArray(image, ("channel", "time", "im_y", "im_x"))
     xp._cache["image_minmax"] = (image.data_ptr(), minmax)  # (find._plane_minmax: the finders skip their own pass)
+    return xp
+
+
+def _rotate_auto(xp, rotation, feature, max_angle, channel, min_confidence, time):
+    import warnings
+
+    from . import skew
+
+    skew.check_rotation(rotation, feature, max_angle, min_confidence)
+    angle, confidence = skew.estimate_rotation(xp, feature, channel=channel, time=time, max_angle=max_angle,
+                                               min_confidence=min_confidence)
+    if confidence < min_confidence:
+        warnings.warn(f"rotate: no grid seen in the image (confidence {confidence:.2f} is below "
+                      f"{min_confidence:g}); it is left as it is", stacklevel=3)
+        angle = 0.0
+    xp = rotate(xp, rotation=angle)
+    xp.attrs["rotation"], xp.attrs["rotation_confidence"] = float(angle), float(confidence)
     return xp
 
 

@@ -12,6 +12,8 @@ from __future__ import annotations
 import functools
 import inspect
 
+from .utils import to_list
+
 
 class Registry:
     """Minimal stand-in for a ``catalogue`` registry (register / get)."""
@@ -143,6 +145,19 @@ def _add_background(pipe, background, smooth, channel, after="stitch"):
     pipe.add_pipe("subtract_background", after=after, radius=background, smooth=smooth, channel=channel)
 
 
+def _add_rotate(pipe, rotation, feature, max_angle, channel, min_confidence, time=0):
+    """``rotate`` with ``rotation=``: a number of degrees as it was, the step's other settings at their defaults, or
+    "auto" (not in the reference) with the settings of the estimate, checked now, not at the first assay."""
+    if not isinstance(rotation, str):
+        pipe.add_pipe("rotate", rotation=rotation)
+        return
+    from .skew import check_rotation
+
+    check_rotation(rotation, feature, max_angle, min_confidence)
+    pipe.add_pipe("rotate", rotation=rotation, rotation_feature=feature, rotation_max=max_angle, rotation_channel=channel,
+                  rotation_min_confidence=min_confidence, rotation_time=time)
+
+
 def microfluidic_chip(data, shape=(8, 8), pinlist=None, blank=None, overlap=102, rotation=0, row_dist=375 / 1.61,
                       col_dist=400 / 1.61, chip_type=None, min_button_diameter=8, max_button_diameter=30,
                       chamber_diameter=60, top_chamber=None, left_chamber=None, low_edge_quantile=0.1,
@@ -154,9 +169,11 @@ def microfluidic_chip(data, shape=(8, 8), pinlist=None, blank=None, overlap=102,
                       depth=None, depth_window=9,
                       despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane",
                       background=None, background_smooth=0, background_channel=None,
-                      profile=None, profile_rings=None, profile_mask="own"):
+                      profile=None, profile_rings=None, profile_mask="own",
+                      rotation_feature=None, rotation_max=10.0, rotation_min_confidence=2.0):
     """registry.py:32-110 (``blend``: ``stitch``'s overlap blending; ``register``, ``max_shift``, ``register_channel``:
-    its tile registration -- neither is in the reference)."""
+    its tile registration; ``rotation="auto"`` with ``rotation_feature``, ``rotation_max``, ``rotation_min_confidence``:
+    ``rotate``'s estimate of the tilt -- none of them is in the reference)."""
     kw = dict(locals())
     kw.pop("data")
     return microfluidic_chip_pipe(**kw)(data=data)
@@ -173,7 +190,8 @@ def microfluidic_chip_pipe(shape=(8, 8), pinlist=None, blank=None, overlap=102, 
                            depth=None, depth_window=9,
                            despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane",
                            background=None, background_smooth=0, background_channel=None,
-                           profile=None, profile_rings=None, profile_mask="own"):
+                           profile=None, profile_rings=None, profile_mask="own",
+                           rotation_feature=None, rotation_max=10.0, rotation_min_confidence=2.0):
     """registry.py:196-271."""
     if chip_type is not None:
         if chip_type == "minichip":
@@ -191,7 +209,9 @@ def microfluidic_chip_pipe(shape=(8, 8), pinlist=None, blank=None, overlap=102, 
     pipe.add_pipe("identify_buttons", shape=shape, pinlist=pinlist, blank=blank)
     pipe.add_pipe("stitch", overlap=overlap, blend=blend, register=register, max_shift=max_shift,
                   register_channel=register_channel)
-    pipe.add_pipe("rotate", rotation=rotation)
+    _add_rotate(pipe, rotation, min_button_diameter if rotation_feature is None else rotation_feature, rotation_max,
+                next(iter(to_list(search_channel)), None), rotation_min_confidence,
+                min(to_list(search_timestep), default=0))
     _add_background(pipe, background, background_smooth, background_channel, after="rotate")
     pipe.add_pipe("find_buttons", row_dist=row_dist, col_dist=col_dist, min_button_diameter=min_button_diameter,
                   max_button_diameter=max_button_diameter, chamber_diameter=chamber_diameter, top_chamber=top_chamber,
@@ -311,9 +331,12 @@ def beads_pipe(flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=5, m
 def image(data, overlap=102, rotation=0, roi_only=False, drop_tiles=True, blend=None,
           register=None, max_shift=8, register_channel=None, depth=None, depth_window=9,
           despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane",
-          background=None, background_smooth=0, background_channel=None):
+          background=None, background_smooth=0, background_channel=None,
+          rotation_feature=16, rotation_max=10.0, rotation_channel=None, rotation_min_confidence=2.0):
     """registry.py:615-669."""
     return image_pipe(overlap=overlap, rotation=rotation, roi_only=roi_only, drop_tiles=drop_tiles, blend=blend,
+                      rotation_feature=rotation_feature, rotation_max=rotation_max, rotation_channel=rotation_channel,
+                      rotation_min_confidence=rotation_min_confidence,
                       register=register, max_shift=max_shift, register_channel=register_channel, depth=depth,
                       depth_window=depth_window, despeckle=despeckle, despeckle_radius=despeckle_radius,
                       despeckle_which=despeckle_which, despeckle_scope=despeckle_scope, background=background,
@@ -323,7 +346,8 @@ def image(data, overlap=102, rotation=0, roi_only=False, drop_tiles=True, blend=
 def image_pipe(overlap=102, rotation=0, roi_only=False, drop_tiles=True, blend=None,
                register=None, max_shift=8, register_channel=None, depth=None, depth_window=9,
                despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane",
-               background=None, background_smooth=0, background_channel=None):
+               background=None, background_smooth=0, background_channel=None,
+               rotation_feature=16, rotation_max=10.0, rotation_channel=None, rotation_min_confidence=2.0):
     """registry.py:672-693."""
     pipe = Pipeline("read")
     pipe.add_pipe("standardize_format")
@@ -332,7 +356,7 @@ def image_pipe(overlap=102, rotation=0, roi_only=False, drop_tiles=True, blend=N
     pipe.add_pipe("stitch", overlap=overlap, blend=blend, register=register, max_shift=max_shift,
                   register_channel=register_channel)
     _add_background(pipe, background, background_smooth, background_channel)
-    pipe.add_pipe("rotate", rotation=rotation)
+    _add_rotate(pipe, rotation, rotation_feature, rotation_max, rotation_channel, rotation_min_confidence)
     pipe.add_pipe("drop", roi_only=roi_only, drop_tiles=drop_tiles)
     pipe.add_pipe("restore_format")
     return pipe
