@@ -44,6 +44,13 @@ extern "C" {
 /* score written for circles that the exact prefilter proved to be below min_roundness */
 #define MG_SCORE_SKIPPED (-2.0f)
 
+/* Walk caps.  Most launchers cap their grid and let the kernel stride over the rest; every such cap has a name here, next
+ * to its entry's other constants (MG_<KERNEL>_WALK...: workgroups in all, ..._PER_PLANE and the like: along x for one
+ * plane), and DESIGN.md, "Capped launches and who walks them twice", lists the loops and the tests that take them round.
+ * A grid's y (and z) holds at most MG_WALK_MAX_Y workgroups: more planes than that are walked with a stride as well. */
+#define MG_WALK_MAX_Y 65535
+#define MG_ZERO_WALK 1024 /* the clearing of counters and tables before an entry's kernel (a grid-stride loop) */
+
 /* Canny map values (OpenCV's): 0 weak candidate, 1 not an edge, 2 strong edge */
 
 int mg_version(void);
@@ -81,6 +88,12 @@ int mg_perimeter_table(int min_r, int max_r, int32_t* out_rc, double* out_expect
  * path: the tile size must be a multiple of 8 (16) pixels): a per-chunk bound an eighth (a sixteenth) of the image's
  * size.  With it the integer-pixel / float32-flat path touches the flat image itself only where a pixel can still raise
  * M2 (same result, less traffic); the bound is computed once per flat image, not once per call. */
+#define MG_FLATFIELD_MAX_WALK 4096          /* mg_flatfield_max: workgroups over all groups ... */
+#define MG_FLATFIELD_MAX_WALK_PER_GROUP 512 /* ... and at most this many per group, on every path but the lean one */
+#define MG_FLATFIELD_MAX_INT_WALK 2048      /* its scalar-operand integer path: workgroups over all groups ... */
+#define MG_FLATFIELD_MAX_INT_WALK_MIN 64    /* ... and at least this many per group (below MG_FLATFIELD_MAX_WALK_PER_GROUP) */
+#define MG_FLATFIELD_MAX_LEAN_WALK 1536 /* its integer-pixel / float32-flat path with the bound: one resident round */
+#define MG_FLATFIELD_BOUND_WALK 2048   /* mg_flatfield_bound */
 int64_t mg_flatfield_max_scratch_floats(int dtype, int ty, int tx);
 int mg_flatfield_bound(const void* d_flat, int flat_dtype, int dtype, int ty, int tx, float* d_scratch,
                        int64_t scratch_floats, void* stream);
@@ -100,6 +113,8 @@ int mg_flatfield_is_identity(int dtype, double dark, const void* d_dark, double 
  * If apply_flatfield == 0 this is the pure stitch copy (any dtype, d_max2 unused).
  * d_minmax (optional, double[n_planes][2] pre-initialised to {+inf, -inf}) receives the
  * per-plane min/max of the values written (feeds to_uint8, utils.py:24-26). */
+#define MG_STITCH_WALK_FILL 2048      /* the stitch passes: rows per row group are halved (32 .. 2) below this many workgroups */
+#define MG_STITCH_WALK_PER_GROUP 1024 /* and with fewer than 32 rows at most this many workgroups walk a plane group's row groups */
 int mg_flatfield_apply_stitch(const void* d_tiles, int dtype, int64_t n_planes, int n_tile_rows, int n_tile_cols,
                               int ty, int tx, int overlap, int apply_flatfield, int planes_per_group,
                               double dark, const void* d_dark, int dark_dtype,
@@ -216,11 +231,13 @@ int mg_track_beads_based(const void* d_planes, int dtype, int n_t, int64_t plane
  * block's rows from the top, each from the left -- and rounded to float32 once: the same bits on every call.  No
  * atomics.  MG_EINVAL, with nothing launched: bin not in {2, 4, 8}, h < bin, w < bin, n_t < 1, an unknown dtype, a
  * null pointer.  One kernel launch; no allocation, no synchronisation. */
+#define MG_BIN_WALK 2048 /* workgroups of 256 items (a run of output columns of one output row) */
 int mg_bin_planes(const void* d_planes, int dtype, int n_t, int64_t plane_stride, int h, int w, int bin,
                   float* d_out, void* stream);
 
 /* Per-plane min/max (utils.py:24-25) of strided planes.  d_minmax double[n_planes][2],
  * pre-initialised to {+inf, -inf}.  Strides are in elements. */
+#define MG_PLANE_MINMAX_WALK 1024 /* workgroups per plane */
 int mg_plane_minmax(const void* d_src, int dtype, int n_planes, int64_t plane_stride, int h, int w,
                     int64_t row_stride, double* d_minmax, void* stream);
 
@@ -241,6 +258,7 @@ int mg_plane_minmax(const void* d_src, int dtype, int n_planes, int64_t plane_st
  * d_minmax (optional, double[n_planes][2] pre-initialised to {+inf, -inf}) receives the per-plane min/max of the
  * values written, as for mg_flatfield_apply_stitch.  MG_EINVAL: a null or misaligned pointer, d_src == d_dst, a
  * negative size, an unknown dtype, a non-finite matrix or offset; MG_OK without a launch when there is no pixel. */
+#define MG_ROTATE_WALK 2048 /* workgroups over all planes; each walks its share of a plane's tiles */
 int mg_affine_bilinear(const void* d_src, void* d_dst, int dtype, int64_t n_planes, int h, int w,
                        const double* matrix, const double* offset, double* d_minmax, void* stream);
 
@@ -290,6 +308,8 @@ int mg_shading_upsample(const double* d_flat_w, const double* d_dark_w, int w, i
  * d_flat / d_dark (float32, stride ty * tx).  u8 / u16 / f32 tiles in float32, f64 in float64; integer outputs
  * clamped to [0, max] and truncated.  d_minmax (optional, double[planes][2] pre-set to {+inf, -inf}): per-plane
  * min / max of the values written. */
+#define MG_SHADING_APPLY_WALK 2048 /* workgroups in all; each walks its share of the row groups */
+#define MG_SHADING_SETUP_WALK 1024 /* k_setup of mg_shading_prepare, k_begin of mg_shading_alm_begin */
 int mg_shading_apply_stitch(const void* d_tiles, int dtype, int n_fields, int64_t planes_per_field, int n_tile_rows,
                             int n_tile_cols, int ty, int tx, int overlap, const float* d_flat, const float* d_dark,
                             void* d_image, double* d_minmax, void* stream);
@@ -391,6 +411,7 @@ int mg_canny_hysteresis(const uint32_t* d_weak, uint32_t* d_strong, int64_t word
 int mg_hysteresis_tiles(int h, int w, int* tiles_x, int* tiles_y);
 
 /* Inspection helper: bitmap -> {0,1} bytes, d_out[n_planes][n_bits]. */
+#define MG_UNPACK_BITS_WALK 4096 /* workgroups per plane */
 int mg_unpack_bits(const uint32_t* d_bits, int64_t words_per_plane, int n_planes, int64_t n_bits, uint8_t* d_out,
                    void* stream);
 
@@ -411,6 +432,7 @@ int mg_edge_grid(const uint32_t* d_edge_bits, int64_t words_per_plane, int n_pla
 /* float32 gradient angle arctan2(dy, dx) (utils.py:118-119, 170) at every edge pixel of the
  * compact list, evaluated in float64 and rounded once: d_angle[n_planes][h][w] is written at
  * edge pixels only. */
+#define MG_EDGE_ANGLES_WALK 1048576 /* workgroups per plane: one edge per thread up to here */
 int mg_edge_angles(const uint8_t* d_blur, int n_planes, int h, int w, const int32_t* d_coords, int64_t coord_cap,
                    const int32_t* d_num_edges, float* d_angle, void* stream);
 
@@ -435,6 +457,9 @@ int mg_dedup_layout(int h, int w, int min_r, int max_r, int* n_tile_rows, int* n
  * their bit in d_bitmap[n_planes][bitmap_words] (mg_dedup_layout), which de-duplicates them:
  * a circle's score depends only on (row, col, r).
  * d_raw (optional, float32 [n_planes][num_iter][3]) receives the unfiltered circles. */
+#define MG_CANDIDATES_WALK 2048     /* workgroups per plane of the general kernel */
+#define MG_CANDIDATES_TAB_WALK 1024 /* of the table kernel: at most this many per plane ... */
+#define MG_CANDIDATES_TAB_FILL 1024 /* ... and about this many over all planes at least */
 int mg_candidate_circles(const int32_t* d_coords, int64_t coord_cap, const int32_t* d_cell_starts,
                          const int32_t* d_cell_counts, const int32_t* d_num_edges, int n_planes, int h, int w,
                          int grid, const uint64_t* d_seeds, int64_t num_iter, int min_r, int max_r,
@@ -505,6 +530,8 @@ int mg_bitmap_to_circles(uint32_t* d_bitmap, int64_t bitmap_words, int n_planes,
  * share a centre, only the first in suppression order (score desc, radius asc) is appended to d_alive --
  * the others have the same suppression ring and are rejected whatever happens to the first one
  * (utils.py:254-292), so the kept set is unchanged; best effort per tile (64 parked circles). */
+#define MG_SCORE_EXACT_WALK 4096     /* the exact scoring pass: workgroups over all planes (16 .. 256 per plane) */
+#define MG_SCORE_PREFILTER_WALK 4096 /* the prefilter: persistent workgroups that are dealt the super-tiles of all planes */
 int mg_score_circles(const float* d_angle, const uint32_t* d_edge_bits, const uint32_t* d_class_bits,
                      int64_t words_per_plane, int n_planes, int h, int w, int32_t* d_circles, int64_t circle_cap,
                      const int32_t* d_layer_offsets, const uint32_t* d_unique_keys, const int32_t* d_tile_ranges,
@@ -610,6 +637,7 @@ int mg_nms_sparse_max_dist(void);
  * images), or the index in d_circles when NULL.  At most out_cap rows per plane are written and d_num_out is clamped to
  * out_cap; which circles drop out then is unspecified.
  * d_scratch: int32[n_planes][3 * out_cap] work space (the kept circles' indices and 64-bit priority keys). */
+#define MG_COLLECT_WALK 8192 /* workgroups per plane of the two gather kernels and of the suppression rounds (mg_nms_*) */
 int mg_collect_circles(const int32_t* d_circles, int64_t circle_cap, const float* d_scores, const int32_t* d_alive,
                        const int32_t* d_num_alive, const uint8_t* d_state, int keep_all, int n_planes,
                        int32_t* d_out, float* d_out_scores, int64_t out_cap, int32_t* d_num_out,
@@ -653,6 +681,7 @@ int mg_counts_to_offsets(const int32_t* d_counts, int n, int cap, int32_t* d_off
  * tables (d_beads / bead_stride / d_assay_offsets as for mg_roi_segment_reduce: compact, or one padded row per assay)
  * and the counts (m, 2) / sums (m, n_c, n_t, 2) of the ROI pass at time index t_index.  m: the rows d_table holds; rows
  * beyond d_assay_offsets[n_assays] are left alone. */
+#define MG_MARKER_TABLE_WALK 2048
 int mg_marker_table(const int32_t* d_beads, int64_t bead_stride, const int32_t* d_assay_offsets, int n_assays, int m,
                     int assay_offset, const int32_t* d_counts, const double* d_sums, int n_c, int n_t, int t_index,
                     double* d_table, void* stream);
@@ -835,6 +864,7 @@ int mg_roi_unmix_keys_in_lds(int n_ln, int64_t n_masked);
  * dtype, n_c / n_t / h / w <= 0 (h above 2^30, w above 2^20), n_k / n_ln out of range, a channel outside [0, n_c) or
  * repeated, a matrix entry or an offset that is not finite, ratios other than 0 / 1, n_out * n_t >= 2^31, a negative
  * stride.  One kernel launch; no allocation, no synchronisation. */
+#define MG_UNMIX_PLANES_WALK_PER_PLANE 8192 /* workgroups of 256 lanes x 4 pixels along one time plane */
 int mg_unmix_planes(const void* d_src, int dtype, int64_t chan_stride, int64_t time_stride, int n_c, int n_t, int h, int w,
                     const int* channels, int n_k, const double* matrix, int n_ln, const double* offset, int ratios,
                     float* d_dst, void* stream);
@@ -946,6 +976,8 @@ int mg_host_write_runs(const int32_t* fds, const int64_t* offsets, const int64_t
  * ---------------------------------------------------------------------------------- */
 #define MG_OVERVIEW_MAX_LEVEL 6
 #define MG_OVERVIEW_MAX_CHANNELS 16
+#define MG_OVERVIEW_WALK 2048      /* mg_render_overview: workgroups of 256 items (a run of output pixels of one row) */
+#define MG_IMAGE_LABELS_WALK 8192  /* mg_roi_image_labels: workgroups of 256 items (four mask pixels of one window row) */
 
 /* Label map of the foreground masks in image coordinates (roi_to_image_labels, plot/image.py:157-168).  The mask of
  * marker g at timepoint t is the roi_len x roi_len bytes at d_fg + g * mask_stride_m + t * mask_stride_t (elements;
@@ -981,6 +1013,8 @@ int mg_render_overview(const void* d_image, int dtype, int64_t chan_stride, int6
  * ---------------------------------------------------------------------------------- */
 #define MG_PERCENTILE_MAX_PREFIXES 4
 #define MG_PERCENTILE_MAX_BITS 11
+#define MG_PERCENTILE_WALK 2048 /* mg_percentile_histogram: workgroups; each walks its share of the chunks */
+#define MG_MONTAGE_WALK 65536   /* mg_render_roi_montage: workgroups of 256 output pixels */
 
 /* One read-once histogram pass of the radix selection of order statistics (hotpath.percentiles picks the bins between
  * passes).  Data: n0 * n1 units of unit_len contiguous elements of `dtype`, unit (i0, i1) at d_data + i0 * stride0 +
@@ -996,7 +1030,7 @@ int mg_render_overview(const void* d_image, int dtype, int64_t chan_stride, int6
  * MG_EINVAL, with nothing launched: an unknown dtype, a null pointer, a negative count or stride, bits outside 1 ..
  * MG_PERCENTILE_MAX_BITS, shift < 0, shift + bits beyond the key, a first pass that leaves leading bits out, a
  * prefix_shift other than shift + bits, a prefix out of range or named twice, a stack so large that one workgroup's
- * share of it could pass the 2^32 of its uint32 bins (2048 workgroups: beyond 8e12 elements).  One kernel launch; no
+ * share of it could pass the 2^32 of its uint32 bins (MG_PERCENTILE_WALK workgroups: beyond 8e12 elements).  One kernel launch; no
  * allocation, no synchronisation. */
 int mg_percentile_histogram(const void* d_data, int dtype, int n0, int64_t stride0, int n1, int64_t stride1,
                             int64_t unit_len, int shift, int bits, int prefix_shift, const uint32_t* prefixes,
@@ -1040,6 +1074,9 @@ int mg_render_roi_montage(const void* d_roi, int dtype, int64_t stride_m, int64_
 #define MG_DEPTH_TILE 32  /* mg_depth_fuse: a workgroup's output tile is MG_DEPTH_TILE x MG_DEPTH_TILE pixels */
 #define MG_DEPTH_MAX_K 15
 #define MG_DEPTH_MAX_Z 255
+#define MG_DEPTH_PROJECT_WALK 4096       /* mg_depth_project: workgroups over all stacks */
+#define MG_DEPTH_FOCUS_WALK 4096         /* mg_depth_focus_totals: workgroups over all slices ... */
+#define MG_DEPTH_FOCUS_WALK_PER_SLICE 64 /* ... and at most this many share a slice (one atomic each) */
 
 /* d_dst (n, h, w) of `dtype` (a buffer other than d_src) = the fold of every stack over z.
  *   MG_DEPTH_MAX: m = slice 0; for z = 1, 2, ...: m = s where s > m; for floats a NaN in any slice gives NaN (the first
@@ -1098,6 +1135,7 @@ int mg_depth_fuse(const void* d_src, int dtype, int64_t n, int z, int h, int w, 
 #define MG_OUTLIER_ALL 3
 #define MG_DESPECKLE_MAX_K 2
 #define MG_DESPECKLE_TILE 64  /* a workgroup's output tile is MG_DESPECKLE_TILE x MG_DESPECKLE_TILE pixels */
+#define MG_DESPECKLE_WALK 2048 /* workgroups over all planes */
 
 /* d_dst (n, h, w) of `dtype` (a buffer other than d_src): d_dst[i, y, x] = m(y, x) of plane i where the CONDITION holds,
  * else d_src[i, y, x] bit for bit.  The condition is the outlier test `which` with `threshold`, or, with a defect map
@@ -1146,6 +1184,7 @@ int mg_outlier_votes(const void* d_src, int dtype, int64_t n, int h, int w, int 
 #define MG_BACKGROUND_ROWS 128  /* the vertical kernel: output rows of a workgroup's step */
 #define MG_BACKGROUND_COLS 64   /* the vertical kernel: columns of a workgroup's step, at most */
 #define MG_BACKGROUND_SPAN 256  /* the horizontal kernels: output columns of a workgroup's step */
+#define MG_BACKGROUND_WALK 16384 /* workgroups of one pass */
 
 /* The bytes of d_scratch that mg_background_planes needs for these sizes (two blocks (n, h, w) of `dtype`; 0 for an
  * empty block), or -1 where it would refuse them. */
@@ -1182,6 +1221,7 @@ int mg_background_planes(const void* d_src, const void* d_filtered, void* d_dst,
 #define MG_SKEW_TILE 64
 #define MG_SKEW_MAX_ANGLES 64
 #define MG_SKEW_MAX_SIDE 32768
+#define MG_SKEW_WALK 2048 /* workgroups; each walks its share of the plane's tiles */
 int mg_skew_profiles(const void* d_plane, int dtype, int h, int w, int64_t row_stride, double lo, double scale,
                      const int32_t* d_cs, int n_angles, uint64_t* d_sums, uint32_t* d_counts, void* stream);
 

@@ -239,7 +239,7 @@ int launch_bg_pass(const T* src, const T* orig, T* dst, int64_t n, int h, int w,
       return MG_ELAUNCH;
     attr_set = true;
   }
-  const unsigned blocks = (unsigned)std::min<int64_t>(total, 16384);
+  const unsigned blocks = (unsigned)std::min<int64_t>(total, MG_BACKGROUND_WALK);
   hipLaunchKernelGGL((k_bg_pass<T, VERT, STAGES, FIRST_MAX, SUBTRACT>), dim3(blocks), dim3(BG_THREADS), shape.lds, s, src, orig,
                      dst, h, w, radius, shape.nl, shape.nl_log2, run, shape.pitch, n_groups, n_runs, total);
   MG_CHECK_LAUNCH();

@@ -13,7 +13,7 @@
 // 16-byte aligned (the run starts a whole number of vectors into the row, so that is a property of the row), element
 // by element otherwise; the last, partial run of a row is read element by element too.  Sums are kept in registers
 // and written as float32, consecutive lanes to consecutive addresses (16- or 8-byte stores where the run is aligned).
-// Items are dealt to a grid of at most 2048 workgroups in a grid-stride loop.  No LDS.
+// Items are dealt to a grid of at most MG_BIN_WALK workgroups in a grid-stride loop.  No LDS.
 #include "mg_common.h"
 
 namespace {
@@ -100,7 +100,7 @@ int launch_bin(const void* d_planes, int n_t, int64_t plane_stride, int h, int w
   const int hb = h / BIN, wb = w / BIN, oc = BinShape<T, BIN>::OC;
   const int cpr = (wb + oc - 1) / oc;
   const int64_t total = (int64_t)n_t * hb * cpr;
-  const int blocks = (int)std::min<int64_t>((total + 255) / 256, 2048);
+  const int blocks = (int)std::min<int64_t>((total + 255) / 256, MG_BIN_WALK);
   hipLaunchKernelGGL((k_bin<T, BIN>), dim3(blocks), dim3(256), 0, s, (const T*)d_planes, plane_stride, w, hb, wb, cpr, total,
                      d_out);
   MG_CHECK_LAUNCH();

@@ -1292,7 +1292,7 @@ __global__ void k_clamp_counts(int32_t* d_num_out, int n_planes, int64_t out_cap
   if (i < n_planes && d_num_out[i] > out_cap) d_num_out[i] = (int32_t)out_cap;
 }
 
-inline int grid_x(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + NT - 1) / NT, 8192)); }
+inline int grid_x(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + NT - 1) / NT, MG_COLLECT_WALK)); }
 
 }  // namespace
 
@@ -1321,8 +1321,8 @@ int launch_candidates(const int32_t* d_coords, int64_t coord_cap, const int32_t*
     // workgroups of 1024 that run ~32 iterations per lane (the table costs each lane 1.5 entries once), but at least
     // ~1024 of them over all planes so that a single plane still fills the chip
     const int64_t per_plane = (num_iter + CT - 1) / CT;
-    int64_t blocks = std::max<int64_t>((num_iter + 32 * CT - 1) / (32 * CT), (1024 + n_planes - 1) / n_planes);
-    blocks = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(blocks, per_plane), 1024));
+    int64_t blocks = std::max<int64_t>((num_iter + 32 * CT - 1) / (32 * CT), (MG_CANDIDATES_TAB_FILL + n_planes - 1) / n_planes);
+    blocks = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(blocks, per_plane), MG_CANDIDATES_TAB_WALK));
     const int span = 2 * grid - 1;
     static bool tab_attr = false;
     if (!tab_attr) {
@@ -1337,7 +1337,7 @@ int launch_candidates(const int32_t* d_coords, int64_t coord_cap, const int32_t*
     MG_CHECK_LAUNCH();
     return MG_OK;
   }
-  hipLaunchKernelGGL(fast ? k_candidates<true> : k_candidates<false>, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((num_iter + NT - 1) / NT, 2048)), n_planes), dim3(NT), 0,
+  hipLaunchKernelGGL(fast ? k_candidates<true> : k_candidates<false>, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((num_iter + NT - 1) / NT, MG_CANDIDATES_WALK)), n_planes), dim3(NT), 0,
                      mg_stream(stream), d_coords,
                      coord_cap, d_cell_starts, d_cell_counts, d_num_edges, h, w, grid, gc, gr * gc, d_seeds, num_iter,
                      min_r, max_r, d_bitmap, bitmap_words, d_raw, d_keys);

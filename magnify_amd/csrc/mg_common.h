@@ -69,7 +69,7 @@ static __global__ void mg_k_zero_words(uint32_t* __restrict__ p, int64_t n_words
 static inline hipError_t mg_zero_async(void* p, size_t bytes, hipStream_t s) {  // bytes: a multiple of 4
   const int64_t n = (int64_t)(bytes / 4);
   if (n == 0) return hipSuccess;
-  const int blocks = (int)(n < 256 * 1024 ? (n + 255) / 256 : 1024);
+  const int blocks = (int)(n < 256 * 1024 ? (n + 255) / 256 : MG_ZERO_WALK);
   hipLaunchKernelGGL(mg_k_zero_words, dim3(blocks), dim3(256), 0, s, reinterpret_cast<uint32_t*>(p), n);
   return hipGetLastError();
 }

@@ -128,7 +128,7 @@ int launch_project(const void* d_src, void* d_dst, int64_t n, int z, int h, int 
   // lanes per plane: one more than the plane's dwords when a plane can start inside a dword
   const int64_t lanes = (plane + PX - 1) / PX + (PX > 1 ? 1 : 0);
   // 16 workgroups per CU in all when there is that much work; each walks its share of the plane
-  hipLaunchKernelGGL((k_depth_project<T, METHOD>), mg_plane_grid((lanes + 255) / 256, n, 4096), dim3(256), 0, s,
+  hipLaunchKernelGGL((k_depth_project<T, METHOD>), mg_plane_grid((lanes + 255) / 256, n, MG_DEPTH_PROJECT_WALK), dim3(256), 0, s,
                      (const T*)d_src, (T*)d_dst, n, z, plane, d_pick, lanes);
   MG_CHECK_LAUNCH();
   return MG_OK;
@@ -199,8 +199,8 @@ int launch_focus_totals(const void* d_src, int64_t n, int z, int h, int w, void*
   const int64_t tiles_x = ((int64_t)w + 255) / 256, tiles_y = ((int64_t)h + FT_ROWS - 1) / FT_ROWS;
   if (tiles_x * tiles_y > 0x7FFFFFFF) return MG_EINVAL;
   static_assert(MG_FOLD_WAVES * MG_WAVE == 256, "mg_block_fold folds workgroups of 256 threads");
-  // one atomic per workgroup and slice: at most 64 workgroups share a slice
-  hipLaunchKernelGGL((k_depth_focus_totals<T>), mg_plane_grid(tiles_x * tiles_y, n_slices, 4096, 64), dim3(256), 0, s,
+  // one atomic per workgroup and slice: at most MG_DEPTH_FOCUS_WALK_PER_SLICE workgroups share a slice
+  hipLaunchKernelGGL((k_depth_focus_totals<T>), mg_plane_grid(tiles_x * tiles_y, n_slices, MG_DEPTH_FOCUS_WALK, MG_DEPTH_FOCUS_WALK_PER_SLICE), dim3(256), 0, s,
                      (const T*)d_src, n_slices, h, w, (int)tiles_x, (int)tiles_y, d_totals);
   MG_CHECK_LAUNCH();
   return MG_OK;

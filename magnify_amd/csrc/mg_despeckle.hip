@@ -129,7 +129,7 @@ int launch_despeckle(const void* d_src, void* d_dst, int64_t n, int h, int w, in
                 "the largest tile (float64, k = 2) leaves room for four workgroups on a CU");
   static_assert(MG_FOLD_WAVES * MG_WAVE == 256, "mg_block_fold folds workgroups of 256 threads");
   // about eight workgroups per CU in all; each walks its share of a plane's tiles and adds to the plane's counter once
-  hipLaunchKernelGGL((k_despeckle<T, K, VOTES>), mg_plane_grid(tiles_x * tiles_y, n, 2048), dim3(256), 0, s, (const T*)d_src,
+  hipLaunchKernelGGL((k_despeckle<T, K, VOTES>), mg_plane_grid(tiles_x * tiles_y, n, MG_DESPECKLE_WALK), dim3(256), 0, s, (const T*)d_src,
                      (T*)d_dst, n, h, w, (int)tiles_x, (int)(tiles_x * tiles_y), which, threshold, d_defects,
                      reinterpret_cast<unsigned long long*>(d_counts), d_votes);
   MG_CHECK_LAUNCH();

@@ -1597,7 +1597,7 @@ __global__ __launch_bounds__(NT) void k_edge_angles(const uint8_t* __restrict__ 
 }
 
 inline dim3 hysteresis_grid(int h, int w, int n_planes) { return dim3((w + TW - 1) / TW, (h + HTH - 1) / HTH, n_planes); }
-inline bool grid_ok(const dim3& g) { return g.y <= 65535 && g.z <= 65535; }
+inline bool grid_ok(const dim3& g) { return g.y <= MG_WALK_MAX_Y && g.z <= MG_WALK_MAX_Y; }
 inline dim3 tile_grid(int h, int w, int n_planes) { return dim3((w + TW - 1) / TW, (h + TH - 1) / TH, n_planes); }
 inline bool words_ok(int64_t words_per_plane, int h, int w) {
   return words_per_plane * 32 >= (((int64_t)h * w + 31) / 32) * 32 + 32;  // one spare word: bits_at reads wi + 1
@@ -1812,7 +1812,7 @@ extern "C" int mg_unpack_bits(const uint32_t* d_bits, int64_t words_per_plane, i
   if (!d_bits || !d_out || n_planes < 0 || n_planes > 65535 || n_bits < 0 || words_per_plane * 32 < n_bits)
     return MG_EINVAL;
   if (n_planes == 0 || n_bits == 0) return MG_OK;
-  const int bx = (int)std::min<int64_t>((n_bits + NT - 1) / NT, 4096);
+  const int bx = (int)std::min<int64_t>((n_bits + NT - 1) / NT, MG_UNPACK_BITS_WALK);
   hipLaunchKernelGGL(k_unpack_bits, dim3(bx, n_planes), dim3(NT), 0, mg_stream(stream), d_bits, words_per_plane, n_bits,
                      d_out);
   MG_CHECK_LAUNCH();
@@ -1874,7 +1874,7 @@ extern "C" int mg_edge_angles(const uint8_t* d_blur, int n_planes, int h, int w,
   if (!d_blur || !d_coords || !d_num_edges || !d_angle || n_planes < 0 || n_planes > 65535 || coord_cap < 0)
     return MG_EINVAL;
   if (n_planes == 0 || coord_cap == 0) return MG_OK;
-  const int bx = (int)std::max<int64_t>(1, std::min<int64_t>((coord_cap + NT - 1) / NT, 1 << 20));  // one edge per thread
+  const int bx = (int)std::max<int64_t>(1, std::min<int64_t>((coord_cap + NT - 1) / NT, MG_EDGE_ANGLES_WALK));  // one edge per thread
   hipLaunchKernelGGL(k_edge_angles, dim3(bx, n_planes), dim3(NT), 0, mg_stream(stream), d_blur, h, w, d_coords,
                      coord_cap, d_num_edges, d_angle);
   MG_CHECK_LAUNCH();

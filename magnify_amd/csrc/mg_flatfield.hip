@@ -492,7 +492,7 @@ int launch_max(const void* d_tiles, int64_t tiles_per_group, int n_groups, int64
   if (tiles_per_group == 0 || n_groups == 0 || tile_elems == 0) return MG_OK;
   constexpr int N = VecOf<T>::N;
   const int64_t nvec = tile_elems / N + 1;
-  const int per_group = std::min(512, std::max(1, 4096 / n_groups));
+  const int per_group = std::min(MG_FLATFIELD_MAX_WALK_PER_GROUP, std::max(1, MG_FLATFIELD_MAX_WALK / n_groups));
   int blocks = (int)std::min<int64_t>((nvec + 255) / 256, per_group);
   if constexpr (IsIntegral<T>::value) {  // (the integer-only kernels exist for integer pixels only)
     const int64_t group_elems = tiles_per_group * tile_elems;
@@ -500,7 +500,7 @@ int launch_max(const void* d_tiles, int64_t tiles_per_group, int n_groups, int64
         (group_elems * (int64_t)sizeof(T)) % 16 == 0) {
       const int64_t gvec = group_elems / N;
       // (every workgroup ends with two compare-and-swap maxima on the group's cache line: few, long-running workgroups)
-      const int gb = (int)std::max<int64_t>(1, std::min<int64_t>(gvec / 256, std::min(512, std::max(64, 2048 / n_groups))));
+      const int gb = (int)std::max<int64_t>(1, std::min<int64_t>(gvec / 256, std::min(MG_FLATFIELD_MAX_WALK_PER_GROUP, std::max(MG_FLATFIELD_MAX_INT_WALK_MIN, MG_FLATFIELD_MAX_INT_WALK / n_groups))));
       hipLaunchKernelGGL((k_flatfield_max_int<T>), dim3(gb, n_groups), dim3(256), 0, s, (const T*)d_tiles, group_elems, dark,
                          flat, d_max2);
       MG_CHECK_LAUNCH();
@@ -512,7 +512,7 @@ int launch_max(const void* d_tiles, int64_t tiles_per_group, int n_groups, int64
         const int64_t cvec = tile_elems / N;  // (d_scratch: the bound of this flat image, mg_flatfield_bound)
         // one resident round of workgroups in all (74 VGPRs: 6 per CU), however many groups share them: every workgroup
         // ends with two compare-and-swap maxima on its group's cache line
-        const int per = (int)std::max<int64_t>(1, std::min<int64_t>((cvec + 255) / 256, std::max(1, 1536 / n_groups)));
+        const int per = (int)std::max<int64_t>(1, std::min<int64_t>((cvec + 255) / 256, std::max(1, MG_FLATFIELD_MAX_LEAN_WALK / n_groups)));
         const int64_t chunks_per_lane = (cvec + (int64_t)per * 256 - 1) / ((int64_t)per * 256) * tiles_per_group;
         with_flag(chunks_per_lane < 512, [&](auto share) {
           hipLaunchKernelGGL((k_flatfield_max_lean<T, decltype(share)::value>), dim3(per, n_groups), dim3(256), 0, s,
@@ -552,7 +552,7 @@ int launch_apply(const StitchSrc<T>& src, int64_t n_planes, int overlap, bool ap
     if (aligned) {
       int rows;
       const dim3 grid = stitch_grid<N>(g.h_out, g.w_out, n_planes, rows);
-      if (grid.y > 65535 || grid.z > 65535) return MG_EINVAL;
+      if (grid.y > MG_WALK_MAX_Y || grid.z > MG_WALK_MAX_Y) return MG_EINVAL;
       // an integer-valued scalar dark inside the pixel range: subtracted in the integer domain
       const bool int_dark = apply && dark_is_int(src.d_dark, src.dark);
       auto launch = [&](auto ap, auto id, auto sub) {
@@ -577,7 +577,7 @@ int launch_minmax(const void* d_src, int n_planes, int64_t plane_stride, int h, 
                   double* d_minmax, hipStream_t s) {
   if (n_planes == 0 || h == 0 || w == 0) return MG_OK;
   const int64_t total = (int64_t)h * ((w + VecOf<T>::N - 1) / VecOf<T>::N);
-  int bx = (int)std::min<int64_t>((total + 255) / 256, 1024);
+  int bx = (int)std::min<int64_t>((total + 255) / 256, MG_PLANE_MINMAX_WALK);
   hipLaunchKernelGGL((k_plane_minmax<T>), dim3(bx, n_planes), dim3(256), 0, s, (const T*)d_src, plane_stride, h, w,
                      row_stride, d_minmax);
   MG_CHECK_LAUNCH();
@@ -614,7 +614,7 @@ extern "C" int mg_flatfield_bound(const void* d_flat, int flat_dtype, int dtype,
     if constexpr (IsIntegral<T>::value) {  // (need > 0: an integer pixel type)
       constexpr int N = VecOf<T>::N;
       const int64_t cvec = tile_elems / N;
-      const dim3 grid((unsigned)std::min<int64_t>((cvec + 255) / 256, 2048));
+      const dim3 grid((unsigned)std::min<int64_t>((cvec + 255) / 256, MG_FLATFIELD_BOUND_WALK));
       hipLaunchKernelGGL((k_flat_rcmax<N>), grid, dim3(256), 0, s, (const float*)d_flat, cvec, d_scratch);
       MG_CHECK_LAUNCH();
       return (int)MG_OK;

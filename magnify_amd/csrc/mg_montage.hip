@@ -119,7 +119,7 @@ extern "C" int mg_render_roi_montage(const void* d_roi, int dtype, int64_t strid
   if (total == 0) return MG_OK;  // no cells: an empty picture
   if (!d_roi || !d_layout || !d_out || n_marks < 1) return MG_EINVAL;
   const MgMaskView bg = {d_bg, bg_stride_m, bg_stride_t}, fg = {d_fg, fg_stride_m, fg_stride_t};
-  const int blocks = (int)std::min<int64_t>((total + 255) / 256, 1 << 16);
+  const int blocks = (int)std::min<int64_t>((total + 255) / 256, MG_MONTAGE_WALK);
   hipStream_t st = mg_stream(stream);
   return mg_dispatch_pixel(dtype, [&](auto t) {
     using T = decltype(t);

@@ -246,7 +246,7 @@ int launch_overview(const void* d_image, int64_t chan_stride, int64_t time_strid
   const int hk = (h + S - 1) / S, wk = (w + S - 1) / S, oc = RunShape<T, S>::OC;
   const int cpr = (wk + oc - 1) / oc;
   const int64_t total = (int64_t)n_t * hk * cpr;
-  const int blocks = (int)std::min<int64_t>((total + 255) / 256, 2048);
+  const int blocks = (int)std::min<int64_t>((total + 255) / 256, MG_OVERVIEW_WALK);
   hipLaunchKernelGGL((k_overview<T, S>), dim3(blocks), dim3(256), 0, s, (const T*)d_image, chan_stride, time_stride, n_c, n_t,
                      h, w, hk, wk, cpr, total, ch, d_labels, d_table, n_marks, overlay, alpha, d_out);
   MG_CHECK_LAUNCH();
@@ -266,7 +266,7 @@ extern "C" int mg_roi_image_labels(const uint8_t* d_fg, int64_t mask_stride_m, i
   if (!mg_mask_view_ok(fg) || !d_origin) return MG_EINVAL;
   const int s = 1 << level, hk = (h + s - 1) / s, wk = (w + s - 1) / s, qpr = (roi_len + 3) / 4;
   const int64_t total = (int64_t)m * n_t * roi_len * qpr;
-  const int blocks = (int)std::min<int64_t>((total + 255) / 256, 8192);
+  const int blocks = (int)std::min<int64_t>((total + 255) / 256, MG_IMAGE_LABELS_WALK);
   hipLaunchKernelGGL(k_image_labels, dim3(blocks), dim3(256), 0, mg_stream(stream), fg, d_origin, n_t, roi_len, qpr,
                      level, h, w, hk, wk, total, d_labels);
   MG_CHECK_LAUNCH();

@@ -163,7 +163,7 @@ extern "C" int mg_percentile_histogram(const void* d_data, int dtype, int n0, in
   const int64_t cpu = (unit_len + chunk_elems - 1) / chunk_elems;
   if (cpu > INT64_MAX / units) return MG_EINVAL;
   const int64_t total = units * cpu;
-  const int blocks = (int)std::min<int64_t>(total, 2048);
+  const int blocks = (int)std::min<int64_t>(total, MG_PERCENTILE_WALK);
   // a workgroup's uint32 bins hold what it counts: at most ceil(total / blocks) chunks
   if ((total + blocks - 1) / blocks > (int64_t)0xFFFFFFFFLL / chunk_elems) return MG_EINVAL;
   const size_t lds = (size_t)(n_prefixes > 0 ? n_prefixes : 1) * ((size_t)1 << bits) * sizeof(uint32_t);

@@ -27,11 +27,11 @@ static inline MgPlanes mg_planes_check(int dtype, int64_t n, int h, int w, std::
 // ---- the grid and its walk --------------------------------------------------------------------------------------------
 
 // Grid of a kernel whose workgroups walk the `items` (tiles, or blocks of lanes; at least 1) of a plane along x and the
-// n planes along y: y = min(n, 65535); x = the items, cut to `per_plane` and to x * y <= `budget` workgroups in all (0:
+// n planes along y: y = min(n, MG_WALK_MAX_Y); x = the items, cut to `per_plane` and to x * y <= `budget` workgroups in all (0:
 // no such limit), and never below 1.  Neither count is bounded by the grid: the kernel strides over both, with
 // MG_FOR_BLOCK_PLANES and MG_FOR_BLOCK_ITEMS (or a loop of its own over items that are not dealt by the workgroup).
 static inline dim3 mg_plane_grid(int64_t items, int64_t n, int64_t budget = 0, int64_t per_plane = 0) {
-  const int64_t gy = std::min<int64_t>(n, 65535);
+  const int64_t gy = std::min<int64_t>(n, MG_WALK_MAX_Y);
   int64_t gx = items;
   if (per_plane) gx = std::min(gx, per_plane);
   if (budget) gx = std::min(gx, budget / gy);

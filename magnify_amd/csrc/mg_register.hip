@@ -338,7 +338,7 @@ int launch_shift(const StitchSrc<T>& src, const ShiftTable& st, int64_t n_planes
   if (n_planes == 0 || g.h_out == 0 || g.w_out == 0) return MG_OK;
   int rows;
   const dim3 grid = stitch_grid<VecOf<T>::N>(g.h_out, g.w_out, n_planes, rows);
-  if (grid.y > 65535 || grid.z > 65535) return MG_EINVAL;
+  if (grid.y > MG_WALK_MAX_Y || grid.z > MG_WALK_MAX_Y) return MG_EINVAL;
   return with_flag(blend, [&](auto bl) {
     hipLaunchKernelGGL((k_shift_stitch<T, MODE, decltype(bl)::value>), grid, dim3(256), 0, s, src, st, (int)n_planes, overlap,
                        g.hy, g.hx, (T*)d_image, d_minmax, rows);

@@ -697,7 +697,7 @@ extern "C" int mg_marker_table(const int32_t* d_beads, int64_t bead_stride, cons
     return MG_EINVAL;
   if (m == 0) return MG_OK;
   if (!d_beads || !d_counts || !d_sums || !d_table) return MG_EINVAL;
-  hipLaunchKernelGGL(k_marker_table, dim3((unsigned)std::min((m + 255) / 256, 2048)), dim3(256), 0, mg_stream(stream),
+  hipLaunchKernelGGL(k_marker_table, dim3((unsigned)std::min((m + 255) / 256, MG_MARKER_TABLE_WALK)), dim3(256), 0, mg_stream(stream),
                      d_beads, bead_stride, d_assay_offsets, n_assays, assay_offset, d_counts, d_sums, n_c, n_t, t_index,
                      d_table);
   MG_CHECK_LAUNCH();

@@ -156,9 +156,9 @@ int launch_affine(const void* d_src, void* d_dst, int64_t n_planes, int h, int w
   const int64_t lanes = ((int64_t)w + PX - 1) / PX + (PX > 1 ? 1 : 0);
   const int64_t tiles_x = (lanes + RT_LX - 1) / RT_LX, tiles_y = ((int64_t)h + RT_ROWS - 1) / RT_ROWS;
   if (tiles_x * tiles_y > 0x7FFFFFFF) return MG_EINVAL;
-  // ~2048 workgroups in all walk the tiles (each ends with min/max atomics on its plane's one cache line)
-  const unsigned gy = (unsigned)std::min<int64_t>(n_planes, 65535);
-  const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(tiles_x * tiles_y, 2048 / gy));
+  // ~MG_ROTATE_WALK workgroups in all walk the tiles (each ends with min/max atomics on its plane's one cache line)
+  const unsigned gy = (unsigned)std::min<int64_t>(n_planes, MG_WALK_MAX_Y);
+  const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(tiles_x * tiles_y, MG_ROTATE_WALK / gy));
   static_assert(RT_LX * RT_LY == 256, "mg_block_minmax folds workgroups of 256 threads");
   hipLaunchKernelGGL((k_affine_bilinear<T>), dim3(gx, gy), dim3(RT_LX * RT_LY), 0, s, (const T*)d_src, (T*)d_dst, n_planes,
                      h, w, a, (int)tiles_x, (int)tiles_y, d_minmax);

@@ -688,14 +688,14 @@ extern "C" int mg_score_circles_keyed(const uint8_t* d_blur, const float* d_angl
     attr_set = true;
   }
   // persistent blocks, super-tiles dealt round-robin (neighbouring super-tiles run at the same time)
-  const int blocks = (int)std::min<int64_t>(total_st, 256 * 2 * 8);
+  const int blocks = (int)std::min<int64_t>(total_st, MG_SCORE_PREFILTER_WALK);
   hipLaunchKernelGGL(k_prefilter, dim3(blocks), dim3(NP), lds_bytes, s, d_edge_bits, d_class_bits, words_per_plane, h, w,
                      d_unique_keys, circle_cap, d_layer_starts, ntr * ntc, ntr, ntc, nsc, n_st, total_st, min_r, max_r, nr,
                      reinterpret_cast<const uint2*>(d_pair_table), d_per_starts, min_roundness, write_skipped, d_scores,
                      d_surv_list, surv_cap, d_num_surv);
   MG_CHECK_LAUNCH();
   // blocks per plane: enough to fill the chip at any batch size, few enough to amortise the table load
-  const int xblocks = std::max(16, std::min(256, 4096 / std::max(n_planes, 1)));
+  const int xblocks = std::max(16, std::min(256, MG_SCORE_EXACT_WALK / std::max(n_planes, 1)));
   if (n_planes <= 4)
     hipLaunchKernelGGL(k_exact<16>, dim3(4 * xblocks, n_planes), dim3(NT), (size_t)per_total * 4, s, d_blur, d_angle,
                        d_edge_bits, words_per_plane, h, w, d_circles, circle_cap, ntc, min_r, max_r, d_per_rc, per_total,

@@ -507,8 +507,8 @@ int launch_shading_apply(const void* d_tiles, int64_t n_planes, int64_t ppf, int
   const int rows = 8;
   const int64_t groups = (h_out + rows - 1) / rows;
   // about 8 workgroups per CU over the whole launch; each takes row groups blockIdx.y, +gridDim.y, ...
-  const int64_t want = std::max<int64_t>(1, 2048 / std::max<int64_t>(1, gx * n_planes));
-  const int gy = (int)std::min<int64_t>(groups, std::min<int64_t>(want, 65535));
+  const int64_t want = std::max<int64_t>(1, MG_SHADING_APPLY_WALK / std::max<int64_t>(1, gx * n_planes));
+  const int gy = (int)std::min<int64_t>(groups, std::min<int64_t>(want, MG_WALK_MAX_Y));
   hipLaunchKernelGGL((k_shading_apply<T>), dim3(gx, gy, (unsigned)n_planes), dim3(256), 0, s, (const T*)d_tiles, ppf,
                      n_tr, n_tc, ty, tx, clip, hy, hx, d_flat, d_dark, (T*)d_image, d_minmax, rows);
   MG_CHECK_LAUNCH();
@@ -548,7 +548,7 @@ extern "C" int mg_shading_prepare(void* d_ws, int n, int w, void* stream) {
   if (!d_ws || !shape_ok(n, w) || n > 65535) return MG_EINVAL;
   const Ws ws = make_ws(d_ws, n, w);
   hipStream_t s = mg_stream(stream);
-  hipLaunchKernelGGL(k_setup, dim3(1024), dim3(256), 0, s, ws);
+  hipLaunchKernelGGL(k_setup, dim3(MG_SHADING_SETUP_WALK), dim3(256), 0, s, ws);
   hipLaunchKernelGGL(k_gram, dim3((unsigned)n, (unsigned)n), dim3(256), 0, s, ws);
   MG_CHECK_LAUNCH();
   return MG_OK;
@@ -571,7 +571,7 @@ extern "C" int mg_shading_alm_begin(void* d_ws, int n, int w, int get_darkfield,
   if (!d_ws || !shape_ok(n, w) || max_iterations < 1) return MG_EINVAL;
   const Ws ws = make_ws(d_ws, n, w);
   hipStream_t s = mg_stream(stream);
-  hipLaunchKernelGGL(k_begin, dim3(1024), dim3(256), 0, s, ws, get_darkfield, max_iterations, mu, lam_f, lam_d, tol,
+  hipLaunchKernelGGL(k_begin, dim3(MG_SHADING_SETUP_WALK), dim3(256), 0, s, ws, get_darkfield, max_iterations, mu, lam_f, lam_d, tol,
                      norm_f, b_up);
   MG_CHECK_LAUNCH();
   return MG_OK;

@@ -176,7 +176,7 @@ extern "C" int mg_skew_profiles(const void* d_plane, int dtype, int h, int w, in
     const SkewArgs<T> args{(const T*)d_plane, h, w, row_stride, lo, scale, d_cs, n_angles, std::min(h, w) + 2, tiles_x, tiles,
                            reinterpret_cast<unsigned long long*>(d_sums), d_counts};
     // about eight workgroups per CU in all; each walks its share of the tiles
-    hipLaunchKernelGGL(k_skew_profiles<T>, mg_plane_grid(tiles, 1, 2048), dim3(256), 0, s, args);
+    hipLaunchKernelGGL(k_skew_profiles<T>, mg_plane_grid(tiles, 1, MG_SKEW_WALK), dim3(256), 0, s, args);
     MG_CHECK_LAUNCH();
     return (int)MG_OK;
   });

@@ -285,11 +285,11 @@ inline dim3 stitch_grid(int h_out, int w_out, int64_t n_planes, int& rows) {
   // rows per workgroup: 32 when that still gives ~8 workgroups per CU, down to 2 for a single assay
   rows = ROWS_PER_BLOCK;
   const int64_t cols_planes = (int64_t)((w_out + 256 * N - 1) / (256 * N)) * ((n_planes + PLANES_PER_BLOCK - 1) / PLANES_PER_BLOCK);
-  while (rows > 2 && cols_planes * ((h_out + rows - 1) / rows) < 2048) rows /= 2;
+  while (rows > 2 && cols_planes * ((h_out + rows - 1) / rows) < MG_STITCH_WALK_FILL) rows /= 2;
   // ... and at most ~1024 workgroups per plane group walk them (each ends with min/max atomics on the plane's one
   // cache line: 2048 workgroups finishing together took 100 us over them)
   int y_blocks = (h_out + rows - 1) / rows;
-  if (rows < ROWS_PER_BLOCK) y_blocks = (int)std::min<int64_t>(y_blocks, std::max<int64_t>(1, 1024 / std::max<int64_t>(1, cols_planes)));
+  if (rows < ROWS_PER_BLOCK) y_blocks = (int)std::min<int64_t>(y_blocks, std::max<int64_t>(1, MG_STITCH_WALK_PER_GROUP / std::max<int64_t>(1, cols_planes)));
   return dim3((w_out + 256 * N - 1) / (256 * N), y_blocks, (unsigned)((n_planes + PLANES_PER_BLOCK - 1) / PLANES_PER_BLOCK));
 }
 

@@ -146,7 +146,7 @@ int launch_stitch(const StitchSrc<T>& src, int64_t n_planes, int overlap, PlaneS
   if (n_planes > 0x7FFFFFF0) return MG_EINVAL;
   int rows;
   const dim3 grid = stitch_grid<VecOf<T>::N>(h_out, w_out, n_planes, rows);
-  if (grid.y > 65535 || grid.z > 65535) return MG_EINVAL;
+  if (grid.y > MG_WALK_MAX_Y || grid.z > MG_WALK_MAX_Y) return MG_EINVAL;
   hipLaunchKernelGGL((k_stitch<T, MODE, BLEND, SUBSET>), grid, dim3(256), 0, s, src, (int)n_planes, overlap, hy, hx,
                      (T*)d_image, d_minmax, rows, sel);
   MG_CHECK_LAUNCH();

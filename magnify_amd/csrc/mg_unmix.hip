@@ -347,7 +347,7 @@ extern "C" int mg_unmix_planes(const void* d_src, int dtype, int64_t chan_stride
   hipStream_t s = mg_stream(stream);
   return mg_dispatch_pixel(dtype, [&](auto t) {
     typedef decltype(t) T;
-    hipLaunchKernelGGL(k_unmix_planes<T>, mg_plane_grid((quads + 255) / 256, n_t, 0, 8192), dim3(256), 0, s,
+    hipLaunchKernelGGL(k_unmix_planes<T>, mg_plane_grid((quads + 255) / 256, n_t, 0, MG_UNMIX_PLANES_WALK_PER_PLANE), dim3(256), 0, s,
                        (const T*)d_src, chan_stride, time_stride, u, ratios, n_t, hw, d_dst);
     MG_CHECK_LAUNCH();
     return MG_OK;

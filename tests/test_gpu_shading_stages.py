@@ -114,7 +114,7 @@ def _read(f, region, dtype, shape):
     return f.view(region, dtype, shape).cpu().numpy()
 
 
-@pytest.mark.parametrize("n, w", [(1, 1), (2, 8), (5, 33), (8, 128), (300, 24)])
+@pytest.mark.parametrize("n, w", [(1, 1), (2, 8), (5, 33), (8, 128), (300, 24), (17, 128)])
 def test_prepare(mg, n, w):
     d = _stack(n, w)
     f = mg.shading._Fitter(_dev(d))
@@ -141,6 +141,29 @@ def test_prepare(mg, n, w):
         assert P % LANES != 0  # a ragged last 256-lane group in k_gram's loop
     if n == 300:
         assert n > LANES
+    if (n, w) == (17, 128):  # k_setup runs on a fixed grid: more values than it has lanes send it round again
+        assert n * P > mg.hotpath.nat.DEFINES["MG_SHADING_SETUP_WALK"] * LANES
+
+
+def test_begin_resets_a_stack_of_more_values_than_its_grid_has_lanes(mg):
+    """k_begin runs on a fixed grid and strides over the n w^2 values of E and Y: 17 images at w = 128 send it round
+    again ("Capped launches and who walks them twice").  The state of a fresh pass is exact: zeros and ones."""
+    n, w = 17, 128
+    assert n * w * w > mg.hotpath.nat.DEFINES["MG_SHADING_SETUP_WALK"] * LANES
+    f = mg.shading._Fitter(_dev(_stack(n, w)))
+    for region, dtype, shape in ((R_E, torch.float32, (n, w, w)), (R_Y, torch.float32, (n, w, w)),
+                                 (R_WHAT, torch.float64, (w, w)), (R_FW, torch.float64, (w, w)),
+                                 (R_AOFF, torch.float64, (w, w)), (R_COEFF, torch.float64, (n,))):
+        f.view(region, dtype, shape).fill_(3.0)
+    f.begin()
+    for region in (R_E, R_Y):
+        assert not _read(f, region, torch.float32, (n, w, w)).any()
+    for region in (R_WHAT, R_FW, R_AOFF):
+        assert not _read(f, region, torch.float64, (w, w)).any()
+    assert (_read(f, R_COEFF, torch.float64, (n,)) == 1.0).all()
+    flags = _read(f, R_FLAGS, torch.int32, (8,))
+    assert flags[FL_DONE] == 0 and flags[FL_ITER] == 0
+    assert (_read(f, R_WEIGHT, torch.float32, (n, w, w)) == 1.0).all()  # (k_setup's, untouched)
 
 
 # ---- DCT -------------------------------------------------------------------------------------------------------------
