@@ -912,6 +912,65 @@ int mg_roi_threshold_masks(const void* d_roi, int dtype, int64_t stride_m, int64
                            uint8_t* d_fg, uint8_t* d_bg, double* d_threshold, int32_t* d_counts, uint8_t* d_segmented,
                            void* stream);
 
+/* Sub-pixel circle fit of every marker of an already gathered roi (refine_markers, refine="edge").  NOT in the
+ * reference, whose finders stop at the integer circle of the RANSAC vote and drop its radius (find.py:561-586,
+ * find.py:383-400).  A radial edge search along n_rays rays about the found circle, then an algebraic (Kasa) circle fit
+ * with one rejection round.  tests/refine_ref.py restates the contract in plain NumPy loops and the kernel equals it
+ * bit for bit.
+ * d_roi points at the first window of ONE channel, element type `dtype`; window (g, t), roi_len x roi_len contiguous
+ * pixels, is at d_roi + g * roi_stride_m + t * roi_stride_t (elements).  d_circle: the start circle {cy, cx, r} of window
+ * (g, t) in window coordinates, int32 in units of 1 / MG_PROFILE_SUBPIXEL pixel, at d_circle + g * circle_stride_m +
+ * t * circle_stride_t (elements; a time stride of 0: one circle for all timepoints).  Circles are device data and cannot
+ * be refused: cy, cx are clamped to mg_roi_radial_profile's range [-1024, 2048] pixels and r to [0, 1024] pixels.
+ * d_cs: DEVICE double[n_rays][2] = {cos, sin}(2 pi k / n_rays), computed by the host; the kernel calls no trigonometric
+ * function and takes no square root.  With K = n_rays, L = roi_len, cy, cx, r now in pixels (the integers / 16.0), all in
+ * float64, every operation rounded once, left to right as written, nothing contracted:
+ *   1. J = 4 reach + 1 samples per ray at rho_j = (r - reach) + 0.5 j; j_lo = the first j with rho_j >= 0, the same for
+ *      all rays of the window.  Sample (k, j) lies at y = cy + rho_j * sin_k, x = cx + rho_j * cos_k.
+ *   2. iy = floor(y), ix = floor(x), fy = y - iy, fx = x - ix.  The sample is inside iff 0 <= iy, iy + 1 <= L - 1 and the
+ *      same in x (a NaN position is outside).  Its value, from the pixels W converted to float64:
+ *      (W[iy][ix] * (1 - fx) + W[iy][ix+1] * fx) * (1 - fy) + (W[iy+1][ix] * (1 - fx) + W[iy+1][ix+1] * fx) * fy.
+ *      A ray is USABLE iff every sample j >= j_lo is inside and its value is finite.
+ *   3. d_j = v_{j+1} - v_{j-1} for j_lo + 1 <= j <= J - 2 (at least one j).
+ *   4. polarity 0 (auto): P+ = sum_k max_j d_j and P- = sum_k max_j (-d_j), both over the usable rays in ascending k;
+ *      the polarity is +1 (brighter outside) iff P+ >= P-, else -1.  polarity +1 / -1: as given.  e_j = polarity * d_j.
+ *   5. j* = the first arg-max of e_j.  The ray is VALID iff it is usable, e_{j*} > 0 and j* is neither the first nor the
+ *      last derivative index.  With e-, e0, e+ = e_{j*-1}, e_{j*}, e_{j*+1}: delta = (0.5 * (e- - e+)) / ((e- - 2 e0) + e+),
+ *      rho_k = rho_{j*} + 0.5 * delta, strength w_k = e0.
+ *   6. KEPT: the valid rays with w_k >= min_strength * max_k w_k.  Fewer than min_rays: status 1.
+ *   7. Fit over a set of n rays, every sum in ascending k: u = rho_k * cos_k, v = rho_k * sin_k (offsets from the start
+ *      centre); ub = (sum u) / n, vb = (sum v) / n; u' = u - ub, v' = v - vb, z = u' u' + v' v'; Suu = sum u' u',
+ *      Suv = sum u' v', Svv = sum v' v', Suz = sum u' z, Svz = sum v' z; det = Suu Svv - Suv Suv;
+ *      a' = (0.5 * (Suz Svv - Svz Suv)) / det, b' = (0.5 * (Svz Suu - Suz Suv)) / det; a = ub + a', b = vb + b';
+ *      R2 = (a' a' + b' b') + (Suu + Svv) / n.  The fit FAILS where det > 0 or R2 > 0 does not hold.
+ *   8. Fit the kept set.  g_k = ((u - a)^2 + (v - b)^2) - R2; ray k is dropped iff g_k g_k > (4 (reject reject)) R2 -- the
+ *      geometric residual against `reject` pixels, without a square root.  If a ray was dropped and at least min_rays
+ *      remain, the rest is fitted again and is the final set; otherwise the kept set is, with its fit.  With g_k of the
+ *      final fit: msq = (sum g_k g_k) / ((4 R2) n), mean strength = (sum w_k) / n.
+ *   9. status: 0 ok; 1 too few rays (rule 6); 2 degenerate -- a fit failed, or a, b, R2, msq or the mean strength is not
+ *      finite; 3 out of reach -- a a + b b > reach^2, or R2 outside [max(r - reach, 0)^2, (r + reach)^2].  Tested in
+ *      this order.
+ *   d_info int32[m][n_t][4]    {status, n_used, n_valid, polarity}: the size of the final set (of the kept set for
+ *                              status 1), the number of valid rays, the polarity used
+ *   d_fit  double[m][n_t][5]   {b (dy), a (dx), R2, msq, mean strength}; all five the quiet NaN 0x7FF8000000000000
+ *                              where status != 0
+ * One workgroup of 256 lanes per (marker, time): the samples as float64 in LDS (at most 33 KB), one lane per ray for
+ * rules 3 and 5 and for the terms of rules 7 and 8, one lane per ordered sum -- the same bits on every call.  The launch is not capped: one workgroup
+ * per window, as mg_roi_radial_profile and mg_roi_threshold_masks launch theirs.
+ * MG_EINVAL, with nothing written: a null pointer, an unknown dtype, m < 0, n_t <= 0, roi_len outside
+ * 1 .. MG_REFINE_MAX_LEN, m * n_t >= 2^31, a negative stride, n_rays outside [8, MG_REFINE_MAX_RAYS], reach outside
+ * [1, MG_REFINE_MAX_REACH], polarity outside {-1, 0, 1}, reject not finite or not > 0, min_strength outside [0, 1],
+ * min_rays outside [3, n_rays].  m = 0 returns MG_OK and writes nothing.  One kernel launch; no allocation, no
+ * synchronisation. */
+#define MG_REFINE_MAX_RAYS 128
+#define MG_REFINE_MAX_REACH 8
+#define MG_REFINE_MAX_LEN 1024
+int mg_roi_refine_circles(const void* d_roi, int dtype, int64_t roi_stride_m, int64_t roi_stride_t,
+                          const int32_t* d_circle, int64_t circle_stride_m, int64_t circle_stride_t,
+                          const double* d_cs, int n_rays, int m, int n_t, int roi_len, int reach, int polarity,
+                          double reject, double min_strength, int min_rays, int32_t* d_info, double* d_fit,
+                          void* stream);
+
 /* ------------------------------------------------------------------------------------
  * A16 / A17 ButtonFinder helpers (find.py:205-402, 632-677)
  * ---------------------------------------------------------------------------------- */

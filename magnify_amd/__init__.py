@@ -22,7 +22,7 @@ from .registry import (  # noqa: F401
     readers,
 )
 from .pipeline import Pipeline  # noqa: F401
-from . import reader, preprocess, shading, stitch, find, identify, postprocess, reduce, utils, filter, segment, depth, despeckle, background, profile, unmix, skew  # noqa: F401,E402  (register components)
+from . import reader, preprocess, shading, stitch, find, identify, postprocess, reduce, utils, filter, segment, depth, despeckle, background, profile, unmix, skew, refine  # noqa: F401,E402  (register components)
 from .utils import seed  # noqa: F401
 from .file import load, save  # noqa: F401
 from . import sink  # noqa: F401,E402
@@ -32,4 +32,4 @@ from . import plot  # noqa: F401,E402
 __all__ = ["component", "microfluidic_chip", "microfluidic_chip_pipe", "mrbles", "mrbles_pipe", "beads", "beads_pipe",
            "image", "image_pipe", "save", "load", "Pipeline", "DataArray", "Dataset", "seed", "find", "identify", "postprocess",
            "preprocess", "reader", "shading", "stitch", "reduce", "utils", "xr_lite", "filter", "plot", "segment", "depth",
-           "despeckle", "background", "profile", "unmix", "skew"]
+           "despeckle", "background", "profile", "unmix", "skew", "refine"]

@@ -1792,6 +1792,61 @@ def threshold_masks(roi_channel: torch.Tensor, fg0: torch.Tensor, bg0: torch.Ten
     return fg, bg, threshold, counts, segmented
 
 
+_DIRECTION_TABLES = {}  # (rays, device) -> double[rays][2] = {cos, sin} on the device, uploaded once
+
+
+def direction_table(rays: int) -> np.ndarray:
+    """double[rays][2] = {cos, sin}(2 pi k / rays), as mg_roi_refine_circles and its oracle read it."""
+    a = (2.0 * np.pi * np.arange(rays, dtype=np.float64)) / float(rays)
+    return np.ascontiguousarray(np.stack([np.cos(a), np.sin(a)], axis=1))
+
+
+def refine_circles(plane: torch.Tensor, circle_q, rays=64, reach=3, polarity=0, reject=1.0, min_strength=0.25,
+                   min_rays=None):
+    """Sub-pixel circle fit of plane (M, T, L, L) -- ONE channel of a gathered roi, uint8 / uint16 / float32 / float64;
+    a view such as ``roi[:, c]`` is read in place -- by mg_roi_refine_circles (include/magnify_hip.h states the contract,
+    tests/refine_ref.py restates it).  ``circle_q``: int32 (M, 3) or (M, T', 3) = {cy, cx, r} in window coordinates, in
+    1/16 pixel, T' = T, or T' = 1 or a view expanded along time: one circle for all timepoints.  ``polarity``: 0 (auto),
+    +1 (brighter outside) or -1; ``min_rays``: None for rays // 2.  -> info int32 (M, T, 4) = {status, n_used, n_valid,
+    polarity}, fit float64 (M, T, 5) = {dy, dx, R^2, mean squared residual, mean strength}, NaN where status != 0.
+    ValueError for a setting ``refine.check_refine`` refuses."""
+    from .refine import MAX_LEN, check_refine
+
+    if plane.dim() != 4 or plane.shape[2] != plane.shape[3]:
+        raise ValueError(f"refine_circles takes one channel's windows (M, T, L, L), got shape {tuple(plane.shape)}")
+    m, t, L, _ = plane.shape
+    rays, reach, polarity, reject, min_strength, min_rays = check_refine(rays, reach, polarity, reject, min_strength,
+                                                                         min_rays, L)
+    code = nat.dtype_code(plane.dtype)
+    require_gpu()
+    plane, psm, pst = _window_view("refine_circles plane", plane, m, t, L)
+    dev = plane.device
+    info = torch.empty((m, t, 4), dtype=torch.int32, device=dev)
+    fit = torch.empty((m, t, 5), dtype=torch.float64, device=dev)
+    if not isinstance(circle_q, torch.Tensor):
+        circle_q = torch.from_numpy(np.ascontiguousarray(circle_q, dtype=np.int32))
+    if circle_q.dtype != torch.int32:
+        raise TypeError(f"refine_circles: circles must be int32 (in 1/16 pixel), got {circle_q.dtype}")
+    if circle_q.dim() == 2:
+        circle_q = circle_q[:, None]
+    n_tc = circle_q.shape[1] if circle_q.dim() == 3 else -1
+    if circle_q.dim() != 3 or circle_q.shape[0] != m or circle_q.shape[2] != 3 or n_tc not in (1, t):
+        raise ValueError(f"refine_circles: circles {tuple(circle_q.shape)} for {m} markers and {t} timepoints")
+    if m == 0:
+        return info, fit
+    circle_q = circle_q.to(dev)
+    if circle_q.stride(2) != 1 or (m > 1 and circle_q.stride(0) < 3) or (n_tc > 1 and 0 < circle_q.stride(1) < 3):
+        circle_q = circle_q.contiguous()
+    csm, cst = (circle_q.stride(0) if m > 1 else 0), (circle_q.stride(1) if n_tc > 1 else 0)
+    key = (rays, str(dev))
+    if key not in _DIRECTION_TABLES:
+        _DIRECTION_TABLES[key] = torch.from_numpy(direction_table(rays)).to(dev)
+    _call("mg_roi_refine_circles", plane.data_ptr(), code, psm, pst, circle_q.data_ptr(), csm, cst,
+          _DIRECTION_TABLES[key].data_ptr(), rays, m, t, L, reach, polarity, reject, min_strength, min_rays,
+          info.data_ptr(), fit.data_ptr(), _stream())
+    return info, fit
+
+
 # --------------------------------------------------------------------------------------
 # plot.overview: the label map of the fg masks in image coordinates and the composite picture
 # --------------------------------------------------------------------------------------

@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import hotpath
-from ._dataset import device_tensor
+from ._dataset import channel_index, device_tensor
 from .xr_lite import DataArray
 
 
@@ -166,9 +166,9 @@ def masked_quantile(xp, q, mask="fg", time=None):
 _MCTR = _MCT + ("ring",)
 
 
-def _marker_centres(xp, L, time):
-    """(mark, time, 2) float64 {y - top, x - left}: every marker's position inside its own window, the window origin
-    being the one the finder cut -- ``find._window_origin`` of ``find._rounded_centres`` of that timepoint's x, y."""
+def _marker_windows(xp, L, time):
+    """(y, x, top, left), each (mark, time): every marker's position and the origin of its window, the one the finder
+    cut -- ``find._window_origin`` of ``find._rounded_centres`` of that timepoint's x, y."""
     from .find import _rounded_centres, _window_origin
 
     if "im_y" not in xp.sizes or "im_x" not in xp.sizes:
@@ -182,10 +182,15 @@ def _marker_centres(xp, L, time):
     if time is not None:
         x, y = (x[:, time:time + 1], y[:, time:time + 1]) if time != -1 else (x[:, -1:], y[:, -1:])
     if x.size == 0:
-        return np.zeros(x.shape + (2,), dtype=np.float64)
+        return y, x, np.zeros(x.shape, dtype=np.int64), np.zeros(x.shape, dtype=np.int64)
     rc = _rounded_centres(y, x).reshape(x.shape + (2,))
-    top = _window_origin(rc[..., 0], L, xp.sizes["im_y"])
-    left = _window_origin(rc[..., 1], L, xp.sizes["im_x"])
+    return y, x, _window_origin(rc[..., 0], L, xp.sizes["im_y"]), _window_origin(rc[..., 1], L, xp.sizes["im_x"])
+
+
+def _marker_centres(xp, L, time):
+    """(mark, time, 2) float64 {y - top, x - left}: every marker's position inside its own window
+    (``_marker_windows``)."""
+    y, x, top, left = _marker_windows(xp, L, time)
     return np.stack([y - top, x - left], axis=-1)
 
 
@@ -258,6 +263,72 @@ def radial_profile(xp, width=1.0, rings=None, edges=None, mask="own", centre="ma
         roi, mk = _roi_and_mask(xp, mask, time)
     count, moments = hotpath.radial_profile(roi, mk, centre_q, edges_q)
     return DataArray(count, _MCTR, coords), DataArray(moments, _MCTR + ("moment",), coords)
+
+
+# ---- the circle below the pixel: edge points along rays, then a circle fit (mg_roi_refine_circles) ------------------------
+def refine_circles(xp, channel=None, rays=64, reach=3, polarity="auto", reject=1.0, min_strength=0.25, min_rays=None,
+                   radius=None, circle="marker"):
+    """The sub-pixel circle of every (marker, timepoint) in the windows of ``channel`` (None: the first), as a dict of
+    DataArrays on (mark, time) (``hotpath.refine_circles``): ``x_fit``, ``y_fit``, ``radius_fit``, ``fit_rms``,
+    ``fit_strength`` float64, NaN where ``fit_status`` != 0; ``fit_rays``, ``fit_status``, ``fit_polarity`` and ``radius``
+    int32 (``refine.refine_markers`` tells what each holds).  ``circle``: "marker" -- each timepoint's own x, y about
+    the finder's window origin with the finder's radius, or ``radius`` (whole pixels: a number, or an array on (mark,)
+    or (mark, time)) where the dataset no longer carries it; the fitted centre is then in image coordinates.  Or a
+    DataArray / array on (mark[, time], 3) = {y, x, r} in window coordinates, in pixels: the fitted centre is in window
+    coordinates too, and ``radius`` reports the start radius rounded to whole pixels.  Start circles are quantised as
+    ``np.rint(v * 16)`` in float64.  The two square roots -- the radius from R^2, the rms from the mean square -- are
+    taken here with NumPy."""
+    from . import refine
+
+    roi_var = xp.data_vars["roi"]
+    L, m, n_t = roi_var.sizes["roi_y"], roi_var.sizes["mark"], roi_var.sizes["time"]
+    settings = refine.check_refine(rays, reach, polarity, reject, min_strength, min_rays, L)
+    ch = channel_index(xp, channel, default=0)  # (a name or an index; None: the first channel)
+    if isinstance(circle, str):
+        if circle != "marker":
+            raise ValueError(f'refine_circles: circle must be "marker" or the circles, got {circle!r}')
+        if "im_y" not in xp.sizes or "im_x" not in xp.sizes:
+            raise ValueError('refine_circles: circle="marker" needs the image sizes im_y / im_x to find the window '
+                             "origins, and this dataset no longer has them (roi_only?): pass circle= (the start circles "
+                             "in window coordinates)")
+        r = refine.finder_radius(xp, radius)
+        y, x, top, left = (np.broadcast_to(v, (m, n_t)) for v in _marker_windows(xp, L, None))
+        c = np.stack([y - top, x - left], axis=-1)  # as reduce.radial_profile(centre="marker") has them
+        origin = np.stack([top, left], axis=-1).astype(np.float64)
+        start = np.concatenate([c, r[..., None].astype(np.float64)], axis=-1)
+    else:
+        if isinstance(circle, DataArray):
+            circle = circle.transpose(*[d for d in ("mark", "time") if d in circle.dims], ...).values
+        start = np.asarray(circle, dtype=np.float64)
+        if start.ndim == 2:
+            start = start[:, None]
+        if start.ndim != 3 or start.shape[0] != m or start.shape[2] != 3 or start.shape[1] not in (1, n_t):
+            raise ValueError(f"refine_circles: circles must be (mark[, time], 3) = {(m, n_t, 3)}, got {start.shape}")
+        if not np.isfinite(start).all():
+            raise ValueError("refine_circles: a start circle is not finite")
+        start = np.broadcast_to(start, (m, n_t, 3))
+        origin = np.zeros((m, n_t, 2), dtype=np.float64)
+        r = np.rint(np.clip(start[..., 2], 0.0, 2.0**30)).astype(np.int64)
+    from .profile import quantise
+
+    circle_q = np.ascontiguousarray(np.clip(quantise(start), -2.0**30, 2.0**30).astype(np.int32))  # (the kernel clamps)
+    if m == 0:
+        info, fit = np.zeros((0, n_t, 4), dtype=np.int32), np.zeros((0, n_t, 5), dtype=np.float64)
+    else:
+        roi = device_tensor(roi_var, _ROI_DIMS)
+        info, fit = hotpath.refine_circles(roi[:, ch], circle_q, *settings)
+        info, fit = info.cpu().numpy(), fit.cpu().numpy()
+    centre = origin + circle_q[..., :2].astype(np.float64) / 16.0  # the start centre as the kernel had it
+    dims = ("mark", "time")
+    return {
+        "x_fit": DataArray(centre[..., 1] + fit[..., 1], dims), "y_fit": DataArray(centre[..., 0] + fit[..., 0], dims),
+        "radius_fit": DataArray(np.sqrt(fit[..., 2]), dims), "fit_rms": DataArray(np.sqrt(fit[..., 3]), dims),
+        "fit_strength": DataArray(np.ascontiguousarray(fit[..., 4]), dims),
+        "fit_rays": DataArray(np.ascontiguousarray(info[..., 1]), dims),
+        "fit_status": DataArray(np.ascontiguousarray(info[..., 0]), dims),
+        "fit_polarity": DataArray(np.ascontiguousarray(info[..., 3]), dims),
+        "radius": DataArray(r.astype(np.int32), dims),
+    }
 
 
 def profile_mean(count, moments):

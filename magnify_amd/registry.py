@@ -95,6 +95,17 @@ def _add_segment(pipe, segment, channel, open_radius, max_grow, bg_guard, roi_le
                   bg_guard=bg_guard)
 
 
+def _add_refine(pipe, refine, channel, rays, reach, polarity, roi_length):
+    """``refine=`` of the marker pipelines ("edge"; not in the reference): ``refine_markers`` directly after the finder --
+    before ``segment_rois`` and ``profile_rois`` -- its settings checked now, not at the first assay.  None adds nothing."""
+    from .refine import check_method, check_refine
+
+    if check_method(refine) is None:
+        return
+    check_refine(rays, reach, polarity, roi_length=roi_length)
+    pipe.add_pipe("refine_markers", channel=channel, rays=rays, reach=reach, polarity=polarity)
+
+
 def _add_profile(pipe, profile, rings, mask, roi_length):
     """``profile=`` of the marker pipelines (a ring width in pixels; not in the reference): ``profile_rois`` after the
     finder -- after ``segment_rois`` where that is present, so that the profile sees the final masks -- and before
@@ -170,6 +181,7 @@ def microfluidic_chip(data, shape=(8, 8), pinlist=None, blank=None, overlap=102,
                       despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane",
                       background=None, background_smooth=0, background_channel=None,
                       profile=None, profile_rings=None, profile_mask="own",
+                      refine=None, refine_channel=None, refine_rays=64, refine_reach=3, refine_polarity="auto",
                       rotation_feature=None, rotation_max=10.0, rotation_min_confidence=2.0):
     """registry.py:32-110 (``blend``: ``stitch``'s overlap blending; ``register``, ``max_shift``, ``register_channel``:
     its tile registration; ``rotation="auto"`` with ``rotation_feature``, ``rotation_max``, ``rotation_min_confidence``:
@@ -191,6 +203,7 @@ def microfluidic_chip_pipe(shape=(8, 8), pinlist=None, blank=None, overlap=102, 
                            despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane",
                            background=None, background_smooth=0, background_channel=None,
                            profile=None, profile_rings=None, profile_mask="own",
+                           refine=None, refine_channel=None, refine_rays=64, refine_reach=3, refine_polarity="auto",
                            rotation_feature=None, rotation_max=10.0, rotation_min_confidence=2.0):
     """registry.py:196-271."""
     if chip_type is not None:
@@ -219,6 +232,8 @@ def microfluidic_chip_pipe(shape=(8, 8), pinlist=None, blank=None, overlap=102, 
                   high_edge_quantile=high_edge_quantile, num_iter=num_iter, min_roundness=min_roundness,
                   cluster_penalty=cluster_penalty, roi_length=roi_length, progress_bar=progress_bar,
                   search_timestep=search_timestep, search_channel=search_channel, interactive=interactive)
+    _add_refine(pipe, refine, next(iter(to_list(search_channel)), None) if refine_channel is None else refine_channel,
+                refine_rays, refine_reach, refine_polarity, roi_length)
     _add_segment(pipe, segment, segment_channel, segment_open, segment_grow, segment_guard, roi_length)
     _add_profile(pipe, profile, profile_rings, profile_mask, roi_length)
     pipe.add_pipe("drop", roi_only=roi_only, drop_tiles=drop_tiles)
@@ -236,8 +251,10 @@ def mrbles(data, spectra, codes, flatfield=1.0, darkfield=0.0, overlap=102, min_
            depth=None, depth_window=9,
            despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane",
            background=None, background_smooth=0, background_channel=None,
+           refine=None, refine_channel=None, refine_rays=64, refine_reach=3, refine_polarity="auto",
            profile=None, profile_rings=None, profile_mask="own", unmix=None):
-    """registry.py:274-399 (``unmix``: ``identify_mrbles``' per-pixel unmixing; not in the reference)."""
+    """registry.py:274-399 (``unmix``: ``identify_mrbles``' per-pixel unmixing; ``refine``: ``refine_markers``' sub-pixel
+    circles; neither is in the reference)."""
     kw = dict(locals())
     kw.pop("data")
     return mrbles_pipe(**kw)(data=data)
@@ -253,6 +270,7 @@ def mrbles_pipe(spectra, codes, flatfield=1.0, darkfield=0.0, overlap=102, min_b
                 depth=None, depth_window=9,
                 despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane",
                 background=None, background_smooth=0, background_channel=None,
+                refine=None, refine_channel=None, refine_rays=64, refine_reach=3, refine_polarity="auto",
                 profile=None, profile_rings=None, profile_mask="own", unmix=None):
     """registry.py:402-451."""
     from .unmix import check_unmix
@@ -271,6 +289,8 @@ def mrbles_pipe(spectra, codes, flatfield=1.0, darkfield=0.0, overlap=102, min_b
                   min_roundness=min_roundness, roi_length=roi_length, search_channel=search_channel,
                   interactive=interactive, track=track, max_drift=max_drift, track_min_score=track_min_score,
                   track_channel=track_channel, track_patch=track_patch, stage_drift=stage_drift)
+    _add_refine(pipe, refine, next(iter(to_list(search_channel)), None) if refine_channel is None else refine_channel,
+                refine_rays, refine_reach, refine_polarity, roi_length)
     _add_segment(pipe, segment, segment_channel, segment_open, segment_grow, segment_guard, roi_length)
     _add_profile(pipe, profile, profile_rings, profile_mask, roi_length)
     pipe.add_pipe("identify_mrbles", spectra=spectra, codes=codes, reference=reference, unmix=unmix)
@@ -289,6 +309,7 @@ def beads(data, flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=10,
           depth=None, depth_window=9,
           despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane",
           background=None, background_smooth=0, background_channel=None,
+          refine=None, refine_channel=None, refine_rays=64, refine_reach=3, refine_polarity="auto",
           profile=None, profile_rings=None, profile_mask="own"):
     """registry.py:454-565."""
     kw = dict(locals())
@@ -306,6 +327,7 @@ def beads_pipe(flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=5, m
                depth=None, depth_window=9,
                despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane",
                background=None, background_smooth=0, background_channel=None,
+               refine=None, refine_channel=None, refine_rays=64, refine_reach=3, refine_polarity="auto",
                profile=None, profile_rings=None, profile_mask="own"):
     """registry.py:568-612 (note the 5/25 defaults here versus 10/50 in ``beads``)."""
     pipe = Pipeline("read")
@@ -321,6 +343,8 @@ def beads_pipe(flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=5, m
                   min_roundness=min_roundness, roi_length=roi_length, search_channel=search_channel,
                   interactive=interactive, track=track, max_drift=max_drift, track_min_score=track_min_score,
                   track_channel=track_channel, track_patch=track_patch, stage_drift=stage_drift)
+    _add_refine(pipe, refine, next(iter(to_list(search_channel)), None) if refine_channel is None else refine_channel,
+                refine_rays, refine_reach, refine_polarity, roi_length)
     _add_segment(pipe, segment, segment_channel, segment_open, segment_grow, segment_guard, roi_length)
     _add_profile(pipe, profile, profile_rings, profile_mask, roi_length)
     pipe.add_pipe("drop", roi_only=roi_only, drop_tiles=drop_tiles)
