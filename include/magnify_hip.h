@@ -787,8 +787,8 @@ int mg_roi_masked_stats_keys_in_lds(int dtype, int roi_len);
  *   d2(i, j) = (i S - cy)^2 + (j S - cx)^2; pixel (i, j) belongs to ring k iff edges[k]^2 <= d2 < edges[k + 1]^2 (a
  *   pixel on an edge goes to the outer ring; inside edges[0] or from edges[n_rings] on it belongs to none); it takes
  *   part iff its mask byte is non-zero (or d_mask is NULL) and its value is not NaN.
- * Limits, so that 32 unsigned bits hold d2: roi_len <= MG_PROFILE_MAX_LEN, 0 <= edges[0] < edges[1] < ... <= 46340, and
- * -1024 S <= cy, cx <= 2048 S -- centres are device data and cannot be refused: the kernel clamps them into that range.
+ * Limits, so that 32 unsigned bits hold d2: roi_len <= MG_PROFILE_MAX_LEN, 0 <= edges[0] < edges[1] < ... <= MG_PROFILE_MAX_EDGE,
+ * and MG_PROFILE_CENTRE_MIN = -1024 S <= cy, cx <= 2048 S = MG_PROFILE_CENTRE_MAX -- centres are device data and cannot be refused: the kernel clamps them into that range.
  *   d_count   int32[m][C][T][n_rings]       the pixels that take part
  *   d_moments double[m][C][T][n_rings][2]   {sum x, sum x^2}; an empty ring: {0, 0}, count 0
  * Integer pixels: both moments are accumulated exactly in 64-bit integers (integer LDS atomics) and converted once: the
@@ -803,6 +803,9 @@ int mg_roi_masked_stats_keys_in_lds(int dtype, int roi_len);
 #define MG_PROFILE_MAX_RINGS 128
 #define MG_PROFILE_SUBPIXEL 16
 #define MG_PROFILE_MAX_LEN 1024
+#define MG_PROFILE_CENTRE_MIN (-16384) /* -1024 S */
+#define MG_PROFILE_CENTRE_MAX 32768    /* 2048 S */
+#define MG_PROFILE_MAX_EDGE 46340      /* the largest integer whose square 31 bits hold */
 int mg_roi_radial_profile(const void* d_roi, int dtype, const uint8_t* d_mask, int64_t mask_stride_m,
                           int64_t mask_stride_t, const int32_t* d_centre, int64_t centre_stride_m,
                           int64_t centre_stride_t, const int32_t* edges, int n_rings, int m, int n_c, int n_t,
@@ -965,6 +968,7 @@ int mg_roi_threshold_masks(const void* d_roi, int dtype, int64_t stride_m, int64
 #define MG_REFINE_MAX_RAYS 128
 #define MG_REFINE_MAX_REACH 8
 #define MG_REFINE_MAX_LEN 1024
+#define MG_REFINE_MAX_RADIUS 16384 /* 1024 S */
 int mg_roi_refine_circles(const void* d_roi, int dtype, int64_t roi_stride_m, int64_t roi_stride_t,
                           const int32_t* d_circle, int64_t circle_stride_m, int64_t circle_stride_t,
                           const double* d_cs, int n_rays, int m, int n_t, int roi_len, int reach, int polarity,

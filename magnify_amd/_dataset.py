@@ -1,5 +1,6 @@
 """What every component asks of a Dataset before it calls the device: a variable as a device tensor in a given order of
-dimensions, a channel name or index as an index, the pages of a variable as a block of planes (``page_view``) and a
+dimensions, the gathered windows with a mask and one timepoint of them (``roi_windows``), a caller's array per marker, a
+channel name or index as an index, the pages of a variable as a block of planes (``page_view``) and a
 tensor of planes as the contiguous block an entry of the library takes (``plane_block``)."""
 from __future__ import annotations
 
@@ -12,7 +13,7 @@ import torch
 
 from . import _native as nat
 from . import hotpath
-from .utils import to_list
+from .utils import to_list, window_origin
 from .xr_lite import DataArray, from_any
 
 
@@ -36,6 +37,89 @@ def device_tensor(var, dims, as_mask=False):
     if "time" in dims and "time" not in var.dims:
         data = data.unsqueeze([d for d in dims if d in var.dims or d == "time"].index("time"))
     return data
+
+
+ROI_DIMS, MASK_DIMS = ("mark", "channel", "time", "roi_y", "roi_x"), ("mark", "time", "roi_y", "roi_x")
+
+
+def time_pick(time):
+    """Timepoint ``time`` (-1: the last) as the slice of length 1 that keeps the time axis; None -- every timepoint --
+    stays None."""
+    if time is None:
+        return None
+    return slice(time, time + 1) if time != -1 else slice(-1, None)
+
+
+def own_mask(fg, bg):
+    """fg | bg, uint8, of the mask tensors (M, T', L, L) ``device_tensor`` gives: the pixels a bead owns (what
+    ``segment_rois`` allows its foreground to grow into, what ``radial_profile`` reads).  One drawn mask for all
+    timepoints -- T' = 1 or a time stride of 0 in both -- gives one union, a time axis of 1."""
+    if all(t.shape[1] == 1 or t.stride(1) == 0 for t in (fg, bg)):
+        fg, bg = fg[:, :1], bg[:, :1]
+    return fg.view(torch.uint8) | bg.view(torch.uint8)
+
+
+def roi_windows(xp, mask, time=None):
+    """(roi (M, C, T, L, L), mask (M, T', L, L) or None) on the device.  ``mask``: a coordinate name, a DataArray on
+    (mark[, time], roi_y, roi_x), None -- every pixel -- or "own": ``own_mask`` of a bead's fg and bg, every pixel on a
+    chip (a dataset with a ``tag`` coordinate).  ``time=k``: timepoint ``k`` only, selected where the data lies: the
+    others are neither moved nor read.  TypeError for a roi that is not uint8 / uint16 / float32 / float64."""
+    roi, one = xp.data_vars["roi"], time_pick(time)
+    if isinstance(mask, str) and mask == "own":
+        mask = None if "tag" in xp.coords else DataArray(
+            own_mask(*(device_tensor(xp.coords[k], MASK_DIMS, as_mask=True) for k in ("fg", "bg"))), MASK_DIMS)
+    elif isinstance(mask, str):
+        mask = xp.coords[mask]
+    if one is not None:
+        roi = roi.isel(time=one)
+        if mask is not None and mask.sizes.get("time", 1) != 1:
+            mask = mask.isel(time=one)
+    roi = device_tensor(roi, ROI_DIMS)
+    nat.dtype_code(roi.dtype)
+    return roi, None if mask is None else device_tensor(mask, MASK_DIMS, as_mask=True)
+
+
+def per_marker(what, value, m, n_t, k, keyword):
+    """``value`` -- the ``keyword=`` argument of ``what``: a DataArray or an array on (mark[, time], k) -- as finite
+    float64 (M, 1 or n_t, k).  ValueError otherwise."""
+    if isinstance(value, DataArray):
+        value = value.transpose(*[d for d in ("mark", "time") if d in value.dims], ...).values
+    a = np.asarray(value, dtype=np.float64)
+    if a.ndim == 2:
+        a = a[:, None]
+    if a.ndim != 3 or a.shape[0] != m or a.shape[2] != k or a.shape[1] not in (1, n_t):
+        raise ValueError(f"{what}: {keyword}= must be (mark[, time], {k}) = {(m, n_t, k)}, got {a.shape}")
+    if not np.isfinite(a).all():
+        raise ValueError(f"{what}: {keyword}= holds a value that is not finite")
+    return a
+
+
+def marker_windows(xp, L, time, what, keyword):
+    """(y, x, top, left), each (mark, time): every marker's position and the origin of its window, the one the finder
+    cut -- ``utils.window_origin`` of ``find._rounded_centres`` of that timepoint's x, y.  ``what`` and ``keyword``: who
+    asks with ``keyword="marker"``, for the message where the dataset no longer knows the image size."""
+    from .find import _rounded_centres
+
+    if "im_y" not in xp.sizes or "im_x" not in xp.sizes:
+        raise ValueError(f'{what}: {keyword}="marker" needs the image sizes im_y / im_x to find the window origins, and '
+                         f"this dataset no longer has them (roi_only?): pass {keyword}= in window coordinates")
+    x, y = (np.asarray(xp.coords[k].transpose(*[d for d in ("mark", "time") if d in xp.coords[k].dims]).values,
+                       dtype=np.float64) for k in ("x", "y"))
+    if x.ndim == 1:
+        x, y = x[:, None], y[:, None]
+    if time is not None:
+        x, y = x[:, time_pick(time)], y[:, time_pick(time)]
+    if x.size == 0:
+        return y, x, np.zeros(x.shape, dtype=np.int64), np.zeros(x.shape, dtype=np.int64)
+    rc = _rounded_centres(y, x).reshape(x.shape + (2,))
+    return y, x, window_origin(rc[..., 0], L, xp.sizes["im_y"]), window_origin(rc[..., 1], L, xp.sizes["im_x"])
+
+
+def marker_centres(xp, L, time, what="radial_profile", keyword="centre"):
+    """(mark, time, 2) float64 {y - top, x - left}: every marker's position inside its own window
+    (``marker_windows``)."""
+    y, x, top, left = marker_windows(xp, L, time, what, keyword)
+    return np.stack([y - top, x - left], axis=-1)
 
 
 class ChannelError(KeyError, ValueError):

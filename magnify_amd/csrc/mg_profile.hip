@@ -23,7 +23,6 @@ namespace {
 
 constexpr int NT = MG_SELECT_THREADS, WV = NT / 64, IN_FLIGHT = 4;
 constexpr int R_MAX = MG_PROFILE_MAX_RINGS, SUB = MG_PROFILE_SUBPIXEL;
-constexpr int CENTRE_MIN = -1024 * SUB, CENTRE_MAX = 2048 * SUB, EDGE_MAX = 46340;
 constexpr int KEEP_BYTES = 16384;    // ring bytes kept in LDS for the later channels: windows up to 128 x 128
 constexpr uint32_t NO_RING = 255u;   // > any ring index
 constexpr int NO_KEY = 0x7FFFFFFF;   // the run key of a pixel without a ring
@@ -45,7 +44,7 @@ struct Geo {
 // The ring of squared distance d2 (<= 2^31 inside a window: mg_roi_radial_profile's limits), NO_RING where it has none.
 // Uniform edges: the candidate floor((sqrt(d2) - e0) / width) in float32 is off by at most one (the error of the
 // conversion, of v_sqrt_f32 and of the product stays below 0.02 ring widths), and one exact comparison with the
-// squares of its two edges -- both <= EDGE_MAX: 32 bits hold them -- settles it.  Otherwise the largest k < n_rings
+// squares of its two edges -- both <= MG_PROFILE_MAX_EDGE: 32 bits hold them -- settles it.  Otherwise the largest k < n_rings
 // with e2[k] <= d2, by bisection over the table.
 __device__ __forceinline__ uint32_t ring_of(const Geo& g, uint32_t d2) {
   if (g.width > 0) {
@@ -211,7 +210,8 @@ __global__ __launch_bounds__(NT) void k_radial_profile(const T* __restrict__ d_r
   const int32_t* centre = d_centre + (int64_t)g_ * centre_stride_m + (int64_t)t * centre_stride_t;
   Geo geo;
   geo.e2 = s_e2;
-  geo.cy = min(max(centre[0], CENTRE_MIN), CENTRE_MAX), geo.cx = min(max(centre[1], CENTRE_MIN), CENTRE_MAX);
+  geo.cy = min(max(centre[0], MG_PROFILE_CENTRE_MIN), MG_PROFILE_CENTRE_MAX);
+  geo.cx = min(max(centre[1], MG_PROFILE_CENTRE_MIN), MG_PROFILE_CENTRE_MAX);
   geo.len = len, geo.n_rings = n_rings, geo.e0 = edges.e0, geo.width = edges.width;
   geo.inv_width = edges.width > 0 ? 1.0f / (float)edges.width : 0.0f, geo.inv_len = 1.0f / (float)len;
   const uint8_t* mask = d_mask ? d_mask + (int64_t)g_ * mask_stride_m + (int64_t)t * mask_stride_t : nullptr;
@@ -263,7 +263,7 @@ extern "C" int mg_roi_radial_profile(const void* d_roi, int dtype, const uint8_t
   if (m < 0 || n_c <= 0 || n_t <= 0 || roi_len <= 0 || roi_len > MG_PROFILE_MAX_LEN) return MG_EINVAL;
   if (n_rings < 1 || n_rings > R_MAX || (int64_t)m * n_c * n_t > INT32_MAX) return MG_EINVAL;
   if (mask_stride_m < 0 || mask_stride_t < 0 || centre_stride_m < 0 || centre_stride_t < 0) return MG_EINVAL;
-  if (edges[0] < 0 || edges[n_rings] > EDGE_MAX) return MG_EINVAL;
+  if (edges[0] < 0 || edges[n_rings] > MG_PROFILE_MAX_EDGE) return MG_EINVAL;
   Edges e = {};
   e.e0 = edges[0], e.width = edges[1] - edges[0];
   for (int k = 0; k <= n_rings; ++k) {

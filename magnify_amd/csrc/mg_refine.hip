@@ -27,7 +27,6 @@ namespace {
 
 constexpr int NT = 256;
 constexpr int K_MAX = MG_REFINE_MAX_RAYS, REACH_MAX = MG_REFINE_MAX_REACH, SUB = MG_PROFILE_SUBPIXEL;
-constexpr int CENTRE_MIN = -1024 * SUB, CENTRE_MAX = 2048 * SUB, RADIUS_MAX = 1024 * SUB;  // centres: mg_roi_radial_profile's
 constexpr int J_MAX = 4 * REACH_MAX + 1;
 static_assert(K_MAX <= NT, "one lane per ray");
 static_assert((size_t)K_MAX * J_MAX * 8 + 12 * 1024 <= 64 * 1024, "the samples and the per-ray tables fit the default LDS");
@@ -70,9 +69,9 @@ __global__ __launch_bounds__(NT) void k_refine_circles(RefineArgs a) {
   const int L = a.len, K = a.n_rays, reach = a.reach, J = 4 * reach + 1;
   const T* win = (const T*)a.roi + (int64_t)g * a.roi_stride_m + (int64_t)t * a.roi_stride_t;
   const int32_t* circle = a.circle + (int64_t)g * a.circle_stride_m + (int64_t)t * a.circle_stride_t;
-  const double cy = (double)min(max(circle[0], CENTRE_MIN), CENTRE_MAX) / (double)SUB;
-  const double cx = (double)min(max(circle[1], CENTRE_MIN), CENTRE_MAX) / (double)SUB;
-  const double r = (double)min(max(circle[2], 0), RADIUS_MAX) / (double)SUB;
+  const double cy = (double)min(max(circle[0], MG_PROFILE_CENTRE_MIN), MG_PROFILE_CENTRE_MAX) / (double)SUB;
+  const double cx = (double)min(max(circle[1], MG_PROFILE_CENTRE_MIN), MG_PROFILE_CENTRE_MAX) / (double)SUB;
+  const double r = (double)min(max(circle[2], 0), MG_REFINE_MAX_RADIUS) / (double)SUB;
   const double rho0 = r - (double)reach;  // rho_j = rho0 + 0.5 j, exact: multiples of 1/16 below 2^11
   int j_lo = 0;
   while (rho0 + 0.5 * (double)j_lo < 0.0) ++j_lo;  // (<= 2 reach: rho_{2 reach} = r >= 0)

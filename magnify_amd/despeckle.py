@@ -13,7 +13,6 @@ are in ``mg_despeckle.hip``; ``tests/despeckle_ref.py`` restates the contract in
 from __future__ import annotations
 
 import math
-import numbers
 
 import numpy as np
 import torch
@@ -21,7 +20,7 @@ import torch
 from . import _native as nat
 from . import registry
 from ._dataset import page_view, plane_block
-from .utils import int_in
+from .utils import int_in, number
 
 TILE = nat.DEFINES["MG_DESPECKLE_TILE"]  # the output tile of a workgroup (TILE x TILE pixels)
 MAX_K = nat.DEFINES["MG_DESPECKLE_MAX_K"]
@@ -36,17 +35,14 @@ def check_despeckle(threshold, radius=1, which="bright", scope="plane", min_frac
     """The settings of ``remove_outliers`` as the pipelines take them: ``threshold`` a finite real number >= 0 (in pixel
     units), ``radius`` 1 or 2, ``which`` "bright", "dark" or "both", ``scope`` "plane" or "sensor", ``min_fraction`` in
     (0, 1].  ValueError otherwise."""
-    if isinstance(threshold, (bool, np.bool_)) or not isinstance(threshold, numbers.Real):
-        raise ValueError(f"despeckle threshold must be a real number, got {threshold!r}")
-    if not math.isfinite(threshold) or threshold < 0:
-        raise ValueError(f"despeckle threshold must be finite and >= 0, got {threshold!r}")
+    if number("despeckle threshold", threshold) < 0:
+        raise ValueError(f"despeckle threshold must be >= 0, got {threshold!r}")
     int_in("despeckle radius", radius, 1, MAX_K)
     if not isinstance(which, str) or which not in WHICH:
         raise ValueError(f"despeckle which must be one of {tuple(WHICH)}, got {which!r}")
     if not isinstance(scope, str) or scope not in SCOPES:
         raise ValueError(f"despeckle scope must be one of {SCOPES}, got {scope!r}")
-    if (isinstance(min_fraction, (bool, np.bool_)) or not isinstance(min_fraction, numbers.Real)
-            or not 0 < min_fraction <= 1):
+    if not 0 < number("despeckle min_fraction", min_fraction) <= 1:
         raise ValueError(f"despeckle min_fraction must be in (0, 1], got {min_fraction!r}")
 
 

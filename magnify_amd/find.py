@@ -321,11 +321,7 @@ def _rounded_centres(y, x):
     return pos.astype(np.int32)
 
 
-def _window_origin(c, L, size):
-    """utils.bounding_box for many centres at once: the L-wide window about c, shifted into [0, size)."""
-    lo = c.astype(np.int64) - L // 2
-    lo = np.where(lo < 0, 0, lo)
-    return np.where(lo + L > size, size - L, lo)
+_window_origin = utils.window_origin  # the finders' rule for where a marker's window begins (their tests ask for it here)
 
 
 class ButtonFinder:
@@ -450,8 +446,8 @@ class ButtonFinder:
                                         want_sums=False)
         roi = out["roi"].view(n_t, m, n_c, L, L).permute(1, 2, 0, 3, 4).contiguous()  # (M, C, T, L, L)
         every = np.concatenate(centers)  # (T * m, 2): position of every centre inside its own window
-        rel = np.stack([every[:, 0] - _window_origin(every[:, 0], L, h), every[:, 1] - _window_origin(every[:, 1], L, w)],
-                       axis=1).astype(np.int32)
+        rel = (every - np.stack([_window_origin(every[:, 0], L, h), _window_origin(every[:, 1], L, w)],
+                                axis=1)).astype(np.int32)
         radii_tm = np.ascontiguousarray(radius.reshape(m, n_t).T).reshape(-1)
         fg, bg = hotpath.button_masks(rel, radii_tm, L, self.chamber_radius, self.max_button_radius, image.device)
         fg = fg.view(n_t, m, L, L).permute(1, 0, 2, 3).contiguous()  # (M, T, L, L)

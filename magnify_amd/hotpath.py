@@ -1569,12 +1569,37 @@ def _window_view(what: str, x: torch.Tensor, m: int, t: int, L: int):
     return x, (x.stride(0) if m > 1 else 0), (x.stride(1) if n_t > 1 else 0)
 
 
-def _mask_view(what: str, mask: torch.Tensor, m: int, t: int, L: int):
-    """``_window_view`` of a bool / uint8 mask, as uint8."""
+def _mask_view(what: str, mask: torch.Tensor | None, m: int, t: int, L: int):
+    """``_window_view`` of a bool / uint8 mask, as uint8; None -- every pixel -- is (None, 0, 0)."""
+    if mask is None:
+        return None, 0, 0
     if mask.dtype == torch.bool:
         mask = mask.view(torch.uint8)
     assert mask.element_size() == 1, f"{what}: {mask.dtype}"
     return _window_view(what, mask, m, t, L)
+
+
+def _marker_table_view(what: str, table, m: int, t: int, k: int, device):
+    """(tensor, marker stride, time stride), in elements, of a table of ``k`` int32 per (marker, time) on ``device``:
+    ``_window_view``'s contract for rows.  ``table``: a tensor, or anything ``np.ascontiguousarray(..., dtype=np.int32)``
+    takes, (M, k) -- one row for all timepoints -- or (M, T', k) with T' = t, or T' = 1 or a view expanded along time
+    (stride 0).  Copied only where the strides require it: rows that are not contiguous or that overlap.  A stride that
+    only ever multiplies index 0 (M <= 1, T' <= 1) is handed over as 0.  TypeError for a tensor of another type,
+    ValueError for any other shape; with no markers nothing is moved."""
+    if not isinstance(table, torch.Tensor):
+        table = torch.from_numpy(np.ascontiguousarray(table, dtype=np.int32))
+    if table.dtype != torch.int32:
+        raise TypeError(f"{what} must be int32, got {table.dtype}")
+    if table.dim() == 2:
+        table = table[:, None]
+    if table.dim() != 3 or table.shape[0] != m or table.shape[2] != k or table.shape[1] not in (1, t):
+        raise ValueError(f"{what} {tuple(table.shape)} for {m} markers, {t} timepoints and rows of {k}")
+    if m == 0:
+        return table, 0, 0
+    table, n_t = table.to(device), table.shape[1]
+    if table.stride(2) != 1 or (m > 1 and table.stride(0) < k) or (n_t > 1 and 0 < table.stride(1) < k):
+        table = table.contiguous()
+    return table, (table.stride(0) if m > 1 else 0), (table.stride(1) if n_t > 1 else 0)
 
 
 def masked_median(roi: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
@@ -1651,24 +1676,10 @@ def radial_profile(roi: torch.Tensor, mask, centre_q, edges_q):
     r = len(edges_q) - 1
     count = torch.empty((m, c, t, r), dtype=torch.int32, device=dev)
     moments = torch.empty((m, c, t, r, 2), dtype=torch.float64, device=dev)
-    if not isinstance(centre_q, torch.Tensor):
-        centre_q = torch.from_numpy(np.ascontiguousarray(centre_q, dtype=np.int32))
-    if centre_q.dtype != torch.int32:
-        raise TypeError(f"radial_profile: centres must be int32 (in 1/16 pixel), got {centre_q.dtype}")
-    if centre_q.dim() == 2:
-        centre_q = centre_q[:, None]
-    n_tc = centre_q.shape[1]
-    if centre_q.dim() != 3 or centre_q.shape[0] != m or centre_q.shape[2] != 2 or n_tc not in (1, t):
-        raise ValueError(f"radial_profile: centres {tuple(centre_q.shape)} for {m} markers and {t} timepoints")
+    centre_q, csm, cst = _marker_table_view("radial_profile: centres", centre_q, m, t, 2, dev)
     if m == 0:
         return count, moments
-    centre_q = centre_q.to(dev)
-    if centre_q.stride(2) != 1 or (m > 1 and centre_q.stride(0) < 2) or (n_tc > 1 and 0 < centre_q.stride(1) < 2):
-        centre_q = centre_q.contiguous()
-    csm, cst = (centre_q.stride(0) if m > 1 else 0), (centre_q.stride(1) if n_tc > 1 else 0)
-    sm = st = 0
-    if mask is not None:
-        mask, sm, st = _mask_view("radial_profile", mask, m, t, L)
+    mask, sm, st = _mask_view("radial_profile", mask, m, t, L)
     _call("mg_roi_radial_profile", roi.data_ptr(), code, _ptr(mask), sm, st, centre_q.data_ptr(), csm, cst,
           edges_q.ctypes.data, r, m, c, t, L, count.data_ptr(), moments.data_ptr(), _stream())
     return count, moments
@@ -1716,9 +1727,7 @@ def unmix_stats(roi: torch.Tensor, mask, matrix, channels=None, offset=None, q=(
         offset = offset.to(dev).contiguous()
     if m == 0:
         return count, total, order
-    sm = st = 0
-    if mask is not None:
-        mask, sm, st = _mask_view("unmix_stats", mask, m, t, L)
+    mask, sm, st = _mask_view("unmix_stats", mask, m, t, L)
     _call("mg_roi_unmix_stats", roi.data_ptr(), code, _ptr(mask), sm, st, m, c, t, L, ch.ctypes.data, len(ch),
           w.ctypes.data, w.shape[0], _ptr(offset), qs.ctypes.data if len(qs) else None, len(qs), count.data_ptr(),
           total.data_ptr(), order.data_ptr() if len(qs) else None, _stream())
@@ -1782,9 +1791,7 @@ def threshold_masks(roi_channel: torch.Tensor, fg0: torch.Tensor, bg0: torch.Ten
         return fg, bg, threshold, counts, segmented
     fg0, fsm, fst = _mask_view("threshold_masks fg0", fg0, m, t, L)
     bg0, bsm, bst = _mask_view("threshold_masks bg0", bg0, m, t, L)
-    asm = ast = 0
-    if allowed is not None:
-        allowed, asm, ast = _mask_view("threshold_masks allowed", allowed, m, t, L)
+    allowed, asm, ast = _mask_view("threshold_masks allowed", allowed, m, t, L)
     _call("mg_roi_threshold_masks", roi_channel.data_ptr(), code, rsm, rst, fg0.data_ptr(), fsm, fst, bg0.data_ptr(), bsm, bst,
           _ptr(allowed), asm, ast,
           m, t, L, int(use_otsu), float(number), int(open_radius), int(max_grow), int(bg_guard), int(min_area),
@@ -1823,21 +1830,9 @@ def refine_circles(plane: torch.Tensor, circle_q, rays=64, reach=3, polarity=0, 
     dev = plane.device
     info = torch.empty((m, t, 4), dtype=torch.int32, device=dev)
     fit = torch.empty((m, t, 5), dtype=torch.float64, device=dev)
-    if not isinstance(circle_q, torch.Tensor):
-        circle_q = torch.from_numpy(np.ascontiguousarray(circle_q, dtype=np.int32))
-    if circle_q.dtype != torch.int32:
-        raise TypeError(f"refine_circles: circles must be int32 (in 1/16 pixel), got {circle_q.dtype}")
-    if circle_q.dim() == 2:
-        circle_q = circle_q[:, None]
-    n_tc = circle_q.shape[1] if circle_q.dim() == 3 else -1
-    if circle_q.dim() != 3 or circle_q.shape[0] != m or circle_q.shape[2] != 3 or n_tc not in (1, t):
-        raise ValueError(f"refine_circles: circles {tuple(circle_q.shape)} for {m} markers and {t} timepoints")
+    circle_q, csm, cst = _marker_table_view("refine_circles: circles", circle_q, m, t, 3, dev)
     if m == 0:
         return info, fit
-    circle_q = circle_q.to(dev)
-    if circle_q.stride(2) != 1 or (m > 1 and circle_q.stride(0) < 3) or (n_tc > 1 and 0 < circle_q.stride(1) < 3):
-        circle_q = circle_q.contiguous()
-    csm, cst = (circle_q.stride(0) if m > 1 else 0), (circle_q.stride(1) if n_tc > 1 else 0)
     key = (rays, str(dev))
     if key not in _DIRECTION_TABLES:
         _DIRECTION_TABLES[key] = torch.from_numpy(direction_table(rays)).to(dev)
@@ -1866,8 +1861,10 @@ def image_labels(fg: torch.Tensor, origin: torch.Tensor, level: int, h: int, w: 
     if m == 0:
         return labels
     fg, sm, st = _mask_view("image_labels", fg, m, t, L)
-    origin = torch.as_tensor(origin).to(device=labels.device, dtype=torch.int32).contiguous()
-    assert tuple(origin.shape) == (m, t, 2) and fg.is_cuda
+    origin, _, _ = _marker_table_view("image_labels: origins", torch.as_tensor(origin).to(torch.int32), m, t, 2,
+                                      labels.device)
+    origin = origin.expand(m, t, 2).contiguous()  # (no strides in this entry)
+    assert fg.is_cuda
     _call("mg_roi_image_labels", fg.data_ptr(), sm, st, origin.data_ptr(), m, t, L, int(level), int(h), int(w),
           labels.data_ptr(), _stream())
     return labels
@@ -2022,8 +2019,8 @@ def render_roi_montage(roi: torch.Tensor, layout, level: int, limits, colors, fg
         roi = roi.contiguous()
     mode = OVERLAYS[overlay]
 
-    (bg, bg_m, bg_t), (fg, fg_m, fg_t) = ((None, 0, 0) if a is None or not mode else
-                                          _mask_view("render_roi_montage", a, m, t, L) for a in (bg, fg))
+    (bg, bg_m, bg_t), (fg, fg_m, fg_t) = (_mask_view("render_roi_montage", a if mode else None, m, t, L)
+                                          for a in (bg, fg))
     assert all(a is None or a.is_cuda for a in (bg, fg))
     d_layout = torch.from_numpy(layout).to(roi.device)
     _call("mg_render_roi_montage", roi.data_ptr(), nat.dtype_code(roi.dtype), roi.stride(0) if m > 1 else 0,

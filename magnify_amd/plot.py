@@ -28,7 +28,8 @@ import numpy as np
 import torch
 
 from . import hotpath, preprocess, xr_lite
-from ._dataset import device_tensor
+from ._dataset import MASK_DIMS, device_tensor
+from .utils import window_origin
 from .xr_lite import DataArray
 
 MAX_LEVEL = hotpath.OVERVIEW_MAX_LEVEL
@@ -107,7 +108,7 @@ def _has_rois(xp):
 def _mask(xp, name, m, n_t, L):
     """Coordinate ``name`` as a (M, T, L, L) bool / uint8 device view (stride 0 along a time of size 1).  ``m`` / ``L``
     None: whatever the coordinate has."""
-    a = device_tensor(_marker_var(xp, name, ("roi_y", "roi_x")), ("mark", "time", "roi_y", "roi_x"), as_mask=True)
+    a = device_tensor(_marker_var(xp, name, ("roi_y", "roi_x")), MASK_DIMS, as_mask=True)
     if m is None:
         m, L = a.shape[0], a.shape[-1]
         if a.shape[2] != L:
@@ -135,16 +136,9 @@ def _markers(xp, n_t, h, w):
     if not (np.isfinite(x).all() and np.isfinite(y).all()):
         raise ValueError("plot: marker positions x / y must be finite")
     valid = per_time("valid", bool) if "valid" in xp else np.ones((m, n_t), dtype=bool)
-    return fg, _origins(x.astype(int), y.astype(int), L, h, w), valid
-
-
-def _origins(x, y, L, h, w):
-    """(..., 2) int32 (top, left) of ``utils.bounding_box(x, y, L, w, h)`` for integer arrays x, y (L <= h, w)."""
-    def lo(c, size):
-        a = np.maximum(c - L // 2, 0)
-        return a - np.maximum(a + L - size, 0)
-
-    return np.stack([lo(y, h), lo(x, w)], axis=-1).astype(np.int32)
+    # truncated as the reference's roi_to_image_labels does; the finders round half to even
+    origin = np.stack([window_origin(y.astype(int), L, h), window_origin(x.astype(int), L, w)], axis=-1)
+    return fg, origin.astype(np.int32), valid
 
 
 def _labels(xp, image, level):

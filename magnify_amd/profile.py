@@ -14,11 +14,10 @@ import numpy as np
 
 from . import _native as nat
 from . import registry
-from .utils import int_in
+from .utils import int_in, number
 
 MAX_RINGS, SUBPIXEL, MAX_LEN = (nat.DEFINES[k] for k in ("MG_PROFILE_MAX_RINGS", "MG_PROFILE_SUBPIXEL", "MG_PROFILE_MAX_LEN"))
-MAX_EDGE = 46340  # in 1/16 pixel: the largest integer whose square 31 bits hold (include/magnify_hip.h)
-CENTRE_MIN, CENTRE_MAX = -1024 * SUBPIXEL, 2048 * SUBPIXEL
+MAX_EDGE, CENTRE_MIN, CENTRE_MAX = (nat.DEFINES[k] for k in ("MG_PROFILE_MAX_EDGE", "MG_PROFILE_CENTRE_MIN", "MG_PROFILE_CENTRE_MAX"))
 PROFILE_VARS = ("profile_count", "profile_sum", "profile_sumsq")
 
 
@@ -27,13 +26,12 @@ def quantise(v):
     return np.rint(np.asarray(v, dtype=np.float64) * float(SUBPIXEL))
 
 
-def _number(name, v):
-    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
-        raise ValueError(f"{name} must be a number, got {v!r}")
-    v = float(v)
-    if not math.isfinite(v):
-        raise ValueError(f"{name} must be finite, got {v!r}")
-    return v
+INT_LIMIT = 2.0**30  # what a caller's float is clipped to before it becomes an int32
+
+
+def quantised(v):
+    """``quantise(v)`` as the int32 the kernels take; they clamp to their own, narrower range."""
+    return np.clip(quantise(v), -INT_LIMIT, INT_LIMIT).astype(np.int32)
 
 
 def check_edges_q(edges_q):
@@ -68,7 +66,7 @@ def ring_edges(width=1.0, rings=None, edges=None, roi_length=None):
             raise ValueError(f"profile needs 1 to {MAX_RINGS} rings, got {len(e) - 1}")
         q = quantise(e)
     else:
-        width = _number("profile width", width)
+        width = number("profile width", width)
         if quantise(width) < 1:
             raise ValueError(f"profile width must be at least 1/{SUBPIXEL} pixel, got {width}")
         if rings is None:
@@ -97,7 +95,7 @@ def check_profile(width=1.0, rings=None, mask="own", roi_length=None, edges=None
         if roi_length > MAX_LEN:
             raise ValueError(f"profile_rois takes windows up to {MAX_LEN} pixels, got roi_length {roi_length}")
     if edges is None and rings is None and roi_length is None:
-        width = _number("profile width", width)
+        width = number("profile width", width)
         if quantise(width) < 1:
             raise ValueError(f"profile width must be at least 1/{SUBPIXEL} pixel, got {width}")
         return None

@@ -11,18 +11,16 @@ import numpy as np
 import torch
 
 from . import hotpath
-from ._dataset import channel_index, device_tensor
+from ._dataset import (MASK_DIMS, ROI_DIMS, channel_index, device_tensor, marker_centres, marker_windows, per_marker,
+                       roi_windows, time_pick)
 from .xr_lite import DataArray
-
-
-_ROI_DIMS, _MASK_DIMS = ("mark", "channel", "time", "roi_y", "roi_x"), ("mark", "time", "roi_y", "roi_x")
 
 
 def _sums_counts(xp, mask):
     """(sums (M, C, T) float64, counts (M, T) int64) of roi under a mask: one call of the masked-sum kernel
     (mg_masked_sums), which reads the mask of every timepoint where it lies."""
-    roi = device_tensor(xp.data_vars["roi"], _ROI_DIMS)
-    sums, cnt = hotpath.masked_sums(roi, device_tensor(xp.coords[mask], _MASK_DIMS, as_mask=True))
+    roi = device_tensor(xp.data_vars["roi"], ROI_DIMS)
+    sums, cnt = hotpath.masked_sums(roi, device_tensor(xp.coords[mask], MASK_DIMS, as_mask=True))
     return sums[..., 0], cnt[..., 0].to(torch.int64).expand(roi.shape[0], roi.shape[2])
 
 
@@ -60,7 +58,7 @@ def masked_median(xp, mask="bg", time=None):
     chip searched at several timesteps, find.py:119-140).  ``time=k``: of timepoint ``k`` only, selected BEFORE the
     reduction as ``assay.isel(time=0)`` does in filter.py:20-22, 69-75 and identify.py:76 -- the other timepoints are
     neither read nor reduced; the result keeps a time axis of length 1."""
-    return DataArray(hotpath.masked_median(*_roi_and_mask(xp, mask, time)), _MCT)
+    return DataArray(hotpath.masked_median(*roi_windows(xp, mask, time)), _MCT)
 
 
 def fg_mean_minus_bg_median(xp, time=None):
@@ -75,26 +73,13 @@ def fg_mean_minus_bg_median(xp, time=None):
 _MCT = ("mark", "channel", "time")
 
 
-def _roi_and_mask(xp, mask, time):
-    """``mask``: a coordinate name, or a DataArray on (mark[, time], roi_y, roi_x)."""
-    roi, m = xp.data_vars["roi"], xp.coords[mask] if isinstance(mask, str) else mask
-    if time is not None:  # selected where the data lies: the other timepoints are neither moved nor read
-        one = slice(time, time + 1) if time != -1 else slice(-1, None)
-        roi = roi.isel(time=one)
-        if m.sizes.get("time", 1) != 1:
-            m = m.isel(time=one)
-    roi = device_tensor(roi, _ROI_DIMS)
-    hotpath.nat.dtype_code(roi.dtype)  # TypeError for anything but uint8 / uint16 / float32 / float64
-    return roi, device_tensor(m, _MASK_DIMS, as_mask=True)
-
-
 def masked_stats(xp, mask="fg", q=(), time=None):
     """(count, stats, order) of roi under ``mask`` -- a coordinate name, or a DataArray on (mark[, time], roi_y, roi_x)
     -- as DataArrays on the device: count (mark, channel, time) int32, stats (mark, channel, time, stat) =
     {sum, m2, min, max} and order (mark, channel, time, quantile, bound) = the two order statistics every fraction of
     ``q`` falls between (``hotpath.masked_stats``).  A pixel takes part iff the mask is set and it is not NaN.
     ``time=k``: of timepoint ``k`` only, selected before the reduction as ``masked_median`` does."""
-    count, stats, order = hotpath.masked_stats(*_roi_and_mask(xp, mask, time), q)
+    count, stats, order = hotpath.masked_stats(*roi_windows(xp, mask, time), q)
     return (DataArray(count, _MCT), DataArray(stats, _MCT + ("stat",)), DataArray(order, _MCT + ("quantile", "bound")))
 
 
@@ -166,43 +151,6 @@ def masked_quantile(xp, q, mask="fg", time=None):
 _MCTR = _MCT + ("ring",)
 
 
-def _marker_windows(xp, L, time):
-    """(y, x, top, left), each (mark, time): every marker's position and the origin of its window, the one the finder
-    cut -- ``find._window_origin`` of ``find._rounded_centres`` of that timepoint's x, y."""
-    from .find import _rounded_centres, _window_origin
-
-    if "im_y" not in xp.sizes or "im_x" not in xp.sizes:
-        raise ValueError('radial_profile: centre="marker" needs the image sizes im_y / im_x to find the window origins, '
-                         "and this dataset no longer has them (roi_only?): pass centre= (\"window\", or the centres "
-                         "in window coordinates)")
-    x, y = (np.asarray(xp.coords[k].transpose(*[d for d in ("mark", "time") if d in xp.coords[k].dims]).values,
-                       dtype=np.float64) for k in ("x", "y"))
-    if x.ndim == 1:
-        x, y = x[:, None], y[:, None]
-    if time is not None:
-        x, y = (x[:, time:time + 1], y[:, time:time + 1]) if time != -1 else (x[:, -1:], y[:, -1:])
-    if x.size == 0:
-        return y, x, np.zeros(x.shape, dtype=np.int64), np.zeros(x.shape, dtype=np.int64)
-    rc = _rounded_centres(y, x).reshape(x.shape + (2,))
-    return y, x, _window_origin(rc[..., 0], L, xp.sizes["im_y"]), _window_origin(rc[..., 1], L, xp.sizes["im_x"])
-
-
-def _marker_centres(xp, L, time):
-    """(mark, time, 2) float64 {y - top, x - left}: every marker's position inside its own window
-    (``_marker_windows``)."""
-    y, x, top, left = _marker_windows(xp, L, time)
-    return np.stack([y - top, x - left], axis=-1)
-
-
-def _own_mask(xp):
-    """fg | bg of every marker, on the device, as a DataArray on (mark, time, roi_y, roi_x): the pixels a bead owns
-    (what ``segment_rois`` allows its foreground to grow into).  One drawn mask for all timepoints gives one union."""
-    fg, bg = (device_tensor(xp.coords[k], _MASK_DIMS, as_mask=True) for k in ("fg", "bg"))
-    if all(t.shape[1] == 1 or t.stride(1) == 0 for t in (fg, bg)):
-        fg, bg = fg[:, :1], bg[:, :1]
-    return DataArray((fg.view(torch.uint8) | bg.view(torch.uint8)).view(torch.bool), _MASK_DIMS)
-
-
 def radial_profile(xp, width=1.0, rings=None, edges=None, mask="own", centre="marker", time=None):
     """(count, moments) of roi in rings about every marker, as DataArrays on the device: count (mark, channel, time,
     ring) int32 and moments (mark, channel, time, ring, moment) float64 = {sum x, sum x^2} (``hotpath.radial_profile``),
@@ -223,45 +171,28 @@ def radial_profile(xp, width=1.0, rings=None, edges=None, mask="own", centre="ma
     if mask is not None and not isinstance(mask, (str, DataArray)):
         raise ValueError(f'radial_profile: mask must be "own", None, a coordinate name or a DataArray, got {mask!r}')
     edges_q = profile.check_profile(width, rings, mask if isinstance(mask, str) else None, L, edges)
-    one = None if time is None else (slice(time, time + 1) if time != -1 else slice(-1, None))
+    one = time_pick(time)
     n_t = roi_var.sizes["time"] if one is None else len(range(roi_var.sizes["time"])[one])
     # the centres, float64 (mark, 1 or time, 2) in pixels
     if isinstance(centre, str):
         if centre == "marker":
-            c = _marker_centres(xp, L, time)
+            c = marker_centres(xp, L, time)
         elif centre == "window":
             c = np.full((m, 1, 2), float(L // 2))
         else:
             raise ValueError(f'radial_profile: centre must be "marker", "window" or the centres, got {centre!r}')
     else:
-        if isinstance(centre, DataArray):
-            centre = centre.transpose(*[d for d in ("mark", "time") if d in centre.dims], ...).values
-        c = np.asarray(centre, dtype=np.float64)
-        if c.ndim == 2:
-            c = c[:, None]
-        if c.ndim != 3 or c.shape[0] != m or c.shape[2] != 2 or c.shape[1] not in (1, roi_var.sizes["time"]):
-            raise ValueError(f"radial_profile: centres must be (mark[, time], 2) = {(m, roi_var.sizes['time'], 2)}, "
-                             f"got {c.shape}")
+        c = per_marker("radial_profile", centre, m, roi_var.sizes["time"], 2, "centre")
         if one is not None and c.shape[1] != 1:
             c = c[:, one]
-    if not np.isfinite(c).all():
-        raise ValueError("radial_profile: a centre is not finite")
-    centre_q = np.clip(profile.quantise(c), -2.0**30, 2.0**30).astype(np.int32)  # (the kernel clamps to its own range)
+    centre_q = profile.quantised(c)  # (finite: per_marker checked a caller's, find._rounded_centres the markers')
     coords = profile.ring_coords(edges_q)
     r = len(edges_q) - 1
     if m == 0:
         n_c = roi_var.sizes["channel"]
         return (DataArray(np.zeros((0, n_c, n_t, r), dtype=np.int32), _MCTR, coords),
                 DataArray(np.zeros((0, n_c, n_t, r, 2), dtype=np.float64), _MCTR + ("moment",), coords))
-    if isinstance(mask, str) and mask == "own":
-        mask = None if "tag" in xp.coords else _own_mask(xp)
-    if mask is None:
-        roi = roi_var if one is None else roi_var.isel(time=one)
-        roi, mk = device_tensor(roi, _ROI_DIMS), None
-        hotpath.nat.dtype_code(roi.dtype)
-    else:
-        roi, mk = _roi_and_mask(xp, mask, time)
-    count, moments = hotpath.radial_profile(roi, mk, centre_q, edges_q)
+    count, moments = hotpath.radial_profile(*roi_windows(xp, mask, time), centre_q, edges_q)
     return DataArray(count, _MCTR, coords), DataArray(moments, _MCTR + ("moment",), coords)
 
 
@@ -278,7 +209,7 @@ def refine_circles(xp, channel=None, rays=64, reach=3, polarity="auto", reject=1
     coordinates too, and ``radius`` reports the start radius rounded to whole pixels.  Start circles are quantised as
     ``np.rint(v * 16)`` in float64.  The two square roots -- the radius from R^2, the rms from the mean square -- are
     taken here with NumPy."""
-    from . import refine
+    from . import profile, refine
 
     roi_var = xp.data_vars["roi"]
     L, m, n_t = roi_var.sizes["roi_y"], roi_var.sizes["mark"], roi_var.sizes["time"]
@@ -287,35 +218,20 @@ def refine_circles(xp, channel=None, rays=64, reach=3, polarity="auto", reject=1
     if isinstance(circle, str):
         if circle != "marker":
             raise ValueError(f'refine_circles: circle must be "marker" or the circles, got {circle!r}')
-        if "im_y" not in xp.sizes or "im_x" not in xp.sizes:
-            raise ValueError('refine_circles: circle="marker" needs the image sizes im_y / im_x to find the window '
-                             "origins, and this dataset no longer has them (roi_only?): pass circle= (the start circles "
-                             "in window coordinates)")
+        y, x, top, left = (np.broadcast_to(v, (m, n_t)) for v in marker_windows(xp, L, None, "refine_circles", "circle"))
         r = refine.finder_radius(xp, radius)
-        y, x, top, left = (np.broadcast_to(v, (m, n_t)) for v in _marker_windows(xp, L, None))
         c = np.stack([y - top, x - left], axis=-1)  # as reduce.radial_profile(centre="marker") has them
         origin = np.stack([top, left], axis=-1).astype(np.float64)
         start = np.concatenate([c, r[..., None].astype(np.float64)], axis=-1)
     else:
-        if isinstance(circle, DataArray):
-            circle = circle.transpose(*[d for d in ("mark", "time") if d in circle.dims], ...).values
-        start = np.asarray(circle, dtype=np.float64)
-        if start.ndim == 2:
-            start = start[:, None]
-        if start.ndim != 3 or start.shape[0] != m or start.shape[2] != 3 or start.shape[1] not in (1, n_t):
-            raise ValueError(f"refine_circles: circles must be (mark[, time], 3) = {(m, n_t, 3)}, got {start.shape}")
-        if not np.isfinite(start).all():
-            raise ValueError("refine_circles: a start circle is not finite")
-        start = np.broadcast_to(start, (m, n_t, 3))
+        start = np.broadcast_to(per_marker("refine_circles", circle, m, n_t, 3, "circle"), (m, n_t, 3))
         origin = np.zeros((m, n_t, 2), dtype=np.float64)
-        r = np.rint(np.clip(start[..., 2], 0.0, 2.0**30)).astype(np.int64)
-    from .profile import quantise
-
-    circle_q = np.ascontiguousarray(np.clip(quantise(start), -2.0**30, 2.0**30).astype(np.int32))  # (the kernel clamps)
+        r = np.rint(np.clip(start[..., 2], 0.0, profile.INT_LIMIT)).astype(np.int64)
+    circle_q = np.ascontiguousarray(profile.quantised(start))
     if m == 0:
         info, fit = np.zeros((0, n_t, 4), dtype=np.int32), np.zeros((0, n_t, 5), dtype=np.float64)
     else:
-        roi = device_tensor(roi_var, _ROI_DIMS)
+        roi = device_tensor(roi_var, ROI_DIMS)
         info, fit = hotpath.refine_circles(roi[:, ch], circle_q, *settings)
         info, fit = info.cpu().numpy(), fit.cpu().numpy()
     centre = origin + circle_q[..., :2].astype(np.float64) / 16.0  # the start centre as the kernel had it
@@ -379,18 +295,13 @@ def unmixed_stats(xp, matrix, channels=None, offset="bg_median", mask="fg", q=(0
         raise ValueError(f'unmixed_stats: offset must be "bg_median", None or a DataArray, got {type(offset).__name__}')
     if mask is not None and not isinstance(mask, (str, DataArray)):
         raise ValueError(f"unmixed_stats: mask must be None, a coordinate name or a DataArray, got {mask!r}")
-    if mask is None:
-        roi = roi_var if time is None else roi_var.isel(time=slice(time, time + 1) if time != -1 else slice(-1, None))
-        roi, mk = device_tensor(roi, _ROI_DIMS), None
-        hotpath.nat.dtype_code(roi.dtype)
-    else:
-        roi, mk = _roi_and_mask(xp, mask, time)
+    roi, mk = roi_windows(xp, mask, time)
     if isinstance(offset, str):
         off = masked_median(xp, "bg", time=time).data
     elif offset is not None:
         off = offset
         if time is not None and off.sizes.get("time", 1) != 1:
-            off = off.isel(time=slice(time, time + 1) if time != -1 else slice(-1, None))
+            off = off.isel(time=time_pick(time))
         off = device_tensor(off, _MCT).to(torch.float64)
     else:
         off = None

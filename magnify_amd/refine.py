@@ -9,13 +9,11 @@ on a blurred disk it reads about a tenth of a pixel under the geometric edge.
 """
 from __future__ import annotations
 
-import math
-
 import numpy as np
 
 from . import _native as nat
 from . import registry
-from .utils import int_in
+from .utils import int_in, number
 
 MAX_RAYS, MAX_REACH, MAX_LEN = (nat.DEFINES[k] for k in ("MG_REFINE_MAX_RAYS", "MG_REFINE_MAX_REACH", "MG_REFINE_MAX_LEN"))
 MIN_RAYS = 8
@@ -24,15 +22,6 @@ POLARITIES = {"auto": 0, "brighter": 1, "darker": -1}
 FLOAT_VARS = ("x_fit", "y_fit", "radius_fit", "fit_rms", "fit_strength")
 INT_VARS = ("fit_rays", "fit_status", "fit_polarity", "radius")
 REFINE_VARS = FLOAT_VARS + INT_VARS
-
-
-def _number(name, v):
-    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
-        raise ValueError(f"{name} must be a number, got {v!r}")
-    v = float(v)
-    if not math.isfinite(v):
-        raise ValueError(f"{name} must be finite, got {v!r}")
-    return v
 
 
 def check_refine(rays=64, reach=3, polarity="auto", reject=1.0, min_strength=0.25, min_rays=None, roi_length=None):
@@ -49,10 +38,10 @@ def check_refine(rays=64, reach=3, polarity="auto", reject=1.0, min_strength=0.2
         polarity = POLARITIES[polarity]
     else:
         polarity = int_in("refine polarity", polarity, -1, 1)
-    reject = _number("refine reject", reject)
+    reject = number("refine reject", reject)
     if not reject > 0:
         raise ValueError(f"refine reject must be a number of pixels > 0, got {reject}")
-    min_strength = _number("refine min_strength", min_strength)
+    min_strength = number("refine min_strength", min_strength)
     if not 0.0 <= min_strength <= 1.0:
         raise ValueError(f"refine min_strength must be in [0, 1], got {min_strength}")
     min_rays = rays // 2 if min_rays is None else int_in("refine min_rays", min_rays, 3, rays)

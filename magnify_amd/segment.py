@@ -65,7 +65,6 @@ def segment_rois(assay, method="otsu", channel=None, open_radius=1, max_grow=4, 
     from . import hotpath
     from .xr_lite import DataArray
 
-    mask_dims, roi_dims = ("mark", "time", "roi_y", "roi_x"), ("mark", "channel", "time", "roi_y", "roi_x")
     roi_var = assay.data_vars["roi"]
     L, m, n_t = roi_var.sizes["roi_y"], roi_var.sizes["mark"], roi_var.sizes["time"]
     check_segment(method, open_radius, max_grow, bg_guard, min_area, L)
@@ -74,21 +73,16 @@ def segment_rois(assay, method="otsu", channel=None, open_radius=1, max_grow=4, 
         return assay.assign_coords(segmented=(("mark", "time"), np.zeros((0, n_t), dtype=bool)),
                                    seg_threshold=(("mark", "time"), np.zeros((0, n_t), dtype=np.float64)))
     hotpath.require_gpu()
-    roi = _dataset.device_tensor(roi_var, roi_dims)
+    roi = _dataset.device_tensor(roi_var, _dataset.ROI_DIMS)
     old_fg, old_bg = assay.coords["fg"], assay.coords["bg"]
-    fg0, bg0 = (_dataset.device_tensor(a, mask_dims, as_mask=True) for a in (old_fg, old_bg))
-    allowed = None
-    if "tag" not in assay.coords:
-        if all(t.shape[1] == 1 or t.stride(1) == 0 for t in (fg0, bg0)):  # one drawn mask for all timepoints: one union
-            allowed = fg0[:, :1].view(torch.uint8) | bg0[:, :1].view(torch.uint8)
-        else:
-            allowed = fg0.view(torch.uint8) | bg0.view(torch.uint8)
+    fg0, bg0 = (_dataset.device_tensor(a, _dataset.MASK_DIMS, as_mask=True) for a in (old_fg, old_bg))
+    allowed = None if "tag" in assay.coords else _dataset.own_mask(fg0, bg0)
     fg, bg, threshold, counts, segmented = hotpath.threshold_masks(
         roi[:, ch], fg0, bg0, allowed, method=method, open_radius=open_radius, max_grow=max_grow, bg_guard=bg_guard,
         min_area=min_area)
     out = assay.assign_coords(
-        fg=DataArray(fg.view(torch.bool), mask_dims, None, "fg", dict(old_fg.attrs)),
-        bg=DataArray(bg.view(torch.bool), mask_dims, None, "bg", dict(old_bg.attrs)),
+        fg=DataArray(fg.view(torch.bool), _dataset.MASK_DIMS, None, "fg", dict(old_fg.attrs)),
+        bg=DataArray(bg.view(torch.bool), _dataset.MASK_DIMS, None, "bg", dict(old_bg.attrs)),
         segmented=(("mark", "time"), segmented.view(torch.bool)),
         seg_threshold=(("mark", "time"), threshold),
     )

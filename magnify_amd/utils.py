@@ -3,6 +3,8 @@ circle tables come from the native library (no GPU needed)."""
 from __future__ import annotations
 
 import inspect
+import math
+import numbers
 import os
 import re
 from collections.abc import Iterable
@@ -48,13 +50,18 @@ def bounding_box(x: int, y: int, box_length: int, image_width: int, image_height
     return top, bottom, left, right
 
 
+def window_origin(c, L, size):
+    """``bounding_box`` for integer arrays: where the L-wide window about every centre ``c`` begins once it is shifted
+    into [0, size) -- int64, the shape of ``c``.  The caller rounds: the finders half to even, ``plot`` by truncation."""
+    lo = np.maximum(np.asarray(c).astype(np.int64) - L // 2, 0)
+    return np.where(lo + L > size, size - L, lo)
+
+
 def roi_mark_chunk(bound: int, n_channels: int, n_times: int, roi_length: int, chunk_bytes: float = 1e6) -> int:
     """Markers per chunk of ``roi / fg / bg`` as the reference chunks them (find.py:185-188, 506-531): every channel
     and timepoint of a marker in one chunk, as many markers as make at least ``chunk_bytes`` -- counted in pixels, "since
     fg/bg bool arrays should also be 1MB" --, at most ``bound`` (the bead count; for chips the reference bounds by the
     number of marker ROWS, find.py:187)."""
-    import math
-
     per_marker = roi_length ** 2 * n_channels * n_times
     return int(max(0, min(math.ceil(chunk_bytes / max(per_marker, 1)), bound)))
 
@@ -90,6 +97,17 @@ def int_in(name, value, lo, hi=None):
         raise ValueError(f"{name} must be in [{lo}, {hi}], got {value}" if hi is not None else
                          f"{name} must be at least {lo}, got {value}")
     return int(value)
+
+
+def number(name, v):
+    """``v`` as a float where it is a finite real number -- no bool, no string.  ValueError that names ``name``
+    otherwise."""
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, numbers.Real):
+        raise ValueError(f"{name} must be a number, got {v!r}")
+    v = float(v)
+    if not math.isfinite(v):
+        raise ValueError(f"{name} must be finite, got {v!r}")
+    return v
 
 
 def to_list(x):

@@ -158,7 +158,7 @@ def test_host_side_matches_the_restatement():
     rng = np.random.default_rng(3)
     for L, h, w in [(40, 96, 96), (41, 50, 120), (72, 72, 300)]:
         x, y = rng.integers(0, w, size=(30, 2)), rng.integers(0, h, size=(30, 2))
-        got = plot._origins(x, y, L, h, w)
+        got = np.stack([utils.window_origin(y, L, h), utils.window_origin(x, L, w)], axis=-1)
         np.testing.assert_array_equal(got, pr.origins(x, y, L, h, w))
         for i in range(30):
             top, bottom, left, right = utils.bounding_box(int(x[i, 0]), int(y[i, 0]), L, w, h)

@@ -10,7 +10,7 @@ import pytest
 import magnify_amd as mg
 import radial_ref as ref
 from magnify_amd import _native as nat
-from magnify_amd import profile, reduce
+from magnify_amd import _dataset, profile, reduce
 
 
 # ---- the oracle ------------------------------------------------------------------------------------------------------------
@@ -188,7 +188,7 @@ def test_marker_centres_at_the_borders_and_half_pixels():
     x = np.array([[1.2, 25.5], [48.7, 26.5], [20.0, 3.5], [20.25, 4.5], [0.0, 49.0], [49.4, 0.4], [25.0, 25.0], [4.0, 46.0]])
     y = np.array([[20.0, 0.3], [20.5, 39.2], [1.0, 21.5], [38.9, 22.5], [0.0, 39.0], [39.4, 0.4], [3.5, 36.5], [4.0, 36.0]])
     ds = ds.assign_coords(x=(("mark", "time"), x), y=(("mark", "time"), y))
-    got = reduce._marker_centres(ds, L, None)
+    got = _dataset.marker_centres(ds, L, None)
     assert got.shape == (8, 2, 2)
     for g in range(8):
         for t in range(2):
@@ -198,8 +198,8 @@ def test_marker_centres_at_the_borders_and_half_pixels():
             assert got[g, t, 0] == y[g, t] - top and got[g, t, 1] == x[g, t] - left, (g, t)
     assert got[0, 1, 1] == 25.5 - 22 and got[1, 1, 1] == 26.5 - 22  # 25.5 -> 26, 26.5 -> 26
     assert got[0, 0, 1] == 1.2 and got[1, 0, 1] == 48.7 - 42 and got[2, 0, 0] == 1.0 and got[3, 0, 0] == 38.9 - 32
-    np.testing.assert_array_equal(reduce._marker_centres(ds, L, 1), got[:, 1:2])
-    np.testing.assert_array_equal(reduce._marker_centres(ds, L, -1), got[:, -1:])
+    np.testing.assert_array_equal(_dataset.marker_centres(ds, L, 1), got[:, 1:2])
+    np.testing.assert_array_equal(_dataset.marker_centres(ds, L, -1), got[:, -1:])
 
 
 # ---- the helpers -----------------------------------------------------------------------------------------------------------

@@ -153,6 +153,11 @@ def test_labels_of_masks_that_differ_per_timepoint(mg, labelled, level):
     np.testing.assert_array_equal(got.cpu().numpy(), want[level])
     again = hotpath.image_labels(dev(fg), origin, level, H, W)  # the same bits on every call
     np.testing.assert_array_equal(again.cpu().numpy(), want[level])
+    # the origins as a host array of another integer type, as a device tensor, and as a view of a wider table
+    wide = np.zeros(origin.shape[:2] + (3,), dtype=np.int32)
+    wide[..., :2] = origin
+    for form in (origin.astype(np.int64), dev(origin.astype(np.int16)), dev(wide)[..., :2]):
+        np.testing.assert_array_equal(hotpath.image_labels(dev(fg), form, level, H, W).cpu().numpy(), want[level])
 
 
 @pytest.mark.parametrize("level", [0, 2])

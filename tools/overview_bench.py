@@ -28,7 +28,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT]
 
-from magnify_amd import hotpath, plot, track  # noqa: E402
+from magnify_amd import hotpath, plot, track, utils  # noqa: E402
 
 SIDE, L = 4096, 100
 
@@ -73,7 +73,7 @@ def main():
     shared = torch.from_numpy(disks).cuda()[:, None].expand(m, n_t, L, L)  # one mask per marker: time stride 0
     fg = shared.contiguous()  # one per (marker, timepoint)
     centres = rng.integers(0, SIDE, size=(2, m, n_t))
-    origin = torch.from_numpy(plot._origins(centres[0], centres[1], L, SIDE, SIDE)).cuda()
+    origin = torch.from_numpy(np.stack([utils.window_origin(centres[1], L, SIDE), utils.window_origin(centres[0], L, SIDE)], axis=-1).astype(np.int32)).cuda()
     table = torch.from_numpy(np.repeat(np.asarray(plot.MARK_COLORS, dtype=np.uint8)[np.arange(m) % 8][:, None], n_t,
                                        axis=1).copy()).cuda()
     limits, colors = [(1000.0, 60000.0)] * n_c, plot.default_colors(n_c)
