@@ -158,6 +158,9 @@ __device__ __forceinline__ MgIndex3 mg_split3(int64_t i, bool small, int nb, int
   return {r, a, (int)(r - (int64_t)a * nb), (int)(i - r * nc)};
 }
 
+// The NaN every kernel writes where a result has nothing to stand on (an empty selection, a window without a threshold).
+constexpr double MG_QNAN = __builtin_nan("");
+
 // NaN-propagating max / min, as np.max / np.min.
 __device__ __forceinline__ double mg_nanmax(double a, double b) { return (a != a) ? a : (b != b) ? b : (a > b ? a : b); }
 __device__ __forceinline__ double mg_nanmin(double a, double b) { return (a != a) ? a : (b != b) ? b : (a < b ? a : b); }

@@ -4,8 +4,9 @@
 //
 // One workgroup per (marker, time) walks the windows of all channels: ring membership depends on (marker, time) only,
 // so the first channel's pass keeps, where the window has at most KEEP_BYTES pixels, one byte per pixel in LDS -- the
-// ring, or NO_RING where the pixel has none -- and the later channels compute no distance.  The windows are ingested as in k_masked_stats (16-byte chunks, IN_FLIGHT steps of loads issued
-// before the first is worked on; the loader is mg_select.h's).
+// ring, or NO_RING where the pixel has none -- and the later channels compute no distance.  The windows are
+// ingested as in k_masked_stats: a pass is a body of mg_windows.h's walk_chunks (16-byte chunks, IN_FLIGHT steps of
+// loads issued before the first is worked on), and the entry stands in that header's frame (check, launch).
 //
 // Integer pixels: count, sum and sum of squares go to the workgroup's table with integer LDS atomics -- exact, and
 // integer addition does not care for the order.  Float pixels: no atomic touches a float.  Of every lane's chunk the
@@ -17,11 +18,11 @@
 // in which no lane has a pixel under the mask is skipped by the whole wave.
 //
 // Roofline: HBM.  Per window L*L*sizeof(T) bytes read, the mask's L*L once per (marker, time); 20 n_rings bytes written.
-#include "mg_select.h"
+#include "mg_windows.h"
 
 namespace {
 
-constexpr int NT = MG_SELECT_THREADS, WV = NT / 64, IN_FLIGHT = 4;
+constexpr int NT = MG_WINDOW_THREADS, WV = MG_WINDOW_WAVES;
 constexpr int R_MAX = MG_PROFILE_MAX_RINGS, SUB = MG_PROFILE_SUBPIXEL;
 constexpr int KEEP_BYTES = 16384;    // ring bytes kept in LDS for the later channels: windows up to 128 x 128
 constexpr uint32_t NO_RING = 255u;   // > any ring index
@@ -118,69 +119,60 @@ __device__ __forceinline__ void pass(const T* __restrict__ v, const uint8_t* __r
                                      uint8_t* keep, uint32_t* s_cnt, Slots<T>& acc) {
   constexpr bool INTEGER = std::is_integral<T>::value;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int chunks = (n + VW - 1) / VW, per_wave = (chunks + WV - 1) / WV;
-  const int begin = min(wave * per_wave, chunks), end = min(begin + per_wave, chunks);
-  for (int c0 = begin; c0 < end; c0 += 64 * IN_FLIGHT) {  // wave-uniform trip counts: every lane takes part in the scans
-    RawChunk<T, VW> raw[IN_FLIGHT];
+  walk_chunks<T, VW, MASKED>(v, mask, n, [&](const RawChunk<T, VW>& raw, int c, const WaveRun& run) {
+    // (wave-uniform: nothing of these 64 chunks is under the mask, and no ring byte is owed to a later channel)
+    if ((KEPT || !keep) && !__ballot((raw.mw[0] | raw.mw[1] | raw.mw[2] | raw.mw[3]) != 0u)) return;
+    const int end = run.end, p0 = c * VW;  // (< 2^24: a float holds it)
+    int row = (int)((float)p0 * g.inv_len), col = p0 - row * g.len;
+    if (col < 0) --row, col += g.len;
+    if (col >= g.len) ++row, col -= g.len;
+    uint32_t rings[4] = {};
+    const bool whole = VW > 1 && c < end && (c + 1) * VW <= n;
+    if (KEPT && whole) load_bytes<VW>(keep + p0, rings);
 #pragma unroll
-    for (int u = 0; u < IN_FLIGHT; ++u) raw[u] = fetch<T, VW, MASKED>(v, mask, n, c0 + 64 * u + lane, end);
-#pragma unroll
-    for (int u = 0; u < IN_FLIGHT; ++u) {
-      if (c0 + 64 * u >= end) break;
-      // (wave-uniform: nothing of these 64 chunks is under the mask, and no ring byte is owed to a later channel)
-      if ((KEPT || !keep) && !__ballot((raw[u].mw[0] | raw[u].mw[1] | raw[u].mw[2] | raw[u].mw[3]) != 0u)) continue;
-      const int c = c0 + 64 * u + lane, p0 = c * VW;  // (< 2^24: a float holds it)
-      int row = (int)((float)p0 * g.inv_len), col = p0 - row * g.len;
-      if (col < 0) --row, col += g.len;
-      if (col >= g.len) ++row, col -= g.len;
-      uint32_t rings[4] = {};
-      const bool whole = VW > 1 && c < end && (c + 1) * VW <= n;
-      if (KEPT && whole) load_bytes<VW>(keep + p0, rings);
-#pragma unroll
-      for (int j = 0; j < VW; ++j) {
-        const bool inside = c < end && p0 + j < n;  // (beyond `end` lie another wave's pixels)
-        uint32_t ring = NO_RING;
-        if (KEPT) {
-          if (whole) ring = (rings[j >> 2] >> (8 * (j & 3))) & 0xFFu;
-          else if (inside) ring = keep[p0 + j];
-        } else if (inside) {
-          ring = ring_of(g, dist2(g, row, col));
-          if (keep) keep[p0 + j] = (uint8_t)ring;
-        }
-        const T x = raw[u].px[j];
-        const bool ok = ring != NO_RING && ((raw[u].mw[j >> 2] >> (8 * (j & 3))) & 0xFFu) != 0u && x == x;
-        if constexpr (INTEGER) {
-          if (ok) {
-            atomicAdd(&s_cnt[ring], 1u);
-            atomicAdd(&acc.sum[ring], (unsigned long long)x);
-            atomicAdd(&acc.sq[ring], (unsigned long long)((uint32_t)x * (uint32_t)x));
-          }
-        } else {
-          if (ok) atomicAdd(&s_cnt[ring], 1u);
-          if (!__ballot(ok)) {  // wave-uniform: 64 times + 0.0, which changes no slot (a slot is never -0.0)
-            if (++col == g.len) col = 0, ++row;
-            continue;
-          }
-          double a = ok ? (double)x : 0.0, b = a * a;
-          const int key = ring == NO_RING ? NO_KEY : (int)((uint32_t)row << 8 | (col * SUB >= g.cx ? 128u : 0u) | ring);
-          seg_scan(key, a, b);
-          const int next = __shfl_down(key, 1);  // (by every lane, before any condition: a lane that sits out returns 0)
-          const bool last = key != NO_KEY && (lane == 63 || next != key);
-          unsigned long long pending = __ballot(last);
-          while (pending) {  // wave-uniform: the runs of the first pending lane's (row, side), all of different rings
-            const int side = __builtin_amdgcn_readlane(key, __ffsll((long long)pending) - 1) >> 7;
-            const bool now = last && (key >> 7) == side;
-            if (now) {
-              double* s = acc.m[wave][key & 127];
-              s[0] += a, s[1] += b;
-            }
-            pending &= ~__ballot(now);
-          }
-        }
-        if (++col == g.len) col = 0, ++row;
+    for (int j = 0; j < VW; ++j) {
+      const bool inside = c < end && p0 + j < n;  // (beyond `end` lie another wave's pixels)
+      uint32_t ring = NO_RING;
+      if (KEPT) {
+        if (whole) ring = (rings[j >> 2] >> (8 * (j & 3))) & 0xFFu;
+        else if (inside) ring = keep[p0 + j];
+      } else if (inside) {
+        ring = ring_of(g, dist2(g, row, col));
+        if (keep) keep[p0 + j] = (uint8_t)ring;
       }
+      const T x = raw.px[j];
+      const bool ok = ring != NO_RING && raw.under_mask(j) && x == x;
+      if constexpr (INTEGER) {
+        if (ok) {
+          atomicAdd(&s_cnt[ring], 1u);
+          atomicAdd(&acc.sum[ring], (unsigned long long)x);
+          atomicAdd(&acc.sq[ring], (unsigned long long)((uint32_t)x * (uint32_t)x));
+        }
+      } else {
+        if (ok) atomicAdd(&s_cnt[ring], 1u);
+        if (!__ballot(ok)) {  // wave-uniform: 64 times + 0.0, which changes no slot (a slot is never -0.0)
+          if (++col == g.len) col = 0, ++row;
+          continue;
+        }
+        double a = ok ? (double)x : 0.0, b = a * a;
+        const int key = ring == NO_RING ? NO_KEY : (int)((uint32_t)row << 8 | (col * SUB >= g.cx ? 128u : 0u) | ring);
+        seg_scan(key, a, b);
+        const int next = __shfl_down(key, 1);  // (by every lane, before any condition: a lane that sits out returns 0)
+        const bool last = key != NO_KEY && (lane == 63 || next != key);
+        unsigned long long pending = __ballot(last);
+        while (pending) {  // wave-uniform: the runs of the first pending lane's (row, side), all of different rings
+          const int side = __builtin_amdgcn_readlane(key, __ffsll((long long)pending) - 1) >> 7;
+          const bool now = last && (key >> 7) == side;
+          if (now) {
+            double* s = acc.m[wave][key & 127];
+            s[0] += a, s[1] += b;
+          }
+          pending &= ~__ballot(now);
+        }
+      }
+      if (++col == g.len) col = 0, ++row;
     }
-  }
+  });
 }
 
 template <typename T>
@@ -191,7 +183,6 @@ __global__ __launch_bounds__(NT) void k_radial_profile(const T* __restrict__ d_r
                                                        int len, int kept, int32_t* __restrict__ d_count,
                                                        double* __restrict__ d_moments) {
   constexpr bool INTEGER = std::is_integral<T>::value;
-  constexpr int VW = 16 / (int)sizeof(T);
   extern __shared__ __attribute__((aligned(16))) unsigned char s_keep[];  // `kept`: n ring bytes
   __shared__ uint32_t s_e2[R_MAX + 1], s_cnt[R_MAX];
   __shared__ Slots<T> s_acc;
@@ -220,12 +211,12 @@ __global__ __launch_bounds__(NT) void k_radial_profile(const T* __restrict__ d_r
   for (int ch = 0; ch < n_c; ++ch) {  // block-uniform throughout
     const int64_t window = ((int64_t)g_ * n_c + ch) * n_t + t;
     const T* v = d_roi + window * n;
-    const bool aligned = (reinterpret_cast<uintptr_t>(v) & 15) == 0;
     uint8_t* keep = kept ? s_keep : nullptr;
-    const bool wide = aligned && (!mask || (reinterpret_cast<uintptr_t>(mask) & (VW - 1)) == 0);
+    const bool wide = window_is_wide(v, mask);
     auto walk = [&](auto masked, auto kept_) {
-      if (wide) pass<T, VW, decltype(masked)::value, decltype(kept_)::value>(v, mask, n, geo, keep, s_cnt, s_acc);
-      else pass<T, 1, decltype(masked)::value, decltype(kept_)::value>(v, mask, n, geo, keep, s_cnt, s_acc);
+      with_chunk_width<T>(wide, [&](auto vw) {
+        pass<T, decltype(vw)::value, decltype(masked)::value, decltype(kept_)::value>(v, mask, n, geo, keep, s_cnt, s_acc);
+      });
     };
     if (kept && ch > 0) {
       if (mask) walk(std::true_type{}, std::true_type{});
@@ -251,7 +242,6 @@ __global__ __launch_bounds__(NT) void k_radial_profile(const T* __restrict__ d_r
     __syncthreads();  // (the ring bytes of the first pass are in place for the others behind the first of these)
   }
 }
-static_assert(WV == 4, "the waves' slots are added out for four waves");
 
 }  // namespace
 
@@ -260,9 +250,10 @@ extern "C" int mg_roi_radial_profile(const void* d_roi, int dtype, const uint8_t
                                      int64_t centre_stride_t, const int32_t* edges, int n_rings, int m, int n_c, int n_t,
                                      int roi_len, int32_t* d_count, double* d_moments, void* stream) {
   if (!d_roi || !d_centre || !edges || !d_count || !d_moments) return MG_EINVAL;
-  if (m < 0 || n_c <= 0 || n_t <= 0 || roi_len <= 0 || roi_len > MG_PROFILE_MAX_LEN) return MG_EINVAL;
-  if (n_rings < 1 || n_rings > R_MAX || (int64_t)m * n_c * n_t > INT32_MAX) return MG_EINVAL;
-  if (mask_stride_m < 0 || mask_stride_t < 0 || centre_stride_m < 0 || centre_stride_t < 0) return MG_EINVAL;
+  if (!mg_windows_check(m, n_c, n_t, roi_len, MG_PROFILE_MAX_LEN,
+                        {mask_stride_m, mask_stride_t, centre_stride_m, centre_stride_t}))
+    return MG_EINVAL;
+  if (n_rings < 1 || n_rings > R_MAX) return MG_EINVAL;
   if (edges[0] < 0 || edges[n_rings] > MG_PROFILE_MAX_EDGE) return MG_EINVAL;
   Edges e = {};
   e.e0 = edges[0], e.width = edges[1] - edges[0];
@@ -271,15 +262,12 @@ extern "C" int mg_roi_radial_profile(const void* d_roi, int dtype, const uint8_t
     if (k > 0 && edges[k] - edges[k - 1] != e.width) e.width = 0;
     e.e2[k] = (uint32_t)edges[k] * (uint32_t)edges[k];
   }
+  const int n = roi_len * roi_len, kept = n_c > 1 && n <= KEEP_BYTES;
   hipStream_t s = mg_stream(stream);
-  return mg_dispatch_pixel(dtype, [&](auto t) {
+  return mg_windows_launch(dtype, m, n_t, [&](auto t, dim3 grid, dim3 block) {
     typedef decltype(t) T;
-    if (m == 0) return MG_OK;
-    const int n = roi_len * roi_len, kept = n_c > 1 && n <= KEEP_BYTES;
-    hipLaunchKernelGGL(k_radial_profile<T>, dim3((unsigned)((int64_t)m * n_t)), dim3(NT), kept ? (size_t)((n + 15) & ~15) : 0,
-                       s, (const T*)d_roi, d_mask, mask_stride_m, mask_stride_t, d_centre, centre_stride_m,
-                       centre_stride_t, e, n_rings, n_c, n_t, roi_len, kept, d_count, d_moments);
-    MG_CHECK_LAUNCH();
-    return MG_OK;
+    hipLaunchKernelGGL(k_radial_profile<T>, grid, block, kept ? (size_t)((n + 15) & ~15) : 0, s, (const T*)d_roi, d_mask,
+                       mask_stride_m, mask_stride_t, d_centre, centre_stride_m, centre_stride_t, e, n_rings, n_c, n_t,
+                       roi_len, kept, d_count, d_moments);
   });
 }

@@ -17,15 +17,15 @@
 //            so the serial part is n_rays dependent additions per step, not per sum.  Counts go through the barrier
 //            (__syncthreads_count), the largest strength through a broadcast loop: neither depends on an order.
 //
-// Roofline: latency.  Per window 4 n_rays (4 reach + 1) taps, mostly cache hits; 56 bytes written.
-#include "mg_common.h"
+// Roofline: latency.  Per window 4 n_rays (4 reach + 1) taps, mostly cache hits; 56 bytes written.  The entry stands
+// in mg_windows.h's frame (check, launch); the kernel streams no window and takes nothing else from it.
+#include "mg_windows.h"
 
 #include <cfloat>
-#include <type_traits>
 
 namespace {
 
-constexpr int NT = 256;
+constexpr int NT = MG_WINDOW_THREADS;
 constexpr int K_MAX = MG_REFINE_MAX_RAYS, REACH_MAX = MG_REFINE_MAX_REACH, SUB = MG_PROFILE_SUBPIXEL;
 constexpr int J_MAX = 4 * REACH_MAX + 1;
 static_assert(K_MAX <= NT, "one lane per ray");
@@ -242,8 +242,9 @@ extern "C" int mg_roi_refine_circles(const void* d_roi, int dtype, int64_t roi_s
                                      double reject, double min_strength, int min_rays, int32_t* d_info, double* d_fit,
                                      void* stream) {
   if (!d_roi || !d_circle || !d_cs || !d_info || !d_fit) return MG_EINVAL;
-  if (m < 0 || n_t <= 0 || roi_len < 1 || roi_len > MG_REFINE_MAX_LEN || (int64_t)m * n_t > INT32_MAX) return MG_EINVAL;
-  if (roi_stride_m < 0 || roi_stride_t < 0 || circle_stride_m < 0 || circle_stride_t < 0) return MG_EINVAL;
+  if (!mg_windows_check(m, 1, n_t, roi_len, MG_REFINE_MAX_LEN,
+                        {roi_stride_m, roi_stride_t, circle_stride_m, circle_stride_t}))
+    return MG_EINVAL;
   if (n_rays < 8 || n_rays > K_MAX || reach < 1 || reach > REACH_MAX || min_rays < 3 || min_rays > n_rays) return MG_EINVAL;
   if (polarity < -1 || polarity > 1) return MG_EINVAL;
   if (!(reject > 0.0) || !(reject <= DBL_MAX) || !(min_strength >= 0.0) || !(min_strength <= 1.0)) return MG_EINVAL;
@@ -251,10 +252,7 @@ extern "C" int mg_roi_refine_circles(const void* d_roi, int dtype, int64_t roi_s
                   n_rays, reach,       polarity,     min_rays, reject,          min_strength,    d_info, d_fit};
   const size_t lds = (size_t)n_rays * (4 * reach + 1) * sizeof(double);
   hipStream_t s = mg_stream(stream);
-  return mg_dispatch_pixel(dtype, [&](auto t) {  // (any other dtype code: MG_EINVAL, with or without markers)
-    if (m == 0) return (int)MG_OK;
-    hipLaunchKernelGGL((k_refine_circles<decltype(t)>), dim3((unsigned)((int64_t)m * n_t)), dim3(NT), lds, s, a);
-    MG_CHECK_LAUNCH();
-    return (int)MG_OK;
+  return mg_windows_launch(dtype, m, n_t, [&](auto t, dim3 grid, dim3 block) {
+    hipLaunchKernelGGL((k_refine_circles<decltype(t)>), grid, block, lds, s, a);
   });
 }

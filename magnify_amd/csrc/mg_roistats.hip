@@ -3,15 +3,15 @@
 // its mask ONCE from global memory, reduces count / sum / min / max on the way in and keeps the keys of the surviving
 // pixels in LDS; the squared deviations and every order statistic asked for then run out of LDS.  The masked median
 // (mg_roi_masked_median: numpy's nanmedian) is the same kernel in its median mode: the middle ranks, nothing else.
+// The read walks mg_windows.h's chunks and runs (its loop frame is written out in ingest), the ranks of the fractions
+// are walked by mg_select.h's order_pairs, and both entries stand in mg_windows.h's frame (check, fractions, launch).
 //
 // Roofline: HBM.  Per window L*L*(sizeof(T) + 1) bytes read, 4 + 32 + 16 n_q bytes written.
-#include "mg_select.h"
+#include "mg_windows.h"
 
 namespace {
 
-constexpr int NT = MG_SELECT_THREADS, WV = NT / 64;
-static_assert(WV == MG_FOLD_WAVES, "mg_block_fold folds four waves");
-constexpr double QNAN = __builtin_nan("");
+constexpr int NT = MG_WINDOW_THREADS, WV = MG_WINDOW_WAVES;
 
 struct StatsQ {
   double q[MG_ROISTATS_MAX_Q];
@@ -37,34 +37,32 @@ struct Seen {
   }
 };
 
-// The pass over the window.  The window is cut into chunks of VW consecutive pixels (VW = 16 bytes of pixels where the
-// window starts on 16 bytes and its mask on VW bytes: one 16-byte load per lane and chunk; VW = 1 otherwise), the chunks
-// into WV equal runs, one per wave, which its lanes walk 64 chunks at a time, the loads of IN_FLIGHT such steps issued
-// before the first is worked on.  COMPACT: wave w writes the keys of its surviving pixels to keys[seg .. seg + its
-// count), seg = its first pixel, in pixel order -- no wave waits for another, and a survivor's slot depends on the mask
-// and the pixels alone.  Returns the wave's count of survivors.
-constexpr int IN_FLIGHT = 4;
+// The pass over the window: mg_windows.h's walk -- chunks of VW pixels, a run of them per wave (wave_run), the loads of
+// IN_FLIGHT steps issued before the first is worked on -- written out here, not as a body of walk_chunks: as a body
+// the instances that select from global memory come out with other registers and the uint16 one 2 % slower a select
+// (DESIGN.md section 38).  COMPACT: wave w writes the keys of its surviving pixels to keys[seg .. seg + its count),
+// seg = its first pixel, in pixel order -- no wave waits for another, and a survivor's slot depends on the mask and the
+// pixels alone.  Returns the wave's count of survivors.
 template <typename T, int VW, bool COMPACT>
 __device__ __forceinline__ int ingest(const T* __restrict__ v, const uint8_t* __restrict__ mask, int n,
                                       typename median_key<T>::type* keys, Seen<T>& seen) {
   typedef typename median_key<T>::type K;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int chunks = (n + VW - 1) / VW, per_wave = (chunks + WV - 1) / WV;
-  const int begin = min(wave * per_wave, chunks), end = min(begin + per_wave, chunks);
+  const int lane = threadIdx.x & 63;
+  const WaveRun run = wave_run(n, VW, threadIdx.x >> 6);
   int written = 0;  // wave-uniform
-  for (int c0 = begin; c0 < end; c0 += 64 * IN_FLIGHT) {  // wave-uniform trip counts: every lane takes part in the scans
+  for (int c0 = run.begin; c0 < run.end; c0 += 64 * IN_FLIGHT) {  // wave-uniform trip counts: every lane scans
     RawChunk<T, VW> raw[IN_FLIGHT];
 #pragma unroll
-    for (int u = 0; u < IN_FLIGHT; ++u) raw[u] = fetch<T, VW>(v, mask, n, c0 + 64 * u + lane, end);
+    for (int u = 0; u < IN_FLIGHT; ++u) raw[u] = fetch<T, VW>(v, mask, n, c0 + 64 * u + lane, run.end);
 #pragma unroll
     for (int u = 0; u < IN_FLIGHT; ++u) {
-      if (c0 + 64 * u >= end) break;
+      if (c0 + 64 * u >= run.end) break;
       K ks[VW];
       bool ok[VW];
       int mine = 0;
 #pragma unroll
       for (int j = 0; j < VW; ++j) {
-        ok[j] = median_key<T>::key(raw[u].px[j], &ks[j]) && ((raw[u].mw[j >> 2] >> (8 * (j & 3))) & 0xFFu) != 0u;
+        ok[j] = median_key<T>::key(raw[u].px[j], &ks[j]) && raw[u].under_mask(j);
         if (ok[j]) {
           seen.take(ks[j]);
           ++mine;
@@ -72,7 +70,7 @@ __device__ __forceinline__ int ingest(const T* __restrict__ v, const uint8_t* __
       }
       const int incl = mg_wave_scan_incl_i32(mine);
       if (COMPACT) {
-        int at = begin * VW + written + incl - mine;  // < the wave's last pixel: no more survivors than pixels
+        int at = run.begin * VW + written + incl - mine;  // < the wave's last pixel: no more survivors than pixels
 #pragma unroll
         for (int j = 0; j < VW; ++j)
           if (ok[j]) keys[at++] = ks[j];
@@ -115,11 +113,11 @@ __global__ __launch_bounds__(NT) void k_masked_stats(const T* __restrict__ d_roi
   // and three median instances take more scalar registers; through at() the prologue is scheduled another way, and
   // the uint16 statistics measured 0.7 % slower)
   const uint8_t* mask = d_mask + (int64_t)g * mask_stride_m + (int64_t)(ct % n_t) * mask_stride_t;
-  constexpr int VW = 16 / (int)sizeof(T);
-  const bool wide = (reinterpret_cast<uintptr_t>(v) & 15) == 0 && (reinterpret_cast<uintptr_t>(mask) & (VW - 1)) == 0;
+  const bool wide = window_is_wide(v, mask);
 
   Seen<T> seen;
-  const int run = wide ? ingest<T, VW, IN_LDS>(v, mask, n, keys, seen) : ingest<T, 1, IN_LDS>(v, mask, n, keys, seen);
+  const int run = with_chunk_width<T>(
+      wide, [&](auto vw) { return ingest<T, decltype(vw)::value, IN_LDS>(v, mask, n, keys, seen); });
   for (int i = threadIdx.x; i < 256; i += NT) hist[i] = 0u;  // (as select_kth wants it)
   if (IN_LDS && (threadIdx.x & 63) == 0) s_run[threadIdx.x >> 6] = run;
   // (mg_block_fold synchronises: s_run, hist and the keys are in place after the first of these)
@@ -136,23 +134,23 @@ __global__ __launch_bounds__(NT) void k_masked_stats(const T* __restrict__ d_roi
   double* order = d_order + window * (MEDIAN ? 1 : n_q * 2);  // (not touched when n_q = 0)
   if (count == 0) {  // block-uniform
     if (MEDIAN) {
-      if (threadIdx.x == 0) order[0] = QNAN;
+      if (threadIdx.x == 0) order[0] = MG_QNAN;
       return;
     }
     if (threadIdx.x == 0) {
       d_count[window] = 0;
-      stats[0] = 0.0, stats[1] = 0.0, stats[2] = QNAN, stats[3] = QNAN;
+      stats[0] = 0.0, stats[1] = 0.0, stats[2] = MG_QNAN, stats[3] = MG_QNAN;
     }
-    for (int i = threadIdx.x; i < 2 * n_q; i += NT) order[i] = QNAN;
+    order_pairs_of_none(n_q, order);
     return;
   }
 
   Runs runs = {};
   if (IN_LDS) {
-    // run w starts at pixel min(w * per_wave, chunks) * chunk (ingest) and holds s_run[w] survivors
-    const int chunk = wide ? VW : 1, chunks = (n + chunk - 1) / chunk, per_wave = (chunks + WV - 1) / WV;
-    const int p1 = min(per_wave, chunks) * chunk, p2 = min(2 * per_wave, chunks) * chunk;
-    const int p3 = min(3 * per_wave, chunks) * chunk;
+    // run w starts at the first pixel of wave w's first chunk (ingest) and holds s_run[w] survivors
+    const int chunk = wide ? wide_chunk<T> : 1;
+    const int p1 = wave_run(n, chunk, 1).begin * chunk, p2 = wave_run(n, chunk, 2).begin * chunk;
+    const int p3 = wave_run(n, chunk, 3).begin * chunk;
     runs.first1 = s_run[0], runs.first2 = runs.first1 + s_run[1], runs.first3 = runs.first2 + s_run[2];
     runs.shift0 = 0;
     runs.step1 = p1 - runs.first1;
@@ -160,13 +158,15 @@ __global__ __launch_bounds__(NT) void k_masked_stats(const T* __restrict__ d_roi
     runs.step3 = (p3 - runs.first3) - (p2 - runs.first2);
   }
   // sorted[rank]: over the survivors' keys in LDS, or over the window's pixels in global memory
+  auto kept_key = [&](int i, K* key) { *key = keys[runs.slot(i)]; return true; };
+  auto pixel_key = [&](int p, K* key) { return mask[p] && median_key<T>::key(v[p], key); };
   auto select = [&](int rank) -> K {
-    if (IN_LDS)
-      return select_kth<K, median_key<T>::LEVELS>(
-          count, [&](int i, K* key) { *key = keys[runs.slot(i)]; return true; }, rank, hist, s_pick);
-    return select_kth<K, median_key<T>::LEVELS>(
-        n, [&](int p, K* key) { return mask[p] && median_key<T>::key(v[p], key); }, rank, hist, s_pick);
+    if (IN_LDS) return select_kth<K, median_key<T>::LEVELS>(count, kept_key, rank, hist, s_pick);
+    return select_kth<K, median_key<T>::LEVELS>(n, pixel_key, rank, hist, s_pick);
   };
+  // sorted[rank + 1], as order_pairs asks for it: a second selection, not next_above (DESIGN.md section 38 has the
+  // figures of both and the rule that decided)
+  auto next = [&](K, int rank) -> K { return select(rank + 1); };
   if (MEDIAN) {
     const K lo = select((count - 1) / 2);
     const K hi = (count & 1) ? lo : select(count / 2);  // block-uniform
@@ -198,52 +198,32 @@ __global__ __launch_bounds__(NT) void k_masked_stats(const T* __restrict__ d_roi
     stats[0] = total, stats[1] = m2, stats[2] = median_key<T>::value(kmin), stats[3] = median_key<T>::value(kmax);
   }
 
-  // sorted[lo], sorted[hi] of every q: pos = (count - 1) q, lo = floor(pos), hi = min(lo + 1, count - 1)
-  int have_rank = -1;  // the last selection, kept: hi of one q is often lo of the next, or lo itself
-  K have_key = 0;
-  for (int j = 0; j < n_q; ++j) {
-    const double pos = (double)(count - 1) * qs.q[j];
-    const int lo = (int)floor(pos), hi = min(lo + 1, count - 1);
-    K pair[2];
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const int rank = e ? hi : lo;
-      if (rank != have_rank) {  // block-uniform
-        have_key = select(rank);
-        have_rank = rank;
-      }
-      pair[e] = have_key;
-    }
-    if (threadIdx.x == 0) {
-      order[2 * j] = median_key<T>::value(pair[0]);
-      order[2 * j + 1] = median_key<T>::value(pair[1]);
-    }
-  }
+  order_pairs<T>(count, qs.q, n_q, select, next, order);
 }
 
-// MEDIAN: d_order is the (m, n_c, n_t) medians, and d_count, d_stats, qs are not looked at.  Runs inside
-// mg_dispatch_pixel, which has refused every other dtype code by now: no markers is MG_OK for a valid dtype only.
-template <typename T, bool MEDIAN>
-int launch_stats(const void* d_roi, const MgMaskView& mask, int m, int n_c, int n_t, int len, const StatsQ& qs, int n_q,
-                 int32_t* d_count, double* d_stats, double* d_order, hipStream_t s) {
-  typedef typename median_key<T>::type K;
-  if (m == 0) return MG_OK;
+// MEDIAN: d_order is the (m, n_c, n_t) medians, and d_count, d_stats, qs are not looked at.
+template <bool MEDIAN>
+int launch_stats(const void* d_roi, int dtype, const MgMaskView& mask, int m, int n_c, int n_t, int len, const StatsQ& qs,
+                 int n_q, int32_t* d_count, double* d_stats, double* d_order, void* stream) {
   const int n = len * len, n_ct = n_c * n_t;
-  const dim3 grid((unsigned)((int64_t)m * n_ct));
-  if (keys_fit(n, sizeof(K)))
-    hipLaunchKernelGGL((k_masked_stats<T, true, MEDIAN>), grid, dim3(NT), (size_t)n * sizeof(K), s, (const T*)d_roi, mask.p,
-                       mask.stride_m, mask.stride_t, n_t, n_ct, n, qs, n_q, d_count, d_stats, d_order);
-  else
-    hipLaunchKernelGGL((k_masked_stats<T, false, MEDIAN>), grid, dim3(NT), 0, s, (const T*)d_roi, mask.p, mask.stride_m,
-                       mask.stride_t, n_t, n_ct, n, qs, n_q, d_count, d_stats, d_order);
-  MG_CHECK_LAUNCH();
-  return MG_OK;
+  hipStream_t s = mg_stream(stream);
+  return mg_windows_launch(dtype, m, n_ct, [&](auto t, dim3 grid, dim3 block) {
+    typedef decltype(t) T;
+    typedef typename median_key<T>::type K;
+    if (keys_fit(n, sizeof(K)))
+      hipLaunchKernelGGL((k_masked_stats<T, true, MEDIAN>), grid, block, (size_t)n * sizeof(K), s, (const T*)d_roi, mask.p,
+                         mask.stride_m, mask.stride_t, n_t, n_ct, n, qs, n_q, d_count, d_stats, d_order);
+    else
+      hipLaunchKernelGGL((k_masked_stats<T, false, MEDIAN>), grid, block, 0, s, (const T*)d_roi, mask.p, mask.stride_m,
+                         mask.stride_t, n_t, n_ct, n, qs, n_q, d_count, d_stats, d_order);
+  });
 }
 
-// What both entry points refuse: one workgroup a window, pixel indices are int.
+// What both entry points refuse beyond mg_windows_check: no roi, no mask (every other window entry takes a null
+// mask), and more than 2^31 - 1 windows a marker -- n_ct is an int in the kernel.
 bool windows_ok(const void* d_roi, const MgMaskView& mask, int m, int n_c, int n_t, int len) {
-  return d_roi && mg_mask_view_ok(mask) && m >= 0 && n_c > 0 && n_t > 0 && len > 0 && len <= MG_ROISTATS_MAX_LEN &&
-         (int64_t)n_c * n_t <= INT32_MAX && (int64_t)m * n_c * n_t <= INT32_MAX;
+  return d_roi && mask.p && (int64_t)n_c * n_t <= INT32_MAX &&
+         mg_windows_check(m, n_c, n_t, len, MG_ROISTATS_MAX_LEN, {mask.stride_m, mask.stride_t});
 }
 
 }  // namespace
@@ -260,16 +240,9 @@ extern "C" int mg_roi_masked_stats(const void* d_roi, int dtype, const uint8_t* 
                                    int32_t* d_count, double* d_stats, double* d_order, void* stream) {
   const MgMaskView mask = {d_mask, mask_stride_m, mask_stride_t};
   if (!windows_ok(d_roi, mask, m, n_c, n_t, roi_len) || !d_count || !d_stats) return MG_EINVAL;
-  if (n_q < 0 || n_q > MG_ROISTATS_MAX_Q || (n_q > 0 && (!q || !d_order))) return MG_EINVAL;
   StatsQ qs = {};
-  for (int j = 0; j < n_q; ++j) {
-    if (!(q[j] >= 0.0 && q[j] <= 1.0)) return MG_EINVAL;  // (NaN fails both)
-    qs.q[j] = q[j];
-  }
-  hipStream_t s = mg_stream(stream);
-  return mg_dispatch_pixel(dtype, [&](auto t) {
-    return launch_stats<decltype(t), false>(d_roi, mask, m, n_c, n_t, roi_len, qs, n_q, d_count, d_stats, d_order, s);
-  });
+  if (!mg_fractions(q, n_q, MG_ROISTATS_MAX_Q, qs.q) || (n_q > 0 && !d_order)) return MG_EINVAL;
+  return launch_stats<false>(d_roi, dtype, mask, m, n_c, n_t, roi_len, qs, n_q, d_count, d_stats, d_order, stream);
 }
 
 extern "C" int mg_roi_masked_median(const void* d_roi, int dtype, const uint8_t* d_mask, int64_t mask_stride_m,
@@ -277,8 +250,5 @@ extern "C" int mg_roi_masked_median(const void* d_roi, int dtype, const uint8_t*
                                     void* stream) {
   const MgMaskView mask = {d_mask, mask_stride_m, mask_stride_t};
   if (!windows_ok(d_roi, mask, m, n_c, n_t, roi_len) || !d_median) return MG_EINVAL;
-  hipStream_t s = mg_stream(stream);
-  return mg_dispatch_pixel(dtype, [&](auto t) {
-    return launch_stats<decltype(t), true>(d_roi, mask, m, n_c, n_t, roi_len, StatsQ{}, 0, nullptr, nullptr, d_median, s);
-  });
+  return launch_stats<true>(d_roi, dtype, mask, m, n_c, n_t, roi_len, StatsQ{}, 0, nullptr, nullptr, d_median, stream);
 }

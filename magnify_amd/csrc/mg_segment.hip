@@ -8,15 +8,15 @@
 // no row padding): a wave's ballot over 64 consecutive pixels IS two words of the plane, and a 3x3 step is two passes
 // over the words -- left / right neighbours are the string shifted by one bit under a column mask, upper / lower
 // neighbours the string shifted by L bits (a funnel shift of two words).  Integer histogram, integer prefix sums, a
-// total order in the arg-max: nothing depends on the order in which threads arrive.
-#include "mg_common.h"
+// total order in the arg-max: nothing depends on the order in which threads arrive.  The entry stands in mg_windows.h's
+// frame (check, launch); the pixel loop is the kernel's own (for_each_pixel: one plane, no mask, a pixel a lane -- on
+// the chunk walk of mg_windows.h the uint8 instance took 92 VGPRs for 44).
+#include "mg_windows.h"
 
 namespace {
 
-constexpr int NT = 256, WV = NT / 64;
-static_assert(WV == MG_FOLD_WAVES, "mg_block_fold folds four waves");
+constexpr int NT = MG_WINDOW_THREADS, WV = MG_WINDOW_WAVES;
 constexpr int HIST_COPIES = 4;  // a power of two
-constexpr double QNAN = __builtin_nan("");
 
 // the bit planes of a window, each `words` 32-bit words (an even number: ballots are stored as 64-bit pairs)
 enum Plane { P_ON, P_OPEN, P_FG, P_TMP, P_FG0, P_BG0, P_ALLOWED, P_NOTFIRST, P_NOTLAST, P_VALID, N_PLANES };
@@ -61,19 +61,19 @@ __device__ __forceinline__ void pack_bytes(const uint8_t* const (&src)[COUNT], i
   }
 }
 
-// f(p, v[p]) for the pixels p = threadIdx.x, + NT, ... of a window, PIXELS_IN_FLIGHT loads issued before the first use
-constexpr int PIXELS_IN_FLIGHT = 8;
+// f(p, v[p]) for the pixels p = threadIdx.x, + NT, ... of a window, PIXEL_LOADS loads issued before the first use
+constexpr int PIXEL_LOADS = 8;
 template <typename T, class F>
 __device__ __forceinline__ void for_each_pixel(const T* __restrict__ v, int n, F&& f) {
-  for (int p0 = threadIdx.x; p0 < n; p0 += NT * PIXELS_IN_FLIGHT) {
-    T x[PIXELS_IN_FLIGHT];
+  for (int p0 = threadIdx.x; p0 < n; p0 += NT * PIXEL_LOADS) {
+    T x[PIXEL_LOADS];
 #pragma unroll
-    for (int u = 0; u < PIXELS_IN_FLIGHT; ++u) {
+    for (int u = 0; u < PIXEL_LOADS; ++u) {
       const int p = p0 + u * NT;
       x[u] = p < n ? v[p] : T(0);
     }
 #pragma unroll
-    for (int u = 0; u < PIXELS_IN_FLIGHT; ++u) {
+    for (int u = 0; u < PIXEL_LOADS; ++u) {
       const int p = p0 + u * NT;
       if (p < n) f(p, x[u]);
     }
@@ -180,7 +180,7 @@ __global__ __launch_bounds__(NT) void k_threshold_masks(SegArgs a) {
   const bool flat = !(range > 0.0) || !(range < INFINITY);  // no pixels: -inf; an infinity among them: inf or NaN
 
   bool segmented = false;
-  double thr = QNAN;
+  double thr = MG_QNAN;
   if (!flat) {  // block-uniform
     // 2. bins (to_uint8's order of operations), as bytes; with a numeric threshold the "bin" is the comparison itself
     // (the histogram in HIST_COPIES interleaved copies, a lane's copy by its number: a background that fills a few
@@ -332,8 +332,8 @@ extern "C" int mg_roi_threshold_masks(const void* d_roi, int dtype, int64_t stri
   const MgMaskView allowed = {d_allowed, al_stride_m, al_stride_t};  // (no pointer: no such mask; its strides still count)
   if (!d_roi || !mg_mask_view_ok(fg0) || !mg_mask_view_ok(bg0) || !d_fg || !d_bg || !d_threshold || !d_counts || !d_segmented)
     return MG_EINVAL;
-  if (m < 0 || n_t <= 0 || roi_len < 1 || roi_len > MG_SEGMENT_MAX_LEN || (int64_t)m * n_t > INT32_MAX) return MG_EINVAL;
-  if (stride_m < 0 || stride_t < 0 || al_stride_m < 0 || al_stride_t < 0) return MG_EINVAL;
+  if (!mg_windows_check(m, 1, n_t, roi_len, MG_SEGMENT_MAX_LEN, {stride_m, stride_t, al_stride_m, al_stride_t}))
+    return MG_EINVAL;
   if (open_radius < 0 || open_radius > MG_SEGMENT_MAX_OPEN || max_grow < 0 || max_grow > MG_SEGMENT_MAX_GROW ||
       bg_guard < 0 || bg_guard > MG_SEGMENT_MAX_GUARD || min_area < 0)
     return MG_EINVAL;
@@ -343,12 +343,8 @@ extern "C" int mg_roi_threshold_masks(const void* d_roi, int dtype, int64_t stri
                d_segmented};
   const int n = roi_len * roi_len, words = 2 * ((n + 63) / 64);
   const size_t lds = (size_t)N_PLANES * words * 4 + (size_t)n;
-  const dim3 grid((unsigned)((int64_t)m * n_t));
   hipStream_t s = mg_stream(stream);
-  return mg_dispatch_pixel(dtype, [&](auto t) {  // (any other dtype code: MG_EINVAL, with or without markers)
-    if (m == 0) return (int)MG_OK;
-    hipLaunchKernelGGL((k_threshold_masks<decltype(t)>), grid, dim3(NT), lds, s, a);
-    MG_CHECK_LAUNCH();
-    return (int)MG_OK;
+  return mg_windows_launch(dtype, m, n_t, [&](auto t, dim3 grid, dim3 block) {
+    hipLaunchKernelGGL((k_threshold_masks<decltype(t)>), grid, block, lds, s, a);
   });
 }

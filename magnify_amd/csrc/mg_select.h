@@ -1,6 +1,8 @@
 // Exact order statistics: the order-preserving key of a pixel (k_masked_stats in mg_roistats.hip, pc_key in
-// mg_percentile.hip) and the byte-wise radix select over the keys of a window, wherever they lie.  And the chunk loader
-// of the kernels that stream whole ROI windows (k_masked_stats, k_radial_profile in mg_profile.hip).
+// mg_percentile.hip), the byte-wise radix select over the keys of a window, wherever they lie (select_kth), the next
+// key up from a selected one (next_above) and the walk over a list of fractions that both quantile kernels take
+// (order_pairs: k_masked_stats, k_unmix_stats in mg_unmix.hip).  What the kernels that stream whole ROI windows share
+// beyond that is mg_windows.h.
 #pragma once
 #include "mg_common.h"
 
@@ -45,54 +47,6 @@ template <> struct median_key<double> {
   }
 };
 
-// A chunk as it comes from memory: VW pixels (16 bytes of them, or one) and their mask bytes, byte j in mw[j / 4].
-// Pixels beyond the window have mask byte 0.  MASKED = false: there is no mask to read, every pixel of the window has
-// byte 1.
-template <typename T, int VW>
-struct RawChunk {
-  T px[VW];
-  uint32_t mw[4];
-};
-// VW (2, 4, 8 or 16) bytes from p, which is aligned to VW, as one load: byte j in w[j / 4].
-template <int VW>
-__device__ __forceinline__ void load_bytes(const uint8_t* p, uint32_t* w) {
-  if constexpr (VW == 16) {
-    const uint4 t = *reinterpret_cast<const uint4*>(p);
-    w[0] = t.x, w[1] = t.y, w[2] = t.z, w[3] = t.w;
-  } else if constexpr (VW == 8) {
-    const uint2 t = *reinterpret_cast<const uint2*>(p);
-    w[0] = t.x, w[1] = t.y;
-  } else if constexpr (VW == 4) {
-    w[0] = *reinterpret_cast<const uint32_t*>(p);
-  } else {
-    w[0] = *reinterpret_cast<const uint16_t*>(p);
-  }
-}
-template <typename T, int VW, bool MASKED = true>
-__device__ __forceinline__ RawChunk<T, VW> fetch(const T* __restrict__ v, const uint8_t* __restrict__ mask, int n, int c,
-                                                 int end) {
-  RawChunk<T, VW> r = {};
-  if (c >= end) return r;
-  if (VW > 1 && (c + 1) * VW <= n) {
-    const uint4 bits = *reinterpret_cast<const uint4*>(v + (int64_t)c * VW);
-    __builtin_memcpy(r.px, &bits, 16);
-    const uint8_t* mp = mask + (int64_t)c * VW;
-    if constexpr (!MASKED) {
-#pragma unroll
-      for (int j = 0; j < VW; j += 4) r.mw[j >> 2] = VW >= 4 ? 0x01010101u : 0x0101u;
-    } else {
-      load_bytes<VW>(mp, r.mw);
-    }
-  } else {  // VW = 1, or the window's last, partial chunk
-#pragma unroll
-    for (int j = 0; j < VW; ++j) {
-      const int p = c * VW + j;
-      if (p < n) r.px[j] = v[p], r.mw[j >> 2] |= (uint32_t)(MASKED ? mask[p] : (uint8_t)1) << (8 * (j & 3));
-    }
-  }
-  return r;
-}
-
 // The k-th smallest (0-based) of the keys of `count` items: one 256-bin histogram per key byte, most significant first,
 // only the keys that share the prefix found so far take part.  key_at(i, &key) gives the key of item i, false where it
 // has none (masked out, NaN); k < the number of items that have one.  The bin that holds the rank is picked by wave 0:
@@ -136,6 +90,55 @@ __device__ __forceinline__ K select_kth(int count, KeyAt key_at, int k, uint32_t
     rank = s_pick[1];
   }
   return prefix;
+}
+
+// sorted[rank + 1] from below = sorted[rank], in one pass over the items instead of one pass per key byte: `below`
+// again where more than rank + 1 keys are <= it, else the smallest key above it (there is one: rank + 1 < the number of
+// items that have a key).  each(see) calls see(key) for every key of this thread's items, wherever the kernel keeps
+// them -- a kernel with two key sources has its two loops there, in front of one pair of folds.  Called by all
+// MG_SELECT_THREADS threads (mg_block_fold synchronises); the same key in every thread.
+template <typename K, class Each>
+__device__ __forceinline__ K next_above(K below, int rank, Each each) {
+  int le = 0;
+  K above = ~(K)0;
+  each([&](K key) {
+    if (key <= below) ++le;
+    else above = key < above ? key : above;
+  });
+  const int le_all = mg_block_fold(le, [](int a, int b) { return a + b; });
+  const K above_all = mg_block_fold(above, [](K a, K b) { return a < b ? a : b; });
+  return le_all > rank + 1 ? below : above_all;
+}
+
+// NaN in the 2 n_q places of a window's order statistics: nothing takes part.  Called by all threads.
+__device__ __forceinline__ void order_pairs_of_none(int n_q, double* order) {
+  for (int i = threadIdx.x; i < 2 * n_q; i += MG_SELECT_THREADS) order[i] = MG_QNAN;
+}
+
+// sorted[lo], sorted[hi] of every fraction q[j], j < n_q, of `count` keys of pixel type T, as values: pos =
+// (count - 1) q, lo = the floor of pos, hi = min(lo + 1, count - 1); order[2 j] and order[2 j + 1], written by thread
+// 0, NaN in all 2 n_q where count is 0 (order_pairs_of_none).  select(rank) gives sorted[rank]; next(below, rank)
+// gives sorted[rank + 1] from below = sorted[rank] -- next_above, or a second select.  The last rank found is kept:
+// hi of one q is often lo of the next, or lo itself.  Called by all threads with block-uniform arguments (select and
+// next synchronise).
+template <typename T, class Select, class Next>
+__device__ __forceinline__ void order_pairs(int count, const double* q, int n_q, Select select, Next next, double* order) {
+  typedef typename median_key<T>::type K;
+  if (count == 0) return order_pairs_of_none(n_q, order);
+  int have_rank = -1;
+  K have_key = 0;
+  for (int j = 0; j < n_q; ++j) {
+    const double pos = (double)(count - 1) * q[j];
+    const int lo = (int)floor(pos), hi = min(lo + 1, count - 1);
+    if (lo != have_rank) have_key = select(lo);
+    const K key_lo = have_key;
+    if (hi != lo) have_key = next(key_lo, lo);
+    have_rank = hi;
+    if (threadIdx.x == 0) {
+      order[2 * j] = median_key<T>::value(key_lo);
+      order[2 * j + 1] = median_key<T>::value(have_key);
+    }
+  }
 }
 
 }  // namespace

@@ -11,8 +11,9 @@
 // in LDS depends on timing; nothing that is written out does: sums never come from LDS and a selection does not care
 // for the order of its items.  The order statistics are the radix select of mg_select.h over the order-preserving keys
 // of the kept volumes, the ratios formed from them on the way -- eight passes for sorted[lo], one more for
-// sorted[lo + 1]: the smallest key above it, unless lo + 2 keys or more are not above it.  A window with more masked
-// pixels computes every value again from global memory in each pass, by the same operations, so the bits are the same.
+// sorted[lo + 1] (next_above; the walk over the fractions is order_pairs, both mg_select.h's).  A window with more
+// masked pixels computes every value again from global memory in each pass, by the same operations, so the bits are the
+// same.  The entry stands in mg_windows.h's frame (check, fractions, launch).
 //
 // mg_unmix_planes: a streaming kernel, four pixels a thread, one vector load per used channel and one float4 store per
 // output plane where the planes' addresses allow, pixel by pixel otherwise and for the last hw % 4 pixels.
@@ -21,15 +22,13 @@
 // L*L + n_fg n_k sizeof(T) bytes per window at most and then make 8 passes over LDS per selected rank: LDS and barrier
 // latency, not memory, set their time.
 #include "mg_planes.h"
-#include "mg_select.h"
+#include "mg_windows.h"
 
 namespace {
 
-constexpr int NT = MG_SELECT_THREADS, WV = NT / 64;
+constexpr int NT = MG_WINDOW_THREADS, WV = MG_WINDOW_WAVES;
 constexpr int K_MAX = MG_UNMIX_MAX_CHANNELS, LN_MAX = MG_UNMIX_MAX_LN, Q_MAX = MG_UNMIX_MAX_Q, D_MAX = 2 * LN_MAX - 1;
 constexpr int GROUP = 4;  // channels whose loads are issued before the first is used
-constexpr double QNAN = __builtin_nan("");
-static_assert(WV == 4, "the waves' partials are added out for four waves");
 
 // What both kernels know of the unmixing: the table, the used channels, the constant offsets (planes) and the fractions
 // (statistics).  A kernel argument: its entries are read with uniform indices, as scalar loads.
@@ -145,12 +144,6 @@ __global__ __launch_bounds__(NT) void k_unmix_stats(const T* __restrict__ d_roi,
   const int n_masked = s_next;
   const bool in_lds = n_masked <= cap;  // block-uniform
   for (int d = 0; d < D; ++d) {
-    const int count = s_count[d];
-    double* order = d_order + (out + d) * n_q * 2;
-    if (count == 0) {  // block-uniform
-      for (int i = threadIdx.x; i < 2 * n_q; i += NT) order[i] = QNAN;
-      continue;
-    }
     const bool ratio = d >= n_ln;
     const int k = ratio ? d - n_ln + 1 : d;
     // the key of item i: of kept pixel i, or of pixel i of the window -- false where it has none (masked out, NaN)
@@ -174,42 +167,20 @@ __global__ __launch_bounds__(NT) void k_unmix_stats(const T* __restrict__ d_roi,
       if (in_lds) return select_kth<uint64_t, 8>(n_masked, kept_key, rank, hist, s_pick);
       return select_kth<uint64_t, 8>(n, pixel_key, rank, hist, s_pick);
     };
-    // sorted[rank + 1] from below = sorted[rank], in one pass instead of eight: `below` again where more than
-    // rank + 1 keys are <= it, else the smallest key above it (there is one: rank + 1 < count)
-    auto next_up = [&](uint64_t below, int rank) -> uint64_t {
-      int le = 0;
-      uint64_t above = ~0ull;
-      auto see = [&](uint64_t key) {
-        if (key <= below) ++le;
-        else above = key < above ? key : above;
-      };
-      uint64_t key;
-      if (in_lds) {
-        for (int i = threadIdx.x; i < n_masked; i += NT)
-          if (kept_key(i, &key)) see(key);
-      } else {
-        for (int p = threadIdx.x; p < n; p += NT)
-          if (pixel_key(p, &key)) see(key);
-      }
-      const int le_all = mg_block_fold(le, [](int a, int b) { return a + b; });
-      const uint64_t above_all = mg_block_fold(above, [](uint64_t a, uint64_t b) { return a < b ? a : b; });
-      return le_all > rank + 1 ? below : above_all;
+    auto next = [&](uint64_t below, int rank) -> uint64_t {
+      return next_above<uint64_t>(below, rank, [&](auto see) {
+        uint64_t key;
+        if (in_lds) {
+          for (int i = threadIdx.x; i < n_masked; i += NT)
+            if (kept_key(i, &key)) see(key);
+        } else {
+          for (int p = threadIdx.x; p < n; p += NT)
+            if (pixel_key(p, &key)) see(key);
+        }
+      });
     };
-    // sorted[lo], sorted[hi] of every q, as k_masked_stats has them
-    int have_rank = -1;  // the last rank found, kept: hi of one q is often lo of the next
-    uint64_t have_key = 0;
-    for (int j = 0; j < n_q; ++j) {
-      const double pos = (double)(count - 1) * u.q[j];
-      const int lo = (int)floor(pos), hi = min(lo + 1, count - 1);
-      if (lo != have_rank) have_key = select(lo);  // block-uniform
-      const uint64_t key_lo = have_key;
-      if (hi != lo) have_key = next_up(key_lo, lo);
-      have_rank = hi;
-      if (threadIdx.x == 0) {
-        order[2 * j] = median_key<double>::value(key_lo);
-        order[2 * j + 1] = median_key<double>::value(have_key);
-      }
-    }
+    // sorted[lo], sorted[hi] of every q -- NaN where the derived value has no item -- as k_masked_stats has them
+    order_pairs<double>(s_count[d], u.q, n_q, select, next, d_order + (out + d) * n_q * 2);
   }
 }
 
@@ -305,27 +276,17 @@ extern "C" int mg_roi_unmix_stats(const void* d_roi, int dtype, const uint8_t* d
                                   const double* matrix, int n_ln, const double* d_offset, const double* q, int n_q,
                                   int32_t* d_count, double* d_sum, double* d_order, void* stream) {
   if (!d_roi || !d_count || !d_sum) return MG_EINVAL;
-  if (m < 0 || n_c <= 0 || n_t <= 0 || roi_len <= 0 || roi_len > MG_UNMIX_MAX_LEN) return MG_EINVAL;
-  if (mask_stride_m < 0 || mask_stride_t < 0) return MG_EINVAL;
-  if (n_q < 0 || n_q > Q_MAX || (n_q > 0 && (!q || !d_order))) return MG_EINVAL;
+  if (!mg_windows_check(m, n_c, n_t, roi_len, MG_UNMIX_MAX_LEN, {mask_stride_m, mask_stride_t})) return MG_EINVAL;
   Unmix u;
   if (!unmix_table(channels, n_k, matrix, n_ln, n_c, &u)) return MG_EINVAL;
-  for (int j = 0; j < n_q; ++j) {
-    if (!(q[j] >= 0.0 && q[j] <= 1.0)) return MG_EINVAL;  // (NaN fails both)
-    u.q[j] = q[j];
-  }
-  const int D = 2 * n_ln - 1;
-  if ((int64_t)m * n_t * D > INT32_MAX || (int64_t)m * n_c * n_t > INT32_MAX) return MG_EINVAL;
+  if (!mg_fractions(q, n_q, Q_MAX, u.q) || (n_q > 0 && !d_order)) return MG_EINVAL;
+  if ((int64_t)m * n_t * (2 * n_ln - 1) > INT32_MAX) return MG_EINVAL;
+  const int n = roi_len * roi_len, cap = (int)keep_cap(n_ln), kept = n < cap ? n : cap;
   hipStream_t s = mg_stream(stream);
-  return mg_dispatch_pixel(dtype, [&](auto t) {
+  return mg_windows_launch(dtype, m, n_t, [&](auto t, dim3 grid, dim3 block) {
     typedef decltype(t) T;
-    if (m == 0) return MG_OK;
-    const int n = roi_len * roi_len, cap = (int)keep_cap(n_ln), kept = n < cap ? n : cap;
-    hipLaunchKernelGGL(k_unmix_stats<T>, dim3((unsigned)((int64_t)m * n_t)), dim3(NT), (size_t)kept * n_ln * 8, s,
-                       (const T*)d_roi, d_mask, mask_stride_m, mask_stride_t, d_offset, u, n_q, n_c, n_t, n, cap, kept,
-                       d_count, d_sum, d_order);
-    MG_CHECK_LAUNCH();
-    return MG_OK;
+    hipLaunchKernelGGL(k_unmix_stats<T>, grid, block, (size_t)kept * n_ln * 8, s, (const T*)d_roi, d_mask, mask_stride_m,
+                       mask_stride_t, d_offset, u, n_q, n_c, n_t, n, cap, kept, d_count, d_sum, d_order);
   });
 }
 

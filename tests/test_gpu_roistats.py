@@ -269,6 +269,71 @@ def test_every_shape_of_q(hp, q):
         check(hp, roi, ref.mask_set(M, T, L, rng), q, what=f"{np.dtype(dtype).name} q={q}")
 
 
+def tie_fractions(n, n_low):
+    """16 fractions for a window of n survivors whose n_low smallest are equal and smaller than the next: 0 and 1, a
+    repeated one, two neighbours (hi of the first is lo of the second), one whose pos is an integer, the two ranks on
+    either side of the step from the lowest value to the next, and some in no order.  Held to ``ref.ranks`` here."""
+    d = np.float64(n - 1)
+    k = n // 2
+    whole = next(j for j in range(1, n - 1) if d * np.float64(j / d) == j)
+    q = [0.75, 0, (k + 0.5) / d, (k + 1.5) / d, 0.3, 0.3, 1, whole / d, (n_low - 0.5) / d, (n_low - 1.5) / d,
+         0.998, 0.01, 0.5, 0.25, 0.125, 0.6]
+    lo, hi = ref.ranks(n, q)
+    assert len(q) == 16 and q[4] == q[5] and hi[2] == lo[3] == k + 1 and lo[2] == k
+    assert d * np.float64(q[7]) == whole == lo[7]
+    assert (lo[8], hi[8]) == (n_low - 1, n_low) and (lo[9], hi[9]) == (n_low - 2, n_low - 1)
+    return tuple(q)
+
+
+@pytest.mark.parametrize("L,in_lds", [(8, True), (79, False)])
+def test_ties_at_every_rank(hp, L, in_lds):
+    """The walk over the fractions where sorted[lo + 1] is sorted[lo] again and where it is the next value up: float64
+    windows under a full mask, keys in LDS (L = 8) and selected from global memory (L = 79).  Marker 0: three distinct
+    values (timepoint 0 with a known number of the lowest, so that two fractions straddle the step; timepoint 1 drawn);
+    marker 1: constant; marker 2: all NaN but one pixel (timepoint 0) and but two (timepoint 1) -- counts of exactly 1
+    and 2 under the full mask.  Every output against the oracle, the order statistics for equality."""
+    assert hp.masked_stats_keys_in_lds(np.float64, L) == in_lds
+    m, c, t, n = 3, 1, 2, L * L
+    rng = np.random.default_rng(L)
+    values = np.array([-2.5, 0.0, 7.25])
+    n_low = n // 3 + 1
+    roi = np.empty((m, c, t, n), dtype=np.float64)
+    roi[0, 0, 0] = rng.permutation(np.concatenate([np.full(n_low, values[0]), rng.choice(values[1:], n - n_low)]))
+    roi[0, 0, 1] = rng.choice(values, n)
+    roi[1] = 3.75
+    roi[2] = np.nan
+    roi[2, 0, 0, n // 2] = 1.5
+    roi[2, 0, 1, [3, n - 1]] = 2.5, -1.5
+    q = tie_fractions(n, n_low)
+    srt = np.sort(roi[0, 0, 0])
+    lo, hi = ref.ranks(n, q)
+    assert (srt[lo] == srt[hi])[hi > lo].any() and (srt[lo] < srt[hi]).any()  # both answers of a next-key-up step
+    count, _, _ = check(hp, roi.reshape(m, c, t, L, L), np.ones((m, t, L, L), dtype=np.uint8), q, what=f"ties L={L}")
+    np.testing.assert_array_equal(count[:, 0], [[n, n], [n, n], [1, 2]])
+
+
+@pytest.mark.parametrize("L,stats_in_lds,unmix_in_lds", [(8, True, True), (90, False, True), (100, False, False)])
+def test_unmix_walks_the_fractions_as_masked_stats_does(hp, L, stats_in_lds, unmix_in_lds):
+    """Both quantile kernels call one walk: with the 1 x 1 matrix [[1.0]] and no offset a volume is the pixel, and
+    mg_roi_unmix_stats gives the count and the bits of every order statistic that mg_roi_masked_stats gives on the same
+    float64 roi, mask and q -- with the keys of both in LDS (L = 8), of unmix only (L = 90), of neither (L = 100, where
+    the mask is full: no other has more masked pixels than unmix keeps)."""
+    m, t = 2, 2
+    rng = np.random.default_rng(L)
+    roi = dev(ref.full_range(np.float64, (m, 1, t, L, L), rng))
+    mask = np.ones((m, t, L, L), dtype=np.uint8) if L == 100 else (rng.random((m, t, L, L)) < 0.5).astype(np.uint8)
+    n_masked = mask.reshape(m, t, -1).sum(axis=-1)
+    assert hp.masked_stats_keys_in_lds(np.float64, L) == stats_in_lds
+    assert all(hp.unmix_keys_in_lds(1, int(k)) == unmix_in_lds for k in n_masked.ravel())
+    q = (0, 0.01, 0.25, 0.5, 0.5, 0.75, 0.998, 1)
+    count, _, order = hp.masked_stats(roi, dev(mask), q)
+    u_count, _, u_order = hp.unmix_stats(roi, dev(mask), np.array([[1.0]]), q=q)
+    assert u_order.shape == (m, t, 1, len(q), 2) and int(count.min()) > 0
+    np.testing.assert_array_equal(u_count.cpu().numpy()[:, :, 0], count.cpu().numpy()[:, 0])
+    np.testing.assert_array_equal(u_order.cpu().numpy()[:, :, 0].view(np.uint64),
+                                  order.cpu().numpy()[:, 0].view(np.uint64))
+
+
 def test_same_bits_on_every_call(hp):
     rng = np.random.default_rng(19)
     for dtype, L in ((np.float32, 33), (np.float64, 79), (np.float64, 16)):
