@@ -460,6 +460,7 @@ int mg_dedup_layout(int h, int w, int min_r, int max_r, int* n_tile_rows, int* n
 #define MG_CANDIDATES_WALK 2048     /* workgroups per plane of the general kernel */
 #define MG_CANDIDATES_TAB_WALK 1024 /* of the table kernel: at most this many per plane ... */
 #define MG_CANDIDATES_TAB_FILL 1024 /* ... and about this many over all planes at least */
+#define MG_CANDIDATES_TAB_RUN 4     /* consecutive iterations a lane of the table kernel takes per trip */
 int mg_candidate_circles(const int32_t* d_coords, int64_t coord_cap, const int32_t* d_cell_starts,
                          const int32_t* d_cell_counts, const int32_t* d_num_edges, int n_planes, int h, int w,
                          int grid, const uint64_t* d_seeds, int64_t num_iter, int min_r, int max_r,

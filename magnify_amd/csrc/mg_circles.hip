@@ -3,7 +3,8 @@
 // on (row, col, r), so candidates are de-duplicated before they are scored.  What this file holds:
 //
 //   candidates   k_candidates_tab (bisectors from an LDS table; the keyed product path) and k_candidates<FAST> (every
-//                other shape, and the bitmap path); both end in circle_from_bisectors / candidate_key
+//                other shape, and the bitmap path); both intersect two bisectors (centre_from_bisectors) and filter the
+//                circle by radius and image (candidate_cell; candidate_key on the squared radius, mg_radius.h)
 //   unique list  keyed: k_tile_dedup -- a workgroup per tile pair collects its 32-bit keys (mg_common.h: mg_key_*) in
 //                LDS layers and emits them sorted;  bitmap: global atomicOr, then k_layer_count / _scan / _emit
 //   scoring      k_score_tiles: a workgroup per centre tile, its edge window in LDS as bits, count-only prefilter, then
@@ -15,7 +16,10 @@
 #include <math.h>
 #include <stdlib.h>
 
+#include <mutex>
+
 #include "mg_common.h"
+#include "mg_radius.h"
 
 namespace {
 
@@ -72,7 +76,9 @@ struct DivFull {
 };
 struct DivUnscaled {
   __device__ __forceinline__ double operator()(double num, double den) const {
-    if (!(fabs(den) > 0.0 && fabs(den) < 1.0e300)) return num / den;  // 0, inf, NaN: the full sequence
+    // 0, denormal, inf, NaN and everything from 2^996 (< 1e300) up take the full sequence: the divisor's exponent
+    // field is in [1, 2018], one unsigned compare on the high dword instead of two float64 compares
+    if ((((uint32_t)__double2hiint(den) & 0x7FFFFFFFu) - 0x00100000u) >= 0x7E200000u) return num / den;
     double y = __builtin_amdgcn_rcp(den);
     double e = fma(-den, y, 1.0);
     y = fma(y, e, y);
@@ -84,13 +90,22 @@ struct DivUnscaled {
   }
 };
 
-// Intersection of two bisectors, each store rounds to float32 (utils.py:337-342): (row, col, radius) in image coordinates.
+// Intersection of two bisectors, each store rounds to float32 (utils.py:337-342): the centre (row, col) in p0-centred
+// coordinates, then (row, col, radius) in image coordinates.
+template <class Div>
+__device__ __forceinline__ float2 centre_from_bisectors(double2 l1, double2 l2, Div div) {
+  const float c_col = (float)div(l1.y - l2.y, l2.x - l1.x + BISECTOR_EPS);
+  return make_float2((float)(l1.x * (double)c_col + l1.y), c_col);
+}
+__device__ __forceinline__ float image_coord(float c, int p0) { return (float)((double)c + (double)p0); }
+// The same float32 for every finite c and |p0| < 2^24, by ONE float32 add: with p0 in [2^k, 2^(k+1)) the
+// float64 sum is exact unless |c| < 2^(k-28), and then either way of rounding gives p0 itself -- the float32 midpoints
+// next to p0 are 2^(k-25) away or more.  (For a NaN the payload may differ: not where the triples are stored.)
+__device__ __forceinline__ float image_coord_f32(float c, int p0) { return c + (float)p0; }
 template <class Div>
 __device__ __forceinline__ float3 circle_from_bisectors(double2 l1, double2 l2, int p0r, int p0c, Div div) {
-  const float c_col = (float)div(l1.y - l2.y, l2.x - l1.x + BISECTOR_EPS);
-  const float c_row = (float)(l1.x * (double)c_col + l1.y);
-  const float rad = sqrtf(c_row * c_row + c_col * c_col);
-  return make_float3((float)((double)c_row + (double)p0r), (float)((double)c_col + (double)p0c), rad);
+  const float2 c = centre_from_bisectors(l1, l2, div);
+  return make_float3(image_coord(c.x, p0r), image_coord(c.y, p0c), sqrtf(c.x * c.x + c.y * c.y));
 }
 
 __device__ __forceinline__ void store_raw(float* __restrict__ d_raw, int64_t index, float3 c) {
@@ -114,6 +129,31 @@ __device__ __forceinline__ void candidate_cell(float3 c, int h, int w, int min_r
   if (ir + irad < 0 || ic + irad < 0 || ir - irad >= h || ic - irad >= w) return;
   const int pr = ir + max_r, pc = ic + max_r;
   emit((pr >> 6) * ntc + (pc >> 6), irad - min_r, pr & 63, pc & 63);
+}
+
+// The same filter as a key, from the squared radius s = fl(fl(c_row^2) + fl(c_col^2)) and a guess of its root
+// (mg_radius.h: no square root where the radius itself is not asked for), for h, w <= 65536.  The on-image tests are
+// made on the rounded floats, which hold the integers they stand for exactly up to 2^24 and are off the image by any
+// compare beyond -- which is also why the |centre| < 1e9 guard of the integer version has no work left (NaN fails
+// every compare, an infinite centre one of them); only what the key holds is converted.
+// a * b + c on operands below 2^24 with a wave-uniform b, full rate.  As assembly: the compiler turns the 24-bit
+// intrinsic back into a 32-bit multiply (quarter rate) where it can fold a shift into it, or spreads the shift that
+// follows over the sum.
+__device__ __forceinline__ uint32_t mad24(uint32_t a, uint32_t b, uint32_t c) {
+  uint32_t d;
+  asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(d) : "v"(a), "s"(b), "v"(c));
+  return d;
+}
+
+__device__ __forceinline__ uint32_t candidate_key(float row, float col, float s, float guess, const MgRadiusTable& rt,
+                                                  const float* t, int h, int w, int ntc) {
+  int layer;
+  const bool in_range = mg_radius_decide(s, guess, rt.lo, rt.hi, t, rt.min_r, rt.max_r, &layer);
+  const float rr = rintf(row), rc = rintf(col), fr = (float)(rt.min_r + layer);
+  // ir + irad >= 0 and ir - irad < h, with the radius on the other side: h + irad is exact, nothing else is rounded
+  if (!(in_range && rr >= -fr && rc >= -fr && rr < (float)h + fr && rc < (float)w + fr)) return MG_NO_KEY;
+  const uint32_t pr = (uint32_t)((int)rr + rt.max_r), pc = (uint32_t)((int)rc + rt.max_r);  // 0 <= pr, pc < 2^17
+  return mg_key_pack((int)mad24(pr >> 6, (uint32_t)ntc, pc >> 6), layer, (int)(pr & 63u), (int)(pc & 63u));
 }
 
 // ---- K7: candidate circles --------------------------------------------------------------------
@@ -204,31 +244,52 @@ __global__ __launch_bounds__(NT) void k_candidates(const int32_t* __restrict__ d
 // Bit-identical to k_candidates<> (test_candidates_degenerate_triplets compares the raw float32 triples and the keys of
 // all three kernels -- grid 20: this one, grid 40: k_candidates<true>, grid 1: k_candidates<false> -- with the
 // oracle's, NaN / inf included).
+//
+// The diet -- what the iteration still spent on things its key does not need:
+//  * a lane takes RUN consecutive iterations a trip: the upper bound of one stratum is the lower bound of the next, the
+//    RNG counter of iteration it + j is a constant away from that of it, the loop's own bookkeeping is paid once per
+//    RUN, and the RUN keys leave as one store -- and the trip goes stage by stage (run_of), so that the gathers of
+//    the run's iterations are in flight together: that, not the instructions, was half of what the diet gained;
+//  * the five gathers address their lists by a 32-bit byte offset from a scalar base (the launcher keeps index * 8
+//    below 2^32) instead of a 64-bit shift and add per lane;
+//  * without raw triples there is no square root: candidate_key decides range and layer from the squared radius;
+//  * the table-index test is one maximum of four and one compare.
 constexpr int CT = 1024;
 constexpr int MAX_TAB_GRID = 32;  // (2 * 32 - 1)^2 * 16 B = 63.5 KB of LDS
+template <int RUN>
+struct KeyRun {  // RUN keys stored at once; aligned like one key
+  uint32_t k[RUN];
+};
 
-__global__ __launch_bounds__(CT) void k_candidates_tab(const int32_t* __restrict__ d_coords, int64_t coord_cap,
+// RAW: the float32 triples are asked for (d_raw), and with them the square root.
+template <int RUN, bool RAW>
+__global__ __launch_bounds__(CT) void k_candidates_tab(const int32_t* __restrict__ d_coords, uint32_t coord_cap,
                                                        const int32_t* __restrict__ d_starts,
                                                        const int32_t* __restrict__ d_counts,
                                                        const int32_t* __restrict__ d_num_edges, int h, int w, int grid,
                                                        int gc, int n_cells, const uint64_t* __restrict__ d_seeds,
-                                                       uint32_t num_iter, int min_r, int max_r,
+                                                       uint32_t num_iter, MgRadiusTable rt,
                                                        float* __restrict__ d_raw, uint32_t* __restrict__ d_keys) {
   extern __shared__ double2 s_tab[];  // [(2 grid - 1)^2]: (m, b) of the bisector of p0 and p0 + (d_row, d_col)
+  __shared__ float s_t[MG_RADIUS_MAX_LAYERS + 1];  // rt.t, where a lane can index it
   const int plane = blockIdx.y;
   const uint32_t n_edges = (uint32_t)d_num_edges[plane];
   if (n_edges == 0) return;
   const int g1 = grid - 1, span = 2 * grid - 1;
   for (int i = threadIdx.x; i < span * span; i += CT) s_tab[i] = bisector(i / span - g1, i - (i / span) * span - g1);
+  if (threadIdx.x <= MG_RADIUS_MAX_LAYERS) s_t[threadIdx.x] = rt.t[threadIdx.x];
   __syncthreads();
-  const int32_t* coords = d_coords + (int64_t)plane * coord_cap * 2;
-  const int32_t* starts = d_starts + (int64_t)plane * n_cells;
-  const int32_t* counts = d_counts + (int64_t)plane * n_cells;
+  // byte offsets below 2^32 (launcher: coord_cap < 2^29, n_cells < 2^30) from plane bases that are wave-uniform
+  const char* coords = reinterpret_cast<const char*>(d_coords + (int64_t)plane * coord_cap * 2);
+  const char* starts = reinterpret_cast<const char*>(d_starts + (int64_t)plane * n_cells);
+  const char* counts = reinterpret_cast<const char*>(d_counts + (int64_t)plane * n_cells);
+  auto point = [&](uint32_t i) { return *reinterpret_cast<const int2*>(coords + (i << 3)); };
   const uint64_t seed = d_seeds[plane];
-  const int ntc = (w + 2 * max_r + 63) >> 6;
-  uint32_t* keys = d_keys ? d_keys + (int64_t)plane * num_iter : nullptr;
+  const int ntc = (w + 2 * rt.max_r + 63) >> 6;
+  uint32_t* keys = d_keys + (int64_t)plane * num_iter;
   const uint32_t K = num_iter;
-  const uint32_t it0 = blockIdx.x * CT + threadIdx.x, stride = gridDim.x * CT;
+  // a lane's trip is the RUN iterations from `it` on; blocks <= 1024 (launcher), K < 2^31: nothing here wraps
+  const uint32_t it0 = (blockIdx.x * CT + threadIdx.x) * RUN, stride = gridDim.x * CT * RUN;
   if (it0 >= K) return;
   // E = eq K + er;  it E = sa K + rem  with  sa = it eq + floor(it er / K),  rem = (it er) mod K
   const uint32_t eq = n_edges / K, er = n_edges - eq * K;
@@ -236,46 +297,85 @@ __global__ __launch_bounds__(CT) void k_candidates_tab(const int32_t* __restrict
   const uint64_t x0 = (uint64_t)it0 * er;                     // < K E < 2^52 (launcher)
   const uint64_t q0 = div_u64(x0, K, inv_k);
   uint32_t sa = it0 * eq + (uint32_t)q0, rem = (uint32_t)(x0 - q0 * K);
-  const uint64_t xs = (uint64_t)stride * er;                  // < 2^20 K
+  // a trip steps (sa, rem) through its RUN iterations one by one; the next trip starts stride - RUN behind them
+  const uint64_t xs = (uint64_t)(stride - RUN) * er;          // < 2^22 K
   const uint64_t qs = div_u64(xs, K, inv_k);
-  const uint32_t sa_step = stride * eq + (uint32_t)qs, rem_step = (uint32_t)(xs - qs * K);
+  const uint32_t sa_step = (stride - RUN) * eq + (uint32_t)qs, rem_step = (uint32_t)(xs - qs * K);
   uint64_t zbase = seed + ((uint64_t)it0 * 3ull + 1ull) * GOLDEN;
   const uint64_t zstep = (uint64_t)stride * 3ull * GOLDEN;
   const uint32_t gmagic = 0xFFFFFFFFu / (uint32_t)grid + 1u;  // exact for operands < 2^16
-  for (uint32_t it = it0; it < K; it += stride, zbase += zstep) {
-    // jittered stratified p0: iteration it owns the slice [sa, sb) of the cell-major edge list
-    const uint32_t sb = sa + eq + (rem + er >= K ? 1u : 0u);  // (rem, er < K < 2^31: no wrap)
-    uint32_t u0 = sa;
-    if (sb > sa + 1u) u0 = sa + __umulhi(mix_top32(zbase), sb - sa);
-    {  // the next iteration's (sa, rem)
+  // The stratum [sa, sb) of the iteration (sa, rem) stands at; moves (sa, rem) on to the next iteration.
+  auto next_stratum = [&]() -> uint32_t {
+    const uint32_t t = rem + er;  // (rem, er < K < 2^31: no wrap)
+    rem = min(t, t - K);          // t - K wraps to something huge exactly when t < K
+    return sa = sa + eq + (t >= K ? 1u : 0u);
+  };
+  // The key of iteration `it` from its three points.
+  auto candidate = [&](uint32_t it, int2 p0, int2 p1, int2 p2) -> uint32_t {
+    // p0-centred integer coordinates (utils.py:319-321), as table indices
+    const int o_r = p0.x - g1, o_c = p0.y - g1;
+    const uint32_t j1r = (uint32_t)(p1.x - o_r), j1c = (uint32_t)(p1.y - o_c);
+    const uint32_t j2r = (uint32_t)(p2.x - o_r), j2c = (uint32_t)(p2.y - o_c);
+    double2 l1, l2;
+    if (max(max(j1r, j1c), max(j2r, j2c)) < (uint32_t)span) {
+      l1 = s_tab[mad24(j1r, (uint32_t)span, j1c)], l2 = s_tab[mad24(j2r, (uint32_t)span, j2c)];
+    } else {  // (cannot happen with a cell-major list made by mg_edge_grid; kept so that no list can index beyond the table)
+      l1 = bisector((int)j1r - g1, (int)j1c - g1), l2 = bisector((int)j2r - g1, (int)j2c - g1);
+    }
+    const float2 c = centre_from_bisectors(l1, l2, DivUnscaled{});
+    const float s = c.x * c.x + c.y * c.y;
+    if (RAW) {  // the triples are asked for, the radius itself among them: the key is decided from it all the same
+      const float3 raw = make_float3(image_coord(c.x, p0.x), image_coord(c.y, p0.y), sqrtf(s));
+      store_raw(d_raw, (int64_t)plane * num_iter + it, raw);
+      return candidate_key(raw.x, raw.y, s, raw.z, rt, s_t, h, w, ntc);
+    }
+    // (1 ulp: a guess is all mg_radius_decide needs)
+    return candidate_key(image_coord_f32(c.x, p0.x), image_coord_f32(c.y, p0.y), s, __builtin_amdgcn_sqrtf(s), rt, s_t, h, w, ntc);
+  };
+  // The N iterations from `it` on, where (sa, rem) and zbase stand; leaves (sa, rem) at it + N.  Stage by stage over
+  // the run, not iteration by iteration: the three gathers of an iteration depend on one another, those of different
+  // iterations do not, and the compiler does not move a load across the branches of the arithmetic -- this way a
+  // lane has N loads in flight at every stage.
+  auto run_of = [&](auto n, uint32_t it, uint32_t* out) {
+    constexpr int N = decltype(n)::value;
+    int2 p0[N], p1[N], p2[N];
+    uint32_t cell[N];
+    uint32_t a = sa;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {  // jittered stratified p0: the iteration owns the slice [a, b) of the edge list
+      const uint32_t b = next_stratum();
+      uint32_t u0 = a;
+      if (b > a + 1u) u0 = a + __umulhi(mix_top32(zbase + (uint64_t)(3 * j) * GOLDEN), b - a);
+      p0[j] = point(u0);
+      a = b;
+    }
+#pragma unroll
+    for (int j = 0; j < N; ++j)  // (cell rows and columns are below 2^16: a 24-bit multiply, full rate)
+      cell[j] = (__umul24(__umulhi((uint32_t)p0[j].x, gmagic), (uint32_t)gc) + __umulhi((uint32_t)p0[j].y, gmagic)) << 2;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      const uint32_t cnt = *reinterpret_cast<const uint32_t*>(counts + cell[j]);
+      const uint32_t base = *reinterpret_cast<const uint32_t*>(starts + cell[j]);
+      const uint64_t z12 = mix64(zbase + (uint64_t)(3 * j + 1) * GOLDEN);
+      p1[j] = point(base + __umulhi((uint32_t)(z12 >> 32), cnt)), p2[j] = point(base + __umulhi((uint32_t)z12, cnt));
+    }
+#pragma unroll
+    for (int j = 0; j < N; ++j) out[j] = candidate(it + j, p0[j], p1[j], p2[j]);
+  };
+  uint32_t it = it0;
+  for (; it + RUN <= K; it += stride, zbase += zstep) {
+    KeyRun<RUN> run;
+    run_of(std::integral_constant<int, RUN>{}, it, run.k);
+    *reinterpret_cast<KeyRun<RUN>*>(keys + it) = run;  // coalesced; k_tile_dedup builds the bitmap tile by tile in LDS
+    {  // the next trip's (sa, rem)
       const uint32_t t = rem + rem_step;
       const bool carry = t >= K;
       sa += sa_step + (carry ? 1u : 0u);
       rem = carry ? t - K : t;
     }
-    const int2 p0 = reinterpret_cast<const int2*>(coords)[u0];
-    const int p0r = p0.x, p0c = p0.y;
-    const int cell = (int)(__umulhi((uint32_t)p0r, gmagic) * (uint32_t)gc + __umulhi((uint32_t)p0c, gmagic));
-    const uint32_t cnt = (uint32_t)counts[cell];
-    const uint32_t base = (uint32_t)starts[cell];
-    const uint64_t z12 = mix64(zbase + GOLDEN);
-    const uint32_t i1 = base + __umulhi((uint32_t)(z12 >> 32), cnt);
-    const uint32_t i2 = base + __umulhi((uint32_t)z12, cnt);
-    const int2 p1 = reinterpret_cast<const int2*>(coords)[i1], p2 = reinterpret_cast<const int2*>(coords)[i2];
-    const int d1r = p1.x - p0r, d1c = p1.y - p0c, d2r = p2.x - p0r, d2c = p2.y - p0c;
-    double2 l1, l2;
-    if ((uint32_t)(d1r + g1) < (uint32_t)span && (uint32_t)(d1c + g1) < (uint32_t)span &&
-        (uint32_t)(d2r + g1) < (uint32_t)span && (uint32_t)(d2c + g1) < (uint32_t)span) {
-      l1 = s_tab[(d1r + g1) * span + d1c + g1], l2 = s_tab[(d2r + g1) * span + d2c + g1];
-    } else {  // (cannot happen with a cell-major list made by mg_edge_grid; kept so that no list can index beyond the table)
-      l1 = bisector(d1r, d1c), l2 = bisector(d2r, d2c);
-    }
-    const float3 c = circle_from_bisectors(l1, l2, p0r, p0c, DivUnscaled{});
-    store_raw(d_raw, ((int64_t)plane * num_iter + it), c);
-    uint32_t key = MG_NO_KEY;
-    candidate_cell(c, h, w, min_r, max_r, ntc, [&](int tile, int layer, int row, int col) { key = mg_key_pack(tile, layer, row, col); });
-    if (keys) keys[it] = key;
   }
+  // the K % RUN iterations behind the last whole run: one lane of the plane, one by one
+  for (; it < K; ++it, zbase += 3ull * GOLDEN) run_of(std::integral_constant<int, 1>{}, it, keys + it);
 }
 
 // ---- K8: bitmap -> ordered unique circle list ---------------------------------------------------
@@ -1314,26 +1414,41 @@ int launch_candidates(const int32_t* d_coords, int64_t coord_cap, const int32_t*
   if (n_planes == 0 || num_iter == 0) return MG_OK;
   const int gr = (h + grid - 1) / grid, gc = (w + grid - 1) / grid;
   const bool fast = num_iter < (1ll << 31) && grid > 1 && h <= 65536 && w <= 65536;
-  // keys from the table kernel (round 4) unless MG_CANDIDATES_V1 is set or the shape is outside its ranges: a grid cell
-  // above 32 (table size; test_candidates_degenerate_triplets[40-*] takes that way), a coordinate list of 2^31 entries
-  static const bool v1 = getenv("MG_CANDIDATES_V1") != nullptr;
-  if (fast && !v1 && d_keys && !d_bitmap && grid <= MAX_TAB_GRID && coord_cap < (1ll << 31)) {
-    // workgroups of 1024 that run ~32 iterations per lane (the table costs each lane 1.5 entries once), but at least
-    // ~1024 of them over all planes so that a single plane still fills the chip
-    const int64_t per_plane = (num_iter + CT - 1) / CT;
+  // keys from the table kernel (round 4) unless MG_CANDIDATES_V1 is set (looked up on every call, as MG_ROI_TILES is)
+  // or the shape is outside its ranges: a grid cell above 32 (table size; test_candidates_degenerate_triplets[40-*]
+  // takes that way), or lists whose byte offsets do not fit 32 bits (2^29 coordinates, 2^30 cells)
+  const bool v1 = getenv("MG_CANDIDATES_V1") != nullptr;
+  if (fast && !v1 && d_keys && !d_bitmap && grid <= MAX_TAB_GRID && coord_cap < (1ll << 29) && (int64_t)gr * gc < (1ll << 30)) {
+    // workgroups of 1024 that run ~32 iterations per lane, MG_CANDIDATES_TAB_RUN of them a trip (the table costs each
+    // lane 1.5 entries once), but at least ~1024 of them over all planes so that a single plane still fills the chip.
+    // The environment's MG_CANDIDATES_TAB_WALK (looked up on every call) can only lower the cap: a test's way to a
+    // second trip at a small size.
+    constexpr int RUN = MG_CANDIDATES_TAB_RUN;
+    int64_t walk = MG_CANDIDATES_TAB_WALK;
+    if (const char* e = getenv("MG_CANDIDATES_TAB_WALK")) walk = std::max<int64_t>(1, std::min<int64_t>(walk, atoll(e)));
+    const int64_t per_plane = (num_iter + CT * RUN - 1) / (CT * RUN);
     int64_t blocks = std::max<int64_t>((num_iter + 32 * CT - 1) / (32 * CT), (MG_CANDIDATES_TAB_FILL + n_planes - 1) / n_planes);
-    blocks = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(blocks, per_plane), MG_CANDIDATES_TAB_WALK));
+    blocks = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(blocks, per_plane), walk));
     const int span = 2 * grid - 1;
-    static bool tab_attr = false;
-    if (!tab_attr) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_candidates_tab), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (2 * MAX_TAB_GRID - 1) * (2 * MAX_TAB_GRID - 1) * (int)sizeof(double2)) != hipSuccess)
-        return MG_ELAUNCH;
-      tab_attr = true;
+    const auto k_candidates_tab_run = d_raw ? k_candidates_tab<RUN, true> : k_candidates_tab<RUN, false>;
+    static std::mutex mu;  // the attribute, and the thresholds of the last (min_r, max_r): a few hundred square roots
+    static bool tab_attr[2] = {false, false};
+    static MgRadiusTable rt = {0.0f, 0.0f, {}, -1, -1};
+    MgRadiusTable table;
+    {
+      std::lock_guard<std::mutex> lock(mu);
+      if (!tab_attr[d_raw != nullptr]) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_candidates_tab_run), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (2 * MAX_TAB_GRID - 1) * (2 * MAX_TAB_GRID - 1) * (int)sizeof(double2)) != hipSuccess)
+          return MG_ELAUNCH;
+        tab_attr[d_raw != nullptr] = true;
+      }
+      if (rt.min_r != min_r || rt.max_r != max_r) mg_radius_table(min_r, max_r, &rt);
+      table = rt;
     }
-    hipLaunchKernelGGL(k_candidates_tab, dim3((unsigned)blocks, n_planes), dim3(CT), (size_t)span * span * sizeof(double2),
-                       mg_stream(stream), d_coords, coord_cap, d_cell_starts, d_cell_counts, d_num_edges, h, w, grid, gc,
-                       gr * gc, d_seeds, (uint32_t)num_iter, min_r, max_r, d_raw, d_keys);
+    hipLaunchKernelGGL(k_candidates_tab_run, dim3((unsigned)blocks, n_planes), dim3(CT), (size_t)span * span * sizeof(double2),
+                       mg_stream(stream), d_coords, (uint32_t)coord_cap, d_cell_starts, d_cell_counts, d_num_edges, h, w, grid, gc,
+                       gr * gc, d_seeds, (uint32_t)num_iter, table, d_raw, d_keys);
     MG_CHECK_LAUNCH();
     return MG_OK;
   }
