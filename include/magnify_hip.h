@@ -1289,6 +1289,68 @@ int mg_background_planes(const void* d_src, const void* d_filtered, void* d_dst,
 int mg_skew_profiles(const void* d_plane, int dtype, int h, int w, int64_t row_stride, double lo, double scale,
                      const int32_t* d_cs, int n_angles, uint64_t* d_sums, uint32_t* d_counts, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Blobs (blobs.py, `find_blobs`; not in the reference; tests/blobs_ref.py restates every rule):
+ * connected components of a thresholded plane as markers of any shape.  Integer arithmetic only; every output is the
+ * same bits from call to call.
+ *
+ * mg_blob_labels.  d_plane: one contiguous (h, w) plane of `dtype`.  A pixel v is ON iff (double)v > threshold, with
+ *   `below` iff (double)v < threshold; NaN is never on.  connectivity is 4 or 8.
+ *   d_labels int32 (h, w): -1 where off, else the component's number 0 .. K-1; components are numbered in raster order
+ *     of their first pixel (smallest y * w + x), the order of scipy.ndimage.label.
+ *   d_num int32: K.
+ *   d_stats int64 [cap][8] = {area, sum_y, sum_x, y_min, x_min, y_max, x_max, first_pixel}; rows 0 .. min(K, cap) - 1
+ *     are written, the others are left alone.
+ *   d_status int32: 0, or MG_BLOB_OVERFLOW (K > cap: d_num holds K, d_labels is complete, d_stats holds the first cap
+ *     components) | MG_BLOB_EBOUND (a bounded loop ran out: an internal error, no output is to be trusted).
+ *   d_scratch: mg_blob_scratch_bytes(h, w, cap) bytes owned by the caller, 16-byte aligned; its contents before the call
+ *     do not matter, and d_num / d_status are re-initialised by the call: a call after a larger plane, or after a call
+ *     that overflowed, is correct.
+ *   Launches (no workgroup ever waits for another): clear; tile pass (one workgroup labels a MG_BLOB_TILE_H x
+ *   MG_BLOB_TILE_W tile in LDS and writes, per on pixel, the linear index of the smallest pixel of its component inside
+ *   the tile); seam pass (unions across the tile borders on that parent array, agent-scope atomics only); compress and
+ *   count roots; one-workgroup scan of the counts; number the roots; flatten and statistics.  Every grid is sized by the
+ *   tile / pixel count, none is capped.
+ *   MG_EINVAL, with nothing launched: a null pointer, an unknown dtype, h or w < 1, h * w beyond int32, a
+ *   connectivity other than 4 or 8, cap < 1, a NaN threshold, scratch_bytes below mg_blob_scratch_bytes, a misaligned
+ *   d_scratch or d_stats.  No allocation, no synchronisation.
+ *
+ * mg_blob_select.  Component k < K = min(*d_num, cap) is kept iff min_area <= area, area <= max_area where
+ *   max_area > 0, and, with clear_border, y_min > 0, x_min > 0, y_max < h - 1 and x_max < w - 1.  The kept components
+ *   are renumbered 0 .. M-1 in their order; d_labels is rewritten in place (kept: the new number, rejected: -2,
+ *   off: -1).  d_num_kept int32: M.  d_stats_out int64 [cap][8]: the kept rows, compacted (must not overlap d_stats).
+ *   d_table int32 [cap][3] = {row, col, r}: row = floor((2 sum_y + area) / (2 area)), col likewise from sum_x, and
+ *   r = the largest integer with 355 (2 r - 1)^2 <= 452 area: the nearest integer to sqrt(area / pi) with pi taken as
+ *   355 / 113.  d_remap int32 [cap]: workspace.  Two launches.  MG_EINVAL: null pointers, h, w as above, cap < 1,
+ *   negative areas.
+ *
+ * mg_blob_fill_holes.  d_clabels / d_cstats: labels and statistics of the COMPLEMENT of the mask (mg_blob_labels with
+ *   connectivity 4 and the opposite polarity).  Every pixel of a complement component whose bounding box touches no side
+ *   of the frame is set to 1 in d_on u8 (h, w): scipy.ndimage.binary_fill_holes with its default structure.  One launch.
+ *   d_cstats has `cap` rows (the complement's component count, or fewer): a pixel whose number is >= cap is left alone,
+ *   no row beyond cap is read.  MG_EINVAL, with nothing launched: a null pointer, h or w < 1, h * w beyond int32,
+ *   cap < 1.
+ *
+ * mg_blob_threshold.  The on mask of mg_blob_labels alone, for the same plane, threshold and `below`: d_on u8 (h, w),
+ *   1 where on, 0 where off.  One launch.  MG_EINVAL, with nothing launched: a null or misaligned pointer, an unknown
+ *   dtype, h or w < 1, h * w beyond int32, a NaN threshold.
+ * ---------------------------------------------------------------------------------- */
+#define MG_BLOB_TILE_H 32
+#define MG_BLOB_TILE_W 64
+#define MG_BLOB_OVERFLOW 1
+#define MG_BLOB_EBOUND 2
+int64_t mg_blob_scratch_bytes(int h, int w, int64_t cap);
+int mg_blob_labels(const void* d_plane, int dtype, int h, int w, double threshold, int below, int connectivity,
+                   int32_t* d_labels, int32_t* d_num, int64_t* d_stats, int64_t cap, int32_t* d_status, void* d_scratch,
+                   int64_t scratch_bytes, void* stream);
+int mg_blob_threshold(const void* d_plane, int dtype, int h, int w, double threshold, int below, uint8_t* d_on,
+                      void* stream);
+int mg_blob_select(int32_t* d_labels, int h, int w, const int64_t* d_stats, const int32_t* d_num, int64_t cap,
+                   int64_t min_area, int64_t max_area, int clear_border, int32_t* d_num_kept, int64_t* d_stats_out,
+                   int32_t* d_table, int32_t* d_remap, void* stream);
+int mg_blob_fill_holes(const int32_t* d_clabels, const int64_t* d_cstats, int64_t cap, int h, int w, uint8_t* d_on,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

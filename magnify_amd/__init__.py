@@ -11,6 +11,7 @@ from .xr_lite import DataArray, Dataset
 from .registry import (  # noqa: F401
     beads,
     beads_pipe,
+    blobs_pipe,
     component,
     components,
     image,
@@ -22,7 +23,7 @@ from .registry import (  # noqa: F401
     readers,
 )
 from .pipeline import Pipeline  # noqa: F401
-from . import reader, preprocess, shading, stitch, find, identify, postprocess, reduce, utils, filter, segment, depth, despeckle, background, profile, unmix, skew, refine  # noqa: F401,E402  (register components)
+from . import reader, preprocess, shading, stitch, find, identify, postprocess, reduce, utils, filter, segment, depth, despeckle, background, profile, unmix, skew, refine, blobs  # noqa: F401,E402  (register components)
 from .utils import seed  # noqa: F401
 from .file import load, save  # noqa: F401
 from . import sink  # noqa: F401,E402
@@ -30,6 +31,7 @@ from .sink import HostSink, SaveSink  # noqa: F401,E402
 from . import plot  # noqa: F401,E402
 
 __all__ = ["component", "microfluidic_chip", "microfluidic_chip_pipe", "mrbles", "mrbles_pipe", "beads", "beads_pipe",
+           "blobs", "blobs_pipe",
            "image", "image_pipe", "save", "load", "Pipeline", "DataArray", "Dataset", "seed", "find", "identify", "postprocess",
            "preprocess", "reader", "shading", "stitch", "reduce", "utils", "xr_lite", "filter", "plot", "segment", "depth",
            "despeckle", "background", "profile", "unmix", "skew", "refine"]

@@ -352,6 +352,51 @@ def beads_pipe(flatfield=1.0, darkfield=0.0, overlap=102, min_bead_diameter=5, m
     return pipe
 
 
+def blobs(data, flatfield=1.0, darkfield=0.0, overlap=102, threshold="otsu", search_channel=None, polarity="bright",
+          smooth=False, connectivity=8, fill_holes=False, min_area=20, max_area=None, clear_border=False, roi_length=None,
+          max_components=1 << 20, roi_only=False, drop_tiles=True, blend=None,
+          register=None, max_shift=8, register_channel=None,
+          depth=None, depth_window=9,
+          despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane",
+          background=None, background_smooth=0, background_channel=None,
+          profile=None, profile_rings=None, profile_mask="own"):
+    """Markers of any shape (not in the reference): ``beads`` with ``find_blobs`` (blobs.py) in the finder's place."""
+    kw = dict(locals())
+    kw.pop("data")
+    return blobs_pipe(**kw)(data=data)
+
+
+def blobs_pipe(flatfield=1.0, darkfield=0.0, overlap=102, threshold="otsu", search_channel=None, polarity="bright",
+               smooth=False, connectivity=8, fill_holes=False, min_area=20, max_area=None, clear_border=False,
+               roi_length=None, max_components=1 << 20, roi_only=False, drop_tiles=True, blend=None,
+               register=None, max_shift=8, register_channel=None,
+               depth=None, depth_window=9,
+               despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane",
+               background=None, background_smooth=0, background_channel=None,
+               profile=None, profile_rings=None, profile_mask="own"):
+    """read -> standardize_format -> depth -> despeckle -> flatfield_correct -> stitch -> background -> find_blobs ->
+    profile -> drop -> restore_format; the finder's settings are checked now, not at the first assay."""
+    from .blobs import check_blobs
+
+    check_blobs(threshold, search_channel, polarity, smooth, connectivity, fill_holes, min_area, max_area, clear_border,
+                roi_length, max_components)
+    pipe = Pipeline("read")
+    pipe.add_pipe("standardize_format")
+    _add_depth(pipe, depth, depth_window)
+    _add_despeckle(pipe, despeckle, despeckle_radius, despeckle_which, despeckle_scope)
+    pipe.add_pipe("flatfield_correct", flatfield=flatfield, darkfield=darkfield)
+    pipe.add_pipe("stitch", overlap=overlap, blend=blend, register=register, max_shift=max_shift,
+                  register_channel=register_channel)
+    _add_background(pipe, background, background_smooth, background_channel)
+    pipe.add_pipe("find_blobs", threshold=threshold, search_channel=search_channel, polarity=polarity, smooth=smooth,
+                  connectivity=connectivity, fill_holes=fill_holes, min_area=min_area, max_area=max_area,
+                  clear_border=clear_border, roi_length=roi_length, max_components=max_components)
+    _add_profile(pipe, profile, profile_rings, profile_mask, roi_length)
+    pipe.add_pipe("drop", roi_only=roi_only, drop_tiles=drop_tiles)
+    pipe.add_pipe("restore_format")
+    return pipe
+
+
 def image(data, overlap=102, rotation=0, roi_only=False, drop_tiles=True, blend=None,
           register=None, max_shift=8, register_channel=None, depth=None, depth_window=9,
           despeckle=None, despeckle_radius=1, despeckle_which="bright", despeckle_scope="plane",
